@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: Nystrom-Koopman fits/sec (K_nm build + A,B,C solve) at N=1e5, m=2000, d=384 (+p=6), fp64.
 
-    python bench.py --gpus 1 --steps 5 --warmup 1
+    python bench.py --gpus 1 --steps 5 --warmup 1 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -12,9 +12,15 @@ receives device pointers).  With N > 1 every rank owns a full replica of the dat
 all-gather one diagnostic scalar per fit at the end (RCCL); value = total fits / max-over-ranks time ("weak" scaling).
 
 Rank 0 prints ONE JSON line carrying `roofline` (dominant kernel: the fp64-MFMA Gram GEMM, timed live with HIP events
-on the library's stream) and, at N=1, `cpu_baseline` (the NumPy/SciPy oracle in reference-faithful mode: by default on
-the full workload, one warm-up + two timed fits, about two minutes; `--cpu-baseline sample` is the quick extrapolated
-form), `value_host_inputs` (host arrays in, host arrays out) and `cv_sweep` (the cloth-shaped hyper-parameter sweep).
+on the library's stream, from the timed fits themselves).  A plain run does only that: set-up, warm-up, the timed steps,
+the outputs (`--dump-outputs`) and the line.  With `--full`, at N=1, the line also carries `cpu_baseline` (the
+NumPy/SciPy oracle in reference-faithful mode: by default on the full workload, one warm-up + two timed fits, about two
+minutes; `--cpu-baseline sample` is the quick extrapolated form) with `parity_full_size`, `value_host_inputs` (host
+arrays in, host arrays out) and `cv_sweep` (the cloth-shaped hyper-parameter sweep).
+
+`--dump-outputs DIR` writes what a caller of the timed path receives from its last step -- the operators A, B, C and the
+weights W of the last timed fit, float64, 45 MB at the default shape -- as DIR/<name>.npy.  The inputs are seeded, so two
+builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -206,6 +212,16 @@ def real_cloth_grid_rate(nk, batch, groups):
                 real_grid_note="reference inputs and GridSearchCV landmark draws (fixtures f0 / f7); median of 3 sweeps after one warm-up")
 
 
+def dump_outputs(path, reg):
+    """What the timed path hands its caller, from the regressor of the last timed step: DIR/{A,B,C,W}.npy in float64."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"A": reg.A, "B": reg.B, "C": reg.C, "W": reg.weights}
+    total = sum(np.asarray(a).size * 8 for a in arrays.values())
+    assert total <= 64 << 20, f"outputs of {total / 2**20:.1f} MiB exceed the 64 MiB dump limit"
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -215,9 +231,14 @@ def main():
     ap.add_argument("--m", type=int, default=2000)
     ap.add_argument("--d", type=int, default=384)
     ap.add_argument("--p", type=int, default=6)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the secondary figures (at N=1: CPU baseline with full-size parity, host-input rate, "
+                         "CV sweeps); a plain run measures the headline fits only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the operators of the last timed fit (A, B, C, W) as DIR/<name>.npy")
     ap.add_argument("--cpu-baseline", choices=["full", "sample", "none"], default="full",
-                    help="full: faithful oracle on the full workload, warm-up + 2 timed fits (~2 min); sample: one fit on "
-                         "--cpu-sample-rows rows, extrapolated (labelled as such); none: skip")
+                    help="the CPU leg of --full.  full: faithful oracle on the full workload, warm-up + 2 timed fits (~2 min); "
+                         "sample: one fit on --cpu-sample-rows rows, extrapolated (labelled as such); none: skip")
     ap.add_argument("--cpu-sample-rows", type=int, default=10000)
     ap.add_argument("--cpu-threads", type=int, default=min(16, os.cpu_count() or 1))
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -225,7 +246,7 @@ def main():
                     help="walk a 15-candidate (lengthscale, gamma) grid instead: step s on rank r fits candidate (r + N s) mod 15 (the "
                          "units of a sharded CV sweep; their cost differs by the square-root iteration count).  Default at "
                          "every N: each unit is the headline fit (l=20, gamma=1e-6), so a 1 -> N curve times the same work per GPU")
-    ap.add_argument("--no-extras", action="store_true", help="skip the host-input and CV-sweep secondary figures")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the host-input and CV-sweep secondary figures")
     ap.add_argument("--concurrency", type=int, default=1,
                     help="host threads issuing independent fits concurrently on each GPU (each with its own context and "
                          "streams); 1 = one fit at a time (the default, and the setting the roofline figure refers to)")
@@ -316,6 +337,8 @@ def main():
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, last)
 
     if rank == 0:
         ms_step = elapsed / args.steps * 1e3
@@ -358,7 +381,7 @@ def main():
                          "note": "algorithmic flop with SYRK symmetry exploited: (m+p)(m+p+1)n + 2m(m+p)n + m(m+1)n + 2dmn "
                                  "in one fused launch; the split-K reduce kernel is excluded from the launch time"},
         }
-        if world == 1 and not args.no_extras:
+        if world == 1 and args.full and not args.no_extras:
             # fits/s as the reference's fit(X, Y) is called: X, Y host NumPy arrays in, operators landed in host arrays
             # (the 620 MB upload from pageable memory is inside; never the headline `value`)
             def host_fit():
@@ -372,7 +395,7 @@ def main():
                 host_fit()
             out["value_host_inputs"] = 3 / (time.perf_counter() - t1)
             out["cv_sweep"] = cv_sweep_rate(nk)
-        mode = "none" if args.no_cpu_baseline else args.cpu_baseline
+        mode = "none" if args.no_cpu_baseline or not args.full else args.cpu_baseline
         if world == 1 and mode != "none":
             base, oracle_fit = None, None
             if mode == "full":

@@ -1,13 +1,14 @@
-"""CPU: the data-format readers against files written in the reference's layout, and (when /root/reference is
-mounted) against the reference's own files and the committed golden copy of them."""
+"""CPU: the data-format readers against files written in the reference's layout, and against the reference's own
+files (their first lines / columns, copied unchanged into tests/golden/reference_csv/ by tests/golden/make_golden_csv.py)
+and the committed golden arrays read from the whole files."""
 import os
+import shutil
 
 import numpy as np
-import pytest
 
 from nys_koop_lqr_amd import datasets, harness
 
-REF = "/root/reference"
+REF_CSV = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_csv")
 
 
 def test_cloth_and_duffing_layouts(tmp_path):
@@ -30,13 +31,24 @@ def test_cloth_and_duffing_layouts(tmp_path):
     assert ref.shape == (192, 1) and np.array_equal(ref[0::3], trajs[0][0::3, :1])  # x coordinates unchanged
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference checkout not mounted")
-def test_readers_on_the_reference_files(golden):
-    trajs, ctrls = datasets.load_cloth_experiment(os.path.join(REF, "8x8_cloth_swing_xyz"), n_trajs=12)
+def test_readers_on_the_reference_files(golden, tmp_path):
+    # the first 2 time steps of the reference's cloth trajectories 10 and 11, as trajectories 0 and 1 of an experiment
+    for j, i in enumerate((10, 11)):
+        for kind in ("state", "input"):
+            shutil.copyfile(os.path.join(REF_CSV, f"{kind}_samples_cloth_swing_{i}.csv"),
+                            tmp_path / f"{kind}_samples_cloth_swing_{j}.csv")
+    trajs, ctrls = datasets.load_cloth_experiment(str(tmp_path), n_trajs=2)
     g = golden("f6_cloth_known_gain.npz")  # trajectories 10..39 as the reference's scripts slice them
-    assert np.array_equal(trajs[10], g["trajs"][0]) and np.array_equal(ctrls[11], g["inputs"][1])
-    X, Y = datasets.load_duffing(os.path.join(REF, "duffing"))
-    assert X.shape == (3, 69900) and Y.shape == (2, 69900)
+    for j in range(2):
+        assert trajs[j].shape == (192, 2) and ctrls[j].shape == (6, 2)
+        assert np.array_equal(trajs[j], g["trajs"][j][:, :2]) and np.array_equal(ctrls[j], g["inputs"][j][:, :2])
+    # the Duffing CSVs cut after their first 20 (forced) / 30 (unforced) columns; f12 holds the whole files assembled
+    X, Y = datasets.load_duffing(REF_CSV)
+    f12 = golden("f12_duffing_full.npz")
+    assert f12["X"].shape == (69900, 3) and f12["Y"].shape == (69900, 2)
+    cols = np.r_[0:20, 20000:20030]  # 20 000 forced columns, then the unforced ones
+    assert X.shape == (3, 50) and Y.shape == (2, 50)
+    assert np.array_equal(X, f12["X"][cols].T) and np.array_equal(Y, f12["Y"][cols].T)
 
 
 def test_cloth_reference_state_matches_shipped_csv(golden):

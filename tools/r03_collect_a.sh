@@ -7,5 +7,5 @@ tail -4 $O/gpu_tests.log
 if grep -q "Memory access fault" $O/gpu_tests.log; then echo "GPU fault"; exit 70; fi
 python3 -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc $?" >> $O/smoke.log; tail -2 $O/smoke.log | cut -c1-400
 python3 tools/cloth_grid_units.py $O/cloth_units.txt > $O/cloth_units.log 2>&1; tail -5 $O/cloth_units.txt
-python3 bench.py > $O/bench_full.log 2>&1; echo "bench rc $?" >> $O/bench_full.log
+python3 bench.py --full > $O/bench_full.log 2>&1; echo "bench rc $?" >> $O/bench_full.log
 grep '^{"metric"' $O/bench_full.log > $O/bench_line.json; tail -2 $O/bench_full.log | cut -c1-600
