@@ -458,6 +458,7 @@ static void destroy_ctx_unregistered(nk_ctx* ctx) {
   (void)hipStreamDestroy(ctx->stream_prep);
   (void)hipStreamDestroy(ctx->stream_copy);
   (void)hipFree(ctx->d_info);
+  for (int i = 0; i < 2; ++i) if (ctx->d_flow[i]) (void)hipFree(ctx->d_flow[i]);
   (void)hipFree(ctx->d_scalars);
   if (ctx->d_zeros) (void)hipFree(ctx->d_zeros);
   if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
@@ -1359,8 +1360,17 @@ static int fit_impl(nk_ctx* ctx, const nk_kernel_desc* kd, const double* X, int6
   double piv_ratio[2] = {1.0, 1.0};
   NK_TRY(cholesky_fail_flags(ctx, sys, 2, chol_failed, piv_ratio));  // synchronises the main stream (which has joined the side stream)
   tr.mark("final sync");
+  bool chol_rerun = false;
+  if (chol_failed[0] == CHOL_FLOW_GIVEUP || chol_failed[1] == CHOL_FLOW_GIVEUP) {
+    // the dataflow factorisation gave up waiting: both systems once more from the saved copy, on the launch-per-step chain
+    ChainOnly chain(ctx);
+    NK_HIP(hipMemcpyAsync(G1, Gsave, gram_doubles(m, d, p) * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+    NK_TRY(cholesky_aug_pair_async(ctx, sys, 2));
+    NK_TRY(cholesky_fail_flags(ctx, sys, 2, chol_failed, piv_ratio));
+    chol_rerun = true;
+  }
   int rank_sys[2] = {mp, m};
-  bool redo_products = false;
+  bool redo_products = chol_rerun;
   if (ctx->strict_spd == 2) chol_failed[0] = chol_failed[1] = -1;  // lstsq-shaped: always the SVD with gelsd's cut-off
   if (chol_failed[0] || chol_failed[1]) {
     if (ctx->strict_spd == 1) {  // NK_ERR_NOT_SPD
@@ -1438,7 +1448,14 @@ static int fit_impl(nk_ctx* ctx, const nk_kernel_desc* kd, const double* X, int6
   }
   {
     const int vr = sqrtm_verdict(ctx, &splan, &it, &resid);  // the iteration was queued without host round trips
-    if (vr == NK_SQRT_RETRY) {
+    if (vr == NK_SQRT_RETRY && splan.flow_gave_up) {
+      // the dataflow factorisation of K_mm gave up waiting: the square root once more with the launch-per-step chain,
+      // then everything that depends on it
+      ChainOnly chain(ctx);
+      NK_TRY(sqrtm_spd(ctx, Kj, m, m, mdl->S, mdl->Sinv, &it, &resid));
+      NK_TRY(sqrt_products());
+      redo_products = true;
+    } else if (vr == NK_SQRT_RETRY) {
       count_event(CNT_SQRT_RETRY);
       // K_mm + jitter I is not positive definite to working precision (or the eigenvalue bound did not hold): the
       // coupled iteration needs no factorisation; then everything that depends on the square root once more

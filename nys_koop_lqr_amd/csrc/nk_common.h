@@ -93,6 +93,9 @@ struct nk_ctx {
   hipEvent_t ev_up[8] = {};     // uploads of the row blocks of a fit from host arrays (pipelined with the passes)
   nk_group* group = nullptr;    // member of a lock-step group (nk_lockstep.h): stream operations are recorded and merged
   nk_member_state* gstate = nullptr;
+  int* d_flow[2] = {nullptr, nullptr};  // flag words of the dataflow Cholesky (nk_chol_flow.hip), per failure-flag slot
+  size_t flow_words[2] = {0, 0};
+  bool chol_flow_off = false;  // set by nk::ChainOnly: the re-run of a factorisation whose dataflow launch gave up
   double* h_stage = nullptr;    // page-locked, device-visible staging block for the small latency-bound calls (rollouts):
   size_t h_stage_bytes = 0;     // kernels read their inputs from it and write their results into it directly (no DMA)
 };
@@ -127,6 +130,14 @@ struct SideScope {
     c->stream = s0;
     c->cur_arena = a0;
   }
+};
+
+// For the lifetime of the scope every blocked Cholesky of the context runs as the launch-per-step chain.
+struct ChainOnly {
+  nk_ctx* c;
+  bool b0;
+  explicit ChainOnly(nk_ctx* ctx) : c(ctx), b0(ctx->chol_flow_off) { c->chol_flow_off = true; }
+  ~ChainOnly() { c->chol_flow_off = b0; }
 };
 
 // factorisation failure flags: slots 0-1 belong to the main stream, 2-3 to the side stream (each stream may have a paired
@@ -176,7 +187,10 @@ int group_enter(nk_ctx* c);
 int group_leave(nk_ctx* c);
 void group_stats(nk_ctx* c, uint64_t out[4]);
 // slow-path counters (nk_runtime_counters)
-enum { CNT_CHAIN_GIVEUP = 0, CNT_JACOBI_GIVEUP = 1, CNT_RANK_TRUNCATED = 2, CNT_SQRT_RETRY = 3, CNT_REFINED = 4, CNT_N = 5 };
+// CNT_CHOL_FLOW_GIVEUP: dataflow Cholesky launches that gave up waiting (re-run on the launch-per-step chain);
+// CNT_CHOL_FLOW: dataflow Cholesky launches issued
+enum { CNT_CHAIN_GIVEUP = 0, CNT_JACOBI_GIVEUP = 1, CNT_RANK_TRUNCATED = 2, CNT_SQRT_RETRY = 3, CNT_REFINED = 4,
+       CNT_CHOL_FLOW_GIVEUP = 5, CNT_CHOL_FLOW = 6, CNT_N = 7 };
 void count_event(int which);
 uint64_t read_counter(int which);
 hipError_t real_stream_sync(hipStream_t s);
@@ -262,6 +276,7 @@ struct SqrtPlan {
   // sqrtm_verdict as NK_SQRT_RETRY and the caller falls back to sqrtm_spd_coupled.
   double lambda_min_hint = 0.0;
   bool early = false;
+  bool flow_gave_up = false;  // the early form's factorisation was a dataflow launch that gave up (sqrtm_verdict)
   // The factorisation chain of sqrtm_prepare is paused before block step `pause_step` until `pause_event` (recorded by
   // the caller BEFORE sqrtm_prepare is called) has completed -- see nk_nystrom_fit: the chain must not run beside the
   // fused Gram launch.
@@ -329,6 +344,13 @@ inline bool chol_fuse_enabled() {  // NYSKOOP_CHOL_FUSE=0 (read per call): separ
   const char* e = getenv("NYSKOOP_CHOL_FUSE");
   return !(e && e[0] == '0');
 }
+// the factorisation of cholesky_aug_pair_async as one tile-dataflow launch (nk_chol_flow.hip): same bits as the chain;
+// NYSKOOP_CHOL_FLOW=0 (read per call) keeps the launch-per-step chain
+bool chol_flow_enabled();
+int cholesky_flow_pair(nk_ctx* ctx, const CholSys* sys, int nsys);
+// failure flag of the systems of a dataflow factorisation that stopped waiting (a bounded wait ran out): cholesky_fail_flags
+// reports it as is (failed[q] == CHOL_FLOW_GIVEUP) and counts CNT_CHOL_FLOW_GIVEUP; the caller re-runs the chain
+constexpr int CHOL_FLOW_GIVEUP = -0x40000000;
 // panel product P <- P Linv_jj^T (64 x 64) of up to two systems (nk_trail.hip); false: not that shape
 bool launch_chol_panel_pair(nk_ctx* ctx, const GemmCall* calls, int ncalls, int* rc);
 // E_q <- E_q L_q^-1 on the extra rows of up to two factored systems, one launch (nk_trsm.hip)

@@ -709,6 +709,10 @@ int cholesky_fail_flags(nk_ctx* ctx, const CholSys* sys, int nsys, int* failed, 
   for (int q = 0; q < nsys; ++q) {
     failed[q] = ctx->h_info[ib + q];
     if (piv_ratio) piv_ratio[q] = 0.0;
+    if (failed[q] == CHOL_FLOW_GIVEUP) {  // the dataflow factorisation stopped waiting: the caller re-runs the chain
+      if (q == 0) count_event(CNT_CHOL_FLOW_GIVEUP);
+      continue;
+    }
     if (failed[q] != 0) continue;
     double dmin, dmax;
     memcpy(&dmin, &ctx->h_piv[2 * (ib + q)], 8);
@@ -747,8 +751,18 @@ int cholesky_aug_pair_async(nk_ctx* ctx, const CholSys* sys, int nsys, hipEvent_
   constexpr int NB = CHOL_NB;
   NK_REQUIRE(nsys >= 1 && nsys <= 2, "cholesky_aug_pair: 1..2 systems");
   NK_TRY(reset_pivots(ctx));
-  int nblk = 0;
-  for (int q = 0; q < nsys; ++q) nblk = std::max(nblk, (sys[q].m + NB - 1) / NB);
+  int nblk = 0, mmin = sys[0].m;
+  for (int q = 0; q < nsys; ++q) {
+    nblk = std::max(nblk, (sys[q].m + NB - 1) / NB);
+    mmin = std::min(mmin, sys[q].m);
+  }
+  // the whole factorisation as one tile-dataflow launch (nk_chol_flow.hip, same bits); lock-step groups record the chain below
+  if (!ctx->chol_flow_off && mmin >= 256 && !ctx_recording(ctx) && chol_flow_enabled()) {
+    if (pause != nullptr && pause_step >= 0 && pause_step < nblk) NK_HIP(hipStreamWaitEvent(ctx->stream, pause, 0));
+    NK_TRY(cholesky_flow_pair(ctx, sys, nsys));
+    NK_TRY(launch_trsm_right_lower_pair(ctx, sys, nsys));
+    return NK_OK;
+  }
   // Measured inside the headline fit (bench.py, same box): with the look-ahead the fit is 1.4 ms SLOWER -- the chain shares
   // the chip with the square-root iteration's GEMMs, its kernels crawl for lack of issue slots rather than for lack of
   // parallelism, and a second stream of them takes more from the GEMMs than the shorter dependency chain gives back.
@@ -1104,6 +1118,17 @@ int sqrtm_finish(nk_ctx* ctx, SqrtPlan* plan, double* S, double* Sinv) {
     NK_HIP(hipStreamSynchronize(ctx->stream));  // the one host round trip of the square root
     c = ctx->h_scalars[0]; sumsq = ctx->h_scalars[1]; trace = ctx->h_scalars[2]; linv2 = ctx->h_scalars[3];
   }
+  if (!plan->early && ctx->h_info[ib] == CHOL_FLOW_GIVEUP) {
+    // the dataflow factorisation gave up waiting: the whole square root once more with the launch-per-step chain
+    count_event(CNT_CHOL_FLOW_GIVEUP);
+    arena_release(ctx, plan->mark);
+    ChainOnly chain(ctx);
+    SqrtPlan again;
+    NK_TRY(sqrtm_prepare(ctx, plan->P, plan->ldp, m, &again));
+    const int rc = sqrtm_finish(ctx, &again, S, Sinv);
+    *plan = again;
+    return rc;
+  }
   if (!plan->early &&
       (ctx->h_info[ib] != 0 || !(c > 0.0) || !std::isfinite(c) || !(linv2 > 0.0) || !std::isfinite(linv2))) {
     // not numerically positive definite for the Cholesky route (e.g. a rank-deficient kernel matrix with a jitter below
@@ -1311,6 +1336,8 @@ int sqrtm_verdict(nk_ctx* ctx, SqrtPlan* plan, int* iters, double* resid) {
     const double flag = ctx->h_scalars[8];
     plan->deferred = false;
     if (plan->early && (ctx->h_info[2] != 0 || flag == 0.0 || !std::isfinite(ctx->h_scalars[10]))) {
+      plan->flow_gave_up = ctx->h_info[2] == CHOL_FLOW_GIVEUP;
+      if (plan->flow_gave_up) count_event(CNT_CHOL_FLOW_GIVEUP);
       plan->iters = plan->kmax;
       plan->resid = ctx->h_scalars[10];
       plan->rc = NK_SQRT_RETRY;

@@ -59,9 +59,24 @@ __device__ __forceinline__ void store_tile(double* T, int ldt, d4 acc, int l15, 
   for (int reg = 0; reg < 4; ++reg) T[(l4 + 4 * reg) * ldt + l15] = acc[reg];
 }
 
+// Barrier between the LDS phases of the diagonal body.  WAVE_SYNC: the body runs in ONE wave of a larger workgroup whose other
+// waves wait elsewhere (nk_chol_flow.hip), so the barrier is the wave's own: LDS operations of one wave complete in order, and
+// the workgroup-scope fences keep the compiler from moving LDS accesses across it.
+template <bool WAVE_SYNC>
+__device__ __forceinline__ void potrf_sync() {
+  if (WAVE_SYNC) {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+  } else {
+    __syncthreads();
+  }
+}
+
 // `which`: the system of a paired factorisation this wave works on; `lane`: 0..63 within the wave (the wave may be one of
-// several in its workgroup: chol_trail_potrf_kernel -- every __syncthreads below then only waits for the waves that are
-// still alive, which is this one once the others have finished their tiles)
+// several in its workgroup: chol_trail_potrf_kernel -- every __syncthreads below (WAVE_SYNC = false) then only waits for the
+// waves that are still alive, which is this one once the others have finished their tiles; chol_flow_kernel: WAVE_SYNC)
+template <bool WAVE_SYNC = false>
 __device__ __forceinline__ void potrf_diag_kernel_body(const PotrfBatch& pb, int blk, int which, int lane) {
   constexpr int NB = CHOL_NB;
   static_assert(NB == 64, "one lane per row, four 16-column panels");
@@ -88,7 +103,7 @@ __device__ __forceinline__ void potrf_diag_kernel_body(const PotrfBatch& pb, int
     if (r < nb && lane < nb) v = A[(int64_t)r * lda + lane];
     As[r * PLD + lane] = v;
   }
-  __syncthreads();
+  potrf_sync<WAVE_SYNC>();
 
   // ---- factor ---------------------------------------------------------------------------------------------------
 #pragma unroll
@@ -132,7 +147,7 @@ __device__ __forceinline__ void potrf_diag_kernel_body(const PotrfBatch& pb, int
     }
 #pragma unroll
     for (int jj = 0; jj < 16; ++jj) As[lane * PLD + c0 + jj] = R[jj];
-    __syncthreads();
+    potrf_sync<WAVE_SYNC>();
     // rank-16 update of the trailing lower tiles on the matrix pipe
 #pragma unroll
     for (int ti = pbk + 1; ti < 4; ++ti)
@@ -150,7 +165,7 @@ __device__ __forceinline__ void potrf_diag_kernel_body(const PotrfBatch& pb, int
 #pragma unroll
         for (int reg = 0; reg < 4; ++reg) As[(16 * ti + l4 + 4 * reg) * PLD + 16 * tj + l15] = c[reg];
       }
-    __syncthreads();
+    potrf_sync<WAVE_SYNC>();
   }
   // L -> global (rows go back whole: nothing reads the upper triangle of a factored diagonal block)
 #pragma unroll 8
@@ -177,7 +192,7 @@ __device__ __forceinline__ void potrf_diag_kernel_body(const PotrfBatch& pb, int
 #pragma unroll
     for (int i = 0; i < 16; ++i) Db[i * PLD + l15] = x[i];
   }
-  __syncthreads();
+  potrf_sync<WAVE_SYNC>();
   auto Lblk = [&](int i, int j) { return As + (16 * i) * PLD + 16 * j; };
   auto Xblk = [&](int i, int j) { return Iv + (16 * i) * PLD + 16 * j; };
   const d4 zero = d4{0.0, 0.0, 0.0, 0.0};
@@ -185,11 +200,11 @@ __device__ __forceinline__ void potrf_diag_kernel_body(const PotrfBatch& pb, int
 #pragma unroll
   for (int i = 1; i < 4; ++i)
     store_tile(Sc + (i - 1) * 16 * SLD, SLD, mm16<false>(Lblk(i, i - 1), PLD, Xblk(i - 1, i - 1), PLD, zero, l15, l4), l15, l4);
-  __syncthreads();
+  potrf_sync<WAVE_SYNC>();
 #pragma unroll
   for (int i = 1; i < 4; ++i)
     store_tile(Xblk(i, i - 1), PLD, mm16<true>(Xblk(i, i), PLD, Sc + (i - 1) * 16 * SLD, SLD, zero, l15, l4), l15, l4);
-  __syncthreads();
+  potrf_sync<WAVE_SYNC>();
   // second: X_{i,i-2} = -D_i (L_{i,i-2} D_{i-2} + L_{i,i-1} X_{i-1,i-2})
 #pragma unroll
   for (int i = 2; i < 4; ++i) {
@@ -197,11 +212,11 @@ __device__ __forceinline__ void potrf_diag_kernel_body(const PotrfBatch& pb, int
     t = mm16<false>(Lblk(i, i - 1), PLD, Xblk(i - 1, i - 2), PLD, t, l15, l4);
     store_tile(Sc + (i - 2) * 16 * SLD, SLD, t, l15, l4);
   }
-  __syncthreads();
+  potrf_sync<WAVE_SYNC>();
 #pragma unroll
   for (int i = 2; i < 4; ++i)
     store_tile(Xblk(i, i - 2), PLD, mm16<true>(Xblk(i, i), PLD, Sc + (i - 2) * 16 * SLD, SLD, zero, l15, l4), l15, l4);
-  __syncthreads();
+  potrf_sync<WAVE_SYNC>();
   // third: X_30 = -D_3 (L_30 D_0 + L_31 X_10 + L_32 X_20)
   {
     d4 t = mm16<false>(Lblk(3, 0), PLD, Xblk(0, 0), PLD, zero, l15, l4);
@@ -209,9 +224,9 @@ __device__ __forceinline__ void potrf_diag_kernel_body(const PotrfBatch& pb, int
     t = mm16<false>(Lblk(3, 2), PLD, Xblk(2, 0), PLD, t, l15, l4);
     store_tile(Sc, SLD, t, l15, l4);
   }
-  __syncthreads();
+  potrf_sync<WAVE_SYNC>();
   store_tile(Xblk(3, 0), PLD, mm16<true>(Xblk(3, 3), PLD, Sc, SLD, zero, l15, l4), l15, l4);
-  __syncthreads();
+  potrf_sync<WAVE_SYNC>();
   // dense 64 x 64 row-major inverse, exact zeros above the block diagonal
 #pragma unroll 8
   for (int i = 0; i < NB; ++i) Linv[i * NB + lane] = (l4 <= (i >> 4)) ? Iv[i * PLD + lane] : 0.0;
