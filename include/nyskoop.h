@@ -39,13 +39,15 @@ enum {
   NK_ERR_NO_DEVICE = -6       /* no gfx950 device visible */
 };
 
-/* kernel families: regressors.py:15-22 (RBF, anisotropic), :24-26 (Matern nu=2.5), :28-30 (DotProduct) */
-enum { NK_KERNEL_RBF = 0, NK_KERNEL_MATERN52 = 1, NK_KERNEL_LINEAR = 2 };
+/* kernel families: regressors.py:15-22 (RBF, anisotropic), :24-26 (Matern nu=2.5), :28-30 (DotProduct), :225-233 (thin-plate
+ * spline r^2 log(sqrt(r^2)), exactly 0 at r = 0; no length scale: n_lengthscale and lengthscale are ignored).  The spline
+ * family is for nk_kernel_matrix and the spline fit (nk_spline_fit); the Nystrom entry points reject it. */
+enum { NK_KERNEL_RBF = 0, NK_KERNEL_MATERN52 = 1, NK_KERNEL_LINEAR = 2, NK_KERNEL_TPS = 3 };
 
 typedef struct nk_kernel_desc {
   int32_t type;              /* NK_KERNEL_* */
   int32_t d;                 /* state dimension the kernel acts on */
-  int32_t n_lengthscale;     /* 1 (isotropic) or d (anisotropic); ignored for LINEAR */
+  int32_t n_lengthscale;     /* 1 (isotropic) or d (anisotropic); ignored for LINEAR and TPS */
   int32_t reserved;
   const double* lengthscale; /* HOST pointer, n_lengthscale entries */
   double sigma0;             /* LINEAR only: k(x,y) = x.y + sigma0^2 */
@@ -98,7 +100,8 @@ int nk_synchronize(nk_ctx* ctx);
 void* nk_stream(nk_ctx* ctx);
 /* how nk_nystrom_fit builds the two n x m kernel blocks: 0 = automatic (Gram form |a|^2+|b|^2-2ab on the MFMA engine
  * when d >= 32, direct differences otherwise), 1 = always direct differences like scipy cdist (regressors.py:141-142
- * -> sklearn -> cdist).  K(Z,Z), lift queries and nk_kernel_matrix always use direct differences.
+ * -> sklearn -> cdist).  K(Z,Z), lift queries and nk_kernel_matrix always use direct differences (nk_kernel_matrix of
+ * NK_KERNEL_TPS excepted).  nk_spline_fit builds its two blocks the same way.
  * Also settable with the environment variable NYSKOOP_KMAT=direct before nk_create. */
 int nk_set_kmat_mode(nk_ctx* ctx, int mode);
 /* Rank-deficient regularised systems.  scipy.linalg.lstsq (regressors.py:155,165; LAPACK gelsd, rcond = eps) silently
@@ -195,7 +198,10 @@ void* nk_host_alloc(uint64_t bytes);
 void nk_host_free(void* ptr);
 
 /* ---- kernel matrix: replaces `kern.kernel(A, B)` (regressors.py:22,26,30 -> sklearn RBF/Matern/DotProduct
- *      __call__): out[i][j] = k(A[i,:], B[j,:]),  A: nA x d, B: nB x d, out: nA x nB. ------------------------ */
+ *      __call__): out[i][j] = k(A[i,:], B[j,:]),  A: nA x d, B: nB x d, out: nA x nB.  Direct differences, except for
+ *      NK_KERNEL_TPS, which follows nk_set_kmat_mode like the kernel blocks of nk_spline_fit (Gram form at d >= 32 in
+ *      the automatic mode: r^2 carries a cancellation error of about eps (|a|^2 + |b|^2) after centring on the mean of
+ *      B, so coincident points give values of that order times |log r^2| instead of exact zeros). ------------------ */
 int nk_kernel_matrix(nk_ctx* ctx, const nk_kernel_desc* kd,
                      const double* A, int64_t lda, int64_t nA,
                      const double* B, int64_t ldb, int64_t nB,
@@ -242,6 +248,25 @@ int nk_model_create(nk_ctx* ctx, const nk_kernel_desc* kd, const double* Zout, i
                     const double* A, const double* B, const double* C, const double* W,
                     nk_model** model);
 int nk_model_destroy(nk_model* model);
+
+/* ---- thin-plate-spline EDMD: replaces KoopmanSplineRegressor.fit given its centres (regressors.py:199-221, the Korda-Mezic
+ *   baseline).  X: n x (d+p) rows [state | input], Y: n x d, row_ranges as in nk_nystrom_fit; centers: m x d rows (the
+ *   reference's `centers`, d x m, transposed).  With Phi_x = TPS(X_state, centres), Phi_y = TPS(Y, centres) (n x m blocks)
+ *   and P = [Phi_x U]^T [Phi_x U] + gamma n_train I:  M_ls = [Phi_y^T ; X_state^T] [Phi_x U] pinv(P),  A = M_ls[:m, :m],
+ *   B = M_ls[:m, m:], C = M_ls[m:, :m], W = C [A B].  pinv follows scipy.linalg.pinv (singular values <= (m+p) eps
+ *   sigma_max dropped); systems whose Cholesky pivots show they cannot come near that cut-off are solved by the blocked
+ *   Cholesky instead.  stats->rank_inner = singular values kept (m+p on the Cholesky path), rank_inner_rec = 0,
+ *   pivot_ratio_inner = smallest / largest Cholesky pivot (0 when it was not used).  fp64 only: the compute dtype of
+ *   nk_set_compute_dtype is ignored (the fit runs in fp64).  strict_spd (nk_set_strict_spd): 1 = a non-positive pivot
+ *   is NK_ERR_NOT_SPD, 2 = always the pseudo-inverse.  Not available to lock-step group members.  The model is a spline
+ *   model: its lift is the raw block TPS(x, centres) (no K_mm^{-1/2}); nk_lift, nk_predict, nk_score_neg_rmse,
+ *   nk_rollout, nk_closed_loop(_batch), nk_model_get ('S' / 'I': NK_ERR_BAD_ARG) and nk_model_get_ops accept it. */
+int nk_spline_fit(nk_ctx* ctx, const double* X, int64_t ldx, const double* Y, int64_t ldy, int64_t n, int32_t d, int32_t p,
+                  const int64_t* row_ranges, int32_t n_ranges, const double* centers, int64_t ldc, int32_t m, double gamma,
+                  nk_model** model, nk_fit_stats* stats);
+/* rebuild a spline model from host copies (un-pickling); A, B, C, W as in nk_model_create (W may be NULL). */
+int nk_spline_model_create(nk_ctx* ctx, const double* centers, int64_t ldc, int32_t m, int32_t d, int32_t p,
+                           const double* A, const double* B, const double* C, const double* W, nk_model** model);
 
 /* which: 'A' m x m, 'B' m x p, 'C' d x m, 'W' d x (m+p), 'S' m x m (K_mm^{1/2}), 'I' m x m (K_mm^{-1/2}),
  *        'Z' m x d landmarks.   regressors.py:158-159,166,169. */

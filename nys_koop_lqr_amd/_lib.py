@@ -9,7 +9,7 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
-NK_KERNEL_RBF, NK_KERNEL_MATERN52, NK_KERNEL_LINEAR = 0, 1, 2
+NK_KERNEL_RBF, NK_KERNEL_MATERN52, NK_KERNEL_LINEAR, NK_KERNEL_TPS = 0, 1, 2, 3
 NK_OK = 0
 _ERR_NAMES = {-1: "NK_ERR_BAD_ARG", -2: "NK_ERR_HIP", -3: "NK_ERR_NOT_SPD", -4: "NK_ERR_OOM",
               -5: "NK_ERR_NO_CONVERGENCE", -6: "NK_ERR_NO_DEVICE"}
@@ -85,6 +85,9 @@ SIGNATURES = {
                                    C.POINTER(_P), C.POINTER(FitStats)]),
     "nk_model_create": (C.c_int, [_P, C.POINTER(KernelDesc), _P, _I64, _I32, _I32, _I32, _D, _P, _P, _P, _P,
                                   C.POINTER(_P)]),
+    "nk_spline_fit": (C.c_int, [_P, _P, _I64, _P, _I64, _I64, _I32, _I32, C.POINTER(_I64), _I32, _P, _I64, _I32, _D,
+                                C.POINTER(_P), C.POINTER(FitStats)]),
+    "nk_spline_model_create": (C.c_int, [_P, _P, _I64, _I32, _I32, _I32, _P, _P, _P, _P, C.POINTER(_P)]),
     "nk_model_destroy": (C.c_int, [_P]),
     "nk_model_get": (C.c_int, [_P, _P, C.c_char, _P, _I64]),
     "nk_model_dims": (C.c_int, [_P, C.POINTER(_I32), C.POINTER(_I32), C.POINTER(_I32)]),

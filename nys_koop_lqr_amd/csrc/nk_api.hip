@@ -188,13 +188,13 @@ static int check_ctx(nk_ctx* ctx) {
   return arena_reset(ctx);
 }
 
-// 1/lengthscale per dimension on the device (ones for the linear kernel)
+// 1/lengthscale per dimension on the device (ones for the linear kernel and the thin-plate spline)
 static int make_winv(nk_ctx* ctx, const nk_kernel_desc* kd, int d, double* dst_dev) {
   NK_REQUIRE(kd != nullptr, "null kernel descriptor");
-  NK_REQUIRE(kd->type >= NK_KERNEL_RBF && kd->type <= NK_KERNEL_LINEAR, "unknown kernel type %d", kd->type);
+  NK_REQUIRE(kd->type >= NK_KERNEL_RBF && kd->type <= NK_KERNEL_TPS, "unknown kernel type %d", kd->type);
   NK_REQUIRE(kd->d == d, "kernel descriptor is for %d dimensions, data has %d", kd->d, d);
   std::vector<double> w((size_t)d, 1.0);
-  if (kd->type != NK_KERNEL_LINEAR) {
+  if (kd->type != NK_KERNEL_LINEAR && kd->type != NK_KERNEL_TPS) {
     NK_REQUIRE(kd->lengthscale != nullptr, "kernel lengthscale pointer is null");
     // sklearn _check_length_scale: an anisotropic kernel must match the data dimension
     NK_REQUIRE(kd->n_lengthscale == 1 || kd->n_lengthscale == d,
@@ -256,12 +256,14 @@ static void pool_drain() {
   g_pool.clear();
 }
 
-static int model_alloc(nk_ctx* ctx, int m, int d, int p, nk_model** out) {
+static int model_alloc(nk_ctx* ctx, int m, int d, int p, nk_model** out, int kind = NK_MODEL_NYSTROM) {
   nk_model* mdl = new nk_model();
   mdl->device = ctx->device;
   mdl->m = m; mdl->d = d; mdl->p = p;
+  mdl->kind = kind;
   const size_t mp = (size_t)m + p;
-  const size_t total = (size_t)m * mp /*G=[A B]*/ + (size_t)d * m /*C*/ + (size_t)d * mp /*W*/ + 2 * (size_t)m * m +
+  const size_t nS = kind == NK_MODEL_SPLINE ? 0 : 2 * (size_t)m * m;  // S, Sinv (a spline model has neither)
+  const size_t total = (size_t)m * mp /*G=[A B]*/ + (size_t)d * m /*C*/ + (size_t)d * mp /*W*/ + nS +
                        (size_t)m * d /*Z*/ + (size_t)d /*winv*/ + 64;
   mdl->bytes = total * sizeof(double);
   mdl->buf = pool_take(ctx->device, mdl->bytes);
@@ -280,8 +282,10 @@ static int model_alloc(nk_ctx* ctx, int m, int d, int p, nk_model** out) {
   mdl->B = mdl->A + m;  // view into G = [A | B], leading dimension m + p
   mdl->C = take((size_t)d * m);
   mdl->W = take((size_t)d * mp);
-  mdl->S = take((size_t)m * m);
-  mdl->Sinv = take((size_t)m * m);
+  if (kind != NK_MODEL_SPLINE) {
+    mdl->S = take((size_t)m * m);
+    mdl->Sinv = take((size_t)m * m);
+  }
   mdl->Z = take((size_t)m * d);
   mdl->winv = take((size_t)d);
   {
@@ -292,10 +296,12 @@ static int model_alloc(nk_ctx* ctx, int m, int d, int p, nk_model** out) {
   return NK_OK;
 }
 
-// phi (nq x m, ld ldo) = k(Xq, Z) * Sinv, processed in row chunks
+// phi (nq x m, ld ldo) = k(Xq, Z) * Sinv, processed in row chunks; a spline model's lift is the raw block k(Xq, Z)
 static int lift_device(nk_ctx* ctx, const nk_model* mdl, const double* Xq, int64_t ldx, int64_t nq, double* out,
                        int64_t ldo) {
   const int m = mdl->m;
+  if (mdl->kind == NK_MODEL_SPLINE)  // regressors.py:225-233
+    return launch_kmat(ctx, mdl->ktype, Xq, ldx, nq, mdl->Z, mdl->d, m, mdl->d, mdl->winv, mdl->sigma0, out, ldo);
   const int64_t chunk = 32768;
   const ArenaMark mk = arena_mark(ctx);
   double* Kq = nullptr;
@@ -787,7 +793,23 @@ int nk_kernel_matrix(nk_ctx* ctx, const nk_kernel_desc* kd, const double* A, int
   NK_TRY(stage_in(ctx, B, ldb, nB, d, &b));
   MatOut o;
   NK_TRY(stage_out(ctx, out, ldo, nA, nB, &o));
-  NK_TRY(launch_kmat(ctx, kd->type, a.ptr, a.ld, nA, b.ptr, b.ld, nB, d, winv, kd->sigma0, o.dev, o.ld));
+  if (kd->type == NK_KERNEL_TPS && ctx->kmat_mode == 0 && d >= 32 && nA >= 2 && nB >= 2) {
+    // the thin-plate spline follows nk_set_kmat_mode, so that the Gram-form blocks of nk_spline_fit can be inspected:
+    // rows centred on the mean of B, |a|^2 + |b|^2 - 2 a.b on the MFMA engine
+    const int64_t lta = (nA + 1) & ~(int64_t)1, ltb = (nB + 1) & ~(int64_t)1;
+    double *center = nullptr, *At = nullptr, *sqa = nullptr, *Bt = nullptr, *sqb = nullptr;
+    NK_TRY(arena_alloc_t(ctx, (size_t)d, &center));
+    NK_TRY(arena_alloc_t(ctx, (size_t)d * lta, &At));
+    NK_TRY(arena_alloc_t(ctx, (size_t)nA, &sqa));
+    NK_TRY(arena_alloc_t(ctx, (size_t)d * ltb, &Bt));
+    NK_TRY(arena_alloc_t(ctx, (size_t)nB, &sqb));
+    NK_TRY(launch_colmean(ctx, b.ptr, b.ld, (int)nB, d, center));
+    NK_TRY(prep_rows(ctx, a.ptr, a.ld, nA, d, winv, center, At, lta, sqa));
+    NK_TRY(prep_rows(ctx, b.ptr, b.ld, nB, d, winv, center, Bt, ltb, sqb));
+    NK_TRY(launch_kmat_gram(ctx, NK_KERNEL_TPS, At, lta, sqa, nA, Bt, ltb, sqb, nB, d, 0.0, o.dev, o.ld));
+  } else {
+    NK_TRY(launch_kmat(ctx, kd->type, a.ptr, a.ld, nA, b.ptr, b.ld, nB, d, winv, kd->sigma0, o.dev, o.ld));
+  }
   NK_TRY(finish_out(ctx, o));
   NK_HIP(hipStreamSynchronize(ctx->stream));
   return NK_OK;
@@ -818,6 +840,7 @@ static int fit_impl(nk_ctx* ctx, const nk_kernel_desc* kd, const double* X, int6
   NK_REQUIRE(mode == FIT_SOLVE || (ldx >= d + p && ldy >= d), "nk_nystrom_fit: leading dimension too small");
   NK_REQUIRE(ldzo >= d, "nk_nystrom_fit: leading dimension too small");
   NK_REQUIRE(std::isfinite(gamma) && std::isfinite(jitter), "nk_nystrom_fit: gamma/jitter not finite");
+  NK_REQUIRE(kd->type != NK_KERNEL_TPS, "nk_nystrom_fit: the thin-plate spline has no Nystrom fit (nk_spline_fit)");
   if (model) *model = nullptr;
   std::vector<int64_t> rng;
   if (mode != FIT_SOLVE && row_ranges && n_ranges > 0) {
@@ -1551,6 +1574,7 @@ int nk_model_create(nk_ctx* ctx, const nk_kernel_desc* kd, const double* Zout, i
   NK_TRY(check_ctx(ctx));
   NK_REQUIRE(kd && Zout && model, "nk_model_create: null argument");
   NK_REQUIRE(m > 0 && d > 0 && p >= 0 && ldz >= d, "nk_model_create: bad sizes");
+  NK_REQUIRE(kd->type != NK_KERNEL_TPS, "nk_model_create: spline models come from nk_spline_model_create");
   *model = nullptr;
   nk_model* mdl = nullptr;
   NK_TRY(model_alloc(ctx, m, d, p, &mdl));
@@ -1568,6 +1592,317 @@ int nk_model_create(nk_ctx* ctx, const nk_kernel_desc* kd, const double* Zout, i
   const int mp = m + p;
   if (A && C) {
     NK_REQUIRE(p == 0 || B != nullptr, "nk_model_create: B missing");
+    MatIn a, b, c, w;
+    NK_TRY(stage_in(ctx, A, m, m, m, &a));
+    NK_TRY(launch_copy2d(ctx, a.ptr, a.ld, mdl->A, mp, m, m));
+    if (p > 0) {
+      NK_TRY(stage_in(ctx, B, p, m, p, &b));
+      NK_TRY(launch_copy2d(ctx, b.ptr, b.ld, mdl->B, mp, m, p));
+    }
+    NK_TRY(stage_in(ctx, C, m, d, m, &c));
+    NK_TRY(launch_copy2d(ctx, c.ptr, c.ld, mdl->C, m, d, m));
+    if (W) {
+      NK_TRY(stage_in(ctx, W, mp, d, mp, &w));
+      NK_TRY(launch_copy2d(ctx, w.ptr, w.ld, mdl->W, mp, d, mp));
+    } else {
+      NK_TRY(launch_gemm(ctx, false, false, d, mp, m, 1.0, mdl->C, m, mdl->A, mp, 0.0, mdl->W, mp));
+    }
+    mdl->has_ops = true;
+  }
+  NK_HIP(hipStreamSynchronize(ctx->stream));
+  guard.m = nullptr;
+  *model = mdl;
+  return NK_OK;
+}
+
+// ---- thin-plate-spline EDMD fit (regressors.py:199-221), fp64 on every path ------------------------------------------
+// Feature matrix F = [Phi_x | U | (pad) | Phi_y] in the layout of the Nystrom fit (Phi_x = TPS(X_state, centres),
+// Phi_y = TPS(Y, centres)), built and contracted in passes of at most `pass_rows` rows; ONE fused Gram launch per pass
+// computes the three products that share the rows:
+//   cov = [Phi_x U]^T [Phi_x U]  ((m+p) x (m+p)),  top = Phi_y^T [Phi_x U]  (m x (m+p)),  bot = X_state^T [Phi_x U]  (d x (m+p))
+// stored one below the other (leading dimension m+p), so that [top; bot] rides along the blocked Cholesky of
+// P = cov + gamma n I as the extra rows of the augmented factorisation and comes out as M_ls = [top; bot] P^-1
+// (P is symmetric).  Systems whose condition could reach scipy.linalg.pinv's cut-off (m+p) eps sigma_max take the
+// Jacobi pseudo-inverse with that cut-off instead (see SPLINE_SVD_WINDOW).
+//
+// Which path: the Cholesky pivots d_k (Schur-complement diagonals) of an SPD matrix satisfy sigma_min <= d_k <= sigma_max,
+// so min d / max d >= sigma_min / sigma_max: a pivot ratio at or below the cut-off (m+p) eps means pinv certainly
+// truncates, but a ratio above it does not prove the opposite.  Measured with the reference's systems (f15 fixtures:
+// cloth n = 3030, d = 192, p = 6, m = 10..500, gamma = 1e-7..1e-5; Duffing m = 10..200) the pivot ratio exceeds
+// sigma_min / sigma_max by a factor 3 (m = 10) to 172 (m = 500), growing about linearly with m.  The safety window
+// therefore scales with the system: every system whose pivot ratio is below 2 (m+p) x (m+p) eps takes the SVD path
+// (at m = 500: a window of 1012 against the measured 172).  The Cholesky result is used only above it.
+static constexpr double SPLINE_SVD_WINDOW_PER_ROW = 2.0;
+
+int nk_spline_fit(nk_ctx* ctx, const double* X, int64_t ldx, const double* Y, int64_t ldy, int64_t n, int32_t d, int32_t p,
+                  const int64_t* row_ranges, int32_t n_ranges, const double* centers, int64_t ldc, int32_t m, double gamma,
+                  nk_model** model, nk_fit_stats* stats) {
+  NK_TRY(check_ctx(ctx));
+  NK_REQUIRE(X && Y && centers && model, "nk_spline_fit: null argument");
+  NK_REQUIRE(n > 0 && d > 0 && p >= 0 && m > 0, "nk_spline_fit: sizes must be positive (n=%lld d=%d p=%d m=%d)",
+             (long long)n, d, p, m);
+  NK_REQUIRE(ldx >= d + p && ldy >= d && ldc >= d, "nk_spline_fit: leading dimension too small");
+  NK_REQUIRE(std::isfinite(gamma), "nk_spline_fit: gamma not finite");
+  NK_REQUIRE(!ctx_recording(ctx), "nk_spline_fit: not available to the members of a lock-step group");
+  *model = nullptr;
+  std::vector<int64_t> rng;
+  if (row_ranges && n_ranges > 0) {
+    for (int i = 0; i < n_ranges; ++i) {
+      const int64_t b = row_ranges[2 * i], e = row_ranges[2 * i + 1];
+      NK_REQUIRE(0 <= b && b <= e && e <= n, "nk_spline_fit: row range %d = [%lld,%lld) outside [0,%lld)", i,
+                 (long long)b, (long long)e, (long long)n);
+      if (e > b) { rng.push_back(b); rng.push_back(e); }
+    }
+  } else {
+    rng.push_back(0); rng.push_back(n);
+  }
+  int64_t n_eff = 0;
+  for (size_t i = 0; i < rng.size(); i += 2) n_eff += rng[i + 1] - rng[i];
+  NK_REQUIRE(n_eff > 0, "nk_spline_fit: no training rows selected");
+  // (nk_set_compute_dtype(F32) is ignored here: the spline systems reach cond 1e13, the fit is fp64 only)
+  const int mp = m + p;
+  const double gamma_n = gamma * (double)n_eff;  // regressors.py:204
+
+  nk_model* mdl = nullptr;
+  NK_TRY(model_alloc(ctx, m, d, p, &mdl, NK_MODEL_SPLINE));
+  struct Guard {
+    nk_ctx* c;
+    nk_model* m;
+    ~Guard() {
+      if (m) {
+        (void)hipStreamSynchronize(c->stream_main);
+        (void)hipStreamSynchronize(c->stream_side);
+        nk_model_destroy(m);
+      }
+    }
+  } guard{ctx, mdl};
+  mdl->ktype = NK_KERNEL_TPS; mdl->sigma0 = 0.0; mdl->jitter = 0.0;
+  hipEvent_t* ev = ctx->ev;
+  NK_HIP(hipEventRecord(ev[0], ctx->stream));
+  NK_TRY(launch_fill(ctx, mdl->winv, d, 1, d, 1.0));  // no length scale
+  MatIn x, y, zc;
+  NK_TRY(stage_in(ctx, X, ldx, n, d + p, &x));
+  NK_TRY(stage_in(ctx, Y, ldy, n, d, &y));
+  if (rng.size() > 2 && (double)n_eff * (2.0 * d + p) * 8.0 <= 256e6) {  // K-fold training set: one contiguous piece
+    const int64_t ldxg = (d + p + 1) & ~(int64_t)1, ldyg = (d + 1) & ~(int64_t)1;
+    double *xg = nullptr, *yg = nullptr;
+    NK_TRY(arena_alloc_t(ctx, (size_t)n_eff * ldxg, &xg));
+    NK_TRY(arena_alloc_t(ctx, (size_t)n_eff * ldyg, &yg));
+    int64_t o = 0;
+    for (size_t i = 0; i < rng.size(); i += 2) {
+      const int64_t b = rng[i], len = rng[i + 1] - rng[i];
+      NK_TRY(launch_copy2d(ctx, x.ptr + b * x.ld, x.ld, xg + o * ldxg, ldxg, len, d + p));
+      NK_TRY(launch_copy2d(ctx, y.ptr + b * y.ld, y.ld, yg + o * ldyg, ldyg, len, d));
+      o += len;
+    }
+    x.ptr = xg; x.ld = ldxg; y.ptr = yg; y.ld = ldyg;
+    rng.assign({(int64_t)0, n_eff});
+  }
+  NK_TRY(stage_in(ctx, centers, ldc, m, d, &zc));
+  NK_TRY(launch_copy2d(ctx, zc.ptr, zc.ld, mdl->Z, d, m, d));
+  NK_HIP(hipEventRecord(ev[1], ctx->stream));
+
+  // Gram accumulators [cov ; top ; bot], (m+p+m+d) x (m+p)
+  double* G = nullptr;
+  const size_t gdoubles = (size_t)(mp + m + d) * mp;
+  NK_TRY(arena_alloc_t(ctx, gdoubles, &G));
+  double* Gtop = G + (size_t)mp * mp;
+  double* Gbot = Gtop + (size_t)m * mp;
+  const int64_t off_out = (mp + 1) & ~1;
+  const int64_t ldf = (off_out + m + 1) & ~(int64_t)1;
+  int64_t pass_rows;
+  {
+    const char* b = getenv("NYSKOOP_F_BUDGET_GB");
+    const double budget = (b ? atof(b) : 48.0) * 1073741824.0;
+    pass_rows = (int64_t)(budget / ((double)ldf * 8.0));
+    if (pass_rows < 1024) pass_rows = 1024;
+    pass_rows &= ~(int64_t)1023;
+  }
+  struct Piece { int64_t b, len; };
+  std::vector<std::vector<Piece>> passes(1);
+  {
+    int64_t used = 0;
+    for (size_t i = 0; i < rng.size(); i += 2) {
+      int64_t b = rng[i];
+      const int64_t e = rng[i + 1];
+      while (b < e) {
+        if (used == pass_rows) { passes.emplace_back(); used = 0; }
+        const int64_t len = std::min(e - b, pass_rows - used);
+        passes.back().push_back(Piece{b, len});
+        used += len;
+        b += len;
+      }
+    }
+  }
+  const bool multi_pass = passes.size() > 1;
+  const int64_t f_rows = multi_pass ? pass_rows : n_eff;
+  double* F = nullptr;
+  NK_TRY(arena_alloc_t(ctx, (size_t)f_rows * ldf + 64, &F));
+  // Gram-form kernel blocks (nk_set_kmat_mode: automatic at d >= 32) or direct differences
+  const bool gram_form = ctx->kmat_mode == 0 && d >= 32;
+  int64_t maxlen = 0;
+  for (auto& ps : passes) for (auto& pc : ps) maxlen = std::max(maxlen, pc.len);
+  const int64_t ldt = (maxlen + 1) & ~(int64_t)1, ldzt = (m + 1) & ~1;
+  double *center = nullptr, *Rt = nullptr, *sqr = nullptr, *Zt = nullptr, *sqz = nullptr;
+  if (gram_form) {
+    NK_TRY(arena_alloc_t(ctx, (size_t)d, &center));
+    NK_TRY(arena_alloc_t(ctx, (size_t)d * ldt, &Rt));
+    NK_TRY(arena_alloc_t(ctx, (size_t)maxlen, &sqr));
+    NK_TRY(arena_alloc_t(ctx, (size_t)d * ldzt, &Zt));
+    NK_TRY(arena_alloc_t(ctx, (size_t)m, &sqz));
+    NK_TRY(launch_colmean(ctx, zc.ptr, zc.ld, m, d, center));  // distances are shift invariant: centred rows cancel less
+    NK_TRY(prep_rows(ctx, zc.ptr, zc.ld, m, d, mdl->winv, center, Zt, ldzt, sqz));
+  }
+  float ms_gram_kernel = 0.f;
+  int gram_launches = 0;
+  bool gram_deferred = false;
+  const bool timed = stats != nullptr;
+  for (size_t ip = 0; ip < passes.size(); ++ip) {
+    const std::vector<Piece>& ps = passes[ip];
+    const double beta = ip == 0 ? 0.0 : 1.0;
+    int64_t o = 0;
+    for (const Piece& pc : ps) {
+      const double* xs = x.ptr + pc.b * x.ld;
+      const double* ys = y.ptr + pc.b * y.ld;
+      if (gram_form) {
+        NK_TRY(prep_rows(ctx, xs, x.ld, pc.len, d, mdl->winv, center, Rt, ldt, sqr));
+        NK_TRY(launch_kmat_gram(ctx, NK_KERNEL_TPS, Rt, ldt, sqr, pc.len, Zt, ldzt, sqz, m, d, 0.0, F + o * ldf, ldf));
+        NK_TRY(prep_rows(ctx, ys, y.ld, pc.len, d, mdl->winv, center, Rt, ldt, sqr));
+        NK_TRY(launch_kmat_gram(ctx, NK_KERNEL_TPS, Rt, ldt, sqr, pc.len, Zt, ldzt, sqz, m, d, 0.0, F + o * ldf + off_out,
+                                ldf));
+      } else {
+        NK_TRY(launch_kmat(ctx, NK_KERNEL_TPS, xs, x.ld, pc.len, zc.ptr, zc.ld, m, d, mdl->winv, 0.0, F + o * ldf, ldf));
+        NK_TRY(launch_kmat(ctx, NK_KERNEL_TPS, ys, y.ld, pc.len, zc.ptr, zc.ld, m, d, mdl->winv, 0.0, F + o * ldf + off_out,
+                           ldf));
+      }
+      if (p > 0) NK_TRY(launch_copy2d(ctx, xs + d, x.ld, F + o * ldf + m, ldf, pc.len, p));
+      o += pc.len;
+    }
+    const int64_t rows = o;
+    if (ip == 0) NK_HIP(hipEventRecord(ev[2], ctx->stream));
+    TnProblem pr[3];
+    pr[0].A = F; pr[0].B = F; pr[0].lda = pr[0].ldb = ldf; pr[0].M = pr[0].N = mp; pr[0].C = G; pr[0].ldc = mp;
+    pr[0].tri = TRI_UPPER_MIRROR;
+    pr[1].A = F + off_out; pr[1].B = F; pr[1].lda = pr[1].ldb = ldf; pr[1].M = m; pr[1].N = mp; pr[1].C = Gtop;
+    pr[1].ldc = mp;
+    pr[2].A = x.ptr + ps[0].b * x.ld; pr[2].lda = x.ld; pr[2].M = d; pr[2].N = mp; pr[2].C = Gbot; pr[2].ldc = mp;
+    pr[2].B = F; pr[2].ldb = ldf;
+    for (int q = 0; q < 3; ++q) pr[q].beta = beta;
+    const bool fast = tn_fast_ok(pr[0]) && tn_fast_ok(pr[1]);
+    const bool fast_x = fast && ps.size() == 1 && tn_fast_ok(pr[2]);
+    if (fast) {
+      float ms1 = 0.f;
+      NK_TRY(launch_gemm_tn_multi(ctx, pr, fast_x ? 3 : 2, rows, 0, timed ? &ms1 : nullptr, multi_pass));
+      if (multi_pass) ms_gram_kernel += ms1; else gram_deferred = timed;
+      gram_launches += 1;
+    } else {  // operands outside the alignment contract of the fused engine: generic engine
+      GemmOpts sym;
+      sym.tri = TRI_UPPER_MIRROR;
+      NK_TRY(launch_gemm(ctx, true, false, mp, mp, rows, 1.0, F, ldf, F, ldf, beta, G, mp, sym));
+      NK_TRY(launch_gemm(ctx, true, false, m, mp, rows, 1.0, F + off_out, ldf, F, ldf, beta, Gtop, mp));
+      gram_launches += 2;
+    }
+    if (!fast_x) {  // bot = X_state^T [Phi_x U], piece by piece
+      int64_t oo = 0;
+      for (const Piece& pc : ps) {
+        NK_TRY(launch_gemm(ctx, true, false, d, mp, pc.len, 1.0, x.ptr + pc.b * x.ld, x.ld, F + oo * ldf, ldf,
+                           (oo == 0 && ip == 0) ? 0.0 : 1.0, Gbot, mp));
+        oo += pc.len;
+      }
+    }
+  }
+  NK_HIP(hipEventRecord(ev[3], ctx->stream));
+
+  // ---- M_ls = [top; bot] pinv(P), P = cov + gamma n I (regressors.py:213-214)
+  NK_TRY(launch_add_diag(ctx, G, mp, mp, gamma_n));
+  double* Gsave = nullptr;  // the assembled system for the pseudo-inverse path (the factorisation works in place)
+  NK_TRY(arena_alloc_t(ctx, gdoubles, &Gsave));
+  NK_HIP(hipMemcpyAsync(Gsave, G, gdoubles * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+  double *Linv = nullptr, *pivlog = nullptr;
+  const int nblk = (mp + CHOL_NB - 1) / CHOL_NB;
+  NK_TRY(arena_alloc_t(ctx, (size_t)nblk * CHOL_WS, &Linv));
+  NK_TRY(arena_alloc_t(ctx, (size_t)mp + 4, &pivlog));
+  CholSys sys;
+  sys.P = G; sys.ldp = mp; sys.m = mp; sys.Linv = Linv; sys.extra = m + d; sys.pivlog = pivlog;  // [P; top; bot]
+  int failed = -1;
+  double piv_ratio = 0.0;
+  if (ctx->strict_spd != 2) {  // (strict = 2: the SVD whatever the pivots)
+    NK_TRY(cholesky_aug_pair_async(ctx, &sys, 1));
+    NK_TRY(cholesky_fail_flags(ctx, &sys, 1, &failed, &piv_ratio));  // synchronises
+    if (failed == CHOL_FLOW_GIVEUP) {
+      ChainOnly chain(ctx);
+      NK_HIP(hipMemcpyAsync(G, Gsave, gdoubles * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+      NK_TRY(cholesky_aug_pair_async(ctx, &sys, 1));
+      NK_TRY(cholesky_fail_flags(ctx, &sys, 1, &failed, &piv_ratio));
+    }
+  }
+  const double eps = 2.220446049250313e-16;
+  const double rcond = (double)mp * eps;  // scipy.linalg.pinv: atol = 0, rtol = max(M, N) eps
+  int rank = mp;
+  const bool use_svd = failed != 0 || !(piv_ratio > SPLINE_SVD_WINDOW_PER_ROW * (double)mp * rcond);
+  if (use_svd) {
+    if (failed != 0 && ctx->strict_spd == 1) {
+      set_error("nk_spline_fit: Cholesky met a non-positive pivot and strict mode is on");
+      return NK_ERR_NOT_SPD;
+    }
+    PinvInfo pi;
+    NK_TRY(pinv_right_divide(ctx, Gsave, mp, mp, Gsave + (size_t)mp * mp, mp, m + d, Gtop, mp, rcond, &pi));
+    if (!pi.converged) {
+      set_error("nk_spline_fit: Jacobi SVD did not converge in %d sweeps", pi.sweeps);
+      return NK_ERR_NO_CONVERGENCE;
+    }
+    rank = pi.rank;
+    if (rank < mp) count_event(CNT_RANK_TRUNCATED);
+  }
+  // ---- operators: A | B = M_ls[:m, :], C = M_ls[m:, :m], W = C [A B] (regressors.py:215-219)
+  NK_HIP(hipEventRecord(ev[4], ctx->stream));
+  NK_TRY(launch_copy2d(ctx, Gtop, mp, mdl->A, mp, m, mp));
+  NK_TRY(launch_copy2d(ctx, Gbot, mp, mdl->C, m, d, m));
+  NK_TRY(launch_gemm(ctx, false, false, d, mp, m, 1.0, mdl->C, m, mdl->A, mp, 0.0, mdl->W, mp));
+  NK_HIP(hipEventRecord(ev[5], ctx->stream));
+  NK_HIP(hipStreamSynchronize(ctx->stream));
+  mdl->has_ops = true;
+  if (stats) {
+    memset(stats, 0, sizeof(*stats));
+    stats->ms_total = ev_ms(ctx, 0, 5);
+    stats->ms_upload = (x.staged || y.staged) ? ev_ms(ctx, 0, 1) : 0.0;
+    stats->ms_kmat = ev_ms(ctx, 1, 2);
+    stats->ms_gram = ev_ms(ctx, 2, 3);
+    stats->ms_solve = ev_ms(ctx, 3, 5);
+    if (gram_deferred) ms_gram_kernel = ev_ms(ctx, 14, 15);
+    stats->ms_gram_kernel_avg = gram_launches ? ms_gram_kernel / gram_launches : 0.0;
+    stats->gram_kernel_launches = gram_launches;
+    const double ne = (double)n_eff;
+    stats->gram_flops = 2.0 * ne * (double)mp * (double)(mp + m + d);
+    stats->kmat_pairs = 2.0 * ne * m * d;
+    stats->rank_inner = rank;
+    stats->rank_inner_rec = 0;
+    stats->pivot_ratio_inner = failed == 0 ? piv_ratio : 0.0;
+  }
+  if (ctx->arena.chunks.size() > 1 || ctx->arena_side.chunks.size() > 1) NK_TRY(arena_reset(ctx));
+  guard.m = nullptr;
+  *model = mdl;
+  return NK_OK;
+}
+
+// rebuild a spline model from host copies (un-pickling KoopmanSplineRegressor)
+int nk_spline_model_create(nk_ctx* ctx, const double* centers, int64_t ldc, int32_t m, int32_t d, int32_t p,
+                           const double* A, const double* B, const double* C, const double* W, nk_model** model) {
+  NK_TRY(check_ctx(ctx));
+  NK_REQUIRE(centers && model, "nk_spline_model_create: null argument");
+  NK_REQUIRE(m > 0 && d > 0 && p >= 0 && ldc >= d, "nk_spline_model_create: bad sizes");
+  *model = nullptr;
+  nk_model* mdl = nullptr;
+  NK_TRY(model_alloc(ctx, m, d, p, &mdl, NK_MODEL_SPLINE));
+  struct Guard { nk_model* m; ~Guard() { if (m) nk_model_destroy(m); } } guard{mdl};
+  mdl->ktype = NK_KERNEL_TPS; mdl->sigma0 = 0.0; mdl->jitter = 0.0;
+  NK_TRY(launch_fill(ctx, mdl->winv, d, 1, d, 1.0));
+  MatIn z;
+  NK_TRY(stage_in(ctx, centers, ldc, m, d, &z));
+  NK_TRY(launch_copy2d(ctx, z.ptr, z.ld, mdl->Z, d, m, d));
+  const int mp = m + p;
+  if (A && C) {
+    NK_REQUIRE(p == 0 || B != nullptr, "nk_spline_model_create: B missing");
     MatIn a, b, c, w;
     NK_TRY(stage_in(ctx, A, m, m, m, &a));
     NK_TRY(launch_copy2d(ctx, a.ptr, a.ld, mdl->A, mp, m, m));
@@ -1622,6 +1957,13 @@ int nk_model_get(nk_ctx* ctx, const nk_model* mdl, char which, double* out, int6
     case 'W': src = mdl->W; lds = mp; rows = d; cols = mp; break;
     case 'S': src = mdl->S; lds = m; rows = m; cols = m; break;
     case 'I': src = mdl->Sinv; lds = m; rows = m; cols = m; break;
+  }
+  if ((which == 'S' || which == 'I') && mdl->kind == NK_MODEL_SPLINE) {
+    set_error("nk_model_get: a spline model has no K_mm^{1/2} / K_mm^{-1/2} ('%c')", which);
+    return NK_ERR_BAD_ARG;
+  }
+  switch (which) {
+    case 'A': case 'B': case 'C': case 'W': case 'S': case 'I': break;
     case 'Z': src = mdl->Z; lds = d; rows = m; cols = d; break;
     default: set_error("nk_model_get: unknown selector '%c'", which); return NK_ERR_BAD_ARG;
   }
@@ -1993,12 +2335,14 @@ static int rollout_impl(nk_ctx* ctx, const nk_model* mdl, const double* G, int64
   if (!have_u) ch.pu = (T > 1) ? p : 0;
   const int64_t ldxo = small ? d : ox.ld, ldzo = small ? m : (out_z ? oz.ld : m);
   bool z0_in_place = false;
-  if (x0 && lifted_chain_ok(m, ch.pu, d)) {  // the lift is done by the chain kernel itself
+  if (x0 && mdl->kind != NK_MODEL_SPLINE && lifted_chain_ok(m, ch.pu, d)) {  // the lift is done by the chain kernel itself
     ch.lift = true; ch.x0 = xin.ptr; ch.x0_stride = xin.ld; ch.Zl = mdl->Z; ch.d = d; ch.winv = mdl->winv;
     ch.Sinv = mdl->Sinv; ch.ktype = mdl->ktype; ch.sigma0 = mdl->sigma0;
   } else if (x0) {
     NK_TRY(lift_device(ctx, mdl, xin.ptr, xin.ld, batch, Zall, ldz));  // z_0 = phi(x_0) for every trajectory
     z0_in_place = true;
+    // the single-launch chain (no lift of its own: a spline model, or d too large for its LDS) reads z_0 from there
+    if (lifted_chain_ok(m, ch.pu, 0)) { ch.z0 = Zall; ch.z0_stride = ldz; }
   } else if (lifted_chain_ok(m, ch.pu, 0)) {
     ch.z0 = xin.ptr; ch.z0_stride = xin.ld;
   } else {

@@ -100,6 +100,7 @@ struct nk_ctx {
   size_t h_stage_bytes = 0;     // kernels read their inputs from it and write their results into it directly (no DMA)
 };
 
+enum { NK_MODEL_NYSTROM = 0, NK_MODEL_SPLINE = 1 };
 struct nk_model {
   int device = 0;
   int32_t m = 0, d = 0, p = 0;
@@ -111,6 +112,7 @@ struct nk_model {
   double *A = nullptr, *B = nullptr, *C = nullptr, *W = nullptr, *S = nullptr, *Sinv = nullptr, *Z = nullptr,
          *winv = nullptr;  // winv: 1/lengthscale per dimension (d entries)
   bool has_ops = false;
+  int32_t kind = 0;  // NK_MODEL_NYSTROM / NK_MODEL_SPLINE (lift = raw thin-plate-spline block, no S, Sinv: both nullptr)
   hipEvent_t ev_fetch = nullptr;  // completion of the last nk_model_get_ops_async (nullptr: nothing pending)
 };
 
@@ -178,6 +180,61 @@ __device__ __forceinline__ double exp_nonpos(double x, double ca_v) {
   return x < -1075.0 ? 0.0 : ldexp(p, (int)k);
 }
 __device__ __forceinline__ double exp_nonpos(double x) { return exp_nonpos(x, exp_nonpos_ca()); }
+
+// log(x) for finite x > 0 (the thin-plate-spline epilogues; sqrt(r^2) of two distinct points).  fdlibm's __ieee754_log
+// (public domain, Sun Microsystems 1993): x = 2^k (1 + f) with 1 + f in [sqrt(2)/2, sqrt(2)), s = f / (2 + f),
+// log(1 + f) = f - hf^2 + s (hf^2 + R(s^2)) with fdlibm's degree-14 minimax R, k ln2 in two parts.  Plain IEEE operations
+// (no contraction, correctly rounded division), so the host build of this function gives the same bits as the device.
+// Error against the C library's log (glibc), measured on the host build over 2.1e7 arguments (7e6 each: uniform in the
+// exponent over [1e-300, 1e300], uniform over [0.5, 2], uniform over [1 - 1e-6, 1 + 1e-6]) and a sweep of subnormals: at
+// most 1 ulp, 97.3 % of the results identical.
+__host__ __device__ __forceinline__ double log_pos(double x) {
+#pragma clang fp contract(off)
+  const double ln2_hi = 6.93147180369123816490e-01, ln2_lo = 1.90821492927058770002e-10;
+  const double Lg1 = 6.666666666666735130e-01, Lg2 = 3.999999999940941908e-01, Lg3 = 2.857142874366239149e-01,
+               Lg4 = 2.222219843214978396e-01, Lg5 = 1.818357216161805012e-01, Lg6 = 1.531383769920937332e-01,
+               Lg7 = 1.479819860511658591e-01;
+  uint64_t bits;
+  __builtin_memcpy(&bits, &x, 8);
+  int32_t hx = (int32_t)(bits >> 32);
+  int k = 0;
+  if (hx < 0x00100000) {  // subnormal: scale up by 2^54
+    x *= 1.80143985094819840000e+16;
+    k -= 54;
+    __builtin_memcpy(&bits, &x, 8);
+    hx = (int32_t)(bits >> 32);
+  }
+  k += (hx >> 20) - 1023;
+  hx &= 0x000fffff;
+  const int32_t i = (hx + 0x95f64) & 0x100000;
+  bits = ((uint64_t)(uint32_t)(hx | (i ^ 0x3ff00000)) << 32) | (bits & 0xffffffffULL);  // x or x/2 normalised
+  __builtin_memcpy(&x, &bits, 8);
+  k += i >> 20;
+  const double f = x - 1.0;
+  const double dk = (double)k;
+  if ((0x000fffff & (2 + hx)) < 3) {  // |f| < 2^-20
+    if (f == 0.0) return k == 0 ? 0.0 : dk * ln2_hi + dk * ln2_lo;
+    const double R = f * f * (0.5 - 0.33333333333333333 * f);
+    return k == 0 ? f - R : dk * ln2_hi - ((R - dk * ln2_lo) - f);
+  }
+  const double s = f / (2.0 + f);
+  const double z = s * s;
+  const double w = z * z;
+  const double t1 = w * (Lg2 + w * (Lg4 + w * Lg6));
+  const double t2 = z * (Lg1 + w * (Lg3 + w * (Lg5 + w * Lg7)));
+  const double R = t2 + t1;
+  if (((hx - 0x6147a) | (0x6b851 - hx)) > 0) {
+    const double hfsq = 0.5 * f * f;
+    return k == 0 ? f - (hfsq - s * (hfsq + R)) : dk * ln2_hi - ((hfsq - (s * (hfsq + R) + dk * ln2_lo)) - f);
+  }
+  return k == 0 ? f - s * (f - R) : dk * ln2_hi - ((s * (f - R) - dk * ln2_lo) - f);
+}
+// thin-plate spline of a squared distance, r^2 log(sqrt(r^2)) in the reference's order of operations (regressors.py:232);
+// exactly 0 at r^2 = 0, where the reference's nan_to_num turns 0 * (-inf) into 0.  r2 >= 0.
+__host__ __device__ __forceinline__ double tps_value(double r2) {
+#pragma clang fp contract(off)
+  return r2 > 0.0 ? r2 * log_pos(sqrt(r2)) : 0.0;
+}
 
 // ---- lock-step groups (nk_group.hip) ----------------------------------------------------------------------------
 nk_group* group_new(int device, int size);

@@ -316,7 +316,8 @@ __device__ __forceinline__ void tn_body(const TnParams& P) {
           out[row * TBM + col] = acc[i][j][reg];
         }
   } else {
-    // kernel-matrix epilogue (EPI = 1 RBF, 2 Matern-5/2, 3 linear; compile-time so that one formula is inlined):
+    // kernel-matrix epilogue (EPI = 1 RBF, 2 Matern-5/2, 3 linear, 4 thin-plate spline; compile-time so that one formula is
+    // inlined):
     // squared distance from the Gram form, then the kernel function
     const bool interior = (tm + 1) * TBM <= pr.M && (tn + 1) * TBM <= pr.N;
     const double exp_ca = exp_nonpos_ca();
@@ -344,6 +345,10 @@ __device__ __forceinline__ void tn_body(const TnParams& P) {
             const double D = fmax(sa + sb[j] - 2.0 * dot, 0.0);
             if (EPI == 1) {
               v = exp_nonpos(-0.5 * D, exp_ca);
+            } else if (EPI == 4) {
+              // r^2 from the Gram form carries a cancellation error of about eps (|a|^2 + |b|^2) (clamped at 0 above), so a
+              // coincident pair gives |v| <~ eps (|a|^2 + |b|^2) |log r^2| / 2 instead of the exact 0 of the direct kernels
+              v = tps_value(D);
             } else {
               const double t = sqrt(D) * 2.23606797749978969641;
               v = (1.0 + t + t * t / 3.0) * exp_nonpos(-t, exp_ca);
@@ -376,7 +381,7 @@ __global__ void __launch_bounds__(256, 2) gram_fused_f64_kernel_batched(const nk
   static nk::TwinReg tn_twin_reg_##E(reinterpret_cast<const void*>(static_cast<void (*)(TnParams)>(gemm_tn_f64_kernel<E>)), \
                                      reinterpret_cast<const void*>(gemm_tn_f64_kernel_batched<E>),                        \
                                      sizeof(nk::ArgPack<TnParams>), "gemm_tn_f64_kernel<" #E ">");
-NK_TN_TWIN(0) NK_TN_TWIN(1) NK_TN_TWIN(2) NK_TN_TWIN(3)
+NK_TN_TWIN(0) NK_TN_TWIN(1) NK_TN_TWIN(2) NK_TN_TWIN(3) NK_TN_TWIN(4)
 static nk::TwinReg gram_fused_twin_reg(reinterpret_cast<const void*>(static_cast<void (*)(TnParams)>(gram_fused_f64_kernel)),
                                        reinterpret_cast<const void*>(gram_fused_f64_kernel_batched),
                                        sizeof(nk::ArgPack<TnParams>), "gram_fused_f64_kernel");
@@ -605,6 +610,8 @@ int launch_gemm_tn_multi(nk_ctx* ctx, const TnProblem* probs, int nprob, int64_t
                                hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
     NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_f64_kernel<3>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
+    NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_f64_kernel<4>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
     NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_f64_kernel_batched<0>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
     NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_f64_kernel_batched<1>),
@@ -612,6 +619,8 @@ int launch_gemm_tn_multi(nk_ctx* ctx, const TnProblem* probs, int nprob, int64_t
     NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_f64_kernel_batched<2>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
     NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_f64_kernel_batched<3>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
+    NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_f64_kernel_batched<4>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
     NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gram_fused_f64_kernel_batched),
                                hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
@@ -761,6 +770,8 @@ int launch_kmat_gram(nk_ctx* ctx, int ktype, const double* At, int64_t ldat, con
                                hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
     NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_f64_kernel<3>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
+    NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_f64_kernel<4>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
     NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_f64_kernel_batched<0>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
     NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_f64_kernel_batched<1>),
@@ -768,6 +779,8 @@ int launch_kmat_gram(nk_ctx* ctx, int ktype, const double* At, int64_t ldat, con
     NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_f64_kernel_batched<2>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
     NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_f64_kernel_batched<3>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
+    NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_f64_kernel_batched<4>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
     NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gram_fused_f64_kernel_batched),
                                hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
@@ -778,6 +791,8 @@ int launch_kmat_gram(nk_ctx* ctx, int ktype, const double* At, int64_t ldat, con
     hipLaunchKernelGGL(gemm_tn_f64_kernel<1>, dim3(grid), dim3(256), TN_LDS_BYTES, ctx->stream, P);
   else if (ktype == NK_KERNEL_MATERN52)
     hipLaunchKernelGGL(gemm_tn_f64_kernel<2>, dim3(grid), dim3(256), TN_LDS_BYTES, ctx->stream, P);
+  else if (ktype == NK_KERNEL_TPS)
+    hipLaunchKernelGGL(gemm_tn_f64_kernel<4>, dim3(grid), dim3(256), TN_LDS_BYTES, ctx->stream, P);
   else
     hipLaunchKernelGGL(gemm_tn_f64_kernel<3>, dim3(grid), dim3(256), TN_LDS_BYTES, ctx->stream, P);
   NK_HIP(hipGetLastError());

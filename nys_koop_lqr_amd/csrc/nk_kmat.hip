@@ -26,6 +26,8 @@ __device__ __forceinline__ double kmat_epilogue(double acc, double sigma0sq) {
   } else if (KTYPE == NK_KERNEL_MATERN52) {
     const double t = sqrt(acc) * 2.23606797749978969641;  // sqrt(5) * r
     return (1.0 + t + t * t / 3.0) * exp_nonpos(-t);
+  } else if (KTYPE == NK_KERNEL_TPS) {
+    return tps_value(acc);  // direct differences: exactly 0 for coincident points
   } else {
     return acc + sigma0sq;
   }
@@ -134,7 +136,7 @@ __global__ void __launch_bounds__(256, 2) kmat_kernel_batched(const nk::ArgPack<
   static nk::TwinReg kmat_twin_reg_##K(                                                                              \
       reinterpret_cast<const void*>(static_cast<void (*)(const double*, int64_t, int, const double*, int64_t, int, int, const double*, double, double*, int64_t, int, int, int)>(kmat_kernel<K>)),                                  \
       reinterpret_cast<const void*>(kmat_kernel_batched<K>), sizeof(nk::ArgPack<const double*, int64_t, int, const double*, int64_t, int, int, const double*, double, double*, int64_t, int, int, int>), "kmat_kernel<" #K ">");
-NK_KMAT_TWIN(0) NK_KMAT_TWIN(1) NK_KMAT_TWIN(2)
+NK_KMAT_TWIN(0) NK_KMAT_TWIN(1) NK_KMAT_TWIN(2) NK_KMAT_TWIN(3)
 
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -212,7 +214,7 @@ __global__ void __launch_bounds__(256) kmat_flat_kernel_batched(
       sizeof(nk::ArgPack<const double*, int64_t, int64_t, const double*, int64_t, int, int, const double*, double, double*, \
                          int64_t, int64_t, int>),                                                                                  \
       "kmat_flat_kernel<" #K ">");
-NK_KFLAT_TWIN(0) NK_KFLAT_TWIN(1) NK_KFLAT_TWIN(2)
+NK_KFLAT_TWIN(0) NK_KFLAT_TWIN(1) NK_KFLAT_TWIN(2) NK_KFLAT_TWIN(3)
 
 // ---------------------------------------------------------------------------------------------------------------
 // A handful of entries (the lift or prediction of ONE state, regressors.py:171-178 inside a control loop; K(Z, Z) at
@@ -301,7 +303,7 @@ __global__ void __launch_bounds__(256) kmat_small_kernel_batched(
       sizeof(nk::ArgPack<const double*, int64_t, int, const double*, int64_t, int, int, const double*, double, double*,      \
                          int64_t>),                                                                                          \
       "kmat_small_kernel<" #K ">");
-NK_KSMALL_TWIN(0) NK_KSMALL_TWIN(1) NK_KSMALL_TWIN(2)
+NK_KSMALL_TWIN(0) NK_KSMALL_TWIN(1) NK_KSMALL_TWIN(2) NK_KSMALL_TWIN(3)
 
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
@@ -315,7 +317,7 @@ int launch_kmat(nk_ctx* ctx, int ktype, const double* A, int64_t lda, int64_t nA
   const int vecO = aligned16(out) && ldo % 2 == 0;
   const double s2 = sigma0 * sigma0;
   if (d <= KFLAT_DMAX && ldo % 2 == 0 && nB % 2 == 0 && aligned16(out) && (size_t)(nB * d + d) * 8 <= 60 * 1024 &&
-      nA * nB >= 4096 && ktype >= NK_KERNEL_RBF && ktype <= NK_KERNEL_LINEAR) {
+      nA * nB >= 4096 && ktype >= NK_KERNEL_RBF && ktype <= NK_KERNEL_TPS) {
     // write-bound regime: flat streaming kernel
     const int64_t pairs = nA * nB / 2;
     int64_t blocks = (pairs + 255) / 256;
@@ -332,19 +334,25 @@ int launch_kmat(nk_ctx* ctx, int ktype, const double* A, int64_t lda, int64_t nA
     else if (ktype == NK_KERNEL_MATERN52)
       hipLaunchKernelGGL((kmat_flat_kernel<NK_KERNEL_MATERN52>), g, dim3(256), lds, ctx->stream, A, lda, nA, B, ldb, (int)nB,
                          d, winv, s2, out, ldo, step_i, step_j);
+    else if (ktype == NK_KERNEL_TPS)
+      hipLaunchKernelGGL((kmat_flat_kernel<NK_KERNEL_TPS>), g, dim3(256), lds, ctx->stream, A, lda, nA, B, ldb, (int)nB, d,
+                         winv, s2, out, ldo, step_i, step_j);
     else
       hipLaunchKernelGGL((kmat_flat_kernel<NK_KERNEL_LINEAR>), g, dim3(256), lds, ctx->stream, A, lda, nA, B, ldb, (int)nB, d,
                          winv, s2, out, ldo, step_i, step_j);
     NK_HIP(hipGetLastError());
     return NK_OK;
   }
-  if (nA * nB <= KSMALL_MAX_ENTRIES && ktype >= NK_KERNEL_RBF && ktype <= NK_KERNEL_LINEAR) {
+  if (nA * nB <= KSMALL_MAX_ENTRIES && ktype >= NK_KERNEL_RBF && ktype <= NK_KERNEL_TPS) {
     const dim3 g((unsigned)((nA * nB + 3) / 4));  // one wave per entry
     if (ktype == NK_KERNEL_RBF)
       hipLaunchKernelGGL((kmat_small_kernel<NK_KERNEL_RBF>), g, dim3(256), 0, ctx->stream, A, lda, (int)nA, B, ldb, (int)nB, d,
                          winv, s2, out, ldo);
     else if (ktype == NK_KERNEL_MATERN52)
       hipLaunchKernelGGL((kmat_small_kernel<NK_KERNEL_MATERN52>), g, dim3(256), 0, ctx->stream, A, lda, (int)nA, B, ldb,
+                         (int)nB, d, winv, s2, out, ldo);
+    else if (ktype == NK_KERNEL_TPS)
+      hipLaunchKernelGGL((kmat_small_kernel<NK_KERNEL_TPS>), g, dim3(256), 0, ctx->stream, A, lda, (int)nA, B, ldb,
                          (int)nB, d, winv, s2, out, ldo);
     else
       hipLaunchKernelGGL((kmat_small_kernel<NK_KERNEL_LINEAR>), g, dim3(256), 0, ctx->stream, A, lda, (int)nA, B, ldb,
@@ -363,6 +371,10 @@ int launch_kmat(nk_ctx* ctx, int ktype, const double* A, int64_t lda, int64_t nA
       break;
     case NK_KERNEL_LINEAR:
       hipLaunchKernelGGL((kmat_kernel<NK_KERNEL_LINEAR>), grid, dim3(256), 0, ctx->stream, A, lda, (int)nA, B, ldb,
+                         (int)nB, d, winv, s2, out, ldo, vecA, vecB, vecO);
+      break;
+    case NK_KERNEL_TPS:
+      hipLaunchKernelGGL((kmat_kernel<NK_KERNEL_TPS>), grid, dim3(256), 0, ctx->stream, A, lda, (int)nA, B, ldb,
                          (int)nB, d, winv, s2, out, ldo, vecA, vecB, vecO);
       break;
     default:

@@ -391,6 +391,10 @@ class KoopmanNystromRegressor(KoopmanRegressor):
         self._raise(ctx, rc)
         self._adopt(ctx, h, stats, m, d, p, (t_host0, t_host1))
 
+    def _landmark_shape(self):
+        """(d, m) of the landmarks the device model lifts with."""
+        return np.asarray(self.nystrom_centers_output).shape
+
     def _ops_key(self):
         # landmarks are a plain attribute (the reference's callers assign them): identity + shape; operators: the
         # version counter bumped by every assignment (ids alone could be reused by a new array after a free)
@@ -404,7 +408,7 @@ class KoopmanNystromRegressor(KoopmanRegressor):
         h = self._ensure_model()
         Xq = _lib.Mat(X.t() if _is_device_tensor(X) else np.asarray(X, dtype=np.float64).T)
         nq = Xq.shape[0]
-        m = np.asarray(self.nystrom_centers_output).shape[1]
+        m = self._landmark_shape()[1]
         out = np.empty((nq, m))
         ctx.wait_for(X)
         _lib.check(ctx.lib.nk_lift(ctx.handle, h, Xq.ptr, Xq.ld, nq, out.ctypes.data, m))
@@ -415,7 +419,7 @@ class KoopmanNystromRegressor(KoopmanRegressor):
         ctx = _lib.get_context()
         h = self._ensure_model()
         Xm = _lib.Mat(X_aug)
-        d = np.asarray(self.nystrom_centers_output).shape[0]
+        d = self._landmark_shape()[0]
         if Xm.shape[1] != d + int(self.n_inputs):
             raise ValueError(f"X_aug has {Xm.shape[1]} columns, expected {d + int(self.n_inputs)}")
         out = np.empty((Xm.shape[0], d))
@@ -429,7 +433,7 @@ class KoopmanNystromRegressor(KoopmanRegressor):
         ctx = _lib.get_context()
         h = self._ensure_model()
         Xm, Ym = _lib.Mat(X_aug), _lib.Mat(Y)
-        d = np.asarray(self.nystrom_centers_output).shape[0]
+        d = self._landmark_shape()[0]
         if Xm.shape[1] != d + int(self.n_inputs):
             raise ValueError(f"X_aug has {Xm.shape[1]} columns, expected {d + int(self.n_inputs)}")
         if Ym.shape != (Xm.shape[0], d):
@@ -449,7 +453,7 @@ class KoopmanNystromRegressor(KoopmanRegressor):
         x0: (batch, d) with controls (batch, T, p) -> (batch, T, d) [and (batch, T, m)]."""
         ctx = _lib.get_context()
         h = self._ensure_model()
-        d, m = np.asarray(self.nystrom_centers_output).shape
+        d, m = self._landmark_shape()
         p = int(self.n_inputs)
         controls = np.asarray(controls, dtype=np.float64)
         single = controls.ndim == 2
@@ -476,7 +480,7 @@ class KoopmanNystromRegressor(KoopmanRegressor):
         the gain (several initial states / references in one call)."""
         ctx = _lib.get_context()
         h = self._ensure_model()
-        d, m = np.asarray(self.nystrom_centers_output).shape
+        d, m = self._landmark_shape()
         p = int(self.n_inputs)
         K = np.ascontiguousarray(K, dtype=np.float64)
         if K.shape != (p, m):
@@ -679,3 +683,146 @@ class KoopmanKernelRegressor(KoopmanRegressor):
             return out.cpu().numpy()
         Kout_test = self.kernel.kernel(np.ascontiguousarray(self.training_outputs.T), Xq)
         return self._gemm(ctx, self.Kout_sqrt_inv, Kout_test)
+
+
+class KoopmanSplineRegressor(KoopmanRegressor):
+    """regressors.py:181-233 (the Korda-Mezic thin-plate-spline baseline), MI355X-native: the two n x m spline blocks, the
+    three Gram products, the regularised pseudo-inverse and the operator products run on the device (nk_spline_fit).
+
+    Same constructor, attributes (`centers` d x m, A, B, C, weights) and random draws as the reference: the centres come
+    from NumPy's global legacy RNG the first time `lift` needs them (in `fit`: from the training states) and are reused
+    by every later fit.  Additive, as for the Nystrom class: `fit` accepts `row_ranges` and device tensors; `rollout`,
+    `score_neg_rmse`, `closed_loop` and `solve_lqr` run the callers' loops on the device.  The device-model plumbing
+    (asynchronous operator fetch, pickling through host copies, lift / predict / rollout / closed loop) is the Nystrom
+    class's, shared method by method below."""
+
+    A = _fetched("A")
+    B = _fetched("B")
+    C = _fetched("C")
+    weights = _fetched("weights")
+
+    def __init__(self, n_inputs, state_bounds_params=None, m=None, gamma=None):
+        self._fetching = False
+        super().__init__(n_inputs, gamma, m)
+        self.state_bounds_params = state_bounds_params
+        self.centers = None
+        self._model = None
+        self._model_key = None
+        self._stats = None
+        self._ops_version = 0
+
+    # shared with the Nystrom class: operator fetch, pickling, device-model lifetime, the callers' loops
+    invalidate_device_model = KoopmanNystromRegressor.invalidate_device_model
+    _wait_fetch = KoopmanNystromRegressor._wait_fetch
+    __getstate__ = KoopmanNystromRegressor.__getstate__
+    __setstate__ = KoopmanNystromRegressor.__setstate__
+    __del__ = KoopmanNystromRegressor.__del__
+    _drop_model = KoopmanNystromRegressor._drop_model
+    _ranges = staticmethod(KoopmanNystromRegressor._ranges)
+    _raise = staticmethod(KoopmanNystromRegressor._raise)
+    _adopt = KoopmanNystromRegressor._adopt
+    predict = KoopmanNystromRegressor.predict
+    score_neg_rmse = KoopmanNystromRegressor.score_neg_rmse
+    rollout = KoopmanNystromRegressor.rollout
+    closed_loop = KoopmanNystromRegressor.closed_loop
+    solve_lqr = KoopmanNystromRegressor.solve_lqr
+    fit_stats_ = KoopmanNystromRegressor.fit_stats_
+
+    def compute_centers(self, X):
+        """regressors.py:187-197, draw for draw: X is d x n (the array `lift` sees first)."""
+        if self.state_bounds_params is not None:
+            length = np.sqrt(np.random.uniform(0, self.state_bounds_params[0], size=(1, self.m)))
+            angle = np.pi * np.random.uniform(0, self.state_bounds_params[1], size=(1, self.m))
+            return np.vstack((length * np.cos(angle), length * np.sin(angle)))
+        centers_indices = np.random.choice(np.arange(0, X.shape[1]), size=self.m, replace=False)
+        if _is_device_tensor(X):
+            return np.ascontiguousarray(X[:, centers_indices.tolist()].cpu().numpy())
+        return np.asarray(X)[:, centers_indices]
+
+    def _landmark_shape(self):
+        return np.asarray(self.centers).shape
+
+    def _ops_key(self):
+        z = self.centers
+        return (id(z), None if z is None else np.shape(z), self.__dict__.get("_ops_version", 0))
+
+    def _ensure_model(self):
+        """Device model for lift / predict / rollout, rebuilt from host copies after un-pickling or when a caller replaced
+        the centres / operators (an unfitted regressor gets a model that can only lift)."""
+        if self.centers is None:
+            raise RuntimeError("regressor has no centres: call fit (or lift) first")
+        key = self._ops_key()
+        if self._model is not None and self._model_key == key:
+            return self._model
+        self._wait_fetch()
+        self._drop_model()
+        ctx = _lib.get_context()
+        Z = np.ascontiguousarray(np.asarray(self.centers, dtype=np.float64).T)  # m x d
+        m, d = Z.shape
+        p = int(self.n_inputs)
+        keep = []
+
+        def ptr(a, shape):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.shape != shape:
+                raise ValueError(f"operator has shape {a.shape}, expected {shape}")
+            keep.append(a)
+            return a.ctypes.data
+
+        pa, pb, pc, pw = ptr(self.A, (m, m)), ptr(self.B, (m, p)), ptr(self.C, (d, m)), ptr(self.weights, (d, m + p))
+        h = C.c_void_p()
+        rc = ctx.lib.nk_spline_model_create(ctx.handle, Z.ctypes.data, d, m, d, p, pa, pb, pc, pw, C.byref(h))
+        self._raise(ctx, rc)
+        self._model, self._model_key = h, key
+        return h
+
+    def fit(self, X, Y, row_ranges=None, fetch=True):
+        """regressors.py:199-221.  X: n x (d+p) rows [state | input], Y: n x d (NumPy arrays or float64 device tensors).
+        row_ranges: [begin, end) row pairs of the training rows (default: all).  Returns None, like the reference."""
+        ctx = _lib.get_context()
+        Xm, Ym = _lib.Mat(X), _lib.Mat(Y)
+        n, d = Ym.shape
+        p = int(self.n_inputs)
+        if Xm.shape != (n, d + p):
+            raise ValueError(f"X has shape {Xm.shape}, expected {(n, d + p)}")
+        rr, n_rr, keep_rr = self._ranges(row_ranges)
+        if self.centers is None:  # regressors.py:207 -> lift(X[:n_states, :]) of the training states
+            rows = None if keep_rr is None else np.concatenate(
+                [np.arange(b, e) for b, e in keep_rr.reshape(-1, 2) if e > b])
+            if _is_device_tensor(X):
+                states = X[:, :d] if rows is None else X[rows.tolist(), :d]
+                self.centers = self.compute_centers(states.t())
+            else:
+                states = np.asarray(X)[:, :d] if rows is None else np.asarray(X)[rows, :d]
+                self.centers = self.compute_centers(states.T)
+        Z = np.ascontiguousarray(np.asarray(self.centers, dtype=np.float64).T)
+        if Z.shape[1] != d:
+            raise ValueError(f"centres have dimension {Z.shape[1]}, data has {d}")
+        m = Z.shape[0]
+        stats = _lib.FitStats()
+        h = C.c_void_p()
+        t_host0 = time.perf_counter()
+        self._drop_model()
+        t_host1 = time.perf_counter()
+        ctx.wait_for(X, Y)
+        rc = ctx.lib.nk_spline_fit(ctx.handle, Xm.ptr, Xm.ld, Ym.ptr, Ym.ld, n, d, p, rr, n_rr, Z.ctypes.data, d, m,
+                                   float(self.gamma), C.byref(h), C.byref(stats))
+        self._raise(ctx, rc)
+        self._adopt(ctx, h, stats, m, d, p, (t_host0, t_host1), fetch)
+
+    def lift(self, X):
+        """regressors.py:223-233: X is d x n_q (not augmented); returns phi, m x n_q.  Draws the centres from X when
+        there are none yet, as the reference does."""
+        if self.centers is None:
+            self.centers = self.compute_centers(X)
+        ctx = _lib.get_context()
+        h = self._ensure_model()
+        Xq = _lib.Mat(X.t() if _is_device_tensor(X) else np.asarray(X, dtype=np.float64).T)
+        nq = Xq.shape[0]
+        m = self._landmark_shape()[1]
+        out = np.empty((nq, m))
+        ctx.wait_for(X)
+        _lib.check(ctx.lib.nk_lift(ctx.handle, h, Xq.ptr, Xq.ld, nq, out.ctypes.data, m))
+        return out.T
