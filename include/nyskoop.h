@@ -343,6 +343,26 @@ int nk_solve_spd(nk_ctx* ctx, const double* P, int64_t ldp, int32_t m, const dou
  * algorithmic flop of one launch.  For rocprofv3 --pmc runs that should not pay for a whole fit. */
 int nk_bench_gram(nk_ctx* ctx, int64_t n, int32_t m, int32_t p, int32_t d, int32_t reps, double* ms_avg, double* flop);
 
+/* The augmented blocked Cholesky that every fit runs, on matrices of the caller's own (tests/test_gpu_chol_accuracy.py).
+ * nsys = 1 or 2 systems [P_q (m_q x m_q, symmetric, leading dimension ldp_q >= m_q); R_q (extra_q x m_q, dense)], all host
+ * arrays, are staged as the fits lay them out (the extra rows below the matrix, leading dimension ldp_q), factorised and
+ * solved in one paired call (tile-dataflow launch where every m_q >= 256 and NYSKOOP_CHOL_FLOW is not 0, the launch-per-step
+ * chain otherwise), and come back as
+ *   L_q (m_q x m_q, dense): the lower factor, P = L L^T.  Only the lower triangle is the factor: tiles of 64 x 64 that lie
+ *       strictly above the block diagonal are never written and return the input, and the strict upper triangle INSIDE a
+ *       diagonal tile holds leftovers of the in-tile elimination (no meaning, and not the same on the two code paths);
+ *   X_q (extra_q x m_q, dense) = R_q P_q^-1;
+ *   failed[q]: 0 = factorised; k > 0 = the first non-positive pivot was met at row k - 1, i.e. LAPACK potrf's `info`
+ *       (L and X are then meaningless from that row on); -1 = all pivots positive but an isolated cluster of them at the
+ *       rounding level (an exact null space; L and X are still returned); NK_CHOL_FLOW_GIVEUP = the dataflow launch
+ *       stopped waiting (set for every system of the call; the fits re-run the chain then, this function does not);
+ *   piv_ratio[q]: smallest / largest pivot (0 when failed[q] is positive or the give-up word).
+ * No recovery or fallback of any kind happens here. */
+#define NK_CHOL_FLOW_GIVEUP (-0x40000000)
+int nk_chol_aug(nk_ctx* ctx, int32_t nsys, const double* const* P, const int64_t* ldp, const int32_t* m,
+                const double* const* R, const int32_t* extra, double* const* L, double* const* X, int32_t* failed,
+                double* piv_ratio);
+
 #ifdef __cplusplus
 }
 #endif

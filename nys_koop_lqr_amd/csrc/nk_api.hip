@@ -1474,8 +1474,22 @@ static int fit_impl(nk_ctx* ctx, const nk_kernel_desc* kd, const double* X, int6
     if (vr == NK_SQRT_RETRY && splan.flow_gave_up) {
       // the dataflow factorisation of K_mm gave up waiting: the square root once more with the launch-per-step chain,
       // then everything that depends on it
+      // (in the same early-queued form, i.e. with the same eigenvalue bound and scaling schedule: the synchronous form would
+      // converge to the same square root along other iterates, and the recovered fit would differ from an undisturbed one
+      // in its last bits)
       ChainOnly chain(ctx);
-      NK_TRY(sqrtm_spd(ctx, Kj, m, m, mdl->S, mdl->Sinv, &it, &resid));
+      SqrtPlan again;
+      again.lambda_min_hint = splan.lambda_min_hint;
+      NK_TRY(sqrtm_prepare(ctx, Kj, m, m, &again));
+      NK_TRY(sqrtm_finish(ctx, &again, mdl->S, mdl->Sinv));
+      NK_HIP(hipStreamSynchronize(ctx->stream));
+      const int vr2 = sqrtm_verdict(ctx, &again, &it, &resid);
+      if (vr2 == NK_SQRT_RETRY) {  // the chain's verdict: not positive definite to working precision
+        count_event(CNT_SQRT_RETRY);
+        NK_TRY(sqrtm_spd_coupled(ctx, Kj, m, m, mdl->S, mdl->Sinv, &it, &resid));
+      } else {
+        NK_TRY(vr2);
+      }
       NK_TRY(sqrt_products());
       redo_products = true;
     } else if (vr == NK_SQRT_RETRY) {
@@ -2653,6 +2667,49 @@ int nk_bench_gram(nk_ctx* ctx, int64_t n, int32_t m, int32_t p, int32_t d, int32
   NK_HIP(hipStreamSynchronize(ctx->stream));
   *ms_avg = total / reps;
   if (flop) *flop = ((double)mp * (mp + 1) + 2.0 * m * mp + (double)m * (m + 1) + 2.0 * d * m) * (double)n;
+  return NK_OK;
+}
+
+int nk_chol_aug(nk_ctx* ctx, int32_t nsys, const double* const* P, const int64_t* ldp, const int32_t* m, const double* const* R,
+                const int32_t* extra, double* const* L, double* const* X, int32_t* failed, double* piv_ratio) {
+  NK_TRY(check_ctx(ctx));
+  NK_REQUIRE(nsys >= 1 && nsys <= 2 && P && ldp && m && R && extra && L && X && failed && piv_ratio, "nk_chol_aug: bad argument");
+  for (int q = 0; q < nsys; ++q)
+    NK_REQUIRE(P[q] && R[q] && L[q] && X[q] && m[q] > 0 && extra[q] > 0 && ldp[q] >= m[q] && !is_device_ptr(P[q]) &&
+                   !is_device_ptr(R[q]) && !is_device_ptr(L[q]) && !is_device_ptr(X[q]),
+               "nk_chol_aug: system %d: host arrays with m > 0, extra > 0, ld >= m", q);
+  // each system as the fits lay it out: the extra rows directly below the matrix, one leading dimension (the caller's)
+  CholSys sys[2];
+  for (int q = 0; q < nsys; ++q) {
+    const int mq = m[q], eq = extra[q];
+    const int64_t ld = ldp[q];
+    const int nblk = (mq + CHOL_NB - 1) / CHOL_NB;
+    double *W = nullptr, *Linv = nullptr, *pivlog = nullptr;
+    NK_TRY(arena_alloc_t(ctx, (size_t)(mq + eq) * ld, &W));
+    NK_TRY(arena_alloc_t(ctx, (size_t)nblk * CHOL_WS, &Linv));
+    NK_TRY(arena_alloc_t(ctx, (size_t)mq + 4, &pivlog));
+    if (ld > mq) NK_HIP(hipMemsetAsync(W, 0, (size_t)(mq + eq) * ld * sizeof(double), ctx->stream));
+    NK_HIP(hipMemcpy2DAsync(W, (size_t)ld * 8, P[q], (size_t)ld * 8, (size_t)mq * 8, (size_t)mq, hipMemcpyHostToDevice,
+                            ctx->stream));
+    NK_HIP(hipMemcpy2DAsync(W + (size_t)mq * ld, (size_t)ld * 8, R[q], (size_t)mq * 8, (size_t)mq * 8, (size_t)eq,
+                            hipMemcpyHostToDevice, ctx->stream));
+    sys[q].P = W; sys[q].ldp = ld; sys[q].m = mq; sys[q].extra = eq; sys[q].Linv = Linv; sys[q].pivlog = pivlog;
+  }
+  NK_TRY(cholesky_aug_pair_async(ctx, sys, nsys));
+  int fl[2] = {0, 0};
+  double pr[2] = {0.0, 0.0};
+  NK_TRY(cholesky_fail_flags(ctx, sys, nsys, fl, pr));  // synchronises; a CHOL_FLOW_GIVEUP word goes out as it is
+  for (int q = 0; q < nsys; ++q) {
+    const int mq = m[q], eq = extra[q];
+    const int64_t ld = ldp[q];
+    failed[q] = fl[q];
+    piv_ratio[q] = pr[q];
+    NK_HIP(hipMemcpy2DAsync(L[q], (size_t)mq * 8, sys[q].P, (size_t)ld * 8, (size_t)mq * 8, (size_t)mq, hipMemcpyDeviceToHost,
+                            ctx->stream));
+    NK_HIP(hipMemcpy2DAsync(X[q], (size_t)mq * 8, sys[q].P + (size_t)mq * ld, (size_t)ld * 8, (size_t)mq * 8, (size_t)eq,
+                            hipMemcpyDeviceToHost, ctx->stream));
+  }
+  NK_HIP(hipStreamSynchronize(ctx->stream));
   return NK_OK;
 }
 

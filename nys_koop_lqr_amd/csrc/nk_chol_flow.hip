@@ -22,6 +22,9 @@
 // wait is bounded: a workgroup that gives up sets the status word (everyone else then stops waiting) and marks the failure
 // flag of every system of the launch with CHOL_FLOW_GIVEUP; the host then re-runs the factorisation on the launch-per-step
 // chain (cholesky_aug_pair_async's callers).
+#include <cstdio>
+#include <cstdlib>
+
 #include "nk_common.h"
 #include "nk_panel_body.h"
 #include "nk_potrf_body.h"
@@ -51,6 +54,7 @@ struct FlowArgs {
   int nsys;
   int total;  // work items
   int fix;
+  int test_giveup;  // test hook (NYSKOOP_CHOL_FLOW_TEST_GIVEUP): the workgroup that draws this ticket gives up; -1: none
   int* hdr;
 };
 
@@ -257,6 +261,10 @@ __global__ void __launch_bounds__(FLOW_THREADS) chol_flow_kernel(FlowArgs a) {
     const int t = sh[1];
     __syncthreads();
     if (t >= a.total) return;
+    if (t == a.test_giveup) {  // test hook: the give-up branch itself, taken at once (nobody waits for it: the status word is up)
+      if (threadIdx.x == 0) give_up(a);
+      return;
+    }
     int q = 0, i = 0, k = 0;
     item_of(a, t, q, i, k);
     const FlowSys s = q ? a.s[1] : a.s[0];
@@ -328,6 +336,21 @@ bool chol_flow_enabled() {  // NYSKOOP_CHOL_FLOW=0 (read per call): the launch-p
   return !(e && e[0] == '0');
 }
 
+// NYSKOOP_CHOL_FLOW_TEST_GIVEUP=<ticket>[,<nsys>[,<extra>]] (read per call; tests/): the workgroup that draws work item
+// <ticket> of a dataflow launch takes the give-up branch instead of working on it, every other workgroup leaves through the
+// status word, and the caller's recovery runs.  <nsys> / <extra> (0 or absent: any) restrict the hook to launches of that many
+// systems / whose first system has that many extra rows (the K_mm launch of a fit has one system, the regularised pair
+// two).  Tickets outside the launch are ignored.  Returns -1 when the hook is not set or does not apply.
+static int flow_test_giveup(const CholSys* sys, int nsys, int total) {
+  const char* e = getenv("NYSKOOP_CHOL_FLOW_TEST_GIVEUP");
+  if (!e || !e[0]) return -1;
+  long ticket = -1, want_nsys = 0, want_extra = 0;
+  if (sscanf(e, "%ld,%ld,%ld", &ticket, &want_nsys, &want_extra) < 1) return -1;
+  if (want_nsys > 0 && want_nsys != nsys) return -1;
+  if (want_extra > 0 && want_extra != sys[0].extra) return -1;
+  return (ticket >= 0 && ticket < total) ? (int)ticket : -1;
+}
+
 // The factorisation part of cholesky_aug_pair_async as one launch (after reset_pivots; the caller queues the backward pass).
 int cholesky_flow_pair(nk_ctx* ctx, const CholSys* sys, int nsys) {
   constexpr int NB = CHOL_NB;
@@ -358,6 +381,7 @@ int cholesky_flow_pair(nk_ctx* ctx, const CholSys* sys, int nsys) {
     NK_HIP(hipMalloc(reinterpret_cast<void**>(&ctx->d_flow[slot]), words * sizeof(int)));
     ctx->flow_words[slot] = words;
   }
+  a.test_giveup = flow_test_giveup(sys, nsys, a.total);
   a.hdr = ctx->d_flow[slot];
   int* f = a.hdr + FLOW_HDR;
   for (int q = 0; q < nsys; ++q) {

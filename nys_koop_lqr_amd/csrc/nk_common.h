@@ -333,6 +333,7 @@ struct SqrtPlan {
   // sqrtm_verdict as NK_SQRT_RETRY and the caller falls back to sqrtm_spd_coupled.
   double lambda_min_hint = 0.0;
   bool early = false;
+  int info_slot = 2;          // failure-flag slot of the stream sqrtm_finish ran on (sqrtm_verdict reads the early form's word there)
   bool flow_gave_up = false;  // the early form's factorisation was a dataflow launch that gave up (sqrtm_verdict)
   // The factorisation chain of sqrtm_prepare is paused before block step `pause_step` until `pause_event` (recorded by
   // the caller BEFORE sqrtm_prepare is called) has completed -- see nk_nystrom_fit: the chain must not run beside the

@@ -1102,6 +1102,7 @@ int sqrtm_finish(nk_ctx* ctx, SqrtPlan* plan, double* S, double* Sinv) {
   const size_t mm = (size_t)m * m;
   const int ib = info_base(ctx);
   plan->deferred = false;
+  plan->info_slot = ib;
   plan->rc = NK_OK; plan->iters = 0; plan->resid = 0.0;
   // With a caller-supplied eigenvalue bound (large aligned matrices) nothing of the factorisation is needed to queue the
   // iteration: the host only waits for the three schedule scalars, copied right at the start of sqrtm_prepare.
@@ -1335,8 +1336,9 @@ int sqrtm_verdict(nk_ctx* ctx, SqrtPlan* plan, int* iters, double* resid) {
   if (plan->deferred) {
     const double flag = ctx->h_scalars[8];
     plan->deferred = false;
-    if (plan->early && (ctx->h_info[2] != 0 || flag == 0.0 || !std::isfinite(ctx->h_scalars[10]))) {
-      plan->flow_gave_up = ctx->h_info[2] == CHOL_FLOW_GIVEUP;
+    const int word = ctx->h_info[plan->info_slot];
+    if (plan->early && (word != 0 || flag == 0.0 || !std::isfinite(ctx->h_scalars[10]))) {
+      plan->flow_gave_up = word == CHOL_FLOW_GIVEUP;
       if (plan->flow_gave_up) count_event(CNT_CHOL_FLOW_GIVEUP);
       plan->iters = plan->kmax;
       plan->resid = ctx->h_scalars[10];
