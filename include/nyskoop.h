@@ -314,6 +314,27 @@ int nk_closed_loop(nk_ctx* ctx, const nk_model* model, const double* K, const do
  * out_u: batch x steps x p (multi-seed / multi-reference sweeps of benchmark_lqr_cloth.py:212-270). */
 int nk_closed_loop_batch(nk_ctx* ctx, const nk_model* model, const double* K, const double* phi0,
                          const double* phi_ref, int32_t steps, int32_t batch, double* out_x, double* out_u);
+/* ---- closed loop around the TRUE plant: replaces the loop of lqr_control in benchmark_lqr_hjb.py:73-97 and
+ *   benchmark_lqr_classic.py:67-89 for the reference's three plants (dynamical_systems.py), which the library restates
+ *   as closed-form maps: one Runge-Kutta step of length Ts in the reference's order of operations, with its k4 evaluated
+ *   at x + k1 Ts, in plain IEEE arithmetic (the host and the device build of a plant give the same bits).
+ *   NK_PLANT_DUFFING: d = 2, f = (x2, -0.5 x2 - x1 (4 x1^2 - 1) + 0.5 u); NK_PLANT_DOUBLE_INTEGRATOR: d = 2, f = (x2, u);
+ *   NK_PLANT_HJB: d = 1, f = -x^3 + u.  Every plant has one input.
+ *   nk_plant_step: x_next = plant(x, u) on the HOST (x, x_next: d doubles, u: one double; no context, no GPU needed).
+ *   nk_plant_loop: `batch` independent loops u_t = K (phi(x_ref) - phi(x_t)), x_{t+1} = plant(x_t, u_t) for t < steps in
+ *   ONE launch, one workgroup per loop, phi = the model's lift.  K: 1 x m gain; x0, x_ref: batch x d (dense);
+ *   out_x: batch x (steps + 1) x d visited states, row 0 = x0; out_u: batch x steps x 1 controls.  Host or device
+ *   pointers.  The gain is folded into the lift once per call (w = K_mm^{-1/2} K^T, u_t = sum_j w_j (k(z_j, x_ref) -
+ *   k(z_j, x_t))), so u_t agrees with K times the difference of two nk_lift results to rounding, not bit for bit; a
+ *   loop's results do not depend on `batch`.  Needs a Nystrom model with an RBF, Matern-5/2 or linear kernel or a
+ *   spline model, p = 1, d = the plant's state dimension and m <= 4096 (NK_ERR_BAD_ARG otherwise); fitted operators
+ *   are not needed.  Not available to lock-step group members. */
+#define NK_PLANT_DUFFING 0
+#define NK_PLANT_DOUBLE_INTEGRATOR 1
+#define NK_PLANT_HJB 2
+int nk_plant_step(int plant, double Ts, const double* x, const double* u, double* x_next);
+int nk_plant_loop(nk_ctx* ctx, const nk_model* model, int plant, double Ts, const double* K, const double* x0,
+                  const double* x_ref, int32_t steps, int32_t batch, double* out_x, double* out_u);
 /* ---- rollout of explicit operators without a model (any estimator that exposes A, B, C: the exact-kernel comparator of
  *   benchmark_lqr_hjb.py:334-381, un-pickled gains): z0: batch x m lifted initial states; A: m x m, B: m x p, C: d x m
  *   (row-major, host or device); U, out_x, out_z as in nk_rollout. --------------------------------------------------- */

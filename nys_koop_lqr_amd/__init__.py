@@ -6,9 +6,11 @@ compute call without the built library and a gfx950 device raises.
 from .kernels import KernelWrapper, LinearKernelWrapper, ThreeDimensionalKernel  # noqa: F401
 from .regressors import (KoopmanKernelRegressor, KoopmanNystromRegressor, KoopmanRegressor,  # noqa: F401
                          KoopmanSplineRegressor, linear_rollout)
+from .dynamical_systems import DoubleIntegrator, DuffingOscillator, HJB  # noqa: F401
 from ._lib import NyskoopError, get_context, library_path, shutdown  # noqa: F401
 
 __all__ = [
     "KoopmanRegressor", "KoopmanNystromRegressor", "KoopmanKernelRegressor", "KoopmanSplineRegressor",
     "ThreeDimensionalKernel", "KernelWrapper", "LinearKernelWrapper", "NyskoopError", "get_context", "library_path", "linear_rollout", "shutdown",
+    "DuffingOscillator", "DoubleIntegrator", "HJB",
 ]

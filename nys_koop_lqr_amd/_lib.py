@@ -10,6 +10,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 
 NK_KERNEL_RBF, NK_KERNEL_MATERN52, NK_KERNEL_LINEAR, NK_KERNEL_TPS = 0, 1, 2, 3
+NK_PLANT_DUFFING, NK_PLANT_DOUBLE_INTEGRATOR, NK_PLANT_HJB = 0, 1, 2
 NK_OK = 0
 _ERR_NAMES = {-1: "NK_ERR_BAD_ARG", -2: "NK_ERR_HIP", -3: "NK_ERR_NOT_SPD", -4: "NK_ERR_OOM",
               -5: "NK_ERR_NO_CONVERGENCE", -6: "NK_ERR_NO_DEVICE"}
@@ -100,6 +101,8 @@ SIGNATURES = {
     "nk_rollout": (C.c_int, [_P, _P, _P, _I64, _P, _I32, _I32, _P, _P]),
     "nk_closed_loop": (C.c_int, [_P, _P, _P, _P, _P, _I32, _P, _P]),
     "nk_closed_loop_batch": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _P, _P]),
+    "nk_plant_step": (C.c_int, [C.c_int, _D, _P, _P, _P]),
+    "nk_plant_loop": (C.c_int, [_P, _P, C.c_int, _D, _P, _P, _P, _I32, _I32, _P, _P]),
     "nk_linear_rollout": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P]),
     "nk_gemm_f32": (C.c_int, [_P, _I64, _I64, _I64, _P, _I64, _P, _I64, _P, _I64]),
     "nk_gemm": (C.c_int, [_P, C.c_int, C.c_int, _I64, _I64, _I64, _D, _P, _I64, _P, _I64, _D, _P, _I64]),

@@ -1,6 +1,7 @@
 // extern "C" entry points of libnyskoop.so (include/nyskoop.h): context, staging of host/device buffers, and the
 // fit / lift / predict / score / rollout pipelines assembled from the device launchers.
 #include "nk_common.h"
+#include "nk_plant.h"
 
 #include <cmath>
 #include <cstdarg>
@@ -2502,6 +2503,58 @@ int nk_closed_loop_batch(nk_ctx* ctx, const nk_model* mdl, const double* K, cons
 int nk_closed_loop(nk_ctx* ctx, const nk_model* mdl, const double* K, const double* phi0, const double* phi_ref,
                    int32_t steps, double* out_x, double* out_u) {
   return nk_closed_loop_batch(ctx, mdl, K, phi0, phi_ref, steps, 1, out_x, out_u);
+}
+
+int nk_plant_step(int plant, double Ts, const double* x, const double* u, double* x_next) {
+  NK_REQUIRE(plant_dim(plant) > 0, "nk_plant_step: unknown plant %d", plant);
+  NK_REQUIRE(x && u && x_next, "nk_plant_step: null argument");
+  double xn[PLANT_MAX_D];
+  if (plant == NK_PLANT_DUFFING) plant_step<NK_PLANT_DUFFING>(Ts, x, u[0], xn);
+  else if (plant == NK_PLANT_DOUBLE_INTEGRATOR) plant_step<NK_PLANT_DOUBLE_INTEGRATOR>(Ts, x, u[0], xn);
+  else plant_step<NK_PLANT_HJB>(Ts, x, u[0], xn);
+  for (int k = 0; k < plant_dim(plant); ++k) x_next[k] = xn[k];
+  return NK_OK;
+}
+
+int nk_plant_loop(nk_ctx* ctx, const nk_model* mdl, int plant, double Ts, const double* K, const double* x0,
+                  const double* x_ref, int32_t steps, int32_t batch, double* out_x, double* out_u) {
+  NK_TRY(check_ctx(ctx));
+  NK_REQUIRE(!ctx_recording(ctx), "nk_plant_loop: not available to the members of a lock-step group");
+  NK_REQUIRE(mdl && K && x0 && x_ref && out_x && out_u, "nk_plant_loop: null argument");
+  NK_REQUIRE(plant_dim(plant) > 0, "nk_plant_loop: unknown plant %d", plant);
+  NK_REQUIRE(mdl->p == 1, "nk_plant_loop: the plants have one input, the model has %d", mdl->p);
+  NK_REQUIRE(mdl->d == plant_dim(plant), "nk_plant_loop: the %s has %d states, the model has %d", plant_name(plant),
+             plant_dim(plant), mdl->d);
+  NK_REQUIRE(steps >= 1 && batch >= 1, "nk_plant_loop: steps = %d and batch = %d must be positive", steps, batch);
+  NK_REQUIRE(mdl->m <= plant_loop_max_m(), "nk_plant_loop: m = %d landmarks, at most %d fit one workgroup", mdl->m,
+             plant_loop_max_m());
+  const bool spline = mdl->kind == NK_MODEL_SPLINE;
+  NK_REQUIRE(spline ? mdl->ktype == NK_KERNEL_TPS
+                    : (mdl->ktype == NK_KERNEL_RBF || mdl->ktype == NK_KERNEL_MATERN52 || mdl->ktype == NK_KERNEL_LINEAR),
+             "nk_plant_loop: kernel type %d is not supported for this model", mdl->ktype);
+  NK_REQUIRE(std::isfinite(Ts), "nk_plant_loop: Ts is not finite");
+  const int m = mdl->m, d = mdl->d;
+  MatIn k, xi, xr;
+  MatOut ox, ou;
+  NK_TRY(stage_in(ctx, K, m, 1, m, &k));
+  NK_TRY(stage_in(ctx, x0, d, batch, d, &xi));
+  NK_TRY(stage_in(ctx, x_ref, d, batch, d, &xr));
+  NK_TRY(stage_out(ctx, out_x, d, (int64_t)batch * (steps + 1), d, &ox));
+  NK_TRY(stage_out(ctx, out_u, 1, (int64_t)batch * steps, 1, &ou));
+  // u = K phi = K (k S^-1)^T = (S^-1 K^T) . k: the product nk_lift forms, contracted with the gain first
+  const double* w = k.ptr;
+  if (!spline) {
+    double* wf = nullptr;
+    NK_TRY(arena_alloc_t(ctx, (size_t)m + 2, &wf));
+    NK_TRY(launch_gemm(ctx, false, true, m, 1, m, 1.0, mdl->Sinv, m, k.ptr, k.ld, 0.0, wf, 1));
+    w = wf;
+  }
+  NK_TRY(launch_plant_loop(ctx, mdl, plant, Ts, w, xi.ptr, xi.ld, xr.ptr, xr.ld, steps, batch, ox.dev, ox.ld, ou.dev,
+                           ou.ld));
+  NK_TRY(finish_out(ctx, ox));
+  NK_TRY(finish_out(ctx, ou));
+  NK_HIP(hipStreamSynchronize(ctx->stream));
+  return NK_OK;
 }
 
 int nk_gemm(nk_ctx* ctx, int transA, int transB, int64_t M, int64_t N, int64_t K, double alpha, const double* A,

@@ -458,6 +458,14 @@ int lifted_chain_mw_reset(nk_ctx* ctx);                                       //
 int lifted_chain_mw_fetch_status(nk_ctx* ctx);                                // queues their copy to the host
 bool lifted_chain_mw_timed_out(nk_ctx* ctx, int* row, int* step, int* traj);  // after the stream has been synchronised
 
+// LQR closed loop around one of the library's plants (nk_plant.h) in ONE launch, one workgroup per trajectory
+// (nk_plant_loop.hip): w = the gain folded into the lift (m entries, p = 1), u_t = sum_j w_j (k(z_j, x_ref) - k(z_j, x_t)),
+// x_{t+1} = plant(x_t, u_t); out_x rows b * (steps + 1) + t (row 0 = x_0), out_u rows b * steps + t
+int plant_loop_max_m();
+int launch_plant_loop(nk_ctx* ctx, const nk_model* mdl, int plant, double Ts, const double* w, const double* x0,
+                      int64_t x0_stride, const double* xref, int64_t xref_stride, int steps, int batch, double* out_x,
+                      int64_t ldx, double* out_u, int64_t ldu);
+
 }  // namespace nk
 
 namespace nk {
@@ -572,6 +580,17 @@ __device__ __forceinline__ double wave_sum64_dpp(double c) {
   a = c; b = c;
   swap32_f64(a, b);
   return a + b;
+}
+
+// kernel value from the accumulated squared distance (RBF, Matern-5/2) or dot product (linear) of the pre-scaled
+// coordinates: the epilogue of the kernel-matrix kernels, for the single-launch loops (nk_rollout.hip, nk_plant_loop.hip)
+__device__ __forceinline__ double chain_kfun(int ktype, double acc, double sigma0sq) {
+  if (ktype == NK_KERNEL_RBF) return exp_nonpos(-0.5 * acc);
+  if (ktype == NK_KERNEL_MATERN52) {
+    const double t = sqrt(acc) * 2.23606797749978969641;
+    return (1.0 + t + t * t / 3.0) * exp_nonpos(-t);
+  }
+  return acc + sigma0sq;
 }
 
 }  // namespace nk

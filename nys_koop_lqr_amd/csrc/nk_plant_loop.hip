@@ -1,0 +1,184 @@
+// LQR closed loop around the TRUE plant (lqr_control of benchmark_lqr_hjb.py:73-97 and benchmark_lqr_classic.py:67-89) as
+// ONE launch: every step lifts the measured state, forms u = K (phi(x_ref) - phi(x)) and advances the plant by one
+// Runge-Kutta step (nk_plant.h).  The gain is folded into the lift once per call,
+//     w = S^-1 K^T  (m entries, p = 1; spline models: w = K^T),     u_t = sum_j w_j (k(z_j, x_ref) - k(z_j, x_t)),
+// so a step costs m kernel values over d <= 2 coordinates and one dot product of length m instead of an m x m product.
+// The difference of the two kernel values is taken landmark by landmark BEFORE the product with w_j: the cancellation of
+// u near the reference state then happens on numbers of order one, not on two dot products of the size of |w|.
+//
+// One workgroup per trajectory, the whole loop inside it, nothing from the host per step.  A step is a latency chain
+// (kernel values -> reduction -> plant -> next kernel values), so the workgroup is the SMALLEST that holds the landmarks
+// at LPT per lane: one wave up to m = 256 (LPT = 1 up to 64 landmarks, 4 beyond), ceil(m / 256) waves up to m = 4096.
+// Each lane keeps its landmarks (scaled by 1 / lengthscale), their kernel values at x_ref and its entries of w in
+// registers for all steps.  Per step: LPT kernel values with the arithmetic of the kernel-matrix kernels (nk_kmat.hip:
+// rounded products with 1 / lengthscale, difference, FMAs over the coordinates in index order, the same epilogue), LPT
+// FMAs, a DPP reduction over the wave; with several waves one LDS word per wave, ONE workgroup barrier, and a DPP
+// reduction of the (zero padded) 16 words that every wave performs alike.  Every summation order is fixed by m alone, so
+// a trajectory has the same bits alone or in any batch.  All lanes advance the plant (same operands, same bits); thread
+// 0 stores x_{t+1} and u_t with ordinary vector stores that nothing in the loop waits for.
+#include "nk_common.h"
+#include "nk_plant.h"
+
+namespace nk {
+
+struct PlantLoopParams {
+  const double* Z;      // m x d landmarks
+  const double* winv;   // d
+  const double* w;      // m folded gain
+  int m;
+  double sigma0sq, Ts;
+  const double* x0; int64_t x0_stride;      // batch x d
+  const double* xref; int64_t xref_stride;  // batch x d (stride 0: shared)
+  double* out_x; int64_t ldx;               // rows b * (steps + 1) + t, d columns
+  double* out_u; int64_t ldu;               // rows b * steps + t, one column
+  int steps;
+};
+
+constexpr int PLANT_LOOP_LPT = 4;
+constexpr int PLANT_LOOP_MAX_WAVES = 16;
+constexpr int PLANT_LOOP_MAX_M = 64 * PLANT_LOOP_LPT * PLANT_LOOP_MAX_WAVES;
+
+template <int KTYPE, int D>
+__device__ __forceinline__ double plant_kval(const double* xs, const double* zs, double sigma0sq) {
+#pragma clang fp contract(off)
+  double acc = 0.0;
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    if (KTYPE == NK_KERNEL_LINEAR) {
+      acc = fma(xs[k], zs[k], acc);
+    } else {
+      const double df = xs[k] - zs[k];
+      acc = fma(df, df, acc);
+    }
+  }
+  if (KTYPE == NK_KERNEL_TPS) return tps_value(acc);
+  return chain_kfun(KTYPE, acc, sigma0sq);
+}
+
+// sum of one value over the 16 lanes of a DPP row, in every lane of the row
+__device__ __forceinline__ double row_sum16_dpp(double c) {
+  c += dpp_f64<0xB1>(c);   // quad_perm [1,0,3,2]
+  c += dpp_f64<0x4E>(c);   // quad_perm [2,3,0,1]
+  c += dpp_f64<0x141>(c);  // row_half_mirror
+  c += dpp_f64<0x140>(c);  // row_mirror
+  return c;
+}
+
+// sum_j w_j (kref_j - k(z_j, x)) over the landmarks of the workgroup, the same bits in every lane
+template <int KTYPE, int D, int LPT>
+__device__ __forceinline__ double plant_feedback(const double* x, const double* wi, const double (&zs)[LPT][D],
+                                                 const double (&wj)[LPT], const double (&kref)[LPT], double sigma0sq,
+                                                 double* red, int lane, int wave, bool multi) {
+  double xs[D];
+  {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int k = 0; k < D; ++k) xs[k] = x[k] * wi[k];
+  }
+  double part = 0.0;
+#pragma unroll
+  for (int l = 0; l < LPT; ++l) part = fma(wj[l], kref[l] - plant_kval<KTYPE, D>(xs, zs[l], sigma0sq), part);
+  double s = wave_sum64_dpp(part);
+  if (multi) {  // uniform over the workgroup
+    if (lane == 0) red[wave] = s;
+    // LDS-only barrier (the global stores of earlier steps need not have retired: nothing reads them back)
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    s = row_sum16_dpp(red[lane & 15]);
+  }
+  return s;
+}
+
+template <int PLANT, int KTYPE, int LPT>
+__global__ void __launch_bounds__(LPT == 1 ? 64 : 64 * PLANT_LOOP_MAX_WAVES) plant_loop_kernel(PlantLoopParams P) {
+  constexpr int D = PlantDim<PLANT>::value;
+  __shared__ double red[2][PLANT_LOOP_MAX_WAVES];  // one partial sum per wave, two buffers (parity of the step)
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nthreads = blockDim.x;
+  const bool multi = nthreads > 64;
+  const int b = blockIdx.x;
+  if (tid < 2 * PLANT_LOOP_MAX_WAVES) (&red[0][0])[tid] = 0.0;  // words of waves that do not exist stay zero
+  double wi[D], zs[LPT][D], wj[LPT], kref[LPT], x[D], xr[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    wi[k] = P.winv[k];
+    x[k] = P.x0[(int64_t)b * P.x0_stride + k];
+    xr[k] = P.xref[(int64_t)b * P.xref_stride + k];
+  }
+  {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int l = 0; l < LPT; ++l) {
+      const int j = tid + l * nthreads;
+      const bool have = j < P.m;  // a slot without a landmark: weight 0, landmark 0 (finite kernel value, exact 0 product)
+      wj[l] = have ? P.w[j] : 0.0;
+#pragma unroll
+      for (int k = 0; k < D; ++k) zs[l][k] = have ? P.Z[(int64_t)j * D + k] * wi[k] : 0.0;
+    }
+    double xrs[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k) xrs[k] = xr[k] * wi[k];
+#pragma unroll
+    for (int l = 0; l < LPT; ++l) kref[l] = plant_kval<KTYPE, D>(xrs, zs[l], P.sigma0sq);
+  }
+  double* ox = P.out_x + (int64_t)b * (P.steps + 1) * P.ldx;
+  double* ou = P.out_u + (int64_t)b * P.steps * P.ldu;
+  if (tid == 0) {
+#pragma unroll
+    for (int k = 0; k < D; ++k) ox[k] = x[k];
+  }
+  __syncthreads();  // red is zeroed
+  for (int t = 0; t < P.steps; ++t) {
+    // buffer t & 1: a wave still reading it in step t is at most one barrier behind the wave that writes it again in t + 2
+    const double u = plant_feedback<KTYPE, D, LPT>(x, wi, zs, wj, kref, P.sigma0sq, red[t & 1], lane, wave, multi);
+    double xn[D];
+    plant_step<PLANT>(P.Ts, x, u, xn);
+#pragma unroll
+    for (int k = 0; k < D; ++k) x[k] = xn[k];
+    if (tid == 0) {
+      ou[(int64_t)t * P.ldu] = u;
+#pragma unroll
+      for (int k = 0; k < D; ++k) ox[(int64_t)(t + 1) * P.ldx + k] = x[k];
+    }
+  }
+}
+
+bool plant_loop_ok(int m) { return m >= 1 && m <= PLANT_LOOP_MAX_M; }
+
+template <int PLANT, int KTYPE>
+static void plant_loop_launch(nk_ctx* ctx, const PlantLoopParams& P, int batch) {
+  if (P.m <= 64) {
+    hipLaunchKernelGGL((plant_loop_kernel<PLANT, KTYPE, 1>), dim3(batch), dim3(64), 0, ctx->stream, P);
+  } else {
+    const int waves = (P.m + 64 * PLANT_LOOP_LPT - 1) / (64 * PLANT_LOOP_LPT);
+    hipLaunchKernelGGL((plant_loop_kernel<PLANT, KTYPE, PLANT_LOOP_LPT>), dim3(batch), dim3(64 * waves), 0, ctx->stream, P);
+  }
+}
+template <int PLANT>
+static int plant_loop_ktype(nk_ctx* ctx, int ktype, const PlantLoopParams& P, int batch) {
+  switch (ktype) {
+    case NK_KERNEL_RBF: plant_loop_launch<PLANT, NK_KERNEL_RBF>(ctx, P, batch); break;
+    case NK_KERNEL_MATERN52: plant_loop_launch<PLANT, NK_KERNEL_MATERN52>(ctx, P, batch); break;
+    case NK_KERNEL_LINEAR: plant_loop_launch<PLANT, NK_KERNEL_LINEAR>(ctx, P, batch); break;
+    case NK_KERNEL_TPS: plant_loop_launch<PLANT, NK_KERNEL_TPS>(ctx, P, batch); break;
+    default: set_error("plant_loop: unknown kernel type %d", ktype); return NK_ERR_BAD_ARG;
+  }
+  NK_HIP(hipGetLastError());
+  return NK_OK;
+}
+
+// all pointers device memory; w: the folded gain (m entries); out_x: batch * (steps + 1) rows of d, out_u: batch * steps
+// rows of one
+int launch_plant_loop(nk_ctx* ctx, const nk_model* mdl, int plant, double Ts, const double* w, const double* x0,
+                      int64_t x0_stride, const double* xref, int64_t xref_stride, int steps, int batch, double* out_x,
+                      int64_t ldx, double* out_u, int64_t ldu) {
+  NK_REQUIRE(plant_dim(plant) == mdl->d && plant_loop_ok(mdl->m) && steps >= 1 && batch >= 1, "plant_loop: bad sizes");
+  PlantLoopParams P;
+  P.Z = mdl->Z; P.winv = mdl->winv; P.w = w; P.m = mdl->m; P.sigma0sq = mdl->sigma0 * mdl->sigma0; P.Ts = Ts;
+  P.x0 = x0; P.x0_stride = x0_stride; P.xref = xref; P.xref_stride = xref_stride;
+  P.out_x = out_x; P.ldx = ldx; P.out_u = out_u; P.ldu = ldu; P.steps = steps;
+  if (plant == NK_PLANT_DUFFING) return plant_loop_ktype<NK_PLANT_DUFFING>(ctx, mdl->ktype, P, batch);
+  if (plant == NK_PLANT_DOUBLE_INTEGRATOR) return plant_loop_ktype<NK_PLANT_DOUBLE_INTEGRATOR>(ctx, mdl->ktype, P, batch);
+  return plant_loop_ktype<NK_PLANT_HJB>(ctx, mdl->ktype, P, batch);
+}
+int plant_loop_max_m() { return PLANT_LOOP_MAX_M; }
+
+}  // namespace nk

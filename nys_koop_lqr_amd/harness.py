@@ -234,6 +234,16 @@ def lqr_control_plant(num_steps, reference, initial_state, regressor, K, plant_s
     return np.array(xs), np.hstack(us)
 
 
+def lqr_control_plant_device(num_steps, reference, initial_state, regressor, K, plant):
+    """lqr_control_plant with the whole loop in ONE device launch (regressor.closed_loop_plant -> nk_plant_loop): `plant` is one
+    of dynamical_systems.DuffingOscillator / DoubleIntegrator / HJB instead of a callable.  Returns (x_s (num_steps,),
+    u_s (p, num_steps)) like lqr_control_plant: x_s is the first coordinate of the states the controls were computed at."""
+    x0 = np.asarray(initial_state, dtype=np.float64).reshape(-1)
+    ref = np.asarray(reference, dtype=np.float64).reshape(-1)
+    states, us = regressor.closed_loop_plant(K, x0, ref, num_steps, plant)
+    return np.array(states[0, :num_steps]), us
+
+
 def open_loop_control(plant_step, initial_state, controls):
     """benchmark_lqr_classic.py:91-97: replay a control sequence (p x T) on the true plant; returns the visited states
     (d x (T + 1)), the initial state first."""

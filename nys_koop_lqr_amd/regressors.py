@@ -502,6 +502,44 @@ class KoopmanNystromRegressor(KoopmanRegressor):
             return ox[0].T, ou[0].T
         return ox, ou
 
+    def closed_loop_plant(self, K, x0, x_ref, num_steps, plant):
+        """LQR closed loop around the TRUE plant (lqr_control of benchmark_lqr_hjb.py:73-97 / benchmark_lqr_classic.py:67-89):
+        u_t = K (phi(x_ref) - phi(x_t)), x_{t+1} = plant(x_t, u_t), all `num_steps` steps in one device launch
+        (nk_plant_loop).  `plant`: one of dynamical_systems.DuffingOscillator / DoubleIntegrator / HJB (its `plant_id` and
+        `Ts` are used), whose state dimension is the model's; one input.
+
+        x0: (d,) / (d, 1)  -> (states (d, num_steps + 1) with x0 first, u (1, num_steps)); a (1, 1) array with d = 1 is this case;
+        x0: (batch, d)     -> (states (batch, num_steps + 1, d), u (batch, num_steps, 1)): independent loops that share the
+        gain; x_ref: one state for all of them or (batch, d).  A loop's results do not depend on the batch it runs in."""
+        ctx = _lib.get_context()
+        h = self._ensure_model()
+        d, m = self._landmark_shape()
+        p = int(self.n_inputs)
+        plant_id, Ts = getattr(plant, "plant_id", None), getattr(plant, "Ts", None)
+        if plant_id is None or Ts is None:
+            raise ValueError("plant must be one of the package's dynamical systems (plant_id) with its step length Ts set")
+        K = np.ascontiguousarray(K, dtype=np.float64)
+        if K.shape != (p, m):
+            raise ValueError(f"gain has shape {K.shape}, expected {(p, m)}")
+        num_steps = int(num_steps)
+        x0 = np.asarray(x0, dtype=np.float64)
+        x_ref = np.asarray(x_ref, dtype=np.float64)
+        single = x0.ndim < 2 or x0.shape == (d, 1)  # a vector or a column, as the reference's drivers pass states
+        if x0.size % d:
+            raise ValueError(f"initial states have shape {x0.shape}, the model has {d} states")
+        xb = np.ascontiguousarray(x0.reshape(1, d) if single else x0.reshape(-1, d))
+        batch = xb.shape[0]
+        if x_ref.size not in (d, batch * d):
+            raise ValueError(f"reference has shape {x_ref.shape}, expected one state of dimension {d} or {(batch, d)}")
+        xr = np.ascontiguousarray(np.broadcast_to(x_ref.reshape(-1, d), (batch, d)))
+        ox, ou = np.empty((batch, max(num_steps, 0) + 1, d)), np.empty((batch, max(num_steps, 0), 1))
+        rc = ctx.lib.nk_plant_loop(ctx.handle, h, int(plant_id), float(Ts), K.ctypes.data, xb.ctypes.data, xr.ctypes.data,
+                                   num_steps, batch, ox.ctypes.data, ou.ctypes.data)
+        self._raise(ctx, rc)
+        if single:
+            return ox[0].T, ou[0].T
+        return ox, ou
+
     def solve_lqr(self, Q=None, R=None, c=0.0075):
         """Host DARE, standing in for control.dlqr(A, B, Q, R) (benchmark_lqr_cloth.py:238-240,262): by default
         Q = c * C^T C symmetrised and R = I.  Returns the gain K (p x m)."""
@@ -725,6 +763,7 @@ class KoopmanSplineRegressor(KoopmanRegressor):
     score_neg_rmse = KoopmanNystromRegressor.score_neg_rmse
     rollout = KoopmanNystromRegressor.rollout
     closed_loop = KoopmanNystromRegressor.closed_loop
+    closed_loop_plant = KoopmanNystromRegressor.closed_loop_plant
     solve_lqr = KoopmanNystromRegressor.solve_lqr
     fit_stats_ = KoopmanNystromRegressor.fit_stats_
 
