@@ -144,7 +144,7 @@ int nk_wait_stream(nk_ctx* ctx, void* producer_stream);
 /* ---- lock-step groups: batched execution of many SMALL fits (the (candidate, fold) units of the hyper-parameter sweep,
  * benchmark_lqr_cloth.py:39-66; multi-seed sweeps :168-203).  One small fit is a chain of a few hundred launch-bound
  * kernels that leaves the chip idle; a group runs `size` of them in lock step.  nk_group_create returns `size` member
- * contexts; each is driven by its own host thread through the ordinary entry points (nk_nystrom_fit,
+ * contexts; each is driven by its own host thread through the ordinary entry points (nk_nystrom_fit, nk_spline_fit,
  * nk_score_neg_rmse, ...).  Inside the library a member's launches are recorded, and whenever members wait for the
  * device the recorded sequences are merged -- equal launches become one launch with blockIdx.z = member -- and issued
  * on one shared stream.  Results are bit-identical to an ordinary context (same kernels, same arguments).
@@ -173,6 +173,26 @@ typedef struct nk_cv_unit {
 } nk_cv_unit;
 int nk_cv_grid(nk_ctx* const* members, int32_t n_members, const double* X, int64_t ldx, const double* Y, int64_t ldy,
                int64_t n, int32_t d, int32_t p, const nk_cv_unit* units, int32_t n_units, double* scores, int32_t* status);
+/* The same sweep for the thin-plate-spline estimator (nk_spline_fit; benchmark_lqr_classic.py:55-60: GridSearchCV over
+ * KoopmanSplineRegressor).  Unit u fits on all rows but [test_begin, test_end) with its own centres and scores the held-out
+ * rows.  The centres are VALUES (m x d rows, dense, host memory), not row indices: the reference draws them from the state
+ * bounds (regressors.py:189-193) or from columns of the training states (:195-197), and the first kind are rows of nothing.
+ * Checked before any unit runs: pointers, sizes, folds; a unit's gamma is checked by its own fit (status[u] =
+ * NK_ERR_BAD_ARG, scores[u] = NaN).  Two phases as in nk_cv_grid: the units whose system takes the pseudo-inverse (pivot
+ * ratio inside the window described at nk_spline_fit) stop there in the first phase and are run together in the second,
+ * where their Jacobi sweeps can merge (by construction, as in nk_cv_grid; the gain of the second phase has not been
+ * measured for spline units).  The scores do not depend on the schedule, and are the bits of nk_spline_fit +
+ * nk_score_neg_rmse on an ordinary context. */
+typedef struct nk_spline_cv_unit {
+  double gamma;
+  int32_t m;
+  int32_t reserved;
+  int64_t test_begin, test_end;
+  const double* centers; /* HOST pointer, m x d rows, dense */
+} nk_spline_cv_unit;
+int nk_spline_cv_grid(nk_ctx* const* members, int32_t n_members, const double* X, int64_t ldx, const double* Y,
+                      int64_t ldy, int64_t n, int32_t d, int32_t p, const nk_spline_cv_unit* units, int32_t n_units,
+                      double* scores, int32_t* status);
 int nk_group_enter(nk_ctx* member);
 int nk_group_leave(nk_ctx* member);
 int nk_group_stats(nk_ctx* member, uint64_t* out4);
@@ -258,7 +278,8 @@ int nk_model_destroy(nk_model* model);
  *   Cholesky instead.  stats->rank_inner = singular values kept (m+p on the Cholesky path), rank_inner_rec = 0,
  *   pivot_ratio_inner = smallest / largest Cholesky pivot (0 when it was not used).  fp64 only: the compute dtype of
  *   nk_set_compute_dtype is ignored (the fit runs in fp64).  strict_spd (nk_set_strict_spd): 1 = a non-positive pivot
- *   is NK_ERR_NOT_SPD, 2 = always the pseudo-inverse.  Not available to lock-step group members.  The model is a spline
+ *   is NK_ERR_NOT_SPD, 2 = always the pseudo-inverse.  Members of a lock-step group may call it (same bits as on an
+ *   ordinary context; stats may be NULL, the ms_* fields are 0 there; nk_spline_cv_grid is the sweep).  The model is a spline
  *   model: its lift is the raw block TPS(x, centres) (no K_mm^{-1/2}); nk_lift, nk_predict, nk_score_neg_rmse,
  *   nk_rollout, nk_closed_loop(_batch), nk_model_get ('S' / 'I': NK_ERR_BAD_ARG) and nk_model_get_ops accept it. */
 int nk_spline_fit(nk_ctx* ctx, const double* X, int64_t ldx, const double* Y, int64_t ldy, int64_t n, int32_t d, int32_t p,

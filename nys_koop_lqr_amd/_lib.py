@@ -33,6 +33,11 @@ class CvUnit(C.Structure):
                 ("landmark_rows", C.POINTER(C.c_int64))]
 
 
+class SplineCvUnit(C.Structure):
+    _fields_ = [("gamma", C.c_double), ("m", C.c_int32), ("reserved", C.c_int32), ("test_begin", C.c_int64),
+                ("test_end", C.c_int64), ("centers", C.POINTER(C.c_double))]
+
+
 class FitStats(C.Structure):
     _fields_ = [("ms_total", C.c_double), ("ms_upload", C.c_double), ("ms_kmat", C.c_double),
                 ("ms_gram", C.c_double), ("ms_sqrt", C.c_double), ("ms_solve", C.c_double),
@@ -73,6 +78,8 @@ SIGNATURES = {
     "nk_runtime_counters": (C.c_int, [C.POINTER(C.c_uint64), C.c_int32]),
     "nk_cv_grid": (C.c_int, [C.POINTER(_P), _I32, _P, _I64, _P, _I64, _I64, _I32, _I32, C.POINTER(CvUnit), _I32,
                              C.POINTER(_D), C.POINTER(_I32)]),
+    "nk_spline_cv_grid": (C.c_int, [C.POINTER(_P), _I32, _P, _I64, _P, _I64, _I64, _I32, _I32, C.POINTER(SplineCvUnit),
+                                    _I32, C.POINTER(_D), C.POINTER(_I32)]),
     "nk_host_alloc": (_P, [C.c_uint64]),
     "nk_host_free": (None, [_P]),
     "nk_kernel_matrix": (C.c_int, [_P, C.POINTER(KernelDesc), _P, _I64, _I64, _P, _I64, _I64, _P, _I64]),
@@ -469,6 +476,35 @@ class LockstepPool:
         lib = self.members[0].lib
         rc = lib.nk_cv_grid(handles, self.size, Xm.ptr, Xm.ld, Ym.ptr, Ym.ld, n, d, p, arr, len(units),
                             scores.ctypes.data_as(C.POINTER(_D)), status.ctypes.data_as(C.POINTER(_I32)))
+        if rc == -1:
+            raise ValueError(lib.nk_last_error().decode())
+        check(rc)
+        return scores, status
+
+    def spline_cv_grid(self, X, Y, n_inputs, units):
+        """nk_spline_cv_grid: `units` = list of (gamma, m, (test_begin, test_end), centers (m x d)) of the thin-plate-spline
+        estimator, run in lock step like cv_grid.  Returns (scores, status)."""
+        Xm, Ym = Mat(X), Mat(Y)
+        n, d = Ym.shape
+        p = int(n_inputs)
+        if Xm.shape != (n, d + p):
+            raise ValueError(f"X has shape {Xm.shape}, expected {(n, d + p)}")
+        arr = (SplineCvUnit * len(units))()
+        keep = []
+        for i, (gamma, m, (lo, hi), centers) in enumerate(units):
+            Z = np.ascontiguousarray(centers, dtype=np.float64)
+            if Z.shape != (int(m), d):
+                raise ValueError(f"centers must be an m x d = {(int(m), d)} array, got {Z.shape}")
+            keep.append(Z)
+            arr[i].gamma, arr[i].m = float(gamma), int(m)
+            arr[i].test_begin, arr[i].test_end = int(lo), int(hi)
+            arr[i].centers = Z.ctypes.data_as(C.POINTER(C.c_double))
+        handles = (_P * self.size)(*[m_.handle for m_ in self.members])
+        scores = np.full(len(units), np.nan)
+        status = np.zeros(len(units), dtype=np.int32)
+        lib = self.members[0].lib
+        rc = lib.nk_spline_cv_grid(handles, self.size, Xm.ptr, Xm.ld, Ym.ptr, Ym.ld, n, d, p, arr, len(units),
+                                   scores.ctypes.data_as(C.POINTER(_D)), status.ctypes.data_as(C.POINTER(_I32)))
         if rc == -1:
             raise ValueError(lib.nk_last_error().decode())
         check(rc)

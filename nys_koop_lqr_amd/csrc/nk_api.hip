@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <algorithm>
 #include <condition_variable>
+#include <functional>
 #include <mutex>
 #include <set>
 #include <thread>
@@ -603,18 +604,21 @@ int nk_group_stats(nk_ctx* ctx, uint64_t* out4) {
   return NK_OK;
 }
 
-int nk_cv_grid(nk_ctx* const* members, int32_t n_members, const double* X, int64_t ldx, const double* Y, int64_t ldy,
-               int64_t n, int32_t d, int32_t p, const nk_cv_unit* units, int32_t n_units, double* scores, int32_t* status) {
-  NK_REQUIRE(members && n_members >= 1 && X && Y && units && scores, "nk_cv_grid: null argument");
-  NK_REQUIRE(n > 0 && d > 0 && p >= 0 && n_units >= 0 && ldx >= d + p && ldy >= d, "nk_cv_grid: bad sizes");
-  for (int k = 0; k < n_members; ++k) NK_REQUIRE(members[k] != nullptr, "nk_cv_grid: null member context");
-  for (int u = 0; u < n_units; ++u) {
-    const nk_cv_unit& cu = units[u];
-    NK_REQUIRE(cu.kernel && cu.landmark_rows && cu.m > 0, "nk_cv_grid: unit %d: null kernel / landmarks", u);
-    NK_REQUIRE(0 <= cu.test_begin && cu.test_begin < cu.test_end && cu.test_end <= n, "nk_cv_grid: unit %d: bad test fold", u);
-    for (int j = 0; j < cu.m; ++j)
-      NK_REQUIRE(cu.landmark_rows[j] >= 0 && cu.landmark_rows[j] < n, "nk_cv_grid: unit %d: landmark row out of range", u);
-  }
+// ---- the one-call sweeps (nk_cv_grid, nk_spline_cv_grid): data set staged once, one host thread per member, rounds of
+// n_members units behind a barrier, two phases.  The estimator enters through two callbacks only.
+struct CvData {  // what a unit sees: the data set in HBM, a host copy of Y (only if asked for), the sizes
+  const double *Xd = nullptr, *Yd = nullptr, *Yh = nullptr;
+  int64_t ldxd = 0, ldyd = 0, ldyh = 0, n = 0;
+  int32_t d = 0, p = 0;
+};
+// fit_score(member, unit, data, scratch, &score): fit + score of one unit on a member that is inside its unit of work;
+// set_phase(member, k, phase) for member k of `members`: 1 = stop at a system that needs the rank-truncating branch (NK_ERR_NOT_SPD: the unit is run again
+// in phase 2), 2 = take the branch, 0 = back to what the caller had set.
+using CvFitScore = std::function<int(nk_ctx*, int, const CvData&, std::vector<double>&, double*)>;
+using CvSetPhase = std::function<void(nk_ctx*, int, int)>;
+static int cv_grid_run(const char* what, nk_ctx* const* members, int32_t n_members, const double* X, int64_t ldx,
+                       const double* Y, int64_t ldy, int64_t n, int32_t d, int32_t p, int32_t n_units, bool want_host_y,
+                       const CvFitScore& fit_score, const CvSetPhase& set_phase, double* scores, int32_t* status) {
   if (n_units == 0) return NK_OK;
   nk_ctx* lead = members[0];
   NK_HIP(hipSetDevice(lead->device));
@@ -640,11 +644,17 @@ int nk_cv_grid(nk_ctx* const* members, int32_t n_members, const double* X, int64
   const double* Yh = Y;
   int64_t ldyh = ldy;
   if (is_device_ptr(Y)) {
-    Yhost.resize((size_t)n * d);
-    NK_HIP(hipMemcpy2D(Yhost.data(), (size_t)d * 8, Y, (size_t)ldy * 8, (size_t)d * 8, (size_t)n, hipMemcpyDeviceToHost));
-    Yh = Yhost.data();
-    ldyh = d;
+    Yh = nullptr;
+    if (want_host_y) {
+      Yhost.resize((size_t)n * d);
+      NK_HIP(hipMemcpy2D(Yhost.data(), (size_t)d * 8, Y, (size_t)ldy * 8, (size_t)d * 8, (size_t)n, hipMemcpyDeviceToHost));
+      Yh = Yhost.data();
+      ldyh = d;
+    }
   }
+  CvData data;
+  data.Xd = Xd; data.Yd = Yd; data.Yh = Yh; data.ldxd = ldxd; data.ldyd = ldyd; data.ldyh = ldyh; data.n = n; data.d = d;
+  data.p = p;
   const int B = n_members;
   // one host thread per member; rounds of B units; everybody is inside its unit before anybody starts (round barrier)
   struct Round {
@@ -665,8 +675,8 @@ int nk_cv_grid(nk_ctx* const* members, int32_t n_members, const double* X, int64
   // unit in strict mode (the factorisation reports the condition and the unit stops there), and the units that reported
   // it are run again TOGETHER in a second phase with the fallback enabled: their Jacobi sweeps merge into shared launches.
   // Same kernels on the same data in both orders: the scores do not depend on the schedule.
-  std::vector<int> saved_strict((size_t)B);
-  for (int k = 0; k < B; ++k) saved_strict[(size_t)k] = members[k]->strict_spd;
+  bool all_lenient = true;
+  for (int k = 0; k < B; ++k) all_lenient = all_lenient && members[k]->strict_spd == 0;
   std::mutex deferred_mu;
   std::vector<int> deferred;
   auto run_units = [&](const std::vector<int>& list, bool defer_rank_deficient) {
@@ -683,18 +693,8 @@ int nk_cv_grid(nk_ctx* const* members, int32_t n_members, const double* X, int64
         round.wait(B);
         if (mine) {
           const int u = list[(size_t)slot];
-          const nk_cv_unit& cu = units[u];
-          Z.resize((size_t)cu.m * d);
-          for (int j = 0; j < cu.m; ++j) memcpy(&Z[(size_t)j * d], Yh + cu.landmark_rows[j] * ldyh, (size_t)d * 8);
-          const int64_t rr[4] = {0, cu.test_begin, cu.test_end, n};
-          nk_model* mdl = nullptr;
-          int rc = nk_nystrom_fit(ctx, cu.kernel, Xd, ldxd, Yd, ldyd, n, d, p, rr, 2, nullptr, 0, Z.data(), d, cu.m, cu.gamma,
-                                  cu.jitter, &mdl, nullptr);
           double sc = std::nan("");
-          if (rc == NK_OK)
-            rc = nk_score_neg_rmse(ctx, mdl, Xd + cu.test_begin * ldxd, ldxd, Yd + cu.test_begin * ldyd, ldyd,
-                                   cu.test_end - cu.test_begin, &sc);
-          if (mdl) nk_model_destroy(mdl);
+          int rc = fit_score(ctx, u, data, Z, &sc);
           tl_ctx = ctx;
           const int rc_leave = group_leave(ctx);  // flushes what the unit recorded after its last synchronisation
           if (rc == NK_OK) rc = rc_leave;
@@ -717,29 +717,95 @@ int nk_cv_grid(nk_ctx* const* members, int32_t n_members, const double* X, int64
   };
   std::vector<int> all((size_t)n_units);
   for (int u = 0; u < n_units; ++u) all[(size_t)u] = u;
-  bool all_lenient = true;
-  for (int k = 0; k < B; ++k) all_lenient = all_lenient && saved_strict[(size_t)k] == 0;
   if (!all_lenient) {  // the caller wants the error (strict contexts): one phase, nothing to defer
     run_units(all, false);
     return NK_OK;
   }
   const bool cv_trace = getenv("NYSKOOP_CV_TRACE") != nullptr;
   const auto t_start = std::chrono::steady_clock::now();
-  for (int k = 0; k < B; ++k) members[k]->strict_spd = 1;
+  for (int k = 0; k < B; ++k) set_phase(members[k], k, 1);
   run_units(all, true);
-  for (int k = 0; k < B; ++k) members[k]->strict_spd = saved_strict[(size_t)k];
+  for (int k = 0; k < B; ++k) set_phase(members[k], k, 0);
   const auto t_mid = std::chrono::steady_clock::now();
   if (!deferred.empty()) {
     std::sort(deferred.begin(), deferred.end());
-    for (int k = 0; k < B; ++k) members[k]->strict_spd = 0;
+    for (int k = 0; k < B; ++k) set_phase(members[k], k, 2);
     run_units(deferred, false);
-    for (int k = 0; k < B; ++k) members[k]->strict_spd = saved_strict[(size_t)k];
+    for (int k = 0; k < B; ++k) set_phase(members[k], k, 0);
   }
   if (cv_trace)
-    fprintf(stderr, "[nyskoop] cv_grid: %d units in %.3f s, %zu rank-deficient units again in %.3f s (%d members)\n", n_units,
+    fprintf(stderr, "[nyskoop] %s: %d units in %.3f s, %zu rank-deficient units again in %.3f s (%d members)\n", what, n_units,
             std::chrono::duration<double>(t_mid - t_start).count(), deferred.size(),
             std::chrono::duration<double>(std::chrono::steady_clock::now() - t_mid).count(), B);
   return NK_OK;
+}
+
+int nk_cv_grid(nk_ctx* const* members, int32_t n_members, const double* X, int64_t ldx, const double* Y, int64_t ldy,
+               int64_t n, int32_t d, int32_t p, const nk_cv_unit* units, int32_t n_units, double* scores, int32_t* status) {
+  NK_REQUIRE(members && n_members >= 1 && X && Y && units && scores, "nk_cv_grid: null argument");
+  NK_REQUIRE(n > 0 && d > 0 && p >= 0 && n_units >= 0 && ldx >= d + p && ldy >= d, "nk_cv_grid: bad sizes");
+  for (int k = 0; k < n_members; ++k) NK_REQUIRE(members[k] != nullptr, "nk_cv_grid: null member context");
+  for (int u = 0; u < n_units; ++u) {
+    const nk_cv_unit& cu = units[u];
+    NK_REQUIRE(cu.kernel && cu.landmark_rows && cu.m > 0, "nk_cv_grid: unit %d: null kernel / landmarks", u);
+    NK_REQUIRE(0 <= cu.test_begin && cu.test_begin < cu.test_end && cu.test_end <= n, "nk_cv_grid: unit %d: bad test fold", u);
+    for (int j = 0; j < cu.m; ++j)
+      NK_REQUIRE(cu.landmark_rows[j] >= 0 && cu.landmark_rows[j] < n, "nk_cv_grid: unit %d: landmark row out of range", u);
+  }
+  auto fit_score = [&](nk_ctx* ctx, int u, const CvData& dt, std::vector<double>& Z, double* sc) -> int {
+    const nk_cv_unit& cu = units[u];
+    Z.resize((size_t)cu.m * d);
+    for (int j = 0; j < cu.m; ++j) memcpy(&Z[(size_t)j * d], dt.Yh + cu.landmark_rows[j] * dt.ldyh, (size_t)d * 8);
+    const int64_t rr[4] = {0, cu.test_begin, cu.test_end, n};
+    nk_model* mdl = nullptr;
+    int rc = nk_nystrom_fit(ctx, cu.kernel, dt.Xd, dt.ldxd, dt.Yd, dt.ldyd, n, d, p, rr, 2, nullptr, 0, Z.data(), d, cu.m,
+                            cu.gamma, cu.jitter, &mdl, nullptr);
+    if (rc == NK_OK)
+      rc = nk_score_neg_rmse(ctx, mdl, dt.Xd + cu.test_begin * dt.ldxd, dt.ldxd, dt.Yd + cu.test_begin * dt.ldyd, dt.ldyd,
+                             cu.test_end - cu.test_begin, sc);
+    if (mdl) nk_model_destroy(mdl);
+    return rc;
+  };
+  // phase 1 = strict mode (the factorisation reports a rank-deficient system and the unit stops there), phase 2 = the fallback
+  std::vector<int> saved_strict((size_t)n_members);
+  for (int k = 0; k < n_members; ++k) saved_strict[(size_t)k] = members[k]->strict_spd;
+  auto set_phase = [&](nk_ctx* ctx, int k, int phase) {
+    ctx->strict_spd = phase == 1 ? 1 : (phase == 2 ? 0 : saved_strict[(size_t)k]);
+  };
+  return cv_grid_run("cv_grid", members, n_members, X, ldx, Y, ldy, n, d, p, n_units, true, fit_score, set_phase, scores,
+                     status);
+}
+
+// The spline sweep (regressors.py:181-221 under GridSearchCV, benchmark_lqr_classic.py:55-60): same rounds, same two phases.
+// Phase 1 stops a unit at the point where nk_spline_fit would enter the pseudo-inverse (pivot ratio inside the SVD window or a
+// failed factorisation); phase 2 runs those units together.
+int nk_spline_cv_grid(nk_ctx* const* members, int32_t n_members, const double* X, int64_t ldx, const double* Y, int64_t ldy,
+                      int64_t n, int32_t d, int32_t p, const nk_spline_cv_unit* units, int32_t n_units, double* scores,
+                      int32_t* status) {
+  NK_REQUIRE(members && n_members >= 1 && X && Y && units && scores, "nk_spline_cv_grid: null argument");
+  NK_REQUIRE(n > 0 && d > 0 && p >= 0 && n_units >= 0 && ldx >= d + p && ldy >= d, "nk_spline_cv_grid: bad sizes");
+  for (int k = 0; k < n_members; ++k) NK_REQUIRE(members[k] != nullptr, "nk_spline_cv_grid: null member context");
+  for (int u = 0; u < n_units; ++u) {
+    const nk_spline_cv_unit& cu = units[u];
+    NK_REQUIRE(cu.centers && cu.m > 0, "nk_spline_cv_grid: unit %d: null centres / m <= 0", u);
+    NK_REQUIRE(!is_device_ptr(cu.centers), "nk_spline_cv_grid: unit %d: centres must be a host pointer", u);
+    NK_REQUIRE(0 <= cu.test_begin && cu.test_begin < cu.test_end && cu.test_end <= n,
+               "nk_spline_cv_grid: unit %d: bad test fold", u);
+  }
+  auto fit_score = [&](nk_ctx* ctx, int u, const CvData& dt, std::vector<double>&, double* sc) -> int {
+    const nk_spline_cv_unit& cu = units[u];
+    const int64_t rr[4] = {0, cu.test_begin, cu.test_end, n};
+    nk_model* mdl = nullptr;
+    int rc = nk_spline_fit(ctx, dt.Xd, dt.ldxd, dt.Yd, dt.ldyd, n, d, p, rr, 2, cu.centers, d, cu.m, cu.gamma, &mdl, nullptr);
+    if (rc == NK_OK)
+      rc = nk_score_neg_rmse(ctx, mdl, dt.Xd + cu.test_begin * dt.ldxd, dt.ldxd, dt.Yd + cu.test_begin * dt.ldyd, dt.ldyd,
+                             cu.test_end - cu.test_begin, sc);
+    if (mdl) nk_model_destroy(mdl);
+    return rc;
+  };
+  auto set_phase = [&](nk_ctx* ctx, int, int phase) { ctx->spline_defer_svd = phase == 1; };
+  return cv_grid_run("spline_cv_grid", members, n_members, X, ldx, Y, ldy, n, d, p, n_units, false, fit_score, set_phase,
+                     scores, status);
 }
 
 int nk_synchronize(nk_ctx* ctx) {
@@ -1658,7 +1724,6 @@ int nk_spline_fit(nk_ctx* ctx, const double* X, int64_t ldx, const double* Y, in
              (long long)n, d, p, m);
   NK_REQUIRE(ldx >= d + p && ldy >= d && ldc >= d, "nk_spline_fit: leading dimension too small");
   NK_REQUIRE(std::isfinite(gamma), "nk_spline_fit: gamma not finite");
-  NK_REQUIRE(!ctx_recording(ctx), "nk_spline_fit: not available to the members of a lock-step group");
   *model = nullptr;
   std::vector<int64_t> rng;
   if (row_ranges && n_ranges > 0) {
@@ -1858,6 +1923,10 @@ int nk_spline_fit(nk_ctx* ctx, const double* X, int64_t ldx, const double* Y, in
   if (use_svd) {
     if (failed != 0 && ctx->strict_spd == 1) {
       set_error("nk_spline_fit: Cholesky met a non-positive pivot and strict mode is on");
+      return NK_ERR_NOT_SPD;
+    }
+    if (ctx->spline_defer_svd) {  // first phase of nk_spline_cv_grid: the unit is run again beside the others of its kind
+      set_error("nk_spline_fit: the system takes the pseudo-inverse (deferred to the second phase of the sweep)");
       return NK_ERR_NOT_SPD;
     }
     PinvInfo pi;

@@ -95,6 +95,8 @@ struct nk_ctx {
   nk_member_state* gstate = nullptr;
   int* d_flow[2] = {nullptr, nullptr};  // flag words of the dataflow Cholesky (nk_chol_flow.hip), per failure-flag slot
   size_t flow_words[2] = {0, 0};
+  bool spline_defer_svd = false;  // first phase of nk_spline_cv_grid: nk_spline_fit stops (NK_ERR_NOT_SPD) where it would
+                                 // enter the pseudo-inverse, so that such units can be run together afterwards
   bool chol_flow_off = false;  // set by nk::ChainOnly: the re-run of a factorisation whose dataflow launch gave up
   double* h_stage = nullptr;    // page-locked, device-visible staging block for the small latency-bound calls (rollouts):
   size_t h_stage_bytes = 0;     // kernels read their inputs from it and write their results into it directly (no DMA)

@@ -8,7 +8,7 @@ import itertools
 import numpy as np
 
 from . import _lib
-from .regressors import KoopmanNystromRegressor
+from .regressors import KoopmanNystromRegressor, KoopmanSplineRegressor
 
 
 def open_loop_forecast(regressor, true_trajectory, test_controls):
@@ -75,20 +75,52 @@ def cv_work_list(n_candidates, n_splits):
     return [(c, f) for c in range(n_candidates) for f in range(n_splits)]
 
 
-def cv_unit_score(X, Y, n_inputs, params, fold, centers_idx=None, error_score=np.nan):
+def spline_centers_draw(params, train_states, rng=None):
+    """The centres a cloned KoopmanSplineRegressor draws at the first `lift` of its `fit` (regressors.py:187-197,
+    compute_centers on the training states), draw for draw from the global legacy RNG: two np.random.uniform calls when
+    the candidate has `state_bounds_params`, one np.random.choice over the training rows otherwise.  train_states:
+    n_train x d rows.  rng: a np.random.RandomState to draw from instead of the global one.  Returns the reference's
+    `centers` attribute, d x m.  Needs no GPU."""
+    rng = np.random if rng is None else rng
+    m = int(params["m"])
+    bounds = params.get("state_bounds_params")
+    if bounds is not None:
+        length = np.sqrt(rng.uniform(0, bounds[0], size=(1, m)))
+        angle = np.pi * rng.uniform(0, bounds[1], size=(1, m))
+        return np.vstack((length * np.cos(angle), length * np.sin(angle)))
+    train_states = np.asarray(train_states)
+    idx = rng.choice(np.arange(0, train_states.shape[0]), size=m, replace=False)
+    return train_states[idx].T
+
+
+def _check_estimator(estimator):
+    if estimator not in ("nystrom", "spline"):
+        raise ValueError(f"estimator must be 'nystrom' or 'spline', got {estimator!r}")
+
+
+def cv_unit_score(X, Y, n_inputs, params, fold, centers_idx=None, error_score=np.nan, estimator="nystrom"):
     """One (candidate, fold) unit: fit on the training rows (two contiguous ranges, no copy), score the held-out
     rows with sklearn's 'neg_root_mean_squared_error' reduced on the device.  A fit that fails numerically
     (LinAlgError: only possible in strict mode, or when the square-root iteration diverges) scores `error_score`,
-    like GridSearchCV's default error_score=nan; error_score='raise' re-raises."""
+    like GridSearchCV's default error_score=nan; error_score='raise' re-raises.
+    estimator='spline': `params` has gamma, m and optionally state_bounds_params, and `centers_idx` is the unit's d x m
+    centre array (None: drawn by the fit from the training states, as the reference does)."""
+    _check_estimator(estimator)
     n = X.shape[0]
     lo, hi = fold
     n_train = n - (hi - lo)
-    reg = KoopmanNystromRegressor(n_inputs, **params)
-    if centers_idx is None:  # what clone()+fit does in the reference: fresh draw from the global legacy RNG
-        centers_idx = np.random.choice(np.arange(0, n_train), size=reg.m, replace=False)
-    centers_idx = np.asarray(centers_idx)
-    rows = np.where(centers_idx < lo, centers_idx, centers_idx + (hi - lo))  # training-row index -> dataset row
-    reg.nystrom_centers_output = np.asarray(Y)[rows].T
+    if estimator == "spline":
+        reg = KoopmanSplineRegressor(n_inputs, state_bounds_params=params.get("state_bounds_params"), m=params["m"],
+                                     gamma=params["gamma"])
+        if centers_idx is not None:
+            reg.centers = np.asarray(centers_idx, dtype=np.float64)
+    else:
+        reg = KoopmanNystromRegressor(n_inputs, **params)
+        if centers_idx is None:  # what clone()+fit does in the reference: fresh draw from the global legacy RNG
+            centers_idx = np.random.choice(np.arange(0, n_train), size=reg.m, replace=False)
+        centers_idx = np.asarray(centers_idx)
+        rows = np.where(centers_idx < lo, centers_idx, centers_idx + (hi - lo))  # training-row index -> dataset row
+        reg.nystrom_centers_output = np.asarray(Y)[rows].T
     try:
         reg.fit(X, Y, row_ranges=[(0, lo), (hi, n)], fetch=False)  # the sweep only scores: A, B, C stay on the device
         return reg.score_neg_rmse(X[lo:hi], Y[lo:hi])
@@ -110,7 +142,7 @@ def _rank_candidates(scores):
 
 
 def grid_search_cv(X, Y, n_inputs, candidates, n_splits=5, centers=None, work=None, workers=1, error_score=np.nan,
-                   batch=0, batch_groups=1):
+                   batch=0, batch_groups=1, estimator="nystrom"):
     """learn_hyperparams (benchmark_lqr_cloth.py:39-66 and the classic/hjb twins) without sklearn's process pool.
 
     candidates: list of dicts with keys kernel / gamma / m.  centers: optional {(c, f): landmark indices into the
@@ -122,8 +154,14 @@ def grid_search_cv(X, Y, n_inputs, candidates, n_splits=5, centers=None, work=No
     fails numerically (GridSearchCV's default: nan; such a candidate ranks last), or 'raise'.  batch: run that many
     units in lock step (include/nyskoop.h, nk_group_create): small fits are chains of launch-bound kernels, a batch shares
     every launch; scores are bit-identical to batch=0.
+    estimator: 'nystrom' (default) or 'spline' (the thin-plate-spline branch of learn_hyperparams,
+    benchmark_lqr_classic.py:54-60).  Spline candidates are dicts with gamma, m and optionally state_bounds_params;
+    `centers` then maps (c, f) to the unit's d x m centre array (the reference's `centers` attribute), and without it the
+    centres are drawn by spline_centers_draw in GridSearchCV's order (n_jobs=1).  Everything else behaves the same.
     Returns split_scores (n_cand x n_splits), mean_test_score, best_index.
     """
+    _check_estimator(estimator)
+    spline = estimator == "spline"
     X = np.ascontiguousarray(X, dtype=np.float64)
     Y = np.ascontiguousarray(Y, dtype=np.float64)
     folds = kfold_slices(X.shape[0], n_splits)
@@ -134,6 +172,10 @@ def grid_search_cv(X, Y, n_inputs, candidates, n_splits=5, centers=None, work=No
     for (c, f) in units:
         if centers is not None:
             idx = centers.get((c, f)) if (c, f) not in mine else centers[(c, f)]
+        elif spline:  # (drawn for every unit, evaluated or not, like the landmark indices below)
+            lo, hi = folds[f]  # (the training states are only read by candidates without state bounds)
+            bounded = candidates[c].get("state_bounds_params") is not None
+            idx = spline_centers_draw(candidates[c], None if bounded else np.vstack((X[:lo, :Y.shape[1]], X[hi:, :Y.shape[1]])))
         else:  # drawn for every unit, evaluated or not: keeps the RNG stream aligned with the serial sweep
             n_train = X.shape[0] - (folds[f][1] - folds[f][0])
             idx = np.random.choice(np.arange(0, n_train), size=candidates[c]["m"], replace=False)
@@ -142,6 +184,8 @@ def grid_search_cv(X, Y, n_inputs, candidates, n_splits=5, centers=None, work=No
 
     def run(item):
         c, f, idx = item
+        if spline:
+            return c, f, cv_unit_score(X, Y, n_inputs, candidates[c], folds[f], idx, error_score, estimator)
         return c, f, cv_unit_score(X, Y, n_inputs, candidates[c], folds[f], idx, error_score)
 
     if batch > 1 and len(todo) > 1:
@@ -149,10 +193,18 @@ def grid_search_cv(X, Y, n_inputs, candidates, n_splits=5, centers=None, work=No
         units = []
         for (c, f, idx) in todo:
             lo, hi = folds[f]
+            if spline:  # (nk_spline_cv_grid: the centres as m x d rows)
+                units.append((candidates[c]["gamma"], candidates[c]["m"], (lo, hi),
+                              np.ascontiguousarray(np.asarray(idx, dtype=np.float64).T)))
+                continue
             idx = np.asarray(idx)
             rows = np.where(idx < lo, idx, idx + (hi - lo))  # training-row index -> dataset row
             kern = candidates[c]["kernel"].kernel
             units.append((kern, candidates[c]["gamma"], 1e-6, candidates[c]["m"], (lo, hi), rows))
+
+        def sweep(pool, sub):
+            return pool.spline_cv_grid(X, Y, n_inputs, sub) if spline else pool.cv_grid(X, Y, n_inputs, sub)
+
         if batch_groups > 1 and len(units) >= 2 * batch:
             # several independent lock-step groups, each on its own stream and driven from its own host thread: the
             # latency-bound factorisation chains of one group overlap with the GEMM-bound stages of another
@@ -162,13 +214,13 @@ def grid_search_cv(X, Y, n_inputs, candidates, n_splits=5, centers=None, work=No
 
             def run_share(gi):
                 sub = [units[i] for i in shares[gi]]
-                return _lib.lockstep_pool(batch, index=gi).cv_grid(X, Y, n_inputs, sub)
+                return sweep(_lib.lockstep_pool(batch, index=gi), sub)
 
             with ThreadPoolExecutor(max_workers=batch_groups) as ex:
                 for gi, (s_g, st_g) in enumerate(ex.map(run_share, range(batch_groups))):
                     sc[shares[gi]], status[shares[gi]] = s_g, st_g
         else:
-            sc, status = _lib.lockstep_pool(batch).cv_grid(X, Y, n_inputs, units)
+            sc, status = sweep(_lib.lockstep_pool(batch), units)
         bad = [int(st) for st in status if st not in (0, -3, -5)]
         if bad:
             raise _lib.NyskoopError(bad[0], "a unit of the batched sweep failed")
