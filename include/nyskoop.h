@@ -193,6 +193,31 @@ typedef struct nk_spline_cv_unit {
 int nk_spline_cv_grid(nk_ctx* const* members, int32_t n_members, const double* X, int64_t ldx, const double* Y,
                       int64_t ldy, int64_t n, int32_t d, int32_t p, const nk_spline_cv_unit* units, int32_t n_units,
                       double* scores, int32_t* status);
+/* ---- the multi-seed system-identification sweep as ONE call: replaces the loops of benchmark_lqr_classic.py:211-255 and
+ *   benchmark_lqr_cloth.py:163-211 (for each seed and each m: draw, fit, validate_dyn_sys on the test trajectories).  Unit u
+ *   fits on the rows `row_ranges` of the shared data set X, Y -- a Nystrom fit with the landmarks Y[landmark_rows[0..m)]
+ *   when `kernel` is set, a thin-plate-spline fit with `centers` (m x d VALUES, host memory) when it is NULL -- and scores
+ *   the test trajectories trajs[traj[0..n_traj)] with nk_rollout_err.  One call may hold units of both estimators.
+ *   trajs: n_trajs x T x d, U: n_trajs x T x p (row T-1 never read), host or device; uploaded once, like the data set.
+ *   err_abs / err_rel (either may be NULL): flat, unit-major -- unit u starts at the sum of n_traj over the units before it.
+ *   status[u] = NK_OK or the unit's error code (all its entries are NaN then).  Checked before any unit runs: pointers,
+ *   sizes, m <= 4096, landmark rows, row ranges and trajectory indices; a unit's gamma is checked by its own fit.  Two
+ *   phases as in nk_cv_grid / nk_spline_cv_grid (units that take the rank-truncating / pseudo-inverse branch run together
+ *   afterwards).  The results do not depend on the schedule: they are the bits of nk_nystrom_fit / nk_spline_fit +
+ *   nk_rollout_err on an ordinary context. */
+typedef struct nk_sysid_unit {
+  const nk_kernel_desc* kernel;   /* NULL: a spline unit (nk_spline_fit), `centers` used; else nk_nystrom_fit */
+  double gamma, jitter;
+  int32_t m, n_ranges;
+  const int64_t* row_ranges;      /* training rows of the shared data set, as in nk_nystrom_fit; NULL = all */
+  const int64_t* landmark_rows;   /* Nystrom: m rows of Y */
+  const double* centers;          /* spline: HOST, m x d dense */
+  const int32_t* traj;            /* indices into the call's test trajectories */
+  int32_t n_traj, reserved;
+} nk_sysid_unit;
+int nk_sysid_grid(nk_ctx* const* members, int32_t n_members, const double* X, int64_t ldx, const double* Y, int64_t ldy,
+                  int64_t n, int32_t d, int32_t p, const double* trajs, const double* U, int32_t n_trajs, int32_t T,
+                  const nk_sysid_unit* units, int32_t n_units, double* err_abs, double* err_rel, int32_t* status);
 int nk_group_enter(nk_ctx* member);
 int nk_group_leave(nk_ctx* member);
 int nk_group_stats(nk_ctx* member, uint64_t* out4);
@@ -326,6 +351,17 @@ int nk_score_neg_rmse(nk_ctx* ctx, const nk_model* model, const double* Xaug, in
  *   out_z (optional, may be NULL): batch x T x m lifted states. ------------------------------------------ */
 int nk_rollout(nk_ctx* ctx, const nk_model* model, const double* x0, int64_t ldx0,
                const double* U, int32_t T, int32_t batch, double* out_x, double* out_z);
+
+/* ---- open-loop validation error: validate_dyn_sys (benchmark_lqr_cloth.py:18-36, _classic.py:23-41) for `batch` trajectories,
+ *   reduced on the device: the simulated trajectory C z_t is never written, two sums per trajectory come back.
+ *   x0 = row 0 of each true trajectory.  traj: batch x T x d, U: batch x T x p (row T-1 never read), host or device.
+ *   err_abs[b] = sqrt(sse / (d T)), err_rel[b] = 100 sqrt(sse) / sqrt(ssim) with sse = sum (x_true - C z)^2 and
+ *   ssim = sum (C z)^2 over the T x d entries; either output (HOST arrays of `batch` doubles) may be NULL.  Same staging and
+ *   recursion as nk_rollout (the lifted states are the same bits); the sums are taken in a fixed order, so a trajectory's
+ *   result does not depend on `batch`.  Nystrom and spline models, m <= 4096, batch <= 65535; ordinary contexts and
+ *   lock-step group members. */
+int nk_rollout_err(nk_ctx* ctx, const nk_model* model, const double* traj, const double* U, int32_t T, int32_t batch,
+                   double* err_abs, double* err_rel);
 
 /* ---- closed loop in lifted space: replaces the loop of lqr_control (benchmark_lqr_cloth.py:79-84).
  *   K: p x m gain; phi0, phi_ref: m-vectors; out_x: steps x d visited states C phi_t; out_u: steps x p. ---- */

@@ -38,6 +38,13 @@ class SplineCvUnit(C.Structure):
                 ("test_end", C.c_int64), ("centers", C.POINTER(C.c_double))]
 
 
+class SysidUnit(C.Structure):
+    _fields_ = [("kernel", C.POINTER(KernelDesc)), ("gamma", C.c_double), ("jitter", C.c_double), ("m", C.c_int32),
+                ("n_ranges", C.c_int32), ("row_ranges", C.POINTER(C.c_int64)), ("landmark_rows", C.POINTER(C.c_int64)),
+                ("centers", C.POINTER(C.c_double)), ("traj", C.POINTER(C.c_int32)), ("n_traj", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
 class FitStats(C.Structure):
     _fields_ = [("ms_total", C.c_double), ("ms_upload", C.c_double), ("ms_kmat", C.c_double),
                 ("ms_gram", C.c_double), ("ms_sqrt", C.c_double), ("ms_solve", C.c_double),
@@ -80,6 +87,8 @@ SIGNATURES = {
                              C.POINTER(_D), C.POINTER(_I32)]),
     "nk_spline_cv_grid": (C.c_int, [C.POINTER(_P), _I32, _P, _I64, _P, _I64, _I64, _I32, _I32, C.POINTER(SplineCvUnit),
                                     _I32, C.POINTER(_D), C.POINTER(_I32)]),
+    "nk_sysid_grid": (C.c_int, [C.POINTER(_P), _I32, _P, _I64, _P, _I64, _I64, _I32, _I32, _P, _P, _I32, _I32,
+                                C.POINTER(SysidUnit), _I32, C.POINTER(_D), C.POINTER(_D), C.POINTER(_I32)]),
     "nk_host_alloc": (_P, [C.c_uint64]),
     "nk_host_free": (None, [_P]),
     "nk_kernel_matrix": (C.c_int, [_P, C.POINTER(KernelDesc), _P, _I64, _I64, _P, _I64, _I64, _P, _I64]),
@@ -106,6 +115,7 @@ SIGNATURES = {
     "nk_predict": (C.c_int, [_P, _P, _P, _I64, _I64, _P, _I64]),
     "nk_score_neg_rmse": (C.c_int, [_P, _P, _P, _I64, _P, _I64, _I64, C.POINTER(_D)]),
     "nk_rollout": (C.c_int, [_P, _P, _P, _I64, _P, _I32, _I32, _P, _P]),
+    "nk_rollout_err": (C.c_int, [_P, _P, _P, _P, _I32, _I32, C.POINTER(_D), C.POINTER(_D)]),
     "nk_closed_loop": (C.c_int, [_P, _P, _P, _P, _P, _I32, _P, _P]),
     "nk_closed_loop_batch": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _P, _P]),
     "nk_plant_step": (C.c_int, [C.c_int, _D, _P, _P, _P]),
@@ -510,6 +520,69 @@ class LockstepPool:
         check(rc)
         return scores, status
 
+    def sysid_grid(self, X, Y, n_inputs, trajs, controls, units):
+        """nk_sysid_grid: the multi-seed system-identification sweep in one call.  X: n x (d+p), Y: n x d (the shared data
+        set); trajs: (n_trajs, T, d) test trajectories, controls: (n_trajs, T, p) (row T-1 never read; None when p = 0).
+        `units` = list of (kernel, gamma, jitter, m, row_ranges, landmarks, traj_indices): kernel = a DeviceKernel for a
+        Nystrom unit, whose `landmarks` are m row indices into Y, or None for a thin-plate-spline unit, whose `landmarks`
+        are its centres (m x d); row_ranges = [begin, end) pairs of training rows or None (all rows); traj_indices = the
+        unit's test trajectories.  Returns (err_abs, err_rel, status, offsets): flat unit-major arrays, unit u owning
+        [offsets[u], offsets[u + 1]); a failed unit holds NaN and its code in status[u]."""
+        units, offsets = sysid_unit_layout(units)
+        Xm, Ym = Mat(X), Mat(Y)
+        n, d = Ym.shape
+        p = int(n_inputs)
+        if Xm.shape != (n, d + p):
+            raise ValueError(f"X has shape {Xm.shape}, expected {(n, d + p)}")
+        tr = np.ascontiguousarray(trajs, dtype=np.float64)
+        if tr.ndim != 3 or tr.shape[2] != d:
+            raise ValueError(f"trajs must be (n_trajs, T, {d}), got {tr.shape}")
+        n_trajs, T = tr.shape[0], tr.shape[1]
+        U = None
+        if p > 0 and T > 1:
+            U = np.ascontiguousarray(controls, dtype=np.float64)
+            if U.shape != (n_trajs, T, p):
+                raise ValueError(f"controls must be {(n_trajs, T, p)}, got {U.shape}")
+        arr = (SysidUnit * len(units))()
+        keep, descs = [], {}
+        for i, (kern, gamma, jitter, m, ranges, marks, tidx) in enumerate(units):
+            arr[i].gamma, arr[i].jitter, arr[i].m = float(gamma), float(jitter), int(m)
+            if kern is not None:
+                if id(kern) not in descs:
+                    descs[id(kern)] = kern.desc(d)
+                arr[i].kernel = C.pointer(descs[id(kern)][0])
+                rows = np.ascontiguousarray(marks, dtype=np.int64)
+                if rows.shape != (int(m),):
+                    raise ValueError("a Nystrom unit's landmarks must be m row indices")
+                keep.append(rows)
+                arr[i].landmark_rows = rows.ctypes.data_as(C.POINTER(C.c_int64))
+            else:
+                Z = np.ascontiguousarray(marks, dtype=np.float64)
+                if Z.shape != (int(m), d):
+                    raise ValueError(f"a spline unit's centres must be m x d = {(int(m), d)}, got {Z.shape}")
+                keep.append(Z)
+                arr[i].centers = Z.ctypes.data_as(C.POINTER(C.c_double))
+            if ranges is not None:
+                rr = np.ascontiguousarray(np.asarray(ranges, dtype=np.int64).reshape(-1))
+                keep.append(rr)
+                arr[i].row_ranges, arr[i].n_ranges = rr.ctypes.data_as(C.POINTER(C.c_int64)), rr.size // 2
+            ti = np.ascontiguousarray(tidx, dtype=np.int32).reshape(-1)
+            keep.append(ti)
+            arr[i].traj, arr[i].n_traj = ti.ctypes.data_as(C.POINTER(C.c_int32)), ti.size
+        handles = (_P * self.size)(*[m_.handle for m_ in self.members])
+        total = int(offsets[-1])
+        err_abs, err_rel = np.full(total, np.nan), np.full(total, np.nan)
+        status = np.zeros(len(units), dtype=np.int32)
+        lib = self.members[0].lib
+        rc = lib.nk_sysid_grid(handles, self.size, Xm.ptr, Xm.ld, Ym.ptr, Ym.ld, n, d, p, tr.ctypes.data,
+                               None if U is None else U.ctypes.data, n_trajs, T, arr, len(units),
+                               err_abs.ctypes.data_as(C.POINTER(_D)), err_rel.ctypes.data_as(C.POINTER(_D)),
+                               status.ctypes.data_as(C.POINTER(_I32)))
+        if rc == -1:
+            raise ValueError(lib.nk_last_error().decode())
+        check(rc)
+        return err_abs, err_rel, status, offsets
+
     def stats(self):
         v = (C.c_uint64 * 4)()
         check(self.members[0].lib.nk_group_stats(self.members[0].handle, v))
@@ -522,6 +595,16 @@ class LockstepPool:
             t.join(timeout=5)
         for m in self.members:
             m.close()
+
+
+def sysid_unit_layout(units):
+    """The flat unit-major layout of nk_sysid_grid's outputs: returns (units as a list, offsets) where unit u owns the
+    entries [offsets[u], offsets[u + 1]) -- the prefix sums of the units' numbers of test trajectories.  Needs no GPU."""
+    units = list(units)
+    counts = [int(np.asarray(u[6]).size) for u in units]
+    if any(c < 1 for c in counts):
+        raise ValueError("every unit needs at least one test trajectory")
+    return units, np.concatenate(([0], np.cumsum(counts, dtype=np.int64))).astype(np.int64)
 
 
 _lockstep_pools = {}

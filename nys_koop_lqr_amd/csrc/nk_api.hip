@@ -614,11 +614,14 @@ struct CvData {  // what a unit sees: the data set in HBM, a host copy of Y (onl
 // fit_score(member, unit, data, scratch, &score): fit + score of one unit on a member that is inside its unit of work;
 // set_phase(member, k, phase) for member k of `members`: 1 = stop at a system that needs the rank-truncating branch (NK_ERR_NOT_SPD: the unit is run again
 // in phase 2), 2 = take the branch, 0 = back to what the caller had set.
+// A unit may produce several numbers (the trajectories of a system-identification unit): fit_score writes up to `max_vals`
+// of them and store(unit, rc, vals) files them -- or NaN when rc != NK_OK -- with the unit's status.
 using CvFitScore = std::function<int(nk_ctx*, int, const CvData&, std::vector<double>&, double*)>;
 using CvSetPhase = std::function<void(nk_ctx*, int, int)>;
+using CvStore = std::function<void(int, int, const double*)>;
 static int cv_grid_run(const char* what, nk_ctx* const* members, int32_t n_members, const double* X, int64_t ldx,
                        const double* Y, int64_t ldy, int64_t n, int32_t d, int32_t p, int32_t n_units, bool want_host_y,
-                       const CvFitScore& fit_score, const CvSetPhase& set_phase, double* scores, int32_t* status) {
+                       const CvFitScore& fit_score, const CvSetPhase& set_phase, const CvStore& store, int max_vals) {
   if (n_units == 0) return NK_OK;
   nk_ctx* lead = members[0];
   NK_HIP(hipSetDevice(lead->device));
@@ -685,7 +688,7 @@ static int cv_grid_run(const char* what, nk_ctx* const* members, int32_t n_membe
     const int n_rounds = (count + B - 1) / B;
     auto worker = [&](int k) {
       nk_ctx* ctx = members[k];
-      std::vector<double> Z;
+      std::vector<double> Z, vals((size_t)max_vals);
       for (int r = 0; r < n_rounds; ++r) {
         const int slot = r * B + k;
         const bool mine = slot < count;
@@ -693,8 +696,8 @@ static int cv_grid_run(const char* what, nk_ctx* const* members, int32_t n_membe
         round.wait(B);
         if (mine) {
           const int u = list[(size_t)slot];
-          double sc = std::nan("");
-          int rc = fit_score(ctx, u, data, Z, &sc);
+          std::fill(vals.begin(), vals.end(), std::nan(""));
+          int rc = fit_score(ctx, u, data, Z, vals.data());
           tl_ctx = ctx;
           const int rc_leave = group_leave(ctx);  // flushes what the unit recorded after its last synchronisation
           if (rc == NK_OK) rc = rc_leave;
@@ -702,8 +705,7 @@ static int cv_grid_run(const char* what, nk_ctx* const* members, int32_t n_membe
             std::lock_guard<std::mutex> lk(deferred_mu);
             deferred.push_back(u);
           } else {
-            scores[u] = rc == NK_OK ? sc : std::nan("");
-            if (status) status[u] = rc;
+            store(u, rc, vals.data());
           }
         }
         round.wait(B);
@@ -772,8 +774,11 @@ int nk_cv_grid(nk_ctx* const* members, int32_t n_members, const double* X, int64
   auto set_phase = [&](nk_ctx* ctx, int k, int phase) {
     ctx->strict_spd = phase == 1 ? 1 : (phase == 2 ? 0 : saved_strict[(size_t)k]);
   };
-  return cv_grid_run("cv_grid", members, n_members, X, ldx, Y, ldy, n, d, p, n_units, true, fit_score, set_phase, scores,
-                     status);
+  auto store = [&](int u, int rc, const double* v) {
+    scores[u] = rc == NK_OK ? v[0] : std::nan("");
+    if (status) status[u] = rc;
+  };
+  return cv_grid_run("cv_grid", members, n_members, X, ldx, Y, ldy, n, d, p, n_units, true, fit_score, set_phase, store, 1);
 }
 
 // The spline sweep (regressors.py:181-221 under GridSearchCV, benchmark_lqr_classic.py:55-60): same rounds, same two phases.
@@ -804,8 +809,125 @@ int nk_spline_cv_grid(nk_ctx* const* members, int32_t n_members, const double* X
     return rc;
   };
   auto set_phase = [&](nk_ctx* ctx, int, int phase) { ctx->spline_defer_svd = phase == 1; };
+  auto store = [&](int u, int rc, const double* v) {
+    scores[u] = rc == NK_OK ? v[0] : std::nan("");
+    if (status) status[u] = rc;
+  };
   return cv_grid_run("spline_cv_grid", members, n_members, X, ldx, Y, ldy, n, d, p, n_units, false, fit_score, set_phase,
-                     scores, status);
+                     store, 1);
+}
+
+// The multi-seed system-identification sweep (benchmark_lqr_classic.py:211-255, benchmark_lqr_cloth.py:163-211) as one call:
+// unit = one fit (either estimator) on some rows of the shared data set + the open-loop error of its test trajectories,
+// reduced on the device.  Same rounds and the same two phases as the hyper-parameter sweeps; the test trajectories and
+// their controls live in HBM once, like the data set.
+static int rollout_err_run(nk_ctx* ctx, const nk_model* mdl, const double* traj, const double* U, int32_t T, int32_t batch,
+                           double* err_abs, double* err_rel);
+
+int nk_sysid_grid(nk_ctx* const* members, int32_t n_members, const double* X, int64_t ldx, const double* Y, int64_t ldy,
+                  int64_t n, int32_t d, int32_t p, const double* trajs, const double* U, int32_t n_trajs, int32_t T,
+                  const nk_sysid_unit* units, int32_t n_units, double* err_abs, double* err_rel, int32_t* status) {
+  NK_REQUIRE(members && n_members >= 1 && X && Y && trajs && units, "nk_sysid_grid: null argument");
+  NK_REQUIRE(n > 0 && d > 0 && p >= 0 && n_units >= 0 && ldx >= d + p && ldy >= d, "nk_sysid_grid: bad sizes");
+  NK_REQUIRE(n_trajs >= 1 && T >= 1 && (p == 0 || T == 1 || U != nullptr), "nk_sysid_grid: bad trajectories / controls missing");
+  for (int k = 0; k < n_members; ++k) NK_REQUIRE(members[k] != nullptr, "nk_sysid_grid: null member context");
+  std::vector<int64_t> offs((size_t)n_units + 1, 0);
+  int max_traj = 1;
+  bool any_nystrom = false;
+  for (int u = 0; u < n_units; ++u) {
+    const nk_sysid_unit& su = units[u];
+    NK_REQUIRE(su.m > 0 && su.m <= 4096, "nk_sysid_grid: unit %d: m = %d outside 1..4096", u, su.m);
+    if (su.kernel) {
+      any_nystrom = true;
+      NK_REQUIRE(su.landmark_rows != nullptr, "nk_sysid_grid: unit %d: null landmark rows", u);
+      for (int j = 0; j < su.m; ++j)
+        NK_REQUIRE(su.landmark_rows[j] >= 0 && su.landmark_rows[j] < n, "nk_sysid_grid: unit %d: landmark row out of range", u);
+    } else {
+      NK_REQUIRE(su.centers != nullptr, "nk_sysid_grid: unit %d: neither a kernel nor centres", u);
+      NK_REQUIRE(!is_device_ptr(su.centers), "nk_sysid_grid: unit %d: centres must be a host pointer", u);
+    }
+    NK_REQUIRE(su.n_ranges >= 0 && (su.n_ranges == 0 || su.row_ranges != nullptr), "nk_sysid_grid: unit %d: bad row ranges", u);
+    for (int i = 0; su.row_ranges && i < su.n_ranges; ++i)
+      NK_REQUIRE(0 <= su.row_ranges[2 * i] && su.row_ranges[2 * i] <= su.row_ranges[2 * i + 1] && su.row_ranges[2 * i + 1] <= n,
+                 "nk_sysid_grid: unit %d: row range %d outside [0,%lld)", u, i, (long long)n);
+    NK_REQUIRE(su.traj != nullptr && su.n_traj >= 1 && su.n_traj <= 65535, "nk_sysid_grid: unit %d: no test trajectories", u);
+    for (int i = 0; i < su.n_traj; ++i)
+      NK_REQUIRE(su.traj[i] >= 0 && su.traj[i] < n_trajs, "nk_sysid_grid: unit %d: trajectory index out of range", u);
+    offs[(size_t)u + 1] = offs[(size_t)u] + su.n_traj;
+    max_traj = std::max(max_traj, (int)su.n_traj);
+  }
+  if (n_units == 0) return NK_OK;
+  NK_HIP(hipSetDevice(members[0]->device));
+  // the test trajectories and their controls: in HBM once for all units (copied on the caller's thread before any member
+  // thread exists: no current context, so the two copies and their wait are issued, not recorded)
+  tl_ctx = nullptr;
+  const bool have_u = p > 0 && T > 1;
+  const int64_t td = (int64_t)T * d, tp = (int64_t)T * p;
+  const double *Td = trajs, *Ud = have_u ? U : nullptr;
+  double *Town = nullptr, *Uown = nullptr;
+  struct Free { double*& a; double*& b; ~Free() { if (a) (void)hipFree(a); if (b) (void)hipFree(b); } } freer{Town, Uown};
+  if (!is_device_ptr(trajs)) {
+    NK_HIP(hipMalloc(reinterpret_cast<void**>(&Town), (size_t)n_trajs * td * 8));
+    NK_HIP(hipMemcpyAsync(Town, trajs, (size_t)n_trajs * td * 8, hipMemcpyHostToDevice, members[0]->stream_main));
+    Td = Town;
+  }
+  if (have_u && !is_device_ptr(U)) {
+    NK_HIP(hipMalloc(reinterpret_cast<void**>(&Uown), (size_t)n_trajs * tp * 8));
+    NK_HIP(hipMemcpyAsync(Uown, U, (size_t)n_trajs * tp * 8, hipMemcpyHostToDevice, members[0]->stream_main));
+    Ud = Uown;
+  }
+  NK_HIP(hipStreamSynchronize(members[0]->stream_main));
+  auto fit_score = [&](nk_ctx* ctx, int u, const CvData& dt, std::vector<double>& Z, double* out) -> int {
+    const nk_sysid_unit& su = units[u];
+    nk_model* mdl = nullptr;
+    int rc;
+    if (su.kernel) {
+      Z.resize((size_t)su.m * d);
+      for (int j = 0; j < su.m; ++j) memcpy(&Z[(size_t)j * d], dt.Yh + su.landmark_rows[j] * dt.ldyh, (size_t)d * 8);
+      rc = nk_nystrom_fit(ctx, su.kernel, dt.Xd, dt.ldxd, dt.Yd, dt.ldyd, n, d, p, su.row_ranges, su.n_ranges, nullptr, 0,
+                          Z.data(), d, su.m, su.gamma, su.jitter, &mdl, nullptr);
+    } else {
+      rc = nk_spline_fit(ctx, dt.Xd, dt.ldxd, dt.Yd, dt.ldyd, n, d, p, su.row_ranges, su.n_ranges, su.centers, d, su.m,
+                         su.gamma, &mdl, nullptr);
+    }
+    if (rc == NK_OK) rc = check_ctx(ctx);
+    if (rc == NK_OK) {
+      // the unit's trajectories as one batch: in place when their indices are consecutive, gathered into the arena otherwise
+      bool consecutive = true;
+      for (int i = 1; i < su.n_traj; ++i) consecutive = consecutive && su.traj[i] == su.traj[0] + i;
+      const double *tq = Td + (int64_t)su.traj[0] * td, *uq = have_u ? Ud + (int64_t)su.traj[0] * tp : nullptr;
+      if (!consecutive) {
+        double *tg = nullptr, *ug = nullptr;
+        rc = arena_alloc_t(ctx, (size_t)su.n_traj * td, &tg);
+        if (rc == NK_OK && have_u) rc = arena_alloc_t(ctx, (size_t)su.n_traj * tp, &ug);
+        for (int i = 0; rc == NK_OK && i < su.n_traj; ++i) {
+          rc = launch_copy2d(ctx, Td + (int64_t)su.traj[i] * td, td, tg + (int64_t)i * td, td, 1, td);
+          if (rc == NK_OK && have_u) rc = launch_copy2d(ctx, Ud + (int64_t)su.traj[i] * tp, tp, ug + (int64_t)i * tp, tp, 1, tp);
+        }
+        tq = tg; uq = ug;
+      }
+      if (rc == NK_OK) rc = rollout_err_run(ctx, mdl, tq, uq, T, su.n_traj, out, out + max_traj);
+    }
+    if (mdl) nk_model_destroy(mdl);
+    return rc;
+  };
+  // phase 1: both estimators stop where they would enter the rank-truncating branch, phase 2: they take it
+  std::vector<int> saved_strict((size_t)n_members);
+  for (int k = 0; k < n_members; ++k) saved_strict[(size_t)k] = members[k]->strict_spd;
+  auto set_phase = [&](nk_ctx* ctx, int k, int phase) {
+    ctx->strict_spd = phase == 1 ? 1 : (phase == 2 ? 0 : saved_strict[(size_t)k]);
+    ctx->spline_defer_svd = phase == 1;
+  };
+  auto store = [&](int u, int rc, const double* v) {
+    const nk_sysid_unit& su = units[u];
+    for (int i = 0; i < su.n_traj; ++i) {
+      if (err_abs) err_abs[offs[(size_t)u] + i] = rc == NK_OK ? v[i] : std::nan("");
+      if (err_rel) err_rel[offs[(size_t)u] + i] = rc == NK_OK ? v[max_traj + i] : std::nan("");
+    }
+    if (status) status[u] = rc;
+  };
+  return cv_grid_run("sysid_grid", members, n_members, X, ldx, Y, ldy, n, d, p, n_units, any_nystrom, fit_score, set_phase,
+                     store, 2 * max_traj);
 }
 
 int nk_synchronize(nk_ctx* ctx) {
@@ -2381,15 +2503,23 @@ static int rollout_steps(nk_ctx* ctx, ChainArgs chain, bool z0_in_place, bool us
 
 static int rollout_impl(nk_ctx* ctx, const nk_model* mdl, const double* G, int64_t ldg, const double* Cop, int64_t ldc,
                         int m, int d, int p, const double* x0, int64_t ldx0, const double* z0, const double* U, int32_t T,
-                        int32_t batch, double* out_x, double* out_z) {
-  // x0 != nullptr: lift through the model; otherwise z0 (batch x m) holds the lifted initial states
-  const int64_t nin = x0 ? d : m;
-  const double* first = x0 ? x0 : z0;
+                        int32_t batch, double* out_x, double* out_z, const double* traj_true = nullptr,
+                        double* err_out = nullptr) {
+  // x0 != nullptr: lift through the model; otherwise z0 (batch x m) holds the lifted initial states.
+  // traj_true != nullptr (nk_rollout_err): the true trajectories (batch x T x d) are staged whole, x0 = their rows 0, and
+  // instead of the trajectory the call returns err_out[b] = (sse, ssim) (HOST, batch x 2) reduced on the device; out_x and
+  // out_z are absent.  Staging and recursion are the same in both modes.
+  const bool err_mode = traj_true != nullptr;
+  const bool from_state = err_mode || x0 != nullptr;
+  const int64_t nin = err_mode ? (int64_t)T * d : (x0 ? d : m);
+  const int64_t ldin = err_mode ? (int64_t)T * d : (x0 ? ldx0 : m);
+  const double* first = err_mode ? traj_true : (x0 ? x0 : z0);
   const bool have_u = p > 0 && T > 1;
   const size_t need = pad256((size_t)batch * nin) + (have_u ? pad256((size_t)batch * T * p) : 0) +
-                      pad256((size_t)batch * T * d) + (out_z ? pad256((size_t)batch * T * m) : 0);
+                      (err_mode ? pad256((size_t)batch * 2)
+                                : pad256((size_t)batch * T * d) + (out_z ? pad256((size_t)batch * T * m) : 0));
   const bool small = need <= SMALL_STAGE_LIMIT && !is_device_ptr(first) && !(have_u && is_device_ptr(U)) &&
-                     !is_device_ptr(out_x) && !(out_z && is_device_ptr(out_z));
+                     (err_mode || (!is_device_ptr(out_x) && !(out_z && is_device_ptr(out_z))));
   double* Zall = nullptr;  // [batch][T][m]
   NK_TRY(arena_alloc_t(ctx, (size_t)batch * T * m, &Zall));
   const int64_t ldz = (int64_t)T * m;
@@ -2399,30 +2529,43 @@ static int rollout_impl(nk_ctx* ctx, const nk_model* mdl, const double* G, int64
   SmallStage st;
   st.ctx = ctx;
   MatIn xin, uin;
-  MatOut ox, oz;
-  double *xdev = nullptr, *zdev = nullptr;
+  MatOut ox, oz, oe;
+  double *xdev = nullptr, *zdev = nullptr, *edev = nullptr;
   if (small) {
     NK_TRY(small_reserve(ctx, need));
-    xin.ptr = small_in(st, first, x0 ? ldx0 : m, batch, nin);
+    xin.ptr = small_in(st, first, ldin, batch, nin);
     xin.ld = nin;
     if (have_u) { uin.ptr = small_in(st, U, (int64_t)T * p, batch, (int64_t)T * p); uin.ld = (int64_t)T * p; }
-    xdev = small_out(st, out_x, d, (int64_t)batch * T, d);
-    if (out_z) zdev = small_out(st, out_z, m, (int64_t)batch * T, m);
+    if (err_mode) {
+      edev = small_out(st, err_out, 2, batch, 2);
+      double* tdev = nullptr;  // every row of the true trajectories is read by the error kernel: from HBM, not over PCIe
+      NK_TRY(arena_alloc_t(ctx, (size_t)batch * nin, &tdev));
+      NK_TRY(launch_copy2d(ctx, xin.ptr, nin, tdev, nin, batch, nin));
+      xin.ptr = tdev;
+    } else {
+      xdev = small_out(st, out_x, d, (int64_t)batch * T, d);
+      if (out_z) zdev = small_out(st, out_z, m, (int64_t)batch * T, m);
+    }
   } else {
-    NK_TRY(stage_in(ctx, first, x0 ? ldx0 : m, batch, nin, &xin));
+    NK_TRY(stage_in(ctx, first, ldin, batch, nin, &xin));
     if (have_u) NK_TRY(stage_in(ctx, U, (int64_t)T * p, batch, (int64_t)T * p, &uin));
-    NK_TRY(stage_out(ctx, out_x, d, (int64_t)batch * T, d, &ox));
-    xdev = ox.dev;
-    if (out_z) { NK_TRY(stage_out(ctx, out_z, m, (int64_t)batch * T, m, &oz)); zdev = oz.dev; }
+    if (err_mode) {
+      NK_TRY(stage_out(ctx, err_out, 2, batch, 2, &oe));
+      edev = oe.dev;
+    } else {
+      NK_TRY(stage_out(ctx, out_x, d, (int64_t)batch * T, d, &ox));
+      xdev = ox.dev;
+      if (out_z) { NK_TRY(stage_out(ctx, out_z, m, (int64_t)batch * T, m, &oz)); zdev = oz.dev; }
+    }
   }
   ch.U = have_u ? uin.ptr : nullptr;
   if (!have_u) ch.pu = (T > 1) ? p : 0;
   const int64_t ldxo = small ? d : ox.ld, ldzo = small ? m : (out_z ? oz.ld : m);
   bool z0_in_place = false;
-  if (x0 && mdl->kind != NK_MODEL_SPLINE && lifted_chain_ok(m, ch.pu, d)) {  // the lift is done by the chain kernel itself
+  if (from_state && mdl->kind != NK_MODEL_SPLINE && lifted_chain_ok(m, ch.pu, d)) {  // the lift is done by the chain kernel itself
     ch.lift = true; ch.x0 = xin.ptr; ch.x0_stride = xin.ld; ch.Zl = mdl->Z; ch.d = d; ch.winv = mdl->winv;
     ch.Sinv = mdl->Sinv; ch.ktype = mdl->ktype; ch.sigma0 = mdl->sigma0;
-  } else if (x0) {
+  } else if (from_state) {
     NK_TRY(lift_device(ctx, mdl, xin.ptr, xin.ld, batch, Zall, ldz));  // z_0 = phi(x_0) for every trajectory
     z0_in_place = true;
     // the single-launch chain (no lift of its own: a spline model, or d too large for its LDS) reads z_0 from there
@@ -2441,17 +2584,37 @@ static int rollout_impl(nk_ctx* ctx, const nk_model* mdl, const double* G, int64
     NK_TRY(launch_copy2d(ctx, uin.ptr, uin.ld, Udev, (int64_t)T * p, batch, (int64_t)T * p));
     ch.U = Udev;
   }
-  const bool try_mw = chain_mw_wanted(ctx, ch);
+  // The error mode promises bits that do not depend on the batch or on the schedule (an ordinary context and a lock-step
+  // member must agree: the sweep is checked bit for bit against the plain loop).  Beyond the single-launch chain that
+  // rules out the multi-workgroup recursion (members cannot take it, and its give-up repeats the recursion with other
+  // kernels) and the per-step GEMM of batches above 16 (another summation order): the error mode always walks the
+  // matrix-vector steps, 16 trajectories at a time -- the path a member takes for a small batch.
+  const bool try_mw = !err_mode && chain_mw_wanted(ctx, ch);
   std::unique_lock<std::mutex> mw_lock(g_chain_mw_mutex, std::defer_lock);
   if (try_mw) mw_lock.lock();
   for (int attempt = 0; attempt < 2; ++attempt) {
     const bool mw = try_mw && attempt == 0;
-    NK_TRY(rollout_steps(ctx, ch, z0_in_place, mw));
-    NK_TRY(launch_gemm(ctx, false, true, (int64_t)batch * T, d, m, 1.0, Zall, m, Cop, ldc, 0.0, xdev, ldxo));
-    if (out_z) NK_TRY(launch_copy2d(ctx, Zall, m, zdev, ldzo, (int64_t)batch * T, m));
-    if (!small) {
-      NK_TRY(finish_out(ctx, ox));
-      if (out_z) NK_TRY(finish_out(ctx, oz));
+    if (err_mode && !lifted_chain_ok(m, ch.pu, ch.lift ? ch.d : 0)) {
+      for (int b0 = 0; b0 < batch; b0 += 16) {
+        ChainArgs sub = ch;
+        sub.batch = batch - b0 < 16 ? batch - b0 : 16;
+        sub.Zall = ch.Zall + (int64_t)b0 * ch.z_stride;
+        if (ch.U) sub.U = ch.U + (int64_t)b0 * ch.u_stride;
+        NK_TRY(rollout_steps(ctx, sub, z0_in_place, false));
+      }
+    } else {
+      NK_TRY(rollout_steps(ctx, ch, z0_in_place, mw));
+    }
+    if (err_mode) {  // x_true - C z and C z squared and summed per trajectory where z lies: no product, no trajectory copy
+      NK_TRY(launch_traj_err(ctx, Zall, ldz, Cop, ldc, xin.ptr, xin.ld, m, d, T, batch, edev));
+      if (!small) NK_TRY(finish_out(ctx, oe));
+    } else {
+      NK_TRY(launch_gemm(ctx, false, true, (int64_t)batch * T, d, m, 1.0, Zall, m, Cop, ldc, 0.0, xdev, ldxo));
+      if (out_z) NK_TRY(launch_copy2d(ctx, Zall, m, zdev, ldzo, (int64_t)batch * T, m));
+      if (!small) {
+        NK_TRY(finish_out(ctx, ox));
+        if (out_z) NK_TRY(finish_out(ctx, oz));
+      }
     }
     NK_HIP(hipStreamSynchronize(ctx->stream));
     // a wave of the single-launch recursion gave up waiting for its neighbours (the device was oversubscribed): the
@@ -2471,6 +2634,33 @@ int nk_rollout(nk_ctx* ctx, const nk_model* mdl, const double* x0, int64_t ldx0,
   const int m = mdl->m, d = mdl->d, p = mdl->p, mp = m + p;
   NK_REQUIRE(p == 0 || T == 1 || U != nullptr, "nk_rollout: controls missing");
   return rollout_impl(ctx, mdl, mdl->A, mp, mdl->C, m, m, d, p, x0, ldx0, nullptr, U, T, batch, out_x, out_z);
+}
+
+// the body of nk_rollout_err for a context whose arena the caller has prepared (check_ctx): the sweep gathers a unit's
+// trajectories into the arena first
+static int rollout_err_run(nk_ctx* ctx, const nk_model* mdl, const double* traj, const double* U, int32_t T, int32_t batch,
+                           double* err_abs, double* err_rel) {
+  const int m = mdl->m, d = mdl->d, p = mdl->p, mp = m + p;
+  std::vector<double> e((size_t)batch * 2);
+  NK_TRY(rollout_impl(ctx, mdl, mdl->A, mp, mdl->C, m, m, d, p, nullptr, 0, nullptr, U, T, batch, nullptr, nullptr, traj,
+                      e.data()));
+  for (int b = 0; b < batch; ++b) {
+    const double sse = e[(size_t)2 * b], ssim = e[(size_t)2 * b + 1];
+    if (err_abs) err_abs[b] = std::sqrt(sse / ((double)d * (double)T));
+    if (err_rel) err_rel[b] = std::sqrt(sse) / std::sqrt(ssim) * 100.0;
+  }
+  return NK_OK;
+}
+
+int nk_rollout_err(nk_ctx* ctx, const nk_model* mdl, const double* traj, const double* U, int32_t T, int32_t batch,
+                   double* err_abs, double* err_rel) {
+  NK_TRY(check_ctx(ctx));
+  NK_REQUIRE(mdl && traj, "nk_rollout_err: null argument");
+  NK_REQUIRE(mdl->has_ops, "nk_rollout_err: model holds no fitted operators");
+  NK_REQUIRE(T >= 1 && batch >= 1 && batch <= 65535, "nk_rollout_err: bad sizes");
+  NK_REQUIRE(traj_err_tile(mdl->m) >= 1, "nk_rollout_err: m = %d is beyond the error kernel's range (4096)", mdl->m);
+  NK_REQUIRE(mdl->p == 0 || T == 1 || U != nullptr, "nk_rollout_err: controls missing");
+  return rollout_err_run(ctx, mdl, traj, U, T, batch, err_abs, err_rel);
 }
 
 int nk_linear_rollout(nk_ctx* ctx, const double* A, const double* B, const double* Cop, int32_t m, int32_t d, int32_t p,

@@ -450,6 +450,11 @@ struct ChainArgs {
 int launch_ref_minus_traj(nk_ctx* ctx, const double* ref, int64_t ref_stride, const double* Phi, int64_t phi_stride,
                           double* D, int64_t d_stride, int steps, int m, int batch);
 bool lifted_chain_ok(int m, int pu, int d_lift);
+// open-loop forecast error reduced on the device (nk_traj_err.hip): out[b] = (sum (x_true - C z)^2, sum (C z)^2) over the T
+// steps of trajectory b, from the lifted states Zall [b][t][m]; the product C z is never stored.  m <= 4096.
+int traj_err_tile(int m);  // time steps per workgroup (0: m out of range)
+int launch_traj_err(nk_ctx* ctx, const double* Zall, int64_t z_stride, const double* Cop, int64_t ldc, const double* Xtrue,
+                    int64_t x_stride, int m, int d, int T, int batch, double* out);
 int launch_lifted_chain(nk_ctx* ctx, const ChainArgs& a);
 // m > 128: multi-workgroup recursion, one launch per group of trajectories that is resident at once (nk_rollout.hip)
 bool lifted_chain_mw_ok(const nk_ctx* ctx, int m, int pu);

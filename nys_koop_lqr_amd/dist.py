@@ -117,6 +117,25 @@ def sharded_grid_search(X, Y, n_inputs, candidates, n_splits=5, centers=None, un
                 best_params=candidates[best] if best >= 0 else None)
 
 
+def sharded_sysid_sweep(X, Y, n_inputs, params, ms, seeds, trajs, controls, test_index, train_ranges=None,
+                        estimator="nystrom", relative=False, extra_draws=0, centers=None, batch=0, batch_groups=1,
+                        streams=None, unit_fn=None):
+    """Distributed counterpart of harness.sysid_sweep: every rank plans the same units with the same draws (one stream per
+    seed, so nothing depends on the world size), the units are dealt round-robin (shard_units), every rank runs its share
+    on its own GPU -- through the lock-step sweep when batch > 1 -- and ONE all-gather assembles the table.  unit_fn: a
+    stand-in for harness.sysid_unit_error (rehearsals without a GPU).  Every rank returns the same
+    (len(seeds), n_test_per_seed, len(ms)) array."""
+    import torch.distributed as dist
+    rank, world = (dist.get_rank(), dist.get_world_size()) if dist.is_initialized() else (0, 1)
+    units = harness.sysid_plan(X, Y, n_inputs, params, ms, seeds, test_index, train_ranges, estimator, extra_draws, centers,
+                               streams)
+    mine = shard_units(len(units), rank, world)
+    local = harness.sysid_run_units(X, Y, n_inputs, params, [units[u] for u in mine], trajs, controls, estimator, relative,
+                                    batch, batch_groups, unit_fn)
+    flat = all_gather_scores(local, len(units), rank, world) if world > 1 else local
+    return harness.sysid_table(units, flat, len(seeds), len(ms))
+
+
 def sample_sharded_fit(reg, X_local, Y_local, landmark_rows=None):
     """One LARGE fit over several GPUs: the samples are sharded, every rank holds all landmarks,
     accumulates the four Gram blocks of its own rows on its GPU (`reg.gram_partial`), ONE all-reduce sums the packed

@@ -242,6 +242,171 @@ def grid_search_cv(X, Y, n_inputs, candidates, n_splits=5, centers=None, work=No
                 best_params=candidates[best] if best >= 0 else None)
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# the multi-seed system-identification sweep (benchmark_lqr_classic.py:211-255, benchmark_lqr_cloth.py:163-211)
+# ---------------------------------------------------------------------------------------------------------------
+def _per_seed(table, si, seed):
+    """Entry of a per-seed argument: a dict is keyed by the seed, anything else is indexed by the seed's position."""
+    if table is None:
+        return None
+    return table[seed] if isinstance(table, dict) else table[si]
+
+
+def train_row_map(ranges, n):
+    """Data-set row of every training row, in the reference's concatenation order: `ranges` = [begin, end) pairs in the
+    order the reference stacks them (benchmark_lqr_cloth.py:117-130 over the shuffled training trajectories); None = all
+    n rows.  A landmark index i the reference drew over its own X refers to data-set row train_row_map(...)[i]."""
+    if ranges is None:
+        return np.arange(n, dtype=np.int64)
+    rr = np.asarray(ranges, dtype=np.int64).reshape(-1, 2)
+    if rr.size and (rr.min() < 0 or rr.max() > n or np.any(rr[:, 1] < rr[:, 0])):
+        raise ValueError(f"training ranges must lie in [0, {n}]")
+    return np.concatenate([np.arange(b, e, dtype=np.int64) for b, e in rr]) if len(rr) else np.zeros(0, dtype=np.int64)
+
+
+def sysid_plan(X, Y, n_inputs, params, ms, seeds, test_index, train_ranges=None, estimator="nystrom", extra_draws=0,
+               centers=None, streams=None):
+    """The units of sysid_sweep and their random draws, made up front (needs no GPU).  For every seed one stream
+    np.random.RandomState(seed) (or `streams`' entry for the seed: a RandomState the caller has already advanced, e.g. by
+    the trajectory shuffle of benchmark_lqr_cloth.py:171-172) is walked in the reference's order -- test trajectory major,
+    m minor, one fit each.  The global NumPy RNG is never touched.
+      nystrom: one choice(arange(n_train), m, replace=False) per fit (regressors.py:130), followed by `extra_draws`
+               discarded draws of the same size; the indices count rows of the reference's concatenated training set and
+               are mapped to rows of the data set (train_row_map);
+      spline:  spline_centers_draw(..., rng=stream) per fit (regressors.py:187-197).
+    centers: {(seed, test, k): landmark indices (nystrom, in the reference's row numbering) or d x m centres (spline)}
+    replaces the draws.  Returns the units in m-major order (k, then seed, then test trajectory), so that a lock-step
+    round holds fits of one shape: dicts with si, ti, k (position in the result table), m, traj (index of the test
+    trajectory), ranges (the seed's training ranges or None) and marks (data-set rows, or the d x m centres)."""
+    _check_estimator(estimator)
+    spline = estimator == "spline"
+    n, d = np.shape(Y)
+    units = []
+    for si, seed in enumerate(seeds):
+        seed = int(seed)
+        rs = _per_seed(streams, si, seed) if streams is not None else np.random.RandomState(seed)
+        ranges = _per_seed(train_ranges, si, seed)
+        rowmap = train_row_map(ranges, n)
+        n_train = len(rowmap)
+        states = None
+        for ti, traj in enumerate(_per_seed(test_index, si, seed)):
+            for k, m in enumerate(ms):
+                m = int(m)
+                if centers is not None:
+                    marks = np.asarray(centers[(seed, ti, k)])
+                    marks = np.asarray(marks, dtype=np.float64) if spline else rowmap[marks.astype(np.int64)]
+                elif spline:
+                    par = dict(params, m=m)
+                    if par.get("state_bounds_params") is None and states is None:
+                        states = np.asarray(X)[rowmap, :d]
+                    marks = spline_centers_draw(par, states, rng=rs)
+                else:
+                    idx = rs.choice(np.arange(0, n_train), size=m, replace=False)
+                    for _ in range(int(extra_draws)):
+                        rs.choice(np.arange(0, n_train), size=m, replace=False)
+                    marks = rowmap[idx]
+                if marks.shape != ((d, m) if spline else (m,)):
+                    raise ValueError(f"unit (seed {seed}, test {ti}, m {m}): landmarks have shape {marks.shape}")
+                units.append(dict(si=si, ti=ti, k=k, m=m, traj=int(traj), marks=marks,
+                                  ranges=None if ranges is None else np.asarray(ranges, dtype=np.int64).reshape(-1, 2)))
+    units.sort(key=lambda u: (u["k"], u["si"], u["ti"]))  # (a stable sort of an already seed-major list)
+    return units
+
+
+def sysid_unit_error(X, Y, n_inputs, params, unit, tr, U, estimator="nystrom", relative=False):
+    """One unit of the sweep on the calling thread's context: fit on the unit's rows with its landmarks, operators left on
+    the device, then the open-loop error of its test trajectory reduced on the device (reg.open_loop_errors).
+    tr: (n_trajs, T, d), U: (n_trajs, T, p) or None, as open_loop_pack lays them out."""
+    m = unit["m"]
+    if estimator == "spline":
+        reg = KoopmanSplineRegressor(n_inputs, state_bounds_params=params.get("state_bounds_params"), m=m,
+                                     gamma=params["gamma"])
+        reg.centers = np.asarray(unit["marks"], dtype=np.float64)
+    else:
+        reg = KoopmanNystromRegressor(n_inputs, **dict(params, m=m))
+        reg.nystrom_centers_output = np.ascontiguousarray(np.asarray(Y)[unit["marks"]].T)
+    reg.fit(X, Y, row_ranges=unit["ranges"], fetch=False)
+    t = unit["traj"]
+    return float(reg.open_loop_errors(tr[t].T[None], None if U is None else U[t].T[None], relative)[0])
+
+
+def sysid_grid_units(params, units, estimator="nystrom"):
+    """The argument tuples of LockstepPool.sysid_grid for planned units (one test trajectory per unit)."""
+    if estimator == "spline":
+        return [(None, params["gamma"], 0.0, u["m"], u["ranges"], np.ascontiguousarray(u["marks"].T), [u["traj"]])
+                for u in units]
+    kern = params["kernel"].kernel
+    jitter = KoopmanNystromRegressor(1, **dict(params, m=1)).jitter
+    return [(kern, params["gamma"], jitter, u["m"], u["ranges"], u["marks"], [u["traj"]]) for u in units]
+
+
+def sysid_run_units(X, Y, n_inputs, params, units, trajs, controls, estimator="nystrom", relative=False, batch=0,
+                    batch_groups=1, unit_fn=None):
+    """Errors of planned units, in their order.  batch=0 (or a `unit_fn` standing in for the device): the plain loop of
+    sysid_unit_error; batch>1: one nk_sysid_grid call per lock-step group (bit-identical numbers).  A unit whose fit fails
+    numerically is NaN; any other failure raises."""
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    Y = np.ascontiguousarray(Y, dtype=np.float64)
+    from .regressors import open_loop_pack
+    tr, U = open_loop_pack(np.asarray(trajs, dtype=np.float64), controls, Y.shape[1], int(n_inputs))
+    if unit_fn is not None or batch <= 1 or len(units) <= 1:
+        fn = unit_fn or sysid_unit_error
+        return np.array([fn(X, Y, n_inputs, params, u, tr, U, estimator, relative) for u in units], dtype=np.float64)
+    tuples = sysid_grid_units(params, units, estimator)
+
+    def sweep(pool, sub):
+        ea, er, st, _ = pool.sysid_grid(X, Y, n_inputs, tr, U, sub)  # one trajectory per unit: offsets = 0, 1, 2, ...
+        return (er if relative else ea), st
+
+    if batch_groups > 1 and len(tuples) >= 2 * batch:  # independent groups on their own streams, as in grid_search_cv
+        from concurrent.futures import ThreadPoolExecutor
+        shares = [list(range(gi, len(tuples), batch_groups)) for gi in range(batch_groups)]
+        err, status = np.full(len(tuples), np.nan), np.zeros(len(tuples), dtype=np.int32)
+        with ThreadPoolExecutor(max_workers=batch_groups) as ex:
+            runs = ex.map(lambda gi: sweep(_lib.lockstep_pool(batch, index=gi), [tuples[i] for i in shares[gi]]),
+                          range(batch_groups))
+            for gi, (e_g, st_g) in enumerate(runs):
+                err[shares[gi]], status[shares[gi]] = e_g, st_g
+    else:
+        err, status = sweep(_lib.lockstep_pool(batch), tuples)
+    bad = [int(st) for st in status if st not in (0, -3, -5)]
+    if bad:
+        raise _lib.NyskoopError(bad[0], "a unit of the batched sweep failed")
+    return np.where(status == 0, err, np.nan)
+
+
+def sysid_table(units, values, n_seeds, n_ms):
+    """(seed, test trajectory, m) table from per-unit values in plan order; entries without a unit are NaN."""
+    n_test = 1 + max((u["ti"] for u in units), default=0)
+    out = np.full((n_seeds, n_test, n_ms), np.nan)
+    for u, v in zip(units, values):
+        out[u["si"], u["ti"], u["k"]] = v
+    return out
+
+
+def sysid_sweep(X, Y, n_inputs, params, ms, seeds, trajs, controls, test_index, train_ranges=None, estimator="nystrom",
+                relative=False, extra_draws=0, centers=None, batch=0, batch_groups=1, streams=None):
+    """The multi-seed system-identification sweep of benchmark_lqr_classic.py:211-255 and benchmark_lqr_cloth.py:163-211:
+    for every seed, every test trajectory of the seed and every m in `ms`: draw landmarks, fit, validate_dyn_sys.
+    Returns the open-loop errors (absolute RMSE, or the relative-% form with relative=True) as an array of shape
+    (len(seeds), n_test_per_seed, len(ms)).
+
+    X: n x (d+p), Y: n x d: ONE data set holding every row any seed trains on; train_ranges[seed] = the [begin, end) row
+    ranges the seed trains on, in the order the reference concatenates them (cloth: one range per training trajectory of
+    the seed's shuffle; the fit accepts them in any order and gathers them in that order, so its training matrix is the
+    reference's, row for row); None = all rows.  trajs: (k, d, T) test trajectories, controls: (k, p, T or T-1);
+    test_index[seed] = the trajectories the seed is tested on.  Per-seed arguments are dicts keyed by the seed or sequences
+    in the order of `seeds`.  params: kernel and gamma (nystrom), or gamma and optionally state_bounds_params (spline); m
+    comes from `ms`.  Draws, `extra_draws`, `centers` and `streams`: see sysid_plan (the shipped cloth CSV needs
+    extra_draws=1 and streams advanced by the seed's shuffle).
+    batch=0: the plain loop of reg.fit(row_ranges=..., fetch=False) + reg.open_loop_errors.  batch>1: the units are
+    ordered m-major and run `batch` at a time in lock step by ONE library call (nk_sysid_grid): same bits, merged launches;
+    batch_groups>1: that many independent groups side by side, as in grid_search_cv."""
+    units = sysid_plan(X, Y, n_inputs, params, ms, seeds, test_index, train_ranges, estimator, extra_draws, centers, streams)
+    vals = sysid_run_units(X, Y, n_inputs, params, units, trajs, controls, estimator, relative, batch, batch_groups)
+    return sysid_table(units, vals, len(seeds), len(ms))
+
+
 def lqr_closed_loop(num_steps, reference, initial_state, regressor, K):
     """The loop of benchmark_lqr_cloth.py:73-84 alone: returns (visited_states (d, 1+num_steps) starting with the initial
     state, u_ops (p, num_steps)).  One device call (lifts of both states + the whole lifted recursion)."""

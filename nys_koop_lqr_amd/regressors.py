@@ -55,6 +55,28 @@ def linear_rollout(A, B, C, z0, controls, return_lifted=False):
     return (out_x, out_z) if return_lifted else out_x
 
 
+def open_loop_pack(trajs, controls, d, p):
+    """Test trajectories (k, d, T) and controls (k, p, T or T-1) in the layout of nk_rollout_err / nk_sysid_grid: returns
+    (k, T, d) and (k, T, p) contiguous arrays (the control row T-1 is never read and is zero when absent; None when p = 0
+    or T = 1).  A single (d, T) trajectory with (p, .) controls is a batch of one.  Needs no GPU."""
+    tr = np.asarray(trajs, dtype=np.float64)
+    if tr.ndim == 2:
+        tr = tr[None]
+        controls = None if controls is None else np.asarray(controls, dtype=np.float64)[None]
+    if tr.ndim != 3 or tr.shape[1] != d:
+        raise ValueError(f"trajectories must be (k, {d}, T), got {tr.shape}")
+    k, _, T = tr.shape
+    out = np.ascontiguousarray(np.transpose(tr, (0, 2, 1)))
+    if p == 0 or T == 1:
+        return out, None
+    ctrl = np.asarray(controls, dtype=np.float64)
+    if ctrl.ndim != 3 or ctrl.shape[0] != k or ctrl.shape[1] != p or ctrl.shape[2] < T - 1:
+        raise ValueError(f"controls have shape {ctrl.shape}, expected ({k}, {p}, >= {T - 1})")
+    U = np.zeros((k, T, p))
+    U[:, : min(T, ctrl.shape[2]), :] = np.transpose(ctrl[:, :, :T], (0, 2, 1))
+    return out, U
+
+
 class KoopmanRegressor(BaseEstimator):
     """regressors.py:32-55."""
 
@@ -472,6 +494,24 @@ class KoopmanNystromRegressor(KoopmanRegressor):
             return (out_x[0].T, out_z[0].T) if return_lifted else out_x[0].T
         return (out_x, out_z) if return_lifted else out_x
 
+    def open_loop_errors(self, trajs, controls, relative=False):
+        """validate_dyn_sys (benchmark_lqr_cloth.py:18-36; relative=True: the %-form of benchmark_lqr_classic.py:39) for k
+        test trajectories in one device call that returns k numbers (nk_rollout_err): the forecast is rolled out from each
+        trajectory's first state and compared with it on the device -- the simulated trajectories are never formed.
+        trajs: (k, d, T) (or one (d, T)); controls: (k, p, T) or (k, p, T-1) (or (p, .)).  Returns (k,) errors."""
+        ctx = _lib.get_context()
+        h = self._ensure_model()
+        d, m = self._landmark_shape()
+        p = int(self.n_inputs)
+        tr, U = open_loop_pack(trajs, controls, d, p)
+        k, T = tr.shape[0], tr.shape[1]
+        out = np.empty(k)
+        ptr = out.ctypes.data_as(C.POINTER(C.c_double))
+        rc = ctx.lib.nk_rollout_err(ctx.handle, h, tr.ctypes.data, None if U is None else U.ctypes.data, T, k,
+                                    None if relative else ptr, ptr if relative else None)
+        self._raise(ctx, rc)
+        return out
+
     def closed_loop(self, K, phi0, phi_ref, num_steps):
         """Lifted closed loop of lqr_control (benchmark_lqr_cloth.py:79-84).
 
@@ -762,6 +802,7 @@ class KoopmanSplineRegressor(KoopmanRegressor):
     predict = KoopmanNystromRegressor.predict
     score_neg_rmse = KoopmanNystromRegressor.score_neg_rmse
     rollout = KoopmanNystromRegressor.rollout
+    open_loop_errors = KoopmanNystromRegressor.open_loop_errors
     closed_loop = KoopmanNystromRegressor.closed_loop
     closed_loop_plant = KoopmanNystromRegressor.closed_loop_plant
     solve_lqr = KoopmanNystromRegressor.solve_lqr
