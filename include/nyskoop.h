@@ -392,6 +392,38 @@ int nk_closed_loop_batch(nk_ctx* ctx, const nk_model* model, const double* K, co
 int nk_plant_step(int plant, double Ts, const double* x, const double* u, double* x_next);
 int nk_plant_loop(nk_ctx* ctx, const nk_model* model, int plant, double Ts, const double* K, const double* x0,
                   const double* x_ref, int32_t steps, int32_t batch, double* out_x, double* out_u);
+/* ---- the multi-model form of nk_plant_loop, scored on the device: the control branch of the sweeps of
+ *   benchmark_lqr_classic.py:256-299 and benchmark_lqr_hjb.py:265-333 (per seed and m: fit, gain, closed loop, replay and
+ *   cost, control RMSE) in ONE call after the fits.  Every unit has its own model, gain, initial state and reference;
+ *   the units of a call share the plant, Ts and steps and may differ in everything else (model kind, kernel family, m).
+ *   Unit u runs exactly the loop of nk_plant_loop(model, K, x0, x_ref, batch = 1): its states and controls have the same
+ *   bits, whatever else the call holds and in whatever order.
+ *   u_opt: n_uopt x steps reference controls (host or device, dense; NULL with n_uopt = 0); unit.uopt = the row a unit is
+ *   scored against, or -1.  out_x: n_units x (steps + 1) x d, out_u: n_units x steps (host or device); EITHER MAY BE NULL
+ *   and is then never written on the device either.  scores: HOST, n_units x 4, may be NULL:
+ *     scores[u] = {sse_u, ss_opt, J, u_absmax},
+ *     sse_u = sum_t (u_t - u_opt[t])^2 and ss_opt = sum_t u_opt[t]^2, summed in step order (both 0 when uopt < 0);
+ *     J = the cost of open_loop_control (benchmark_lqr_hjb.py:99-107): J = sum_k x0_k^2, then per step
+ *         J = (J + sum_k x_{t+1,k}^2) + u_t^2, plain IEEE operations in this order (squares rounded, sums over k in index
+ *         order): a host loop over the returned x, u gives the same bits;
+ *     u_absmax = max_t |u_t|, NaN from the first NaN control on: a diverged unit shows without its trajectory.
+ *   Everything is checked before anything is launched; a bad unit is NK_ERR_BAD_ARG with its index in nk_last_error().
+ *   Per unit the conditions of nk_plant_loop hold (p = 1, d = the plant's, m <= 4096, kernel family).  K, x0, x_ref and
+ *   scores are host memory.  Not all of out_x, out_u, scores may be NULL.  Ordinary contexts only (not lock-step
+ *   members).  A model is not tied to the context that fitted it: models fitted by lock-step members (or by any other
+ *   context) on the same device are accepted as they are.
+ *   Device side: one record per unit in a table staged with one copy, blockIdx.x selects the record; one launch per class
+ *   of (kernel family, landmarks per lane, waves per workgroup). */
+typedef struct nk_plant_unit {
+  const nk_model* model; /* Nystrom (RBF / Matern-5/2 / linear) or spline model, p = 1, d = the plant's, m <= 4096 */
+  const double* K;       /* HOST, 1 x m gain */
+  const double* x0;      /* HOST, d */
+  const double* x_ref;   /* HOST, d */
+  int32_t uopt;          /* row of u_opt this unit is scored against, or -1 */
+  int32_t reserved;
+} nk_plant_unit;
+int nk_plant_loop_multi(nk_ctx* ctx, int plant, double Ts, int32_t steps, const nk_plant_unit* units, int32_t n_units,
+                        const double* u_opt, int32_t n_uopt, double* out_x, double* out_u, double* scores);
 /* ---- rollout of explicit operators without a model (any estimator that exposes A, B, C: the exact-kernel comparator of
  *   benchmark_lqr_hjb.py:334-381, un-pickled gains): z0: batch x m lifted initial states; A: m x m, B: m x p, C: d x m
  *   (row-major, host or device); U, out_x, out_z as in nk_rollout. --------------------------------------------------- */

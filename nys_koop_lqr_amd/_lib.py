@@ -45,6 +45,13 @@ class SysidUnit(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class PlantUnit(C.Structure):
+    """nk_plant_unit (include/nyskoop.h), one unit of nk_plant_loop_multi: four pointers (model, K, x0, x_ref) and two
+    int32 (uopt, reserved): 40 bytes, no padding."""
+    _fields_ = [("model", C.c_void_p), ("K", C.c_void_p), ("x0", C.c_void_p), ("x_ref", C.c_void_p),
+                ("uopt", C.c_int32), ("reserved", C.c_int32)]
+
+
 class FitStats(C.Structure):
     _fields_ = [("ms_total", C.c_double), ("ms_upload", C.c_double), ("ms_kmat", C.c_double),
                 ("ms_gram", C.c_double), ("ms_sqrt", C.c_double), ("ms_solve", C.c_double),
@@ -120,6 +127,7 @@ SIGNATURES = {
     "nk_closed_loop_batch": (C.c_int, [_P, _P, _P, _P, _P, _I32, _I32, _P, _P]),
     "nk_plant_step": (C.c_int, [C.c_int, _D, _P, _P, _P]),
     "nk_plant_loop": (C.c_int, [_P, _P, C.c_int, _D, _P, _P, _P, _I32, _I32, _P, _P]),
+    "nk_plant_loop_multi": (C.c_int, [_P, C.c_int, _D, _I32, C.POINTER(PlantUnit), _I32, _P, _I32, _P, _P, _P]),
     "nk_linear_rollout": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P]),
     "nk_gemm_f32": (C.c_int, [_P, _I64, _I64, _I64, _P, _I64, _P, _I64, _P, _I64]),
     "nk_gemm": (C.c_int, [_P, C.c_int, C.c_int, _I64, _I64, _I64, _D, _P, _I64, _P, _I64, _D, _P, _I64]),
@@ -313,6 +321,44 @@ class Context:
         if code is None:
             raise ValueError("dtype must be 'f64' or 'f32'")
         check(self.lib.nk_set_compute_dtype(self.handle, code))
+
+    def plant_loop_multi(self, plant_id, Ts, steps, models, gains, x0s, x_refs, u_opt=None, uopt_rows=None,
+                         want_x=False, want_u=False, want_scores=True):
+        """nk_plant_loop_multi: one closed loop around the true plant per unit, all units in one call, scored on the device.
+        models: device-model handles (one per unit); gains: one (1, m) / (m,) array per unit; x0s, x_refs: (n_units, d);
+        u_opt: (n_uopt, steps) reference controls or None; uopt_rows: the row each unit is scored against (-1: none;
+        default: row 0 for every unit when u_opt is given).  Returns (scores (n_units, 4) or None, states
+        (n_units, steps + 1, d) or None, controls (n_units, steps) or None); scores[u] = sse_u, ss_opt, J, u_absmax."""
+        n = len(models)
+        steps = int(steps)
+        x0s = np.ascontiguousarray(x0s, dtype=np.float64).reshape(n, -1) if n else np.zeros((0, 1))
+        d = x0s.shape[1]
+        x_refs = np.ascontiguousarray(np.asarray(x_refs, dtype=np.float64).reshape(n, d)) if n else np.zeros((0, d))
+        if len(gains) != n:
+            raise ValueError(f"{len(gains)} gains for {n} models")
+        Ks = [np.ascontiguousarray(K, dtype=np.float64).reshape(-1) for K in gains]
+        uo, n_uopt = None, 0
+        if u_opt is not None:
+            uo = np.ascontiguousarray(np.asarray(u_opt, dtype=np.float64).reshape(-1, max(steps, 1)))
+            n_uopt = uo.shape[0]
+        if uopt_rows is None:
+            uopt_rows = [0 if n_uopt else -1] * n
+        arr = (PlantUnit * max(n, 1))()
+        for i in range(n):
+            h = models[i]
+            arr[i].model = h.value if isinstance(h, C.c_void_p) else h
+            arr[i].K, arr[i].x0, arr[i].x_ref = Ks[i].ctypes.data, x0s[i].ctypes.data, x_refs[i].ctypes.data
+            arr[i].uopt = int(uopt_rows[i])
+        sc = np.full((n, 4), np.nan) if want_scores else None
+        ox = np.empty((n, max(steps, 0) + 1, d)) if want_x else None
+        ou = np.empty((n, max(steps, 0))) if want_u else None
+        ptr = lambda a: None if a is None else a.ctypes.data
+        rc = self.lib.nk_plant_loop_multi(self.handle, int(plant_id), float(Ts), steps, arr, n, ptr(uo), n_uopt, ptr(ox),
+                                          ptr(ou), ptr(sc))
+        if rc == -1:
+            raise ValueError(self.lib.nk_last_error().decode())
+        check(rc)
+        return sc, ox, ou
 
     def set_kmat_mode(self, mode):
         """0 = automatic (Gram form on the MFMA engine for d >= 32), 1 = always direct differences."""

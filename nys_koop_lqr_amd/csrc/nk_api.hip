@@ -2816,6 +2816,105 @@ int nk_plant_loop(nk_ctx* ctx, const nk_model* mdl, int plant, double Ts, const 
   return NK_OK;
 }
 
+int nk_plant_loop_multi(nk_ctx* ctx, int plant, double Ts, int32_t steps, const nk_plant_unit* units, int32_t n_units,
+                        const double* u_opt, int32_t n_uopt, double* out_x, double* out_u, double* scores) {
+  NK_TRY(check_ctx(ctx));
+  NK_REQUIRE(!ctx_recording(ctx), "nk_plant_loop_multi: not available to the members of a lock-step group");
+  NK_REQUIRE(plant_dim(plant) > 0, "nk_plant_loop_multi: unknown plant %d", plant);
+  NK_REQUIRE(units != nullptr && n_units >= 1, "nk_plant_loop_multi: n_units = %d units at %p: at least one is needed",
+             n_units, (const void*)units);
+  NK_REQUIRE(steps >= 1, "nk_plant_loop_multi: steps = %d must be positive", steps);
+  NK_REQUIRE(std::isfinite(Ts), "nk_plant_loop_multi: Ts is not finite");
+  NK_REQUIRE(out_x || out_u || scores, "nk_plant_loop_multi: out_x, out_u and scores are all null: nothing to return");
+  NK_REQUIRE(n_uopt >= 0 && (n_uopt == 0 || u_opt != nullptr), "nk_plant_loop_multi: n_uopt = %d rows of a null u_opt",
+             n_uopt);
+  NK_REQUIRE(!is_device_ptr(scores), "nk_plant_loop_multi: scores must be host memory");
+  const int d = plant_dim(plant);
+  // every unit is checked before anything is queued; the staging layout is laid out on the way (slots start on 256 bytes
+  // and a gain row has the even leading dimension stage_in gives it in nk_plant_loop: the fold sees the same operands)
+  auto slot = [](size_t doubles) { return (doubles + 31) & ~(size_t)31; };
+  std::vector<size_t> k_off((size_t)n_units), w_off((size_t)n_units);
+  size_t in_doubles = 0, w_doubles = 0;
+  for (int u = 0; u < n_units; ++u) {
+    const nk_plant_unit& un = units[u];
+    const nk_model* mdl = un.model;
+    NK_REQUIRE(mdl && un.K && un.x0 && un.x_ref, "nk_plant_loop_multi: unit %d: null argument", u);
+    NK_REQUIRE(mdl->device == ctx->device, "nk_plant_loop_multi: unit %d: the model lives on device %d, the context on %d",
+               u, mdl->device, ctx->device);
+    NK_REQUIRE(mdl->p == 1, "nk_plant_loop_multi: unit %d: the plants have one input, the model has %d", u, mdl->p);
+    NK_REQUIRE(mdl->d == d, "nk_plant_loop_multi: unit %d: the %s has %d states, the model has %d", u, plant_name(plant), d,
+               mdl->d);
+    NK_REQUIRE(mdl->m >= 1 && mdl->m <= plant_loop_max_m(),
+               "nk_plant_loop_multi: unit %d: m = %d landmarks, at most %d fit one workgroup", u, mdl->m, plant_loop_max_m());
+    const bool spline = mdl->kind == NK_MODEL_SPLINE;
+    NK_REQUIRE(spline ? mdl->ktype == NK_KERNEL_TPS
+                      : (mdl->ktype == NK_KERNEL_RBF || mdl->ktype == NK_KERNEL_MATERN52 || mdl->ktype == NK_KERNEL_LINEAR),
+               "nk_plant_loop_multi: unit %d: kernel type %d is not supported for this model", u, mdl->ktype);
+    NK_REQUIRE(un.uopt >= -1 && un.uopt < n_uopt, "nk_plant_loop_multi: unit %d: uopt = %d, u_opt has %d rows", u, un.uopt,
+               n_uopt);
+    NK_REQUIRE(!is_device_ptr(un.K) && !is_device_ptr(un.x0) && !is_device_ptr(un.x_ref),
+               "nk_plant_loop_multi: unit %d: K, x0 and x_ref must be host memory", u);
+    k_off[u] = in_doubles;
+    in_doubles += slot((size_t)mdl->m + (mdl->m & 1)) + slot(2 * (size_t)d);  // K | x0, x_ref
+    if (!spline) {
+      w_off[u] = w_doubles;
+      w_doubles += slot((size_t)mdl->m + 2);
+    }
+  }
+  // one staging block for every gain, initial state and reference: one copy
+  std::vector<double> h_in(in_doubles, 0.0);
+  for (int u = 0; u < n_units; ++u) {
+    const nk_plant_unit& un = units[u];
+    const int m = un.model->m;
+    double* dst = h_in.data() + k_off[u];
+    std::copy(un.K, un.K + m, dst);
+    dst += slot((size_t)m + (m & 1));
+    std::copy(un.x0, un.x0 + d, dst);
+    std::copy(un.x_ref, un.x_ref + d, dst + d);
+  }
+  double *d_in = nullptr, *d_w = nullptr, *d_sc = nullptr;
+  NK_TRY(arena_alloc_t(ctx, in_doubles, &d_in));
+  NK_HIP(hipMemcpyAsync(d_in, h_in.data(), in_doubles * 8, hipMemcpyHostToDevice, ctx->stream));
+  if (w_doubles) NK_TRY(arena_alloc_t(ctx, w_doubles, &d_w));
+  if (scores) NK_TRY(arena_alloc_t(ctx, (size_t)n_units * 4, &d_sc));
+  MatIn uo;
+  MatOut ox, ou;
+  if (n_uopt > 0) NK_TRY(stage_in(ctx, u_opt, steps, n_uopt, steps, &uo));
+  if (out_x) NK_TRY(stage_out(ctx, out_x, d, (int64_t)n_units * (steps + 1), d, &ox));
+  if (out_u) NK_TRY(stage_out(ctx, out_u, 1, (int64_t)n_units * steps, 1, &ou));
+  std::vector<PlantLoopUnit> recs((size_t)n_units);
+  std::vector<int> ktypes((size_t)n_units);
+  for (int u = 0; u < n_units; ++u) {
+    const nk_plant_unit& un = units[u];
+    const nk_model* mdl = un.model;
+    const int m = mdl->m;
+    const double* k_dev = d_in + k_off[u];
+    const double* xs = k_dev + slot((size_t)m + (m & 1));
+    // u = K phi = K (k S^-1)^T = (S^-1 K^T) . k, the fold of nk_plant_loop by the same call; the folds of all units are
+    // queued back to back, nothing waits between them
+    const double* w = k_dev;
+    if (mdl->kind != NK_MODEL_SPLINE) {
+      double* wf = d_w + w_off[u];
+      NK_TRY(launch_gemm(ctx, false, true, m, 1, m, 1.0, mdl->Sinv, m, k_dev, m + (m & 1), 0.0, wf, 1));
+      w = wf;
+    }
+    PlantLoopUnit& r = recs[u];
+    r.Z = mdl->Z; r.winv = mdl->winv; r.w = w; r.x0 = xs; r.xref = xs + d;
+    r.out_x = out_x ? ox.dev + (int64_t)u * (steps + 1) * ox.ld : nullptr; r.ldx = out_x ? ox.ld : 0;
+    r.out_u = out_u ? ou.dev + (int64_t)u * steps * ou.ld : nullptr; r.ldu = out_u ? ou.ld : 0;
+    r.u_opt = un.uopt >= 0 ? uo.ptr + (int64_t)un.uopt * uo.ld : nullptr;
+    r.score = scores ? d_sc + 4 * (size_t)u : nullptr;
+    r.sigma0sq = mdl->sigma0 * mdl->sigma0; r.m = m; r.reserved = 0;
+    ktypes[u] = mdl->ktype;
+  }
+  NK_TRY(launch_plant_loop_multi(ctx, plant, Ts, steps, recs.data(), ktypes.data(), n_units));
+  if (out_x) NK_TRY(finish_out(ctx, ox));
+  if (out_u) NK_TRY(finish_out(ctx, ou));
+  if (scores) NK_HIP(hipMemcpyAsync(scores, d_sc, (size_t)n_units * 32, hipMemcpyDeviceToHost, ctx->stream));
+  NK_HIP(hipStreamSynchronize(ctx->stream));  // (h_in and recs are read by the copies queued above)
+  return NK_OK;
+}
+
 int nk_gemm(nk_ctx* ctx, int transA, int transB, int64_t M, int64_t N, int64_t K, double alpha, const double* A,
             int64_t lda, const double* B, int64_t ldb, double beta, double* C, int64_t ldc) {
   NK_TRY(check_ctx(ctx));

@@ -472,6 +472,25 @@ int plant_loop_max_m();
 int launch_plant_loop(nk_ctx* ctx, const nk_model* mdl, int plant, double Ts, const double* w, const double* x0,
                       int64_t x0_stride, const double* xref, int64_t xref_stride, int steps, int batch, double* out_x,
                       int64_t ldx, double* out_u, int64_t ldu);
+// The multi-model form (nk_plant_loop_multi): one record per unit, every pointer device memory.  The records are sorted
+// into classes of (kernel family, landmarks per lane, waves per workgroup), staged with one copy and run with one launch
+// per class; a workgroup finds its record by its block index.  out_x / out_u / u_opt / score may be null per unit.
+struct PlantLoopUnit {
+  const double* Z;      // m x d landmarks
+  const double* winv;   // d
+  const double* w;      // m folded gain
+  const double* x0;     // d
+  const double* xref;   // d
+  double* out_x;        // (steps + 1) rows of ldx, or nullptr
+  double* out_u;        // steps rows of ldu, or nullptr
+  const double* u_opt;  // steps controls to score against, or nullptr
+  double* score;        // {sse_u, ss_opt, J, u_absmax}, or nullptr
+  int64_t ldx, ldu;
+  double sigma0sq;
+  int m, reserved;
+};
+int launch_plant_loop_multi(nk_ctx* ctx, int plant, double Ts, int steps, PlantLoopUnit* units, const int* ktypes,
+                            int n_units);
 
 }  // namespace nk
 

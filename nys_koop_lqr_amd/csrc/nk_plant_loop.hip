@@ -19,6 +19,9 @@
 #include "nk_common.h"
 #include "nk_plant.h"
 
+#include <algorithm>
+#include <vector>
+
 namespace nk {
 
 struct PlantLoopParams {
@@ -88,20 +91,23 @@ __device__ __forceinline__ double plant_feedback(const double* x, const double* 
   return s;
 }
 
-template <int PLANT, int KTYPE, int LPT>
-__global__ void __launch_bounds__(LPT == 1 ? 64 : 64 * PLANT_LOOP_MAX_WAVES) plant_loop_kernel(PlantLoopParams P) {
+// One loop, as a workgroup sees it, is a PlantLoopUnit (nk_common.h).  nk_plant_loop builds the record from its kernel arguments
+// (PlantLoopParams and the block index); nk_plant_loop_multi reads it from a table in device memory, blockIdx.x = the record.
+// The loop of one workgroup.  SCORED = false: the body of nk_plant_loop (out_x, out_u always stored, no scores).
+// SCORED = true: out_x / out_u may be null (uniform over the workgroup), and the four scores of include/nyskoop.h are
+// accumulated in registers -- every lane holds u_t and x_{t+1} -- and stored once by thread 0 after the last step.
+template <int PLANT, int KTYPE, int LPT, bool SCORED>
+__device__ __forceinline__ void plant_loop_body(const PlantLoopUnit& P, double Ts, int steps, double (&red)[2][PLANT_LOOP_MAX_WAVES]) {
   constexpr int D = PlantDim<PLANT>::value;
-  __shared__ double red[2][PLANT_LOOP_MAX_WAVES];  // one partial sum per wave, two buffers (parity of the step)
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nthreads = blockDim.x;
   const bool multi = nthreads > 64;
-  const int b = blockIdx.x;
   if (tid < 2 * PLANT_LOOP_MAX_WAVES) (&red[0][0])[tid] = 0.0;  // words of waves that do not exist stay zero
   double wi[D], zs[LPT][D], wj[LPT], kref[LPT], x[D], xr[D];
 #pragma unroll
   for (int k = 0; k < D; ++k) {
     wi[k] = P.winv[k];
-    x[k] = P.x0[(int64_t)b * P.x0_stride + k];
-    xr[k] = P.xref[(int64_t)b * P.xref_stride + k];
+    x[k] = P.x0[k];
+    xr[k] = P.xref[k];
   }
   {
 #pragma clang fp contract(off)
@@ -119,26 +125,93 @@ __global__ void __launch_bounds__(LPT == 1 ? 64 : 64 * PLANT_LOOP_MAX_WAVES) pla
 #pragma unroll
     for (int l = 0; l < LPT; ++l) kref[l] = plant_kval<KTYPE, D>(xrs, zs[l], P.sigma0sq);
   }
-  double* ox = P.out_x + (int64_t)b * (P.steps + 1) * P.ldx;
-  double* ou = P.out_u + (int64_t)b * P.steps * P.ldu;
-  if (tid == 0) {
+  double* ox = P.out_x;
+  double* ou = P.out_u;
+  const bool st_x = !SCORED || ox != nullptr, st_u = !SCORED || ou != nullptr;
+  if (tid == 0 && st_x) {
 #pragma unroll
     for (int k = 0; k < D; ++k) ox[k] = x[k];
   }
+  // scores (SCORED only): sse = sum (u_t - u_opt[t])^2, sso = sum u_opt[t]^2, J = the running cost of the reference's
+  // open_loop_control in its order, umax = max |u_t|, NaN from the first NaN control on
+  double sse = 0.0, sso = 0.0, J = 0.0, umax = 0.0, uo = 0.0;
+  const double* uopt = SCORED ? P.u_opt : nullptr;
+  if (SCORED) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      const double sq = x[k] * x[k];
+      J = k == 0 ? sq : J + sq;
+    }
+    if (uopt) uo = uopt[0];
+  }
   __syncthreads();  // red is zeroed
-  for (int t = 0; t < P.steps; ++t) {
+  for (int t = 0; t < steps; ++t) {
     // buffer t & 1: a wave still reading it in step t is at most one barrier behind the wave that writes it again in t + 2
     const double u = plant_feedback<KTYPE, D, LPT>(x, wi, zs, wj, kref, P.sigma0sq, red[t & 1], lane, wave, multi);
     double xn[D];
-    plant_step<PLANT>(P.Ts, x, u, xn);
+    plant_step<PLANT>(Ts, x, u, xn);
 #pragma unroll
     for (int k = 0; k < D; ++k) x[k] = xn[k];
-    if (tid == 0) {
-      ou[(int64_t)t * P.ldu] = u;
+    if (SCORED) {
+#pragma clang fp contract(off)
+      double sx = 0.0;
 #pragma unroll
-      for (int k = 0; k < D; ++k) ox[(int64_t)(t + 1) * P.ldx + k] = x[k];
+      for (int k = 0; k < D; ++k) {
+        const double sq = x[k] * x[k];
+        sx = k == 0 ? sq : sx + sq;
+      }
+      const double usq = u * u;
+      J = (J + sx) + usq;
+      const double au = fabs(u);
+      umax = (au > umax || au != au) ? au : umax;  // a NaN enters once and stays: no later comparison is true
+      if (uopt) {
+        const double df = u - uo;
+        const double dsq = df * df, osq = uo * uo;
+        sse = sse + dsq;
+        sso = sso + osq;
+        uo = uopt[t + 1 < steps ? t + 1 : t];  // next step's value, loaded a step ahead (not on the chain)
+      }
+    }
+    if (tid == 0) {
+      if (st_u) ou[(int64_t)t * P.ldu] = u;
+      if (st_x) {
+#pragma unroll
+        for (int k = 0; k < D; ++k) ox[(int64_t)(t + 1) * P.ldx + k] = x[k];
+      }
     }
   }
+  if (SCORED && tid == 0 && P.score) {
+    P.score[0] = sse;
+    P.score[1] = sso;
+    P.score[2] = J;
+    P.score[3] = umax;
+  }
+}
+
+template <int PLANT, int KTYPE, int LPT>
+__global__ void __launch_bounds__(LPT == 1 ? 64 : 64 * PLANT_LOOP_MAX_WAVES) plant_loop_kernel(PlantLoopParams P) {
+  constexpr int D = PlantDim<PLANT>::value;
+  (void)D;
+  __shared__ double red[2][PLANT_LOOP_MAX_WAVES];  // one partial sum per wave, two buffers (parity of the step)
+  const int b = blockIdx.x;
+  PlantLoopUnit U;
+  U.Z = P.Z; U.winv = P.winv; U.w = P.w; U.m = P.m; U.reserved = 0; U.sigma0sq = P.sigma0sq;
+  U.x0 = P.x0 + (int64_t)b * P.x0_stride;
+  U.xref = P.xref + (int64_t)b * P.xref_stride;
+  U.out_x = P.out_x + (int64_t)b * (P.steps + 1) * P.ldx; U.ldx = P.ldx;
+  U.out_u = P.out_u + (int64_t)b * P.steps * P.ldu; U.ldu = P.ldu;
+  U.u_opt = nullptr; U.score = nullptr;
+  plant_loop_body<PLANT, KTYPE, LPT, false>(U, P.Ts, P.steps, red);
+}
+
+// the multi-model form: unit blockIdx.x of `table` (all units of a launch share KTYPE, LPT and the block size)
+template <int PLANT, int KTYPE, int LPT>
+__global__ void __launch_bounds__(LPT == 1 ? 64 : 64 * PLANT_LOOP_MAX_WAVES)
+    plant_loop_multi_kernel(const PlantLoopUnit* __restrict__ table, double Ts, int steps) {
+  __shared__ double red[2][PLANT_LOOP_MAX_WAVES];
+  const PlantLoopUnit U = table[blockIdx.x];
+  plant_loop_body<PLANT, KTYPE, LPT, true>(U, Ts, steps, red);
 }
 
 bool plant_loop_ok(int m) { return m >= 1 && m <= PLANT_LOOP_MAX_M; }
@@ -180,5 +253,83 @@ int launch_plant_loop(nk_ctx* ctx, const nk_model* mdl, int plant, double Ts, co
   return plant_loop_ktype<NK_PLANT_HJB>(ctx, mdl->ktype, P, batch);
 }
 int plant_loop_max_m() { return PLANT_LOOP_MAX_M; }
+
+// ---- multi-model form ------------------------------------------------------------------------------------------------
+static void plant_loop_class(int m, int* lpt, int* waves) {  // the workgroup shape nk_plant_loop gives a model of m landmarks
+  if (m <= 64) {
+    *lpt = 1;
+    *waves = 1;
+  } else {
+    *lpt = PLANT_LOOP_LPT;
+    *waves = (m + 64 * PLANT_LOOP_LPT - 1) / (64 * PLANT_LOOP_LPT);
+  }
+}
+
+template <int PLANT, int KTYPE>
+static void plant_loop_multi_launch(nk_ctx* ctx, const PlantLoopUnit* table, int count, int lpt, int waves, double Ts,
+                                    int steps) {
+  if (lpt == 1)
+    hipLaunchKernelGGL((plant_loop_multi_kernel<PLANT, KTYPE, 1>), dim3(count), dim3(64), 0, ctx->stream, table, Ts, steps);
+  else
+    hipLaunchKernelGGL((plant_loop_multi_kernel<PLANT, KTYPE, PLANT_LOOP_LPT>), dim3(count), dim3(64 * waves), 0,
+                       ctx->stream, table, Ts, steps);
+}
+template <int PLANT>
+static int plant_loop_multi_ktype(nk_ctx* ctx, int ktype, const PlantLoopUnit* table, int count, int lpt, int waves,
+                                  double Ts, int steps) {
+  switch (ktype) {
+    case NK_KERNEL_RBF: plant_loop_multi_launch<PLANT, NK_KERNEL_RBF>(ctx, table, count, lpt, waves, Ts, steps); break;
+    case NK_KERNEL_MATERN52: plant_loop_multi_launch<PLANT, NK_KERNEL_MATERN52>(ctx, table, count, lpt, waves, Ts, steps); break;
+    case NK_KERNEL_LINEAR: plant_loop_multi_launch<PLANT, NK_KERNEL_LINEAR>(ctx, table, count, lpt, waves, Ts, steps); break;
+    case NK_KERNEL_TPS: plant_loop_multi_launch<PLANT, NK_KERNEL_TPS>(ctx, table, count, lpt, waves, Ts, steps); break;
+    default: set_error("plant_loop_multi: unknown kernel type %d", ktype); return NK_ERR_BAD_ARG;
+  }
+  NK_HIP(hipGetLastError());
+  return NK_OK;
+}
+
+// units: host records holding device pointers, ktypes: the kernel family of each.  The records are sorted into classes of
+// (kernel family, landmarks per lane, waves) -- stable, so the order inside a class is the caller's --, staged with ONE
+// copy and run with one launch per class.  `units` is reordered in place and must stay alive until the stream has been
+// synchronised (the copy reads it).
+int launch_plant_loop_multi(nk_ctx* ctx, int plant, double Ts, int steps, PlantLoopUnit* units, const int* ktypes,
+                            int n_units) {
+  NK_REQUIRE(plant_dim(plant) > 0 && steps >= 1 && n_units >= 1, "plant_loop_multi: bad sizes");
+  struct Key { int ktype, lpt, waves, idx; };
+  std::vector<Key> keys((size_t)n_units);
+  for (int u = 0; u < n_units; ++u) {
+    NK_REQUIRE(plant_loop_ok(units[u].m), "plant_loop_multi: unit %d: bad m", u);
+    keys[u].ktype = ktypes[u];
+    keys[u].idx = u;
+    plant_loop_class(units[u].m, &keys[u].lpt, &keys[u].waves);
+  }
+  auto less = [](const Key& a, const Key& b) {
+    if (a.ktype != b.ktype) return a.ktype < b.ktype;
+    if (a.lpt != b.lpt) return a.lpt < b.lpt;
+    return a.waves < b.waves;
+  };
+  std::stable_sort(keys.begin(), keys.end(), less);
+  {
+    std::vector<PlantLoopUnit> sorted((size_t)n_units);
+    for (int u = 0; u < n_units; ++u) sorted[u] = units[keys[u].idx];
+    std::copy(sorted.begin(), sorted.end(), units);
+  }
+  PlantLoopUnit* table = nullptr;
+  NK_TRY(arena_alloc_t(ctx, (size_t)n_units, &table));
+  NK_HIP(hipMemcpyAsync(table, units, sizeof(PlantLoopUnit) * (size_t)n_units, hipMemcpyHostToDevice, ctx->stream));
+  for (int b = 0; b < n_units;) {
+    int e = b + 1;
+    while (e < n_units && !less(keys[b], keys[e])) ++e;
+    const Key& k = keys[b];
+    if (plant == NK_PLANT_DUFFING)
+      NK_TRY(plant_loop_multi_ktype<NK_PLANT_DUFFING>(ctx, k.ktype, table + b, e - b, k.lpt, k.waves, Ts, steps));
+    else if (plant == NK_PLANT_DOUBLE_INTEGRATOR)
+      NK_TRY(plant_loop_multi_ktype<NK_PLANT_DOUBLE_INTEGRATOR>(ctx, k.ktype, table + b, e - b, k.lpt, k.waves, Ts, steps));
+    else
+      NK_TRY(plant_loop_multi_ktype<NK_PLANT_HJB>(ctx, k.ktype, table + b, e - b, k.lpt, k.waves, Ts, steps));
+    b = e;
+  }
+  return NK_OK;
+}
 
 }  // namespace nk

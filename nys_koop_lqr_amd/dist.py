@@ -39,18 +39,20 @@ def shard_units(n_units, rank, world):
 
 
 def all_gather_scores(local_scores, n_units, rank, world):
-    """One all-gather of fixed-size per-rank score vectors (NaN padded); returns the (n_units,) array in unit order."""
+    """One all-gather of fixed-size per-rank score vectors (NaN padded); returns the (n_units,) array in unit order
+    ((n_units, k) when every unit carries k numbers)."""
     import torch
     import torch.distributed as dist
     per = (n_units + world - 1) // world
-    buf = np.full(per, np.nan)
+    local_scores = np.asarray(local_scores, dtype=np.float64)  # (n_local,) or (n_local, k): k numbers per unit
+    buf = np.full((per,) + local_scores.shape[1:], np.nan)
     buf[: len(local_scores)] = local_scores
     use_cuda = dist.get_backend() == "nccl"
     dev = torch.device("cuda", torch.cuda.current_device()) if use_cuda else torch.device("cpu")
     mine = torch.from_numpy(buf).to(dev)
     gathered = [torch.empty_like(mine) for _ in range(world)]
     dist.all_gather(gathered, mine)
-    out = np.full(n_units, np.nan)
+    out = np.full((n_units,) + local_scores.shape[1:], np.nan)
     for r in range(world):
         idx = shard_units(n_units, r, world)
         out[idx] = gathered[r].cpu().numpy()[: len(idx)]
@@ -134,6 +136,22 @@ def sharded_sysid_sweep(X, Y, n_inputs, params, ms, seeds, trajs, controls, test
                                     batch, batch_groups, unit_fn)
     flat = all_gather_scores(local, len(units), rank, world) if world > 1 else local
     return harness.sysid_table(units, flat, len(seeds), len(ms))
+
+
+def sharded_lqr_sweep(X, Y, n_inputs, params, ms, seeds, plant, x0, x_ref, num_steps, estimator="nystrom", gain_fn=None,
+                      c=1.0, u_opt=None, batch=32, workers=4, centers=None, fit_fn=None, loop_fn=None):
+    """Distributed counterpart of harness.lqr_sweep: every rank plans the same units with the same draws, the units are
+    dealt round-robin (shard_units), every rank fits, solves and runs its share on its own GPU (one plant_loop_multi call
+    per rank) and ONE all-gather assembles the four scores of every unit.  Trajectories stay on their ranks.  Every rank
+    returns the same dict of (len(seeds), len(ms)) tables (harness.lqr_sweep without `timing` and trajectories)."""
+    import torch.distributed as dist
+    rank, world = (dist.get_rank(), dist.get_world_size()) if dist.is_initialized() else (0, 1)
+    units = harness.lqr_plan(X, Y, n_inputs, params, ms, seeds, estimator, centers)
+    mine = shard_units(len(units), rank, world)
+    local, _, _, _ = harness.lqr_run_units(X, Y, n_inputs, params, [units[u] for u in mine], plant, x0, x_ref, num_steps,
+                                           estimator, gain_fn, c, u_opt, batch, workers, False, fit_fn, loop_fn)
+    flat = all_gather_scores(local, len(units), rank, world) if world > 1 else local
+    return harness.lqr_result(units, flat, None, None, len(seeds), len(ms))
 
 
 def sample_sharded_fit(reg, X_local, Y_local, landmark_rows=None):

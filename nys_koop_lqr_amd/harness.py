@@ -479,6 +479,265 @@ def control_rmse_percent(us, u_opt):
     return np.sqrt(np.sum(np.square(us - u_opt))) / np.sqrt(np.sum(np.square(u_opt))) * 100
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# the multi-seed CONTROL sweep (benchmark_lqr_classic.py:256-299, benchmark_lqr_hjb.py:265-333)
+# ---------------------------------------------------------------------------------------------------------------
+SCORE_NAMES = ("sse_u", "ss_opt", "J", "u_absmax")
+
+
+def rmse_control_percent(sse_u, ss_opt):
+    """benchmark_lqr_hjb.py:313 from the two sums: 100 sqrt(sum (u - u_opt)^2) / sqrt(sum u_opt^2)."""
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return 100.0 * np.sqrt(np.asarray(sse_u, dtype=np.float64)) / np.sqrt(np.asarray(ss_opt, dtype=np.float64))
+
+
+def control_scores(states, controls, u_opt=None):
+    """The four scores of nk_plant_loop_multi on the host, in the device's order of operations, from one loop's visited
+    states (d, steps + 1) (x0 first) and controls (steps,) / (1, steps): sse_u and ss_opt (step order; 0 without u_opt),
+    J = the cost of open_loop_control (benchmark_lqr_hjb.py:99-107: J = sum_k x0_k^2, then (J + sum_k x_{t+1,k}^2) + u_t^2)
+    and u_absmax (NaN from the first NaN control on); plus rmse_control (benchmark_lqr_hjb.py:313).  Returns a dict of
+    floats.  Needs no GPU."""
+    xs = np.asarray(states, dtype=np.float64)
+    xs = xs.reshape(1, -1) if xs.ndim == 1 else xs
+    us = np.asarray(controls, dtype=np.float64).reshape(-1)
+    steps = us.size
+    if xs.shape[1] != steps + 1:
+        raise ValueError(f"states have shape {xs.shape}, expected (d, {steps + 1})")
+    uo = None if u_opt is None else np.asarray(u_opt, dtype=np.float64).reshape(-1)
+    if uo is not None and uo.size != steps:
+        raise ValueError(f"u_opt has {uo.size} entries, the loop has {steps} steps")
+
+    def sumsq(col):
+        acc = float(col[0]) * float(col[0])
+        for v in col[1:]:
+            acc = acc + float(v) * float(v)
+        return acc
+
+    J, sse, sso, umax = sumsq(xs[:, 0]), 0.0, 0.0, 0.0
+    for t in range(steps):
+        u = float(us[t])
+        J = (J + sumsq(xs[:, t + 1])) + u * u
+        au = abs(u)
+        if au > umax or au != au:
+            umax = au
+        if uo is not None:
+            df = u - float(uo[t])
+            sse = sse + df * df
+            sso = sso + float(uo[t]) * float(uo[t])
+    return dict(sse_u=sse, ss_opt=sso, J=J, u_absmax=umax, rmse_control=float(rmse_control_percent(sse, sso)))
+
+
+def hjb_optimal_control(x0, num_steps, plant):
+    """The analytic optimum the HJB driver compares against (benchmark_lqr_hjb.py:304-311), on the host: from x0,
+    u = x^3 - x sqrt(1 + x^4), x <- plant(x, u), J <- J + x^2 + u^2 starting at x0^2.  Returns (u_opt (num_steps,), J_true)."""
+    x = np.asarray(x0, dtype=np.float64).reshape(-1, 1)
+    J = x ** 2
+    u_opt = np.empty(int(num_steps))
+    for i in range(int(num_steps)):
+        u = x ** 3 - x * np.sqrt(1 + x ** 4)
+        u_opt[i] = u.squeeze()
+        x = np.asarray(plant.update_SOM(x, u), dtype=np.float64).reshape(-1, 1)
+        J = J + x ** 2 + u ** 2
+    return u_opt, float(np.squeeze(J))
+
+
+def _broadcast_states(x, n, d, what):
+    x = np.asarray(x, dtype=np.float64)
+    if x.size == d:
+        return np.ascontiguousarray(np.broadcast_to(x.reshape(1, d), (n, d)))
+    if x.size != n * d:
+        raise ValueError(f"{what} has shape {x.shape}, expected one state of dimension {d} or {(n, d)}")
+    return np.ascontiguousarray(x.reshape(n, d))
+
+
+def plant_loop_multi(regressors, gains, x0s, x_refs, num_steps, plant, u_opt=None, return_trajectories=False,
+                     uopt_rows=None):
+    """One closed loop around the TRUE plant per (regressor, gain, x0, x_ref) unit -- lqr_control, open_loop_control and
+    the control RMSE of benchmark_lqr_hjb.py:73-107,313 -- for all units in ONE device call (nk_plant_loop_multi).  Unit u
+    is bit for bit regressors[u].closed_loop_plant(gains[u], x0s[u], x_refs[u], num_steps, plant); the units may mix model
+    kinds, kernels and landmark counts.  x0s, x_refs: (n_units, d) or one state for all.  u_opt: (num_steps,) scored
+    against by every unit, or (k, num_steps) with uopt_rows[u] = the row of unit u (-1: none; default: row u when
+    k = n_units > 1, else row 0).
+    Returns a dict of (n_units,) arrays sse_u, ss_opt, J, u_absmax (see include/nyskoop.h) and rmse_control =
+    100 sqrt(sse_u) / sqrt(ss_opt); with return_trajectories also states (n_units, num_steps + 1, d) and controls
+    (n_units, num_steps).  Without them nothing but the scores leaves the device."""
+    regs = list(regressors)
+    n = len(regs)
+    plant_id, Ts = getattr(plant, "plant_id", None), getattr(plant, "Ts", None)
+    if plant_id is None or Ts is None:
+        raise ValueError("plant must be one of the package's dynamical systems (plant_id) with its step length Ts set")
+    d = int(plant.n_states)
+    ctx = _lib.get_context()
+    handles = [r._ensure_model() for r in regs]
+    Ks = []
+    for r, K in zip(regs, gains):
+        K = np.ascontiguousarray(K, dtype=np.float64)
+        m = r._landmark_shape()[1]
+        if K.size != m:
+            raise ValueError(f"gain has shape {K.shape}, expected {(1, m)}")
+        Ks.append(K)
+    if len(Ks) != n:
+        raise ValueError(f"{len(Ks)} gains for {n} regressors")
+    rows = uopt_rows
+    if u_opt is not None:
+        uo = np.asarray(u_opt, dtype=np.float64).reshape(-1, int(num_steps))
+        if rows is None:
+            rows = list(range(n)) if uo.shape[0] == n and n > 1 else [0] * n
+    sc, ox, ou = ctx.plant_loop_multi(plant_id, Ts, num_steps, handles, Ks, _broadcast_states(x0s, n, d, "x0s"),
+                                      _broadcast_states(x_refs, n, d, "x_refs"), u_opt=None if u_opt is None else uo,
+                                      uopt_rows=rows, want_x=return_trajectories, want_u=return_trajectories)
+    out = {name: sc[:, i].copy() for i, name in enumerate(SCORE_NAMES)}
+    out["rmse_control"] = rmse_control_percent(out["sse_u"], out["ss_opt"])
+    if return_trajectories:
+        out["states"], out["controls"] = ox, ou
+    return out
+
+
+def lqr_default_gain(c=1.0):
+    """gain_fn of lqr_sweep: K = dlqr(A, B, c C^T C symmetrised, I), the arithmetic of regressor.solve_lqr(c=c)."""
+    from .lqr import dlqr
+
+    def gain(A, B, C):
+        Q = c * C.T @ C
+        Q = (Q + Q.T) / 2
+        return dlqr(A, B, Q, np.eye(np.shape(B)[1]))[0]
+
+    return gain
+
+
+def lqr_plan(X, Y, n_inputs, params, ms, seeds, estimator="nystrom", centers=None):
+    """The units of lqr_sweep: sysid_plan's per-seed protocol (one np.random.RandomState(seed) per seed walked in the
+    reference's order, m minor; all rows train) with one slot per (seed, m).  Needs no GPU."""
+    return sysid_plan(X, Y, n_inputs, params, ms, seeds, [[0]] * len(seeds), None, estimator, 0,
+                      None if centers is None else {(int(s), 0, k): v for (s, k), v in centers.items()})
+
+
+def lqr_fit_unit(X, Y, n_inputs, params, unit, estimator="nystrom"):
+    """The fit of one planned unit on the calling thread's context, operators fetched; returns the fitted regressor, or
+    None when the fit fails numerically."""
+    m = unit["m"]
+    if estimator == "spline":
+        reg = KoopmanSplineRegressor(n_inputs, state_bounds_params=params.get("state_bounds_params"), m=m,
+                                     gamma=params["gamma"])
+        reg.centers = np.asarray(unit["marks"], dtype=np.float64)
+    else:
+        reg = KoopmanNystromRegressor(n_inputs, **dict(params, m=m))
+        reg.nystrom_centers_output = np.ascontiguousarray(np.asarray(Y)[unit["marks"]].T)
+    try:
+        reg.fit(X, Y, row_ranges=unit["ranges"])
+    except np.linalg.LinAlgError:
+        return None
+    except _lib.NyskoopError as e:
+        if e.code != -5:
+            raise
+        return None
+    return reg
+
+
+def lqr_run_units(X, Y, n_inputs, params, units, plant, x0, x_ref, num_steps, estimator="nystrom", gain_fn=None, c=1.0,
+                  u_opt=None, batch=32, workers=4, return_trajectories=False, fit_fn=None, loop_fn=None):
+    """Scores of planned units, in their order: an (n_units, 4) array (SCORE_NAMES; NaN for a unit whose fit or gain
+    failed), the trajectories (or None, None) and the wall-clock split.  fit_fn / loop_fn stand in for lqr_fit_unit /
+    plant_loop_multi (rehearsals without a GPU; with a fit_fn the fits run as a plain loop)."""
+    import time
+    X = np.ascontiguousarray(X, dtype=np.float64)
+    Y = np.ascontiguousarray(Y, dtype=np.float64)
+    gain_fn = gain_fn or lqr_default_gain(c)
+    loop_fn = loop_fn or plant_loop_multi
+    n = len(units)
+    gain_s = [0.0] * n
+
+    def gain_of(i, reg):
+        t0 = time.perf_counter()
+        try:
+            return np.asarray(gain_fn(np.asarray(reg.A), np.asarray(reg.B), np.asarray(reg.C)), dtype=np.float64)
+        finally:
+            gain_s[i] = time.perf_counter() - t0
+
+    pool = _lib.worker_pool(max(1, int(workers)))
+    regs, futures = [None] * n, [None] * n
+    t0 = time.perf_counter()
+    lockstep = fit_fn is None and batch > 1 and n > 1
+    fit = (lambda u: (fit_fn or lqr_fit_unit)(X, Y, n_inputs, params, u, estimator))
+    step = int(batch) if lockstep else 1
+    lpool = _lib.lockstep_pool(step) if lockstep else None
+    for r in range(0, n, step):
+        idx = list(range(r, min(r + step, n)))
+        fitted = lpool.run_round(fit, [units[i] for i in idx]) if lockstep else [fit(units[i]) for i in idx]
+        for i, reg in zip(idx, fitted):  # the gains of this round are solved on the host while the next round fits
+            regs[i] = reg
+            if reg is not None:
+                futures[i] = pool.submit(gain_of, i, reg)
+    t1 = time.perf_counter()
+    gains = [None] * n
+    for i, f in enumerate(futures):
+        if f is not None:
+            try:
+                gains[i] = f.result()
+            except Exception:  # noqa: BLE001 -- a unit without a gain scores NaN, like GridSearchCV's error_score=nan
+                gains[i] = None
+    t2 = time.perf_counter()
+    live = [i for i in range(n) if gains[i] is not None]
+    scores = np.full((n, len(SCORE_NAMES)), np.nan)
+    states = controls = None
+    if live:
+        res = loop_fn([regs[i] for i in live], [gains[i] for i in live], x0, x_ref, num_steps, plant, u_opt=u_opt,
+                      return_trajectories=return_trajectories)
+        for k, name in enumerate(SCORE_NAMES):
+            scores[live, k] = res[name]
+        if return_trajectories:
+            states = np.full((n,) + np.shape(res["states"])[1:], np.nan)
+            controls = np.full((n,) + np.shape(res["controls"])[1:], np.nan)
+            states[live], controls[live] = res["states"], res["controls"]
+    t3 = time.perf_counter()
+    timing = dict(fit_s=t1 - t0, gain_wait_s=t2 - t1, loop_s=t3 - t2, gain_cpu_s=float(sum(gain_s)), total_s=t3 - t0)
+    return scores, states, controls, timing
+
+
+def lqr_table(units, values, n_seeds, n_ms):
+    """(seed, m) table from per-unit values in plan order: sysid_table with its single test slot dropped; per-unit arrays
+    (trajectories) keep their trailing axes."""
+    values = np.asarray(values, dtype=np.float64)
+    if values.ndim == 1:
+        return sysid_table(units, values, n_seeds, n_ms)[:, 0, :]
+    out = np.full((n_seeds, n_ms) + values.shape[1:], np.nan)
+    for u, v in zip(units, values):
+        out[u["si"], u["k"]] = v
+    return out
+
+
+def lqr_sweep(X, Y, n_inputs, params, ms, seeds, plant, x0, x_ref, num_steps, estimator="nystrom", gain_fn=None, c=1.0,
+              u_opt=None, batch=32, workers=4, return_trajectories=False, centers=None, fit_fn=None, loop_fn=None):
+    """The control branch of the reference's one-input drivers (benchmark_lqr_classic.py:256-299: seeds x {Nystrom,
+    splines}; benchmark_lqr_hjb.py:265-333: seeds x m) as one call: for every seed and every m in `ms`
+    fit -> K = dlqr(A, B, c C^T C, I) -> `num_steps` feedback steps around the true plant -> replay cost and control scores.
+      draws:  sysid_plan's per-seed protocol (lqr_plan): one RandomState(seed) per seed, reference order; `centers`
+              {(seed, k): landmarks} replaces them;
+      fits:   `batch` at a time through the lock-step pool (batch <= 1: a plain loop; same bits);
+      gains:  gain_fn(A, B, C) -> K (1 x m) (default lqr_default_gain(c): the host Riccati solve), computed in `workers`
+              host threads while later rounds fit; a unit whose gain raises gets NaN scores and is not run;
+      loops:  ONE plant_loop_multi call over all surviving units, scored on the device (u_opt: (num_steps,) or None).
+    x0, x_ref: one state each, shared by the units.  Returns a dict of (len(seeds), len(ms)) tables sse_u, ss_opt, J,
+    u_absmax, rmse_control, the planned `units`, the wall-clock split `timing` (fit_s, gain_wait_s, loop_s; gain_cpu_s =
+    host seconds summed over the gain solves, which overlap the fits) and, with return_trajectories, states
+    (len(seeds), len(ms), num_steps + 1, d) and controls (len(seeds), len(ms), num_steps)."""
+    _check_estimator(estimator)
+    units = lqr_plan(X, Y, n_inputs, params, ms, seeds, estimator, centers)
+    scores, states, controls, timing = lqr_run_units(X, Y, n_inputs, params, units, plant, x0, x_ref, num_steps, estimator,
+                                                     gain_fn, c, u_opt, batch, workers, return_trajectories, fit_fn, loop_fn)
+    return lqr_result(units, scores, states, controls, len(seeds), len(ms), timing)
+
+
+def lqr_result(units, scores, states, controls, n_seeds, n_ms, timing=None):
+    """The dict lqr_sweep returns, from per-unit values in plan order."""
+    out = {name: lqr_table(units, scores[:, k], n_seeds, n_ms) for k, name in enumerate(SCORE_NAMES)}
+    out["rmse_control"] = rmse_control_percent(out["sse_u"], out["ss_opt"])
+    out["units"], out["timing"] = units, timing
+    if states is not None:
+        out["states"], out["controls"] = lqr_table(units, states, n_seeds, n_ms), lqr_table(units, controls, n_seeds, n_ms)
+    return out
+
+
 def create_data_matrices(trajs, controls, indices):
     """benchmark_lqr_cloth.py:117-130: snapshot pairs from trajectories (d x T) and controls (p x T)."""
     states = np.hstack([trajs[i][:, :-1] for i in indices])
