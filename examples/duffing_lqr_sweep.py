@@ -6,8 +6,12 @@ the true oscillator from (-0.5, 0) to the origin and score the run -- the fits i
 them, and all closed loops of an estimator in ONE device call (nk_plant_loop_multi) that returns four numbers per unit.
 Needs an MI355X (the library has no CPU path):
 
-    python3 examples/duffing_lqr_sweep.py
+    python3 examples/duffing_lqr_sweep.py [--gain device]
+
+--gain device solves all gains of an estimator in ONE call of the batched device Riccati solver (nk_model_lqr_gain_batch)
+after the fits instead of scipy in host threads (the default, and the choice for replaying the reference's numbers).
 """
+import argparse
 import os
 import sys
 
@@ -16,6 +20,10 @@ import numpy as np
 
 import nys_koop_lqr_amd as nk
 from nys_koop_lqr_amd import harness
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--gain", choices=("host", "device"), default="host")
+gain = ap.parse_args().gain
 
 G = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
 g = np.load(os.path.join(G, "f12_duffing_full.npz"))
@@ -26,7 +34,7 @@ configs = {"nystrom": dict(kernel=nk.KernelWrapper([1, 1]), gamma=float(g["gamma
            "spline": dict(gamma=1e-6, state_bounds_params=(1.0, 2.0))}
 
 for estimator, params in configs.items():
-    res = harness.lqr_sweep(X, Y, 1, params, [20], seeds, plant, x0, ref, steps, estimator=estimator, batch=8)
+    res = harness.lqr_sweep(X, Y, 1, params, [20], seeds, plant, x0, ref, steps, estimator=estimator, batch=8, gain=gain)
     J, umax, tm = res["J"][:, 0], res["u_absmax"][:, 0], res["timing"]
     ok = np.isfinite(J)
     print(f"{estimator:8s}: {ok.sum()}/{len(seeds)} units ran; cost J median {np.median(J[ok]):.4f} "
@@ -34,6 +42,7 @@ for estimator, params in configs.items():
           f"fits {tm['fit_s']:.2f} s, waiting for gains {tm['gain_wait_s']:.2f} s, closed loops {tm['loop_s'] * 1e3:.1f} ms")
 
 # one unit with its trajectory, against the reference's recorded run of seed 0
-one = harness.lqr_sweep(X, Y, 1, configs["nystrom"], [20], [0], plant, x0, ref, steps, return_trajectories=True)
+one = harness.lqr_sweep(X, Y, 1, configs["nystrom"], [20], [0], plant, x0, ref, steps, return_trajectories=True,
+                        gain=gain)
 us = one["controls"][0, 0]
 print("seed 0 controls vs the reference's run:", float(np.linalg.norm(us - g["lqr_us_0"][0]) / np.linalg.norm(g["lqr_us_0"])))

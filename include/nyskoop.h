@@ -424,6 +424,45 @@ typedef struct nk_plant_unit {
 } nk_plant_unit;
 int nk_plant_loop_multi(nk_ctx* ctx, int plant, double Ts, int32_t steps, const nk_plant_unit* units, int32_t n_units,
                         const double* u_opt, int32_t n_uopt, double* out_x, double* out_u, double* scores);
+/* ---- the gains of the sweep: K = dlqr(A, B, Q, R) (benchmark_lqr_hjb.py:293,356, benchmark_lqr_classic.py:288,
+ *   benchmark_lqr_cloth.py:262: control.dlqr) for MANY independent problems in one call.  P solves the discrete algebraic
+ *   Riccati equation A'PA - P - A'PB (R + B'PB)^-1 B'PA + Q = 0 by the structure-preserving doubling iteration
+ *     A_0 = A, G_0 = B R^-1 B', H_0 = Q;  W = I + G H,  [X_A | X_G] = W^-1 [A_k | G],
+ *     A+ = A_k X_A,  G+ = sym(G + A_k X_G A_k'),  H+ = H + sym(A_k' H X_A),
+ *   stopped when |H+ - H|_1 <= tol |H+|_1 or after max_iter steps (the reference values are tol = 1e-13, max_iter = 40);
+ *   P = H and K = (R + B'PB)^-1 B'PA.  One workgroup owns one problem from start to finish (products on the fp64 matrix
+ *   pipe, LU with partial row pivoting for W), so a problem's results do not depend on what else the call holds or in
+ *   which order.  Limits: 1 <= m <= 256, 1 <= p <= 8.  Per problem the device workspace is 7 M^2 doubles, M = m rounded up
+ *   to 16; the library issues launches in chunks so that the workspace of one launch stays under NK_DARE_WS_CAP_BYTES.
+ *   out_status[u]: 0 = converged; 1 = max_iter reached; 2 = non-finite values, a zero or non-finite pivot of W, or R /
+ *   R + B'PB not positive definite.  For a status other than 0 the problem's out_K and out_P are NaN; the other problems of
+ *   the call are not affected.  out_iters[u] (may be NULL) = steps taken.
+ *   Everything is checked before anything is queued; a bad problem is NK_ERR_BAD_ARG with its index in nk_last_error(),
+ *   and no output is written.  All operands and results are HOST memory (staged with one copy per array kind).  Ordinary
+ *   contexts only (not lock-step members). */
+#define NK_DARE_WS_CAP_BYTES (1ll << 30)
+typedef struct nk_dare_problem {
+  int32_t m, p;
+  const double* A; int64_t lda;  /* m x m */
+  const double* B; int64_t ldb;  /* m x p */
+  const double* Q; int64_t ldq;  /* m x m, symmetric positive semi-definite */
+  const double* R; int64_t ldr;  /* p x p, symmetric positive definite */
+  double* out_K;                 /* p x m, dense */
+  double* out_P;                 /* m x m, dense; NULL skips the copy */
+  double* out_delta;             /* the last relative step |H+ - H|_1 / |H+|_1 (NaN if no step was taken); may be NULL */
+} nk_dare_problem;
+int nk_dare_batch(nk_ctx* ctx, const nk_dare_problem* problems, int32_t n, double tol, int32_t max_iter,
+                  int32_t* out_status, int32_t* out_iters);
+/* The sweep's entry: the gains of n fitted models, K_u = dlqr(A_u, B_u, c sym(C_u'C_u), R), read from the models' device
+ * allocations; the cost is formed on the device by the solver's own product and only the gains travel back.
+ * R: HOST, p x p dense (then every model has p inputs), or NULL for the identity.  out_K: HOST, the gains back to back
+ * (model u: p_u x m_u, dense).  Status, limits and checks as in nk_dare_batch.  Models need not belong to ctx: only the
+ * device must match (models fitted by lock-step members are accepted); the call itself is for ordinary contexts.
+ * nk_model_lqr_cost returns the cost matrix c sym(C'C) (m x m) exactly as the solver forms it, so that nk_dare_batch fed
+ * nk_model_get's operators and this matrix reproduces nk_model_lqr_gain_batch bit for bit. */
+int nk_model_lqr_gain_batch(nk_ctx* ctx, const nk_model* const* models, int32_t n, double c, const double* R_or_NULL,
+                            double tol, int32_t max_iter, double* out_K, int32_t* out_status, int32_t* out_iters);
+int nk_model_lqr_cost(nk_ctx* ctx, const nk_model* model, double c, double* Q, int64_t ldq);
 /* ---- rollout of explicit operators without a model (any estimator that exposes A, B, C: the exact-kernel comparator of
  *   benchmark_lqr_hjb.py:334-381, un-pickled gains): z0: batch x m lifted initial states; A: m x m, B: m x p, C: d x m
  *   (row-major, host or device); U, out_x, out_z as in nk_rollout. --------------------------------------------------- */

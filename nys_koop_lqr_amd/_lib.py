@@ -52,6 +52,13 @@ class PlantUnit(C.Structure):
                 ("uopt", C.c_int32), ("reserved", C.c_int32)]
 
 
+class DareProblem(C.Structure):
+    """nk_dare_problem (include/nyskoop.h), one problem of nk_dare_batch."""
+    _fields_ = [("m", C.c_int32), ("p", C.c_int32), ("A", C.c_void_p), ("lda", C.c_int64), ("B", C.c_void_p),
+                ("ldb", C.c_int64), ("Q", C.c_void_p), ("ldq", C.c_int64), ("R", C.c_void_p), ("ldr", C.c_int64),
+                ("out_K", C.c_void_p), ("out_P", C.c_void_p), ("out_delta", C.c_void_p)]
+
+
 class FitStats(C.Structure):
     _fields_ = [("ms_total", C.c_double), ("ms_upload", C.c_double), ("ms_kmat", C.c_double),
                 ("ms_gram", C.c_double), ("ms_sqrt", C.c_double), ("ms_solve", C.c_double),
@@ -128,6 +135,10 @@ SIGNATURES = {
     "nk_plant_step": (C.c_int, [C.c_int, _D, _P, _P, _P]),
     "nk_plant_loop": (C.c_int, [_P, _P, C.c_int, _D, _P, _P, _P, _I32, _I32, _P, _P]),
     "nk_plant_loop_multi": (C.c_int, [_P, C.c_int, _D, _I32, C.POINTER(PlantUnit), _I32, _P, _I32, _P, _P, _P]),
+    "nk_dare_batch": (C.c_int, [_P, C.POINTER(DareProblem), _I32, _D, _I32, C.POINTER(_I32), C.POINTER(_I32)]),
+    "nk_model_lqr_gain_batch": (C.c_int, [_P, C.POINTER(_P), _I32, _D, _P, _D, _I32, _P, C.POINTER(_I32),
+                                          C.POINTER(_I32)]),
+    "nk_model_lqr_cost": (C.c_int, [_P, _P, _D, _P, _I64]),
     "nk_linear_rollout": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P]),
     "nk_gemm_f32": (C.c_int, [_P, _I64, _I64, _I64, _P, _I64, _P, _I64, _P, _I64]),
     "nk_gemm": (C.c_int, [_P, C.c_int, C.c_int, _I64, _I64, _I64, _D, _P, _I64, _P, _I64, _D, _P, _I64]),
@@ -359,6 +370,87 @@ class Context:
             raise ValueError(self.lib.nk_last_error().decode())
         check(rc)
         return sc, ox, ou
+
+    def dare_batch(self, As, Bs, Qs, Rs, tol=1e-13, max_iter=40, want_P=True):
+        """nk_dare_batch: K = dlqr(A, B, Q, R) for every problem of the lists in one call, one workgroup per problem.
+        Returns (Ks, Ps or None, status, iterations, deltas): lists of (p, m) and (m, m) arrays and int32 / float64
+        arrays of length n; status 0 = converged, 1 = max_iter reached, 2 = non-finite / singular (outputs NaN)."""
+        n = len(As)
+        if not (len(Bs) == len(Qs) == len(Rs) == n):
+            raise ValueError("As, Bs, Qs, Rs must have the same length")
+        arr = (DareProblem * max(n, 1))()
+        keep, Ks, Ps = [], [], []
+        delta = np.full(max(n, 1), np.nan)
+        for i in range(n):
+            A = np.ascontiguousarray(As[i], dtype=np.float64)
+            if A.ndim != 2 or A.shape[0] != A.shape[1]:
+                raise ValueError(f"problem {i}: A must be square, got {A.shape}")
+            m = A.shape[0]
+            B = np.ascontiguousarray(np.asarray(Bs[i], dtype=np.float64).reshape(m, -1))
+            p = B.shape[1]
+            Q = np.ascontiguousarray(np.asarray(Qs[i], dtype=np.float64).reshape(m, m))
+            R = np.ascontiguousarray(np.asarray(Rs[i], dtype=np.float64).reshape(p, p))
+            K = np.full((p, m), np.nan)
+            P = np.full((m, m), np.nan) if want_P else None
+            keep.append((A, B, Q, R))
+            Ks.append(K)
+            Ps.append(P)
+            a = arr[i]
+            a.m, a.p = m, p
+            a.A, a.lda, a.B, a.ldb = A.ctypes.data, max(m, 1), B.ctypes.data, max(p, 1)
+            a.Q, a.ldq, a.R, a.ldr = Q.ctypes.data, max(m, 1), R.ctypes.data, max(p, 1)
+            a.out_K = K.ctypes.data
+            a.out_P = P.ctypes.data if want_P else None
+            a.out_delta = delta.ctypes.data + 8 * i
+        status = np.full(max(n, 1), -1, dtype=np.int32)
+        iters = np.zeros(max(n, 1), dtype=np.int32)
+        rc = self.lib.nk_dare_batch(self.handle, arr, n, float(tol), int(max_iter),
+                                    status.ctypes.data_as(C.POINTER(_I32)), iters.ctypes.data_as(C.POINTER(_I32)))
+        if rc == -1:
+            raise ValueError(self.lib.nk_last_error().decode())
+        check(rc)
+        return Ks, (Ps if want_P else None), status[:n], iters[:n], delta[:n]
+
+    def model_lqr_gain_batch(self, models, c, R=None, tol=1e-13, max_iter=40, dims=None):
+        """nk_model_lqr_gain_batch: K_u = dlqr(A_u, B_u, c sym(C_u'C_u), R) for n device models in one call (R = None: the
+        identity).  models: device-model handles; dims: their (m, p) pairs (queried with nk_model_dims when None).
+        Returns (Ks, status, iterations); a unit with status != 0 has a NaN gain."""
+        n = len(models)
+        hs = (_P * max(n, 1))()
+        for i, h in enumerate(models):
+            hs[i] = h.value if isinstance(h, C.c_void_p) else h
+        if dims is None:
+            dims = []
+            for i in range(n):
+                m, d, p = _I32(), _I32(), _I32()
+                check(self.lib.nk_model_dims(hs[i], C.byref(m), C.byref(d), C.byref(p)))
+                dims.append((m.value, p.value))
+        sizes = [int(m) * int(p) for m, p in dims]
+        out = np.full(max(sum(sizes), 1), np.nan)
+        Rm = None if R is None else np.ascontiguousarray(R, dtype=np.float64)
+        status = np.full(max(n, 1), -1, dtype=np.int32)
+        iters = np.zeros(max(n, 1), dtype=np.int32)
+        rc = self.lib.nk_model_lqr_gain_batch(self.handle, hs, n, float(c), None if Rm is None else Rm.ctypes.data,
+                                              float(tol), int(max_iter), out.ctypes.data,
+                                              status.ctypes.data_as(C.POINTER(_I32)), iters.ctypes.data_as(C.POINTER(_I32)))
+        if rc == -1:
+            raise ValueError(self.lib.nk_last_error().decode())
+        check(rc)
+        Ks, off = [], 0
+        for (m, p), sz in zip(dims, sizes):
+            Ks.append(out[off:off + sz].reshape(int(p), int(m)).copy())
+            off += sz
+        return Ks, status[:n], iters[:n]
+
+    def model_lqr_cost(self, model, m, c):
+        """nk_model_lqr_cost: the cost matrix c sym(C'C) (m x m) exactly as nk_model_lqr_gain_batch forms it."""
+        Q = np.empty((int(m), int(m)))
+        h = model.value if isinstance(model, C.c_void_p) else model
+        rc = self.lib.nk_model_lqr_cost(self.handle, h, float(c), Q.ctypes.data, int(m))
+        if rc == -1:
+            raise ValueError(self.lib.nk_last_error().decode())
+        check(rc)
+        return Q
 
     def set_kmat_mode(self, mode):
         """0 = automatic (Gram form on the MFMA engine for d >= 32), 1 = always direct differences."""

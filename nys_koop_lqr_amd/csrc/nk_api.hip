@@ -2915,6 +2915,206 @@ int nk_plant_loop_multi(nk_ctx* ctx, int plant, double Ts, int32_t steps, const 
   return NK_OK;
 }
 
+}  // extern "C"
+
+// One problem of the batched Riccati solver as the two entry points hand it over: operands in host memory (nk_dare_batch;
+// dense copies are packed and staged with one copy per array kind) or in a model's device allocation (the model entries).
+struct DareItem {
+  int m = 0, p = 0, d = 0;
+  const double *hA = nullptr, *hB = nullptr, *hQ = nullptr, *hR = nullptr;  // host operands ...
+  int64_t lda = 0, ldb = 0, ldq = 0, ldr = 0;
+  const double *dA = nullptr, *dB = nullptr, *dC = nullptr;                 // ... or device operands (lda, ldb; ldc = m)
+  double c = 0.0;
+  double *outK = nullptr, *outP = nullptr, *out_delta = nullptr;            // host results
+  int q_only = 0;
+};
+
+// Runs the items in launches whose workspace stays under NK_DARE_WS_CAP_BYTES; every argument has been checked.
+static int dare_run(nk_ctx* ctx, const std::vector<DareItem>& items, double tol, int max_iter, int32_t* out_status,
+                    int32_t* out_iters) {
+  const size_t n = items.size();
+  size_t b = 0;
+  while (b < n) {
+    size_t e = b, ws = 0;
+    while (e < n) {
+      const size_t w = dare_ws_doubles(dare_pad(items[e].m)) * 8;
+      if (e > b && ws + w > (size_t)NK_DARE_WS_CAP_BYTES) break;
+      ws += w;
+      ++e;
+    }
+    const size_t cnt = e - b;
+    const ArenaMark mk = arena_mark(ctx);
+    // host staging: one block per array kind, one block for the results
+    size_t nA = 0, nB = 0, nR = 0, nK = 0, nP = 0;
+    for (size_t u = b; u < e; ++u) {
+      const DareItem& it = items[u];
+      if (it.hA) { nA += (size_t)it.m * it.m; nB += (size_t)it.m * it.p; }
+      if (it.hR) nR += (size_t)it.p * it.p;
+      nK += (size_t)it.p * it.m;
+      if (it.outP) nP += (size_t)it.m * it.m;
+    }
+    std::vector<double> hA(nA), hQ(nA), hB(nB), hR(nR);
+    double *dA = nullptr, *dQ = nullptr, *dB = nullptr, *dR = nullptr, *dW = nullptr, *dOut = nullptr;
+    int* dInt = nullptr;
+    DareRec* dTab = nullptr;
+    if (nA) { NK_TRY(arena_alloc_t(ctx, nA, &dA)); NK_TRY(arena_alloc_t(ctx, nA, &dQ)); NK_TRY(arena_alloc_t(ctx, nB, &dB)); }
+    if (nR) NK_TRY(arena_alloc_t(ctx, nR, &dR));
+    NK_TRY(arena_alloc_t(ctx, ws / 8, &dW));
+    const size_t nOut = nK + nP + cnt;
+    NK_TRY(arena_alloc_t(ctx, nOut, &dOut));
+    NK_TRY(arena_alloc_t(ctx, 2 * cnt, &dInt));
+    NK_TRY(arena_alloc_t(ctx, cnt, &dTab));
+    std::vector<DareRec> recs(cnt);
+    size_t oA = 0, oB = 0, oR = 0, oK = 0, oP = nK, oW = 0;
+    for (size_t u = b; u < e; ++u) {
+      const DareItem& it = items[u];
+      DareRec& r = recs[u - b];
+      const int m = it.m, p = it.p;
+      r = DareRec{};
+      r.m = m; r.p = p; r.M = dare_pad(m); r.d = it.d; r.c = it.c; r.q_only = it.q_only;
+      if (it.hA) {
+        for (int i = 0; i < m; ++i) {
+          std::copy(it.hA + (int64_t)i * it.lda, it.hA + (int64_t)i * it.lda + m, hA.data() + oA + (size_t)i * m);
+          std::copy(it.hQ + (int64_t)i * it.ldq, it.hQ + (int64_t)i * it.ldq + m, hQ.data() + oA + (size_t)i * m);
+          std::copy(it.hB + (int64_t)i * it.ldb, it.hB + (int64_t)i * it.ldb + p, hB.data() + oB + (size_t)i * p);
+        }
+        r.A = dA + oA; r.lda = m; r.Q = dQ + oA; r.ldq = m; r.B = dB + oB; r.ldb = p;
+        oA += (size_t)m * m; oB += (size_t)m * p;
+      } else {
+        r.A = it.dA; r.lda = it.lda; r.B = it.dB; r.ldb = it.ldb; r.C = it.dC; r.ldc = m;
+      }
+      if (it.hR) {
+        for (int a = 0; a < p; ++a) std::copy(it.hR + (int64_t)a * it.ldr, it.hR + (int64_t)a * it.ldr + p, hR.data() + oR + (size_t)a * p);
+        r.R = dR + oR;
+        oR += (size_t)p * p;
+      }
+      r.ws = dW + oW; oW += dare_ws_doubles(r.M);
+      r.outK = dOut + oK; oK += (size_t)p * m;
+      if (it.outP) { r.outP = dOut + oP; oP += (size_t)m * m; }
+      r.delta = dOut + nK + nP + (u - b);
+      r.status = dInt + (u - b);
+      r.iters = dInt + cnt + (u - b);
+    }
+    if (nA) {
+      NK_HIP(hipMemcpyAsync(dA, hA.data(), nA * 8, hipMemcpyHostToDevice, ctx->stream));
+      NK_HIP(hipMemcpyAsync(dQ, hQ.data(), nA * 8, hipMemcpyHostToDevice, ctx->stream));
+      NK_HIP(hipMemcpyAsync(dB, hB.data(), nB * 8, hipMemcpyHostToDevice, ctx->stream));
+    }
+    if (nR) NK_HIP(hipMemcpyAsync(dR, hR.data(), nR * 8, hipMemcpyHostToDevice, ctx->stream));
+    NK_HIP(hipMemcpyAsync(dTab, recs.data(), cnt * sizeof(DareRec), hipMemcpyHostToDevice, ctx->stream));
+    NK_TRY(launch_dare(ctx, dTab, (int)cnt, tol, max_iter));
+    std::vector<double> hOut(nOut);
+    std::vector<int> hInt(2 * cnt);
+    NK_HIP(hipMemcpyAsync(hOut.data(), dOut, nOut * 8, hipMemcpyDeviceToHost, ctx->stream));
+    NK_HIP(hipMemcpyAsync(hInt.data(), dInt, 2 * cnt * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    NK_HIP(hipStreamSynchronize(ctx->stream));
+    oK = 0; oP = nK;
+    for (size_t u = b; u < e; ++u) {
+      const DareItem& it = items[u];
+      const size_t km = (size_t)it.p * it.m, mm = (size_t)it.m * it.m;
+      if (it.outK) std::copy(hOut.data() + oK, hOut.data() + oK + km, it.outK);
+      oK += km;
+      if (it.outP) { std::copy(hOut.data() + oP, hOut.data() + oP + mm, it.outP); oP += mm; }
+      if (it.out_delta) *it.out_delta = hOut[nK + nP + (u - b)];
+      if (out_status) out_status[u] = hInt[u - b];
+      if (out_iters) out_iters[u] = hInt[cnt + (u - b)];
+    }
+    arena_release(ctx, mk);
+    b = e;
+  }
+  return NK_OK;
+}
+
+static int dare_check_common(nk_ctx* ctx, const char* who, double tol, int32_t max_iter) {
+  NK_REQUIRE(!ctx_recording(ctx), "%s: not available to the members of a lock-step group", who);
+  NK_REQUIRE(std::isfinite(tol) && tol >= 0.0, "%s: tol must be finite and non-negative", who);
+  NK_REQUIRE(max_iter >= 1 && max_iter <= 1000, "%s: max_iter = %d must lie in 1 .. 1000", who, max_iter);
+  return NK_OK;
+}
+
+extern "C" {
+
+int nk_dare_batch(nk_ctx* ctx, const nk_dare_problem* problems, int32_t n, double tol, int32_t max_iter,
+                  int32_t* out_status, int32_t* out_iters) {
+  NK_TRY(check_ctx(ctx));
+  NK_TRY(dare_check_common(ctx, "nk_dare_batch", tol, max_iter));
+  NK_REQUIRE(problems != nullptr && n >= 1, "nk_dare_batch: n = %d problems at %p: at least one is needed", n,
+             (const void*)problems);
+  NK_REQUIRE(out_status != nullptr, "nk_dare_batch: out_status is null");
+  std::vector<DareItem> items((size_t)n);
+  for (int u = 0; u < n; ++u) {  // everything is checked before anything is queued
+    const nk_dare_problem& pr = problems[u];
+    NK_REQUIRE(pr.m >= 1 && pr.m <= DARE_MAX_M, "nk_dare_batch: problem %d: m = %d must lie in 1 .. %d", u, pr.m, DARE_MAX_M);
+    NK_REQUIRE(pr.p >= 1 && pr.p <= DARE_MAX_P, "nk_dare_batch: problem %d: p = %d must lie in 1 .. %d", u, pr.p, DARE_MAX_P);
+    NK_REQUIRE(pr.A && pr.B && pr.Q && pr.R && pr.out_K, "nk_dare_batch: problem %d: null argument", u);
+    NK_REQUIRE(pr.lda >= pr.m && pr.ldq >= pr.m && pr.ldb >= pr.p && pr.ldr >= pr.p,
+               "nk_dare_batch: problem %d: leading dimension too small", u);
+    NK_REQUIRE(!is_device_ptr(pr.A) && !is_device_ptr(pr.B) && !is_device_ptr(pr.Q) && !is_device_ptr(pr.R) &&
+                   !is_device_ptr(pr.out_K) && !is_device_ptr(pr.out_P) && !is_device_ptr(pr.out_delta),
+               "nk_dare_batch: problem %d: operands and results must be host memory", u);
+    DareItem& it = items[u];
+    it.m = pr.m; it.p = pr.p;
+    it.hA = pr.A; it.lda = pr.lda; it.hB = pr.B; it.ldb = pr.ldb; it.hQ = pr.Q; it.ldq = pr.ldq; it.hR = pr.R; it.ldr = pr.ldr;
+    it.outK = pr.out_K; it.outP = pr.out_P; it.out_delta = pr.out_delta;
+  }
+  return dare_run(ctx, items, tol, max_iter, out_status, out_iters);
+}
+
+static int dare_check_model(nk_ctx* ctx, const char* who, const nk_model* mdl, int u) {
+  NK_REQUIRE(mdl != nullptr, "%s: model %d is null", who, u);
+  NK_REQUIRE(mdl->device == ctx->device, "%s: model %d lives on device %d, the context on %d", who, u, mdl->device,
+             ctx->device);
+  NK_REQUIRE(mdl->has_ops, "%s: model %d has no fitted operators", who, u);
+  NK_REQUIRE(mdl->m >= 1 && mdl->m <= DARE_MAX_M, "%s: model %d: m = %d must lie in 1 .. %d", who, u, mdl->m, DARE_MAX_M);
+  NK_REQUIRE(mdl->p >= 1 && mdl->p <= DARE_MAX_P, "%s: model %d: p = %d must lie in 1 .. %d", who, u, mdl->p, DARE_MAX_P);
+  return NK_OK;
+}
+
+int nk_model_lqr_gain_batch(nk_ctx* ctx, const nk_model* const* models, int32_t n, double c, const double* R, double tol,
+                            int32_t max_iter, double* out_K, int32_t* out_status, int32_t* out_iters) {
+  NK_TRY(check_ctx(ctx));
+  NK_TRY(dare_check_common(ctx, "nk_model_lqr_gain_batch", tol, max_iter));
+  NK_REQUIRE(models != nullptr && n >= 1, "nk_model_lqr_gain_batch: n = %d models at %p: at least one is needed", n,
+             (const void*)models);
+  NK_REQUIRE(out_K != nullptr && out_status != nullptr, "nk_model_lqr_gain_batch: null output");
+  NK_REQUIRE(std::isfinite(c) && c >= 0.0, "nk_model_lqr_gain_batch: c must be finite and non-negative");
+  NK_REQUIRE(!is_device_ptr(out_K) && !is_device_ptr(R), "nk_model_lqr_gain_batch: R and out_K must be host memory");
+  std::vector<DareItem> items((size_t)n);
+  size_t off = 0;
+  for (int u = 0; u < n; ++u) {
+    const nk_model* mdl = models[u];
+    NK_TRY(dare_check_model(ctx, "nk_model_lqr_gain_batch", mdl, u));
+    NK_REQUIRE(R == nullptr || mdl->p == models[0]->p,
+               "nk_model_lqr_gain_batch: model %d has %d inputs, R is %d x %d", u, mdl->p, models[0]->p, models[0]->p);
+    DareItem& it = items[u];
+    it.m = mdl->m; it.p = mdl->p; it.d = mdl->d; it.c = c;
+    it.dA = mdl->A; it.dB = mdl->B; it.lda = it.ldb = mdl->m + mdl->p; it.dC = mdl->C;
+    it.hR = R; it.ldr = mdl->p;
+    it.outK = out_K + off;
+    off += (size_t)mdl->p * mdl->m;
+  }
+  return dare_run(ctx, items, tol, max_iter, out_status, out_iters);
+}
+
+int nk_model_lqr_cost(nk_ctx* ctx, const nk_model* model, double c, double* Q, int64_t ldq) {
+  NK_TRY(check_ctx(ctx));
+  NK_REQUIRE(!ctx_recording(ctx), "nk_model_lqr_cost: not available to the members of a lock-step group");
+  NK_TRY(dare_check_model(ctx, "nk_model_lqr_cost", model, 0));
+  NK_REQUIRE(Q != nullptr && ldq >= model->m && !is_device_ptr(Q), "nk_model_lqr_cost: Q must be host memory with ldq >= m");
+  NK_REQUIRE(std::isfinite(c), "nk_model_lqr_cost: c is not finite");
+  const int m = model->m;
+  std::vector<double> q((size_t)m * m);
+  std::vector<DareItem> items(1);
+  DareItem& it = items[0];
+  it.m = m; it.p = model->p; it.d = model->d; it.c = c;
+  it.dA = model->A; it.dB = model->B; it.lda = it.ldb = m + model->p; it.dC = model->C;
+  it.outP = q.data(); it.q_only = 1;
+  int32_t st = 0;
+  NK_TRY(dare_run(ctx, items, 0.0, 1, &st, nullptr));
+  for (int i = 0; i < m; ++i) std::copy(q.begin() + (size_t)i * m, q.begin() + (size_t)(i + 1) * m, Q + (int64_t)i * ldq);
+  return NK_OK;
+}
+
 int nk_gemm(nk_ctx* ctx, int transA, int transB, int64_t M, int64_t N, int64_t K, double alpha, const double* A,
             int64_t lda, const double* B, int64_t ldb, double beta, double* C, int64_t ldc) {
   NK_TRY(check_ctx(ctx));

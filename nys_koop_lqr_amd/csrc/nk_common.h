@@ -492,6 +492,32 @@ struct PlantLoopUnit {
 int launch_plant_loop_multi(nk_ctx* ctx, int plant, double Ts, int steps, PlantLoopUnit* units, const int* ktypes,
                             int n_units);
 
+// ---- batched Riccati solver (nk_dare.hip): one workgroup per problem, blockIdx.x = the record.  Every pointer is device
+// memory.  ws: the problem's workspace of dare_ws_doubles(M) doubles, M = m rounded up to 16.  Either Q (m x m) or C
+// (d x m: the cost is c sym(C'C), formed by the kernel's own product) is set.  R: p x p dense, nullptr = identity.
+constexpr int DARE_MAX_M = 256;
+constexpr int DARE_MAX_P = 8;
+struct DareRec {
+  const double* A; int64_t lda;  // m x m
+  const double* B; int64_t ldb;  // m x p
+  const double* Q; int64_t ldq;  // m x m, or nullptr
+  const double* C; int64_t ldc;  // d x m, or nullptr
+  const double* R;               // p x p dense, or nullptr
+  double c;
+  double* ws;
+  double* outK;    // p x m dense
+  double* outP;    // m x m dense, or nullptr
+  double* delta;   // last relative step, or nullptr
+  int* status;     // 0 converged, 1 max_iter reached, 2 non-finite values or a singular pivot
+  int* iters;
+  int m, p, M, d;
+  int q_only;      // 1: write the cost matrix H_0 to outP and stop (nk_model_lqr_cost)
+  int reserved;
+};
+inline int dare_pad(int m) { return (m + 15) & ~15; }
+inline size_t dare_ws_doubles(int M) { return (size_t)7 * M * M; }
+int launch_dare(nk_ctx* ctx, const DareRec* table_dev, int count, double tol, int max_iter);
+
 }  // namespace nk
 
 namespace nk {

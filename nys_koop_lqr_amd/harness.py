@@ -635,11 +635,21 @@ def lqr_fit_unit(X, Y, n_inputs, params, unit, estimator="nystrom"):
 
 
 def lqr_run_units(X, Y, n_inputs, params, units, plant, x0, x_ref, num_steps, estimator="nystrom", gain_fn=None, c=1.0,
-                  u_opt=None, batch=32, workers=4, return_trajectories=False, fit_fn=None, loop_fn=None):
+                  u_opt=None, batch=32, workers=4, return_trajectories=False, fit_fn=None, loop_fn=None, gain="host",
+                  gain_batch_fn=None):
     """Scores of planned units, in their order: an (n_units, 4) array (SCORE_NAMES; NaN for a unit whose fit or gain
     failed), the trajectories (or None, None) and the wall-clock split.  fit_fn / loop_fn stand in for lqr_fit_unit /
-    plant_loop_multi (rehearsals without a GPU; with a fit_fn the fits run as a plain loop)."""
+    plant_loop_multi (rehearsals without a GPU; with a fit_fn the fits run as a plain loop).
+    gain="device": the gains of all fitted units come from ONE nk_model_lqr_gain_batch call after the fits (K =
+    dlqr(A, B, c sym(C'C), I) by the batched doubling solver; gain_fn is not used); a unit whose solve reports a non-zero
+    status gets NaN scores and is not run.  timing keeps its keys: gain_wait_s is that call, gain_cpu_s is 0.
+    gain_batch_fn(regs, c) -> (Ks, status, iterations) stands in for the device call."""
     import time
+    if gain not in ("host", "device"):
+        raise ValueError(f"gain must be 'host' or 'device', got {gain!r}")
+    if gain == "device" and gain_fn is not None:
+        raise ValueError("gain='device' solves K = dlqr(A, B, c C'C, I) on the device: gain_fn cannot be combined with it")
+    device_gain = gain == "device"
     X = np.ascontiguousarray(X, dtype=np.float64)
     Y = np.ascontiguousarray(Y, dtype=np.float64)
     gain_fn = gain_fn or lqr_default_gain(c)
@@ -666,10 +676,18 @@ def lqr_run_units(X, Y, n_inputs, params, units, plant, x0, x_ref, num_steps, es
         fitted = lpool.run_round(fit, [units[i] for i in idx]) if lockstep else [fit(units[i]) for i in idx]
         for i, reg in zip(idx, fitted):  # the gains of this round are solved on the host while the next round fits
             regs[i] = reg
-            if reg is not None:
+            if reg is not None and not device_gain:
                 futures[i] = pool.submit(gain_of, i, reg)
     t1 = time.perf_counter()
     gains = [None] * n
+    if device_gain:
+        fitted_idx = [i for i in range(n) if regs[i] is not None]
+        if fitted_idx:
+            from .regressors import _lqr_gain_batch
+            Ks, status, _ = (gain_batch_fn or _lqr_gain_batch)([regs[i] for i in fitted_idx], c)
+            for i, K, st in zip(fitted_idx, Ks, status):
+                if int(st) == 0:
+                    gains[i] = np.asarray(K, dtype=np.float64)
     for i, f in enumerate(futures):
         if f is not None:
             try:
@@ -707,7 +725,8 @@ def lqr_table(units, values, n_seeds, n_ms):
 
 
 def lqr_sweep(X, Y, n_inputs, params, ms, seeds, plant, x0, x_ref, num_steps, estimator="nystrom", gain_fn=None, c=1.0,
-              u_opt=None, batch=32, workers=4, return_trajectories=False, centers=None, fit_fn=None, loop_fn=None):
+              u_opt=None, batch=32, workers=4, return_trajectories=False, centers=None, fit_fn=None, loop_fn=None,
+              gain="host", gain_batch_fn=None):
     """The control branch of the reference's one-input drivers (benchmark_lqr_classic.py:256-299: seeds x {Nystrom,
     splines}; benchmark_lqr_hjb.py:265-333: seeds x m) as one call: for every seed and every m in `ms`
     fit -> K = dlqr(A, B, c C^T C, I) -> `num_steps` feedback steps around the true plant -> replay cost and control scores.
@@ -716,6 +735,8 @@ def lqr_sweep(X, Y, n_inputs, params, ms, seeds, plant, x0, x_ref, num_steps, es
       fits:   `batch` at a time through the lock-step pool (batch <= 1: a plain loop; same bits);
       gains:  gain_fn(A, B, C) -> K (1 x m) (default lqr_default_gain(c): the host Riccati solve), computed in `workers`
               host threads while later rounds fit; a unit whose gain raises gets NaN scores and is not run;
+              gain="device": all gains in ONE nk_model_lqr_gain_batch call after the fits instead (see lqr_run_units;
+              gain="host" stays the choice for replaying the reference's numbers);
       loops:  ONE plant_loop_multi call over all surviving units, scored on the device (u_opt: (num_steps,) or None).
     x0, x_ref: one state each, shared by the units.  Returns a dict of (len(seeds), len(ms)) tables sse_u, ss_opt, J,
     u_absmax, rmse_control, the planned `units`, the wall-clock split `timing` (fit_s, gain_wait_s, loop_s; gain_cpu_s =
@@ -724,7 +745,8 @@ def lqr_sweep(X, Y, n_inputs, params, ms, seeds, plant, x0, x_ref, num_steps, es
     _check_estimator(estimator)
     units = lqr_plan(X, Y, n_inputs, params, ms, seeds, estimator, centers)
     scores, states, controls, timing = lqr_run_units(X, Y, n_inputs, params, units, plant, x0, x_ref, num_steps, estimator,
-                                                     gain_fn, c, u_opt, batch, workers, return_trajectories, fit_fn, loop_fn)
+                                                     gain_fn, c, u_opt, batch, workers, return_trajectories, fit_fn, loop_fn,
+                                                     gain, gain_batch_fn)
     return lqr_result(units, scores, states, controls, len(seeds), len(ms), timing)
 
 

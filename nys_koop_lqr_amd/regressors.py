@@ -15,6 +15,16 @@ from . import _lib
 from .lqr import dlqr
 
 
+def _lqr_gain_batch(regs, c, R=None, tol=1e-13, max_iter=40):
+    """(Ks, status, iterations) of nk_model_lqr_gain_batch for fitted regressors (one device call, chunked by the
+    library).  A module-level seam: tests without a GPU replace it."""
+    ctx = _lib.get_context()
+    handles = [r._ensure_model() for r in regs]
+    dims = [(int(r._landmark_shape()[1]), int(r.n_inputs)) for r in regs]
+    return ctx.model_lqr_gain_batch(handles, c, R, tol=tol, max_iter=max_iter, dims=dims)
+
+
+
 def _is_device_tensor(x):
     return hasattr(x, "data_ptr") and hasattr(x, "stride")
 
@@ -580,9 +590,20 @@ class KoopmanNystromRegressor(KoopmanRegressor):
             return ox[0].T, ou[0].T
         return ox, ou
 
-    def solve_lqr(self, Q=None, R=None, c=0.0075):
+    def solve_lqr(self, Q=None, R=None, c=0.0075, device=False):
         """Host DARE, standing in for control.dlqr(A, B, Q, R) (benchmark_lqr_cloth.py:238-240,262): by default
-        Q = c * C^T C symmetrised and R = I.  Returns the gain K (p x m)."""
+        Q = c * C^T C symmetrised and R = I.  Returns the gain K (p x m).
+        device=True: the batched device solver with this one model (nk_model_lqr_gain_batch: Q = c sym(C'C) formed on the
+        device from the model's own operators, so Q must be None; m <= 256, p <= 8); raises np.linalg.LinAlgError when
+        the iteration does not converge or breaks down, as scipy does."""
+        if device:
+            if Q is not None:
+                raise ValueError("solve_lqr(device=True) forms Q = c sym(C'C) on the device: pass c, not Q")
+            Ks, status, _ = _lqr_gain_batch([self], c, R)
+            if int(status[0]) != 0:
+                raise np.linalg.LinAlgError(f"device Riccati solve failed with status {int(status[0])} "
+                                            "(1: max_iter reached, 2: non-finite values or a singular pivot)")
+            return Ks[0]
         if Q is None:
             Q = c * self.C.T @ self.C
             Q = (Q + Q.T) / 2
