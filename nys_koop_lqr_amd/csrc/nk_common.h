@@ -55,6 +55,29 @@ struct ArenaMark {
 
 }  // namespace nk
 
+// Slots of nk_ctx::ev (timing enabled).  Who records / who waits or reads:
+enum {
+  EV_FIT_BEGIN = 0,      // a fit's entry, main stream / the fit's statistics
+  EV_STAGED = 1,         // inputs and landmarks staged, main stream / the fit's statistics
+  EV_KMAT_DONE = 2,      // kernel blocks of the first pass queued (FIT_SOLVE: accumulators loaded), main / statistics
+  EV_GRAM_DONE = 3,      // last Gram contraction, main stream / the fit's statistics
+  EV_SOLVE_BEGIN = 4,    // main stream after it joined the side stream (spline fit: before the operators) / statistics
+  EV_FIT_END = 5,        // operator products, main stream / the fit's statistics
+  EV_SQRT_BEGIN = 6,     // side stream in front of the square-root iteration / statistics
+  EV_SQRT_END = 7,       // side stream behind the square-root iteration / statistics
+  EV_LANDMARKS = 8,      // landmark matrices built (main or preparation stream) / the preparation stream, and the main
+                         // stream where it assembles the systems
+  EV_SQRT_PREPARED = 9,  // sqrtm_prepare's chain, preparation stream / the side stream in front of the iteration
+  EV_SQRT_RESID = 10,    // residual copy of the synchronous square-root iteration (nk_linalg.hip) / the host, same place
+  EV_SQRT_SCALARS = 11,  // sqrtm_prepare's schedule scalars on their way to the host / the host in sqrtm_finish
+  EV_FORK = 12,          // scratch fork point, recorded on the main stream and waited for at once by the stream that
+                         // branches off: the landmark matrices aside, the pipelined upload, the Y rows' preparation
+  EV_YPREP_DONE = 13,    // Y rows prepared on the side stream (overlap_prep) / the main stream before their kernel block
+  EV_GEMM_T0 = 14,       // recorded by the GEMM engines (nk_gemm*.hip) around a timed launch; read there, or by the
+  EV_GEMM_T1 = 15,       // fits after their own synchronisation when the launch was timed without one (sync_timing = false)
+  EV_COUNT = 16
+};
+
 struct nk_member_state;
 struct nk_ctx {
   int device = 0;
@@ -80,7 +103,7 @@ struct nk_ctx {
   double* h_scalars = nullptr; // pinned host mirror
   int* h_info = nullptr;       // pinned host mirror of d_info (kept apart from h_scalars: both streams may be in flight)
   double* d_zeros = nullptr;   // 4 KiB zero page (K-tail rows of the LDS-DMA GEMM)
-  hipEvent_t ev[16];
+  hipEvent_t ev[EV_COUNT];  // indexed by the EV_* slots above
   int num_cu = 256;
   int kmat_mode = 0;  // 0 auto (Gram form on MFMA for d >= 32), 1 always direct differences (NYSKOOP_KMAT=direct)
   // optional refinement of the two regularised solves with doubled-precision residuals (nk_set_refine): applied to a system

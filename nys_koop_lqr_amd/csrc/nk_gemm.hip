@@ -469,11 +469,11 @@ int launch_gemm(nk_ctx* ctx, bool transA, bool transB, int64_t M, int64_t N, int
     p.slab = slab;
   }
   NK_TRY(gemm_set_attrs());
-  if (ms_kernel) NK_HIP(hipEventRecord(ctx->ev[14], ctx->stream));
+  if (ms_kernel) NK_HIP(hipEventRecord(ctx->ev[EV_GEMM_T0], ctx->stream));
   gemm_dispatch(ctx, transA, transB, dim3((unsigned)p.nblocks, 1), b);
   NK_HIP(hipGetLastError());
   if (ms_kernel) {
-    NK_HIP(hipEventRecord(ctx->ev[15], ctx->stream));
+    NK_HIP(hipEventRecord(ctx->ev[EV_GEMM_T1], ctx->stream));
   }
   if (splitk > 1) {
     const int64_t total = M * N;
@@ -484,8 +484,8 @@ int launch_gemm(nk_ctx* ctx, bool transA, bool transB, int64_t M, int64_t N, int
     NK_HIP(hipGetLastError());
   }
   if (ms_kernel) {
-    NK_HIP(hipEventSynchronize(ctx->ev[15]));
-    NK_HIP(hipEventElapsedTime(ms_kernel, ctx->ev[14], ctx->ev[15]));
+    NK_HIP(hipEventSynchronize(ctx->ev[EV_GEMM_T1]));
+    NK_HIP(hipEventElapsedTime(ms_kernel, ctx->ev[EV_GEMM_T0], ctx->ev[EV_GEMM_T1]));
   }
   arena_release(ctx, mark);  // stream order makes the slab reusable by later launches
   return NK_OK;

@@ -626,21 +626,21 @@ int launch_gemm_tn_multi(nk_ctx* ctx, const TnProblem* probs, int nprob, int64_t
                                hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
     g_tn_attr_set = true;
   }
-  if (ms_kernel) NK_HIP(hipEventRecord(ctx->ev[14], ctx->stream));
+  if (ms_kernel) NK_HIP(hipEventRecord(ctx->ev[EV_GEMM_T0], ctx->stream));
   P.sqa = P.sqb = nullptr; P.out = nullptr; P.ldo = 0; P.ktype = 0; P.sigma0sq = 0.0;
   if (nprob >= 3)  // the fit's fused Gram launch
     hipLaunchKernelGGL(gram_fused_f64_kernel, dim3((unsigned)(ntiles * splitk)), dim3(256), TN_LDS_BYTES, ctx->stream, P);
   else
     hipLaunchKernelGGL(gemm_tn_f64_kernel<0>, dim3((unsigned)(ntiles * splitk)), dim3(256), TN_LDS_BYTES, ctx->stream, P);
   NK_HIP(hipGetLastError());
-  if (ms_kernel) NK_HIP(hipEventRecord(ctx->ev[15], ctx->stream));
+  if (ms_kernel) NK_HIP(hipEventRecord(ctx->ev[EV_GEMM_T1], ctx->stream));
   if (splitk > 1) {
     hipLaunchKernelGGL(gemm_tn_reduce_kernel, dim3((unsigned)ntiles * RPARTS), dim3(256), 0, ctx->stream, R);
     NK_HIP(hipGetLastError());
   }
-  if (ms_kernel && sync_timing) {  // otherwise the caller reads ev[14] -> ev[15] after its own synchronisation
-    NK_HIP(hipEventSynchronize(ctx->ev[15]));
-    NK_HIP(hipEventElapsedTime(ms_kernel, ctx->ev[14], ctx->ev[15]));
+  if (ms_kernel && sync_timing) {  // otherwise the caller reads EV_GEMM_T0 -> EV_GEMM_T1 after its own synchronisation
+    NK_HIP(hipEventSynchronize(ctx->ev[EV_GEMM_T1]));
+    NK_HIP(hipEventElapsedTime(ms_kernel, ctx->ev[EV_GEMM_T0], ctx->ev[EV_GEMM_T1]));
   }
   arena_release(ctx, mark);
   return NK_OK;

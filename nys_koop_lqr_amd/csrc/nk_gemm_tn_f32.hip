@@ -528,7 +528,7 @@ int launch_gemm_tn_f32_multi(nk_ctx* ctx, const TnProblemF* probs, int nprob, in
   P.slab = slab;
   P.sqa = P.sqb = nullptr; P.out = nullptr; P.ldo = 0; P.sigma0sq = 0.f;
   R.nprob = nprob; R.splitk = splitk; R.slab = slab; R.skip_state = nullptr; R.skip_step = 0; R.resid_partials = nullptr;
-  if (ms_kernel) NK_HIP(hipEventRecord(ctx->ev[14], ctx->stream));
+  if (ms_kernel) NK_HIP(hipEventRecord(ctx->ev[EV_GEMM_T0], ctx->stream));
   if (use_asm)
     hipLaunchKernelGGL(gram_fused_f32_asm_kernel, dim3((unsigned)(ntiles * splitk)), dim3(256), F32_LDS_BYTES, ctx->stream, P);
   else if (nprob >= 3)
@@ -536,11 +536,11 @@ int launch_gemm_tn_f32_multi(nk_ctx* ctx, const TnProblemF* probs, int nprob, in
   else
     hipLaunchKernelGGL(gemm_tn_f32_kernel<0>, dim3((unsigned)(ntiles * splitk)), dim3(256), F32_LDS_BYTES, ctx->stream, P);
   NK_HIP(hipGetLastError());
-  if (ms_kernel) NK_HIP(hipEventRecord(ctx->ev[15], ctx->stream));
+  if (ms_kernel) NK_HIP(hipEventRecord(ctx->ev[EV_GEMM_T1], ctx->stream));
   if (splitk > 1) NK_TRY(launch_tn_reduce(ctx, R, ntiles));
   if (ms_kernel && sync_timing) {
-    NK_HIP(hipEventSynchronize(ctx->ev[15]));
-    NK_HIP(hipEventElapsedTime(ms_kernel, ctx->ev[14], ctx->ev[15]));
+    NK_HIP(hipEventSynchronize(ctx->ev[EV_GEMM_T1]));
+    NK_HIP(hipEventElapsedTime(ms_kernel, ctx->ev[EV_GEMM_T0], ctx->ev[EV_GEMM_T1]));
   }
   arena_release(ctx, mark);
   return NK_OK;

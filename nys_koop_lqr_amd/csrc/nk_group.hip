@@ -478,7 +478,7 @@ hipError_t x_event_elapsed(float* ms, hipEvent_t a, hipEvent_t b) {
   return hipEventElapsedTime(ms, a, b);
 }
 
-// ---- group life cycle (called from nk_api.hip) ---------------------------------------------------------------------
+// ---- group life cycle (called from nk_api.hip and nk_sweep.hip) ---------------------------------------------------------------------
 nk_group* group_new(int device, int size) {
   nk_group* g = new nk_group();
   g->device = device;

@@ -774,12 +774,12 @@ int cholesky_aug_pair_async(nk_ctx* ctx, const CholSys* sys, int nsys, hipEvent_
   const bool lookahead = la_env && la >= 0 && nblk >= 4 && !ctx_recording(ctx);
   hipStream_t s_chain = ctx->stream;
   hipStream_t s_rest = lookahead ? ctx->stream_la[la] : ctx->stream;
-  hipEvent_t* ev = lookahead ? ctx->ev_la[la] : nullptr;  // [0..1] panel done (parity of the step), [2..3] rest done
+  hipEvent_t* la_evt = lookahead ? ctx->ev_la[la] : nullptr;  // [0..1] panel done (parity of the step), [2..3] rest done
   bool rest_pending = false;
   hipEvent_t last_rest = nullptr;
   if (lookahead) {  // the look-ahead stream starts behind whatever the chain's stream has queued so far
-    NK_HIP(hipEventRecord(ev[1], s_chain));
-    NK_HIP(hipStreamWaitEvent(s_rest, ev[1], 0));
+    NK_HIP(hipEventRecord(la_evt[1], s_chain));
+    NK_HIP(hipStreamWaitEvent(s_rest, la_evt[1], 0));
   }
   const bool fuse = chol_fuse_enabled();
   bool diag_done = false;  // the diagonal block of this step was factored by the previous step's fused launch
@@ -855,7 +855,7 @@ int cholesky_aug_pair_async(nk_ctx* ctx, const CholSys* sys, int nsys, hipEvent_
     if (!lookahead) {
       NK_TRY(update(trail));
     } else {
-      hipEvent_t evP = ev[jb & 1], evR = ev[2 + (jb & 1)], evR_prev = ev[2 + ((jb + 1) & 1)];
+      hipEvent_t evP = la_evt[jb & 1], evR = la_evt[2 + (jb & 1)], evR_prev = la_evt[2 + ((jb + 1) & 1)];
       NK_HIP(hipEventRecord(evP, s_chain));                               // panel(jb) is complete
       if (rest_pending) NK_HIP(hipStreamWaitEvent(s_chain, evR_prev, 0));  // the next column has its older updates
       NK_TRY(update(next));
@@ -1022,7 +1022,7 @@ int sqrtm_prepare(nk_ctx* ctx, const double* P, int64_t ldp, int m, SqrtPlan* pl
   }
   // the three scalars of the scaling schedule are on the host long before the iteration is queued
   NK_HIP(hipMemcpyAsync(ctx->h_scalars + 12, plan->d_sc, 3 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-  NK_HIP(hipEventRecord(ctx->ev[11], ctx->stream));
+  NK_HIP(hipEventRecord(ctx->ev[EV_SQRT_SCALARS], ctx->stream));
   double* E = plan->W + mm;
   NK_TRY(launch_copy2d(ctx, P, ldp, plan->W, m, m, m));
   NK_TRY(launch_fill(ctx, E, m, m, m, 0.0));
@@ -1109,7 +1109,7 @@ int sqrtm_finish(nk_ctx* ctx, SqrtPlan* plan, double* S, double* Sinv) {
   plan->early = plan->lambda_min_hint > 0.0 && m >= 1024 && m % 2 == 0;
   double c, sumsq, trace, linv2 = 0.0;
   if (plan->early) {
-    NK_HIP(hipEventSynchronize(ctx->ev[11]));
+    NK_HIP(hipEventSynchronize(ctx->ev[EV_SQRT_SCALARS]));
     c = ctx->h_scalars[12]; sumsq = ctx->h_scalars[13]; trace = ctx->h_scalars[14];
     if (!(c > 0.0) || !std::isfinite(c)) plan->early = false;
   }
@@ -1290,7 +1290,7 @@ int sqrtm_finish(nk_ctx* ctx, SqrtPlan* plan, double* S, double* Sinv) {
     if (check) {
       NK_TRY(launch_frob_minus_identity(ctx, M, m, m, ctx->d_scalars));
       NK_HIP(hipMemcpyAsync(ctx->h_scalars, ctx->d_scalars, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-      NK_HIP(hipEventRecord(ctx->ev[10], ctx->stream));
+      NK_HIP(hipEventRecord(ctx->ev[EV_SQRT_RESID], ctx->stream));
     }
     const double s2 = 3.0 / (a_lo + std::sqrt(a_lo * b_hi) + b_hi);
     const double sc = std::sqrt(s2);
@@ -1308,7 +1308,7 @@ int sqrtm_finish(nk_ctx* ctx, SqrtPlan* plan, double* S, double* Sinv) {
     Xn = (Xn == Xa) ? Xb : Xa;
     Xtn = (Xtn == Xta) ? Xtb : Xta;
     if (check) {
-      NK_HIP(hipEventSynchronize(ctx->ev[10]));
+      NK_HIP(hipEventSynchronize(ctx->ev[EV_SQRT_RESID]));
       r = std::sqrt(ctx->h_scalars[0] / m);
       if (!std::isfinite(r)) break;
       if (r < 1e-7) {

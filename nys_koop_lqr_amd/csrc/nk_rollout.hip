@@ -3,7 +3,7 @@
 // 128x128 MFMA tile of the GEMM engine would idle 127/128 of its rows.  One wave per output row: the 64 lanes stride
 // over the row of G = [A | B] (coalesced 512-B segments), up to 8 trajectories share each load of G, wavefront
 // reduction, lane 0 stores.  G (32 MB at m = 2000) is re-read every step and stays in L2 / Infinity Cache.
-// Larger batches use the GEMM engine (nk_api.hip).
+// Larger batches use the GEMM engine (nk_control.hip).
 #include "nk_common.h"
 
 namespace nk {
@@ -242,7 +242,7 @@ __global__ void __launch_bounds__(CHAIN_THREADS) lifted_chain_kernel(ChainParams
 // launch than the device holds at once (W * trajectories <= number of CUs; with more, workgroups of later trajectories
 // can fill an XCD's slots while they wait for siblings that then never get a slot), so every workgroup of the launch is
 // resident once the kernels ahead of it in other queues have drained.  Two such launches side by side could still
-// starve each other, so the host serialises them (nk_api.hip) and a wave that has polled MW_POLL_LIMIT times gives up:
+// starve each other, so the host serialises them (nk_control.hip) and a wave that has polled MW_POLL_LIMIT times gives up:
 // it raises *status and publishes NaN, which releases everybody behind it -- the grid always drains, and the caller
 // repeats the recursion with one launch per step.
 // ---------------------------------------------------------------------------------------------------------------

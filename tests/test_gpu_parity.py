@@ -709,3 +709,53 @@ def test_large_landmark_counts_vs_oracle(nk, O, m, p, family):
     assert relf(reg.predict(X[:200]), ref.predict(X[:200])) < 1e-6
     assert relf(reg.lift(X[:50, :d].T), ref.lift(X[:50, :d].T)) < 1e-6
     assert relf(reg.weights, reg.C @ np.hstack([reg.A, reg.B])) < 1e-12
+
+
+def _rbf_fit(nk, X, Y, p, m, idx):
+    reg = nk.KoopmanNystromRegressor(p, kernel=nk.ThreeDimensionalKernel(6.0, 6.0, 6.0, Y.shape[1]), gamma=1e-4, m=m)
+    reg.nystrom_centers_output = Y.T[:, idx]
+    reg.fit(X, Y)
+    return reg
+
+
+@pytest.mark.gpu
+def test_landmark_matrices_beside_the_kernel_blocks_vs_oracle(nk, O, monkeypatch):
+    """n >= 20000 with m >= 1024: the landmark matrices are built on the preparation stream beside the kernel blocks
+    (the default) or, with NYSKOOP_LANDMARKS_ASIDE=0, on the main stream in front of them.  Both fits are held to the
+    oracle as in test_large_landmark_counts_vs_oracle (predict and lift relative error < 1e-6).  The same kernels run on
+    the same data in both, so the operators should also be the same bits; that equality has not been measured on a
+    device yet, so it is printed, not asserted."""
+    n, d, p, m = 20480, 32, 1, 1024
+    X, Y, rng = _synth(n, d, p, 7)
+    idx = rng.choice(n, m, replace=False)
+    ref = O.KoopmanNystromOracle(p, kernel=O.ThreeDimensionalKernel(6.0, 6.0, 6.0, d), gamma=1e-4, m=m, faithful=False)
+    ref.nystrom_centers_output = Y.T[:, idx]
+    ref.fit(X, Y)
+    want_p, want_l = ref.predict(X[:200]), ref.lift(X[:50, :d].T)
+    fits = []
+    for aside in ("1", "0"):
+        monkeypatch.setenv("NYSKOOP_LANDMARKS_ASIDE", aside)
+        reg = _rbf_fit(nk, X, Y, p, m, idx)
+        assert relf(reg.predict(X[:200]), want_p) < 1e-6, aside
+        assert relf(reg.lift(X[:50, :d].T), want_l) < 1e-6, aside
+        fits.append(reg)
+    print("\n[landmarks aside] same bits as in front of the kernel blocks:",
+          {w: bool(np.array_equal(getattr(fits[0], w), getattr(fits[1], w))) for w in ("A", "C", "weights")})
+
+
+@pytest.mark.gpu
+def test_pipelined_host_upload_matches_single_upload(nk, monkeypatch):
+    """Host arrays of 64 MB and more are uploaded in six row blocks, block k + 1 beside the kernel blocks and the Gram
+    launch of block k (one Gram launch per block); NYSKOOP_HOST_PASSES=1 uploads everything first and contracts in one
+    launch.  The summation order over the rows differs, nothing else: the bound is the 1e-9 of
+    test_multi_pass_accumulation_matches_single_pass (not yet measured at this shape)."""
+    n, d, p, m = 126976, 32, 1, 32
+    X, Y, rng = _synth(n, d, p, 9)
+    idx = rng.choice(n, m, replace=False)
+    piped = _rbf_fit(nk, X, Y, p, m, idx)
+    assert piped.fit_stats_["gram_kernel_launches"] == 6
+    monkeypatch.setenv("NYSKOOP_HOST_PASSES", "1")
+    one = _rbf_fit(nk, X, Y, p, m, idx)
+    errs = dict(A=relf(piped.A, one.A), C=relf(piped.C, one.C), W=relf(piped.weights, one.weights))
+    print("\n[pipelined upload] relative differences:", errs)
+    assert max(errs.values()) < 1e-9, errs

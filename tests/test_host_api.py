@@ -131,7 +131,7 @@ def test_no_raw_hip_stream_call_escapes_the_lockstep_wrappers():
     the recording: the only ones allowed are listed here with the reason they are safe."""
     allowed = {
         # nk_cv_grid stages X / Y once, before any member thread exists (blocking copies on the caller's thread)
-        ("nk_api.hip", "hipMemcpy2D("): 3,
+        ("nk_sweep.hip", "hipMemcpy2D("): 3,
         # one-time zero page of a context, blocking on purpose (both streams read it)
         ("nk_gemm_tn.hip", "hipMemset("): 1,
     }

@@ -42,7 +42,7 @@ for c in range(len(cands)):  # centres = training states of the unit's fold (reg
         centers[(c, f)] = harness.spline_centers_draw(cands[c], np.vstack((S[:lo], S[hi:])), rng=np.random.RandomState(17 * c + f))
 n_units = len(centers)
 
-# which side of SPLINE_SVD_WINDOW each unit falls on (nk_api.hip: pseudo-inverse unless the smallest / largest Cholesky
+# which side of SPLINE_SVD_WINDOW each unit falls on (nk_fit.hip: pseudo-inverse unless the smallest / largest Cholesky
 # pivot exceeds 2 (m+p)^2 eps), read from the statistics of one ordinary fit per unit
 pinv_units = 0
 for (c, f), Z in centers.items():
