@@ -213,6 +213,16 @@ def check(rc):
         raise NyskoopError(rc, load_library().nk_last_error().decode("utf-8", "replace"))
 
 
+def check_mapped(rc):
+    """check() for the calls whose failures have Python equivalents: NK_ERR_BAD_ARG raises ValueError and NK_ERR_NOT_SPD
+    np.linalg.LinAlgError, as NumPy / SciPy / sklearn would for the same input."""
+    if rc == -1:
+        raise ValueError(load_library().nk_last_error().decode())
+    if rc == -3:
+        raise np.linalg.LinAlgError(load_library().nk_last_error().decode())
+    check(rc)
+
+
 def runtime_counters():
     """Process-wide counts of the library's silent slow paths (nk_runtime_counters): single-launch recursions and Jacobi
     sweeps that gave up waiting for non-resident workgroups, fits that took the rank-truncating branch of the
@@ -366,9 +376,7 @@ class Context:
         ptr = lambda a: None if a is None else a.ctypes.data
         rc = self.lib.nk_plant_loop_multi(self.handle, int(plant_id), float(Ts), steps, arr, n, ptr(uo), n_uopt, ptr(ox),
                                           ptr(ou), ptr(sc))
-        if rc == -1:
-            raise ValueError(self.lib.nk_last_error().decode())
-        check(rc)
+        check_mapped(rc)
         return sc, ox, ou
 
     def dare_batch(self, As, Bs, Qs, Rs, tol=1e-13, max_iter=40, want_P=True):
@@ -406,9 +414,7 @@ class Context:
         iters = np.zeros(max(n, 1), dtype=np.int32)
         rc = self.lib.nk_dare_batch(self.handle, arr, n, float(tol), int(max_iter),
                                     status.ctypes.data_as(C.POINTER(_I32)), iters.ctypes.data_as(C.POINTER(_I32)))
-        if rc == -1:
-            raise ValueError(self.lib.nk_last_error().decode())
-        check(rc)
+        check_mapped(rc)
         return Ks, (Ps if want_P else None), status[:n], iters[:n], delta[:n]
 
     def model_lqr_gain_batch(self, models, c, R=None, tol=1e-13, max_iter=40, dims=None):
@@ -433,9 +439,7 @@ class Context:
         rc = self.lib.nk_model_lqr_gain_batch(self.handle, hs, n, float(c), None if Rm is None else Rm.ctypes.data,
                                               float(tol), int(max_iter), out.ctypes.data,
                                               status.ctypes.data_as(C.POINTER(_I32)), iters.ctypes.data_as(C.POINTER(_I32)))
-        if rc == -1:
-            raise ValueError(self.lib.nk_last_error().decode())
-        check(rc)
+        check_mapped(rc)
         Ks, off = [], 0
         for (m, p), sz in zip(dims, sizes):
             Ks.append(out[off:off + sz].reshape(int(p), int(m)).copy())
@@ -447,9 +451,7 @@ class Context:
         Q = np.empty((int(m), int(m)))
         h = model.value if isinstance(model, C.c_void_p) else model
         rc = self.lib.nk_model_lqr_cost(self.handle, h, float(c), Q.ctypes.data, int(m))
-        if rc == -1:
-            raise ValueError(self.lib.nk_last_error().decode())
-        check(rc)
+        check_mapped(rc)
         return Q
 
     def set_kmat_mode(self, mode):
@@ -595,14 +597,35 @@ class LockstepPool:
             out.extend(self.run_round(fn, items[r:r + self.size]))
         return out
 
-    def cv_grid(self, X, Y, n_inputs, units):
-        """nk_cv_grid: `units` = list of (DeviceKernel, gamma, jitter, m, (test_begin, test_end), landmark_rows) run in
-        lock step, len(members) at a time, entirely inside the library (no Python per unit).  Returns (scores, status)."""
+    @staticmethod
+    def _grid_data(X, Y, n_inputs):
+        """The shared data set of a grid call, checked: (Xm, Ym, n, d, p)."""
         Xm, Ym = Mat(X), Mat(Y)
         n, d = Ym.shape
         p = int(n_inputs)
         if Xm.shape != (n, d + p):
             raise ValueError(f"X has shape {Xm.shape}, expected {(n, d + p)}")
+        return Xm, Ym, n, d, p
+
+    def _grid_call(self, name, data, extra, arr, n_scores, n_score_arrays=1):
+        """The grid entry point `name` on the members' contexts: data set, the call's own arguments `extra`, the units
+        `arr`, then `n_score_arrays` NaN-filled float64 outputs of n_scores entries and one int32 status per unit.
+        Returns (*scores, status)."""
+        Xm, Ym, n, d, p = data
+        handles = (_P * self.size)(*[m_.handle for m_ in self.members])
+        scores = [np.full(n_scores, np.nan) for _ in range(n_score_arrays)]
+        status = np.zeros(len(arr), dtype=np.int32)
+        rc = getattr(self.members[0].lib, name)(handles, self.size, Xm.ptr, Xm.ld, Ym.ptr, Ym.ld, n, d, p, *extra, arr,
+                                                len(arr), *[a.ctypes.data_as(C.POINTER(_D)) for a in scores],
+                                                status.ctypes.data_as(C.POINTER(_I32)))
+        check_mapped(rc)
+        return (*scores, status)
+
+    def cv_grid(self, X, Y, n_inputs, units):
+        """nk_cv_grid: `units` = list of (DeviceKernel, gamma, jitter, m, (test_begin, test_end), landmark_rows) run in
+        lock step, len(members) at a time, entirely inside the library (no Python per unit).  Returns (scores, status)."""
+        data = self._grid_data(X, Y, n_inputs)
+        d = data[3]
         arr = (CvUnit * len(units))()
         keep = []
         descs = {}
@@ -618,25 +641,13 @@ class LockstepPool:
             arr[i].gamma, arr[i].jitter, arr[i].m = float(gamma), float(jitter), int(m)
             arr[i].test_begin, arr[i].test_end = int(lo), int(hi)
             arr[i].landmark_rows = rows.ctypes.data_as(C.POINTER(C.c_int64))
-        handles = (_P * self.size)(*[m_.handle for m_ in self.members])
-        scores = np.full(len(units), np.nan)
-        status = np.zeros(len(units), dtype=np.int32)
-        lib = self.members[0].lib
-        rc = lib.nk_cv_grid(handles, self.size, Xm.ptr, Xm.ld, Ym.ptr, Ym.ld, n, d, p, arr, len(units),
-                            scores.ctypes.data_as(C.POINTER(_D)), status.ctypes.data_as(C.POINTER(_I32)))
-        if rc == -1:
-            raise ValueError(lib.nk_last_error().decode())
-        check(rc)
-        return scores, status
+        return self._grid_call("nk_cv_grid", data, (), arr, len(units))
 
     def spline_cv_grid(self, X, Y, n_inputs, units):
         """nk_spline_cv_grid: `units` = list of (gamma, m, (test_begin, test_end), centers (m x d)) of the thin-plate-spline
         estimator, run in lock step like cv_grid.  Returns (scores, status)."""
-        Xm, Ym = Mat(X), Mat(Y)
-        n, d = Ym.shape
-        p = int(n_inputs)
-        if Xm.shape != (n, d + p):
-            raise ValueError(f"X has shape {Xm.shape}, expected {(n, d + p)}")
+        data = self._grid_data(X, Y, n_inputs)
+        d = data[3]
         arr = (SplineCvUnit * len(units))()
         keep = []
         for i, (gamma, m, (lo, hi), centers) in enumerate(units):
@@ -647,16 +658,7 @@ class LockstepPool:
             arr[i].gamma, arr[i].m = float(gamma), int(m)
             arr[i].test_begin, arr[i].test_end = int(lo), int(hi)
             arr[i].centers = Z.ctypes.data_as(C.POINTER(C.c_double))
-        handles = (_P * self.size)(*[m_.handle for m_ in self.members])
-        scores = np.full(len(units), np.nan)
-        status = np.zeros(len(units), dtype=np.int32)
-        lib = self.members[0].lib
-        rc = lib.nk_spline_cv_grid(handles, self.size, Xm.ptr, Xm.ld, Ym.ptr, Ym.ld, n, d, p, arr, len(units),
-                                   scores.ctypes.data_as(C.POINTER(_D)), status.ctypes.data_as(C.POINTER(_I32)))
-        if rc == -1:
-            raise ValueError(lib.nk_last_error().decode())
-        check(rc)
-        return scores, status
+        return self._grid_call("nk_spline_cv_grid", data, (), arr, len(units))
 
     def sysid_grid(self, X, Y, n_inputs, trajs, controls, units):
         """nk_sysid_grid: the multi-seed system-identification sweep in one call.  X: n x (d+p), Y: n x d (the shared data
@@ -667,11 +669,8 @@ class LockstepPool:
         unit's test trajectories.  Returns (err_abs, err_rel, status, offsets): flat unit-major arrays, unit u owning
         [offsets[u], offsets[u + 1]); a failed unit holds NaN and its code in status[u]."""
         units, offsets = sysid_unit_layout(units)
-        Xm, Ym = Mat(X), Mat(Y)
-        n, d = Ym.shape
-        p = int(n_inputs)
-        if Xm.shape != (n, d + p):
-            raise ValueError(f"X has shape {Xm.shape}, expected {(n, d + p)}")
+        data = self._grid_data(X, Y, n_inputs)
+        d, p = data[3:]
         tr = np.ascontiguousarray(trajs, dtype=np.float64)
         if tr.ndim != 3 or tr.shape[2] != d:
             raise ValueError(f"trajs must be (n_trajs, T, {d}), got {tr.shape}")
@@ -707,18 +706,8 @@ class LockstepPool:
             ti = np.ascontiguousarray(tidx, dtype=np.int32).reshape(-1)
             keep.append(ti)
             arr[i].traj, arr[i].n_traj = ti.ctypes.data_as(C.POINTER(C.c_int32)), ti.size
-        handles = (_P * self.size)(*[m_.handle for m_ in self.members])
-        total = int(offsets[-1])
-        err_abs, err_rel = np.full(total, np.nan), np.full(total, np.nan)
-        status = np.zeros(len(units), dtype=np.int32)
-        lib = self.members[0].lib
-        rc = lib.nk_sysid_grid(handles, self.size, Xm.ptr, Xm.ld, Ym.ptr, Ym.ld, n, d, p, tr.ctypes.data,
-                               None if U is None else U.ctypes.data, n_trajs, T, arr, len(units),
-                               err_abs.ctypes.data_as(C.POINTER(_D)), err_rel.ctypes.data_as(C.POINTER(_D)),
-                               status.ctypes.data_as(C.POINTER(_I32)))
-        if rc == -1:
-            raise ValueError(lib.nk_last_error().decode())
-        check(rc)
+        extra = (tr.ctypes.data, None if U is None else U.ctypes.data, n_trajs, T)
+        err_abs, err_rel, status = self._grid_call("nk_sysid_grid", data, extra, arr, int(offsets[-1]), 2)
         return err_abs, err_rel, status, offsets
 
     def stats(self):

@@ -120,6 +120,8 @@ int arena_alloc(nk_ctx* ctx, size_t bytes, void** out) {
 
 // ---- staging ---------------------------------------------------------------------------------------------------
 int stage_in(nk_ctx* ctx, const double* p, int64_t ld, int64_t rows, int64_t cols, MatIn* out) {
+  out->rows = rows;
+  out->cols = cols;
   if (rows <= 0 || cols <= 0) {
     out->ptr = p;
     out->ld = ld;
@@ -327,8 +329,8 @@ float ev_ms(nk_ctx* ctx, int a, int b) {
 }
 
 
-// ---- small-call staging (nk_api_internal.h)
-int small_reserve(nk_ctx* ctx, size_t bytes) {
+// ---- call staging (nk_api_internal.h)
+static int small_reserve(nk_ctx* ctx, size_t bytes) {
   if (ctx->h_stage_bytes >= bytes) return NK_OK;
   if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
   ctx->h_stage = nullptr;
@@ -337,21 +339,54 @@ int small_reserve(nk_ctx* ctx, size_t bytes) {
   ctx->h_stage_bytes = bytes;
   return NK_OK;
 }
-const double* small_in(SmallStage& st, const double* host, int64_t ld, int64_t rows, int64_t cols) {
-  double* dst = reinterpret_cast<double*>(reinterpret_cast<char*>(st.ctx->h_stage) + st.off);
-  for (int64_t r = 0; r < rows; ++r) memcpy(dst + r * cols, host + r * ld, (size_t)cols * 8);
-  st.off += (((size_t)rows * cols * 8) + 255) & ~(size_t)255;
-  return dst;
+int CallStage::commit() {
+  size_t need = 0;
+  for (const Operand& o : ops) need += pad256((size_t)o.rows * o.cols);
+  pinned = need <= SMALL_STAGE_LIMIT;
+  for (size_t i = 0; pinned && i < ops.size(); ++i) pinned = !is_device_ptr(ops[i].ptr);
+  if (!pinned) {
+    for (const Operand& o : ops) {
+      if (o.in) NK_TRY(stage_in(ctx, o.ptr, o.ld, o.rows, o.cols, o.in));
+      else NK_TRY(stage_out(ctx, const_cast<double*>(o.ptr), o.ld, o.rows, o.cols, o.out));
+    }
+    return NK_OK;
+  }
+  NK_TRY(small_reserve(ctx, need));
+  char* slot = reinterpret_cast<char*>(ctx->h_stage);
+  for (const Operand& o : ops) {
+    double* dst = reinterpret_cast<double*>(slot);
+    slot += pad256((size_t)o.rows * o.cols);
+    if (o.in) {
+      for (int64_t r = 0; r < o.rows; ++r) memcpy(dst + r * o.cols, o.ptr + r * o.ld, (size_t)o.cols * 8);
+      o.in->ptr = dst; o.in->ld = o.cols; o.in->staged = true; o.in->rows = o.rows; o.in->cols = o.cols;
+    } else {
+      o.out->dev = dst; o.out->ld = o.cols; o.out->host = const_cast<double*>(o.ptr); o.out->host_ld = o.ld;
+      o.out->rows = o.rows; o.out->cols = o.cols;
+    }
+  }
+  return NK_OK;
 }
-double* small_out(SmallStage& st, double* user, int64_t user_ld, int64_t rows, int64_t cols) {
-  double* dst = reinterpret_cast<double*>(reinterpret_cast<char*>(st.ctx->h_stage) + st.off);
-  st.off += (((size_t)rows * cols * 8) + 255) & ~(size_t)255;
-  st.outs.push_back(SmallStage::Out{dst, user, user_ld, rows, cols});
-  return dst;
+int CallStage::resident(MatIn* v, int64_t ld) {
+  const char *lo = reinterpret_cast<const char*>(ctx->h_stage), *at = reinterpret_cast<const char*>(v->ptr);
+  if (!pinned || at < lo || at >= lo + ctx->h_stage_bytes) return NK_OK;
+  double* dst = nullptr;
+  NK_TRY(arena_alloc_t(ctx, (size_t)v->rows * ld, &dst));
+  NK_TRY(launch_copy2d(ctx, v->ptr, v->ld, dst, ld, v->rows, v->cols));
+  v->ptr = dst;
+  v->ld = ld;
+  return NK_OK;
 }
-void small_finish(SmallStage& st) {  // after the stream has been synchronised
-  for (auto& o : st.outs)
-    for (int64_t r = 0; r < o.rows; ++r) memcpy(o.user + r * o.user_ld, o.stage + r * o.cols, (size_t)o.cols * 8);
+int CallStage::queue_outputs() {
+  if (pinned) return NK_OK;
+  for (const Operand& o : ops)
+    if (o.out) NK_TRY(finish_out(ctx, *o.out));
+  return NK_OK;
+}
+void CallStage::deliver() {
+  if (!pinned) return;
+  for (const Operand& o : ops)
+    if (o.out)
+      for (int64_t r = 0; r < o.rows; ++r) memcpy(o.out->host + r * o.ld, o.out->dev + r * o.cols, (size_t)o.cols * 8);
 }
 
 }  // namespace nk
@@ -910,31 +945,20 @@ int nk_lift(nk_ctx* ctx, const nk_model* mdl, const double* Xq, int64_t ldx, int
   NK_REQUIRE(mdl && Xq && out, "nk_lift: null argument");
   NK_REQUIRE(nq >= 0 && ldx >= mdl->d && ldo >= mdl->m, "nk_lift: bad sizes");
   if (nq == 0) return NK_OK;
-  // a few states (one per tick of a controller that closes the loop on a plant, benchmark_lqr_hjb.py:73-97): through the
-  // page-locked block, no hipMemcpy of pageable memory (whose completion wait alone costs 30-100 us, depending on how
+  // a few states (one per tick of a controller that closes the loop on a plant, benchmark_lqr_hjb.py:73-97) go through the
+  // page-locked block: no hipMemcpy of pageable memory (whose completion wait alone costs 30-100 us, depending on how
   // the runtime decides to wait)
-  const size_t need = pad256((size_t)nq * mdl->d) + pad256((size_t)nq * mdl->m);
-  if (need <= SMALL_STAGE_LIMIT && !is_device_ptr(Xq) && !is_device_ptr(out)) {
-    SmallStage st;
-    st.ctx = ctx;
-    NK_TRY(small_reserve(ctx, need));
-    const double* xh = small_in(st, Xq, ldx, nq, mdl->d);
-    double* oh = small_out(st, out, ldo, nq, mdl->m);
-    double* xd = nullptr;  // every wave of the kernel-matrix kernel reads its state row: from HBM, not over PCIe
-    NK_TRY(arena_alloc_t(ctx, (size_t)nq * mdl->d, &xd));
-    NK_TRY(launch_copy2d(ctx, xh, mdl->d, xd, mdl->d, nq, mdl->d));
-    NK_TRY(lift_device(ctx, mdl, xd, mdl->d, nq, oh, mdl->m));
-    NK_HIP(hipStreamSynchronize(ctx->stream));
-    small_finish(st);
-    return NK_OK;
-  }
+  CallStage st(ctx);
   MatIn x;
-  NK_TRY(stage_in(ctx, Xq, ldx, nq, mdl->d, &x));
   MatOut o;
-  NK_TRY(stage_out(ctx, out, ldo, nq, mdl->m, &o));
+  st.in(&x, Xq, ldx, nq, mdl->d);
+  st.out(&o, out, ldo, nq, mdl->m);
+  NK_TRY(st.commit());
+  NK_TRY(st.resident(&x, mdl->d));  // every wave of the kernel-matrix kernel reads its state row
   NK_TRY(lift_device(ctx, mdl, x.ptr, x.ld, nq, o.dev, o.ld));
-  NK_TRY(finish_out(ctx, o));
+  NK_TRY(st.queue_outputs());
   NK_HIP(hipStreamSynchronize(ctx->stream));
+  st.deliver();
   return NK_OK;
 }
 
@@ -946,29 +970,17 @@ int nk_predict(nk_ctx* ctx, const nk_model* mdl, const double* Xaug, int64_t ldx
   NK_REQUIRE(nq >= 0 && ldx >= mdl->d + mdl->p && ldo >= mdl->d, "nk_predict: bad sizes");
   if (nq == 0) return NK_OK;
   const int64_t dp = mdl->d + mdl->p;
-  const size_t need = pad256((size_t)nq * dp) + pad256((size_t)nq * mdl->d);
-  if (need <= SMALL_STAGE_LIMIT && !is_device_ptr(Xaug) && !is_device_ptr(out)) {  // see nk_lift
-    SmallStage st;
-    st.ctx = ctx;
-    NK_TRY(small_reserve(ctx, need));
-    const double* xh = small_in(st, Xaug, ldx, nq, dp);
-    double* oh = small_out(st, out, ldo, nq, mdl->d);
-    const int64_t ldd = dp + (dp & 1);
-    double* xd = nullptr;
-    NK_TRY(arena_alloc_t(ctx, (size_t)nq * ldd, &xd));
-    NK_TRY(launch_copy2d(ctx, xh, dp, xd, ldd, nq, dp));
-    NK_TRY(predict_device(ctx, mdl, xd, ldd, nq, oh, mdl->d));
-    NK_HIP(hipStreamSynchronize(ctx->stream));
-    small_finish(st);
-    return NK_OK;
-  }
+  CallStage st(ctx);  // see nk_lift
   MatIn x;
-  NK_TRY(stage_in(ctx, Xaug, ldx, nq, mdl->d + mdl->p, &x));
   MatOut o;
-  NK_TRY(stage_out(ctx, out, ldo, nq, mdl->d, &o));
+  st.in(&x, Xaug, ldx, nq, dp);
+  st.out(&o, out, ldo, nq, mdl->d);
+  NK_TRY(st.commit());
+  NK_TRY(st.resident(&x, dp + (dp & 1)));
   NK_TRY(predict_device(ctx, mdl, x.ptr, x.ld, nq, o.dev, o.ld));
-  NK_TRY(finish_out(ctx, o));
+  NK_TRY(st.queue_outputs());
   NK_HIP(hipStreamSynchronize(ctx->stream));
+  st.deliver();
   return NK_OK;
 }
 

@@ -14,6 +14,7 @@ struct MatIn {
   const double* ptr = nullptr;
   int64_t ld = 0;
   bool staged = false;
+  int64_t rows = 0, cols = 0;
 };
 int stage_in(nk_ctx* ctx, const double* p, int64_t ld, int64_t rows, int64_t cols, MatIn* out);
 struct MatOut {
@@ -52,21 +53,32 @@ struct HostTrace {
 };
 float ev_ms(nk_ctx* ctx, int a, int b);  // a, b: EV_* slots
 
-// ---- small-call staging: the latency-bound entry points (rollouts, closed loops) read their host inputs from, and write
-//      their host outputs into, one page-locked block that the GPU addresses directly -- no DMA descriptors, no staging
-//      copies on the stream; the host moves the bytes with memcpy before the launch and after the one synchronisation.
-struct SmallStage {
-  nk_ctx* ctx = nullptr;
-  size_t off = 0;
-  struct Out { double* stage; double* user; int64_t user_ld; int64_t rows, cols; };
-  std::vector<Out> outs;
-};
+// ---- call staging of the latency-bound entry points (lift, predict, rollouts, closed loops): the entry point declares
+//      its operands once, commit() picks one of two transports and fills the views, and one body works on them.
+//      Page-locked transport -- chosen exactly when the 256-byte-padded operands together fit SMALL_STAGE_LIMIT and no
+//      declared pointer is device memory: operands live in one page-locked block that the GPU addresses directly, with
+//      tight leading dimensions -- no DMA descriptors, no staging copies on the stream; the host moves the bytes with
+//      memcpy before the launch and after the one synchronisation.  Arena transport otherwise: stage_in / stage_out.
 constexpr size_t SMALL_STAGE_LIMIT = (size_t)4 << 20;
-int small_reserve(nk_ctx* ctx, size_t bytes);
-const double* small_in(SmallStage& st, const double* host, int64_t ld, int64_t rows, int64_t cols);
-double* small_out(SmallStage& st, double* user, int64_t user_ld, int64_t rows, int64_t cols);
-void small_finish(SmallStage& st);  // after the stream has been synchronised
 inline size_t pad256(size_t doubles) { return ((doubles * 8) + 255) & ~(size_t)255; }
+class CallStage {
+ public:
+  explicit CallStage(nk_ctx* c) : ctx(c) {}
+  // declare an operand (recorded only; the views are valid after commit); a null output is skipped
+  void in(MatIn* view, const double* p, int64_t ld, int64_t rows, int64_t cols) { ops.push_back({view, nullptr, p, ld, rows, cols}); }
+  void out(MatOut* view, double* p, int64_t ld, int64_t rows, int64_t cols) { if (p) ops.push_back({nullptr, view, p, ld, rows, cols}); }
+  int commit();
+  // an input that every wave reads: when it lies in the page-locked block it is copied into the arena (leading dimension
+  // ld) and the view moved there -- from HBM, not an uncached PCIe read per wave; on the arena transport nothing happens
+  int resident(MatIn* view, int64_t ld);
+  int queue_outputs();  // arena transport: the device-to-host copies, once per attempt; before the synchronisation
+  void deliver();       // page-locked transport: the memcpy back to the caller; once, after the synchronisation
+ private:
+  struct Operand { MatIn* in; MatOut* out; const double* ptr; int64_t ld, rows, cols; };
+  nk_ctx* ctx;
+  bool pinned = false;
+  std::vector<Operand> ops;
+};
 
 // the body of nk_rollout_err for a context whose arena the caller has prepared (check_ctx): the sweep gathers a unit's
 // trajectories into the arena first (nk_control.hip)

@@ -107,6 +107,39 @@ static int rollout_steps(nk_ctx* ctx, ChainArgs chain, bool z0_in_place, bool us
   return NK_OK;
 }
 
+// The recursion of `ch`, then what `after` queues behind it, then the one synchronisation of the attempt.  When the
+// single-launch multi-workgroup recursion is the path (chain_mw_wanted) the mutex is held for the whole call, and when
+// a wave of it gave up waiting for its neighbours (the device was oversubscribed) the trajectories are not valid: z_0 is
+// untouched, so everything is repeated once with one launch per step.
+// batch_invariant (the error mode): the bits must not depend on the batch or on the schedule -- an ordinary context and a
+// lock-step member must agree, the sweep is checked bit for bit against the plain loop.  Beyond the single-launch chain
+// that rules out the multi-workgroup recursion and the per-step GEMM of batches above 16 (another summation order): the
+// matrix-vector steps are walked 16 trajectories at a time, the path a member takes for a small batch.
+template <class After>
+static int run_chain(nk_ctx* ctx, const ChainArgs& ch, bool z0_in_place, bool batch_invariant, After after) {
+  const bool try_mw = !batch_invariant && chain_mw_wanted(ctx, ch);
+  std::unique_lock<std::mutex> mw_lock(g_chain_mw_mutex, std::defer_lock);
+  if (try_mw) mw_lock.lock();
+  for (int attempt = 0; attempt < 2; ++attempt) {
+    const bool mw = try_mw && attempt == 0;
+    if (batch_invariant && !lifted_chain_ok(ch.m, ch.pu, ch.lift ? ch.d : 0)) {
+      for (int b0 = 0; b0 < ch.batch; b0 += 16) {
+        ChainArgs sub = ch;
+        sub.batch = ch.batch - b0 < 16 ? ch.batch - b0 : 16;
+        sub.Zall = ch.Zall + (int64_t)b0 * ch.z_stride;
+        if (ch.U) sub.U = ch.U + (int64_t)b0 * ch.u_stride;
+        NK_TRY(rollout_steps(ctx, sub, z0_in_place, false));
+      }
+    } else {
+      NK_TRY(rollout_steps(ctx, ch, z0_in_place, mw));
+    }
+    NK_TRY(after());
+    NK_HIP(hipStreamSynchronize(ctx->stream));
+    if (!(mw && chain_mw_gave_up(ctx))) break;
+  }
+  return NK_OK;
+}
+
 static int rollout_impl(nk_ctx* ctx, const nk_model* mdl, const double* G, int64_t ldg, const double* Cop, int64_t ldc,
                         int m, int d, int p, const double* x0, int64_t ldx0, const double* z0, const double* U, int32_t T,
                         int32_t batch, double* out_x, double* out_z, const double* traj_true = nullptr,
@@ -121,52 +154,26 @@ static int rollout_impl(nk_ctx* ctx, const nk_model* mdl, const double* G, int64
   const int64_t ldin = err_mode ? (int64_t)T * d : (x0 ? ldx0 : m);
   const double* first = err_mode ? traj_true : (x0 ? x0 : z0);
   const bool have_u = p > 0 && T > 1;
-  const size_t need = pad256((size_t)batch * nin) + (have_u ? pad256((size_t)batch * T * p) : 0) +
-                      (err_mode ? pad256((size_t)batch * 2)
-                                : pad256((size_t)batch * T * d) + (out_z ? pad256((size_t)batch * T * m) : 0));
-  const bool small = need <= SMALL_STAGE_LIMIT && !is_device_ptr(first) && !(have_u && is_device_ptr(U)) &&
-                     (err_mode || (!is_device_ptr(out_x) && !(out_z && is_device_ptr(out_z))));
   double* Zall = nullptr;  // [batch][T][m]
   NK_TRY(arena_alloc_t(ctx, (size_t)batch * T * m, &Zall));
   const int64_t ldz = (int64_t)T * m;
   ChainArgs ch;
   ch.G = G; ch.ldg = ldg; ch.m = m; ch.pu = p; ch.T = T; ch.batch = batch; ch.Zall = Zall; ch.z_stride = ldz;
   ch.u_stride = (int64_t)T * p;
-  SmallStage st;
-  st.ctx = ctx;
+  CallStage st(ctx);
   MatIn xin, uin;
   MatOut ox, oz, oe;
-  double *xdev = nullptr, *zdev = nullptr, *edev = nullptr;
-  if (small) {
-    NK_TRY(small_reserve(ctx, need));
-    xin.ptr = small_in(st, first, ldin, batch, nin);
-    xin.ld = nin;
-    if (have_u) { uin.ptr = small_in(st, U, (int64_t)T * p, batch, (int64_t)T * p); uin.ld = (int64_t)T * p; }
-    if (err_mode) {
-      edev = small_out(st, err_out, 2, batch, 2);
-      double* tdev = nullptr;  // every row of the true trajectories is read by the error kernel: from HBM, not over PCIe
-      NK_TRY(arena_alloc_t(ctx, (size_t)batch * nin, &tdev));
-      NK_TRY(launch_copy2d(ctx, xin.ptr, nin, tdev, nin, batch, nin));
-      xin.ptr = tdev;
-    } else {
-      xdev = small_out(st, out_x, d, (int64_t)batch * T, d);
-      if (out_z) zdev = small_out(st, out_z, m, (int64_t)batch * T, m);
-    }
+  st.in(&xin, first, ldin, batch, nin);
+  if (have_u) st.in(&uin, U, (int64_t)T * p, batch, (int64_t)T * p);
+  if (err_mode) {
+    st.out(&oe, err_out, 2, batch, 2);
   } else {
-    NK_TRY(stage_in(ctx, first, ldin, batch, nin, &xin));
-    if (have_u) NK_TRY(stage_in(ctx, U, (int64_t)T * p, batch, (int64_t)T * p, &uin));
-    if (err_mode) {
-      NK_TRY(stage_out(ctx, err_out, 2, batch, 2, &oe));
-      edev = oe.dev;
-    } else {
-      NK_TRY(stage_out(ctx, out_x, d, (int64_t)batch * T, d, &ox));
-      xdev = ox.dev;
-      if (out_z) { NK_TRY(stage_out(ctx, out_z, m, (int64_t)batch * T, m, &oz)); zdev = oz.dev; }
-    }
+    st.out(&ox, out_x, d, (int64_t)batch * T, d);
+    st.out(&oz, out_z, m, (int64_t)batch * T, m);
   }
-  ch.U = have_u ? uin.ptr : nullptr;
+  NK_TRY(st.commit());
+  if (err_mode) NK_TRY(st.resident(&xin, nin));  // every row of the true trajectories is read by the error kernel
   if (!have_u) ch.pu = (T > 1) ? p : 0;
-  const int64_t ldxo = small ? d : ox.ld, ldzo = small ? m : (out_z ? oz.ld : m);
   bool z0_in_place = false;
   if (from_state && mdl->kind != NK_MODEL_SPLINE && lifted_chain_ok(m, ch.pu, d)) {  // the lift is done by the chain kernel itself
     ch.lift = true; ch.x0 = xin.ptr; ch.x0_stride = xin.ld; ch.Zl = mdl->Z; ch.d = d; ch.winv = mdl->winv;
@@ -182,52 +189,20 @@ static int rollout_impl(nk_ctx* ctx, const nk_model* mdl, const double* G, int64
     NK_TRY(launch_copy2d(ctx, xin.ptr, xin.ld, Zall, ldz, batch, m));
     z0_in_place = true;
   }
-  if (z0_in_place && small && have_u) {
-    // the stepwise / multi-workgroup paths read the controls from every wave of every step: not from page-locked host
-    // memory (an uncached PCIe read per wave, ~30 us per step at m = 500) but from a device copy
-    double* Udev = nullptr;
-    NK_TRY(arena_alloc_t(ctx, (size_t)batch * T * p, &Udev));
-    NK_TRY(launch_copy2d(ctx, uin.ptr, uin.ld, Udev, (int64_t)T * p, batch, (int64_t)T * p));
-    ch.U = Udev;
-  }
-  // The error mode promises bits that do not depend on the batch or on the schedule (an ordinary context and a lock-step
-  // member must agree: the sweep is checked bit for bit against the plain loop).  Beyond the single-launch chain that
-  // rules out the multi-workgroup recursion (members cannot take it, and its give-up repeats the recursion with other
-  // kernels) and the per-step GEMM of batches above 16 (another summation order): the error mode always walks the
-  // matrix-vector steps, 16 trajectories at a time -- the path a member takes for a small batch.
-  const bool try_mw = !err_mode && chain_mw_wanted(ctx, ch);
-  std::unique_lock<std::mutex> mw_lock(g_chain_mw_mutex, std::defer_lock);
-  if (try_mw) mw_lock.lock();
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    const bool mw = try_mw && attempt == 0;
-    if (err_mode && !lifted_chain_ok(m, ch.pu, ch.lift ? ch.d : 0)) {
-      for (int b0 = 0; b0 < batch; b0 += 16) {
-        ChainArgs sub = ch;
-        sub.batch = batch - b0 < 16 ? batch - b0 : 16;
-        sub.Zall = ch.Zall + (int64_t)b0 * ch.z_stride;
-        if (ch.U) sub.U = ch.U + (int64_t)b0 * ch.u_stride;
-        NK_TRY(rollout_steps(ctx, sub, z0_in_place, false));
-      }
-    } else {
-      NK_TRY(rollout_steps(ctx, ch, z0_in_place, mw));
-    }
+  // the stepwise / multi-workgroup paths read the controls from every wave of every step: not from page-locked host
+  // memory (an uncached PCIe read per wave, ~30 us per step at m = 500) but from a device copy
+  if (z0_in_place && have_u) NK_TRY(st.resident(&uin, (int64_t)T * p));
+  ch.U = have_u ? uin.ptr : nullptr;
+  NK_TRY(run_chain(ctx, ch, z0_in_place, /*batch_invariant=*/err_mode, [&]() -> int {
     if (err_mode) {  // x_true - C z and C z squared and summed per trajectory where z lies: no product, no trajectory copy
-      NK_TRY(launch_traj_err(ctx, Zall, ldz, Cop, ldc, xin.ptr, xin.ld, m, d, T, batch, edev));
-      if (!small) NK_TRY(finish_out(ctx, oe));
+      NK_TRY(launch_traj_err(ctx, Zall, ldz, Cop, ldc, xin.ptr, xin.ld, m, d, T, batch, oe.dev));
     } else {
-      NK_TRY(launch_gemm(ctx, false, true, (int64_t)batch * T, d, m, 1.0, Zall, m, Cop, ldc, 0.0, xdev, ldxo));
-      if (out_z) NK_TRY(launch_copy2d(ctx, Zall, m, zdev, ldzo, (int64_t)batch * T, m));
-      if (!small) {
-        NK_TRY(finish_out(ctx, ox));
-        if (out_z) NK_TRY(finish_out(ctx, oz));
-      }
+      NK_TRY(launch_gemm(ctx, false, true, (int64_t)batch * T, d, m, 1.0, Zall, m, Cop, ldc, 0.0, ox.dev, ox.ld));
+      if (out_z) NK_TRY(launch_copy2d(ctx, Zall, m, oz.dev, oz.ld, (int64_t)batch * T, m));
     }
-    NK_HIP(hipStreamSynchronize(ctx->stream));
-    // a wave of the single-launch recursion gave up waiting for its neighbours (the device was oversubscribed): the
-    // trajectories are not valid; z_0 is untouched, so the recursion is repeated with one launch per step
-    if (!(mw && chain_mw_gave_up(ctx))) break;
-  }
-  if (small) small_finish(st);
+    return st.queue_outputs();
+  }));
+  st.deliver();
   return NK_OK;
 }
 
@@ -415,31 +390,15 @@ int nk_closed_loop_batch(nk_ctx* ctx, const nk_model* mdl, const double* K, cons
   NK_REQUIRE(mdl && K && phi0 && phi_ref && out_x && out_u, "nk_closed_loop: null argument");
   NK_REQUIRE(mdl->has_ops && steps >= 1 && batch >= 1 && mdl->p > 0, "nk_closed_loop: bad model or sizes");
   const int m = mdl->m, d = mdl->d, p = mdl->p, mp = m + p;
-  const size_t need = pad256((size_t)p * m) + 2 * pad256((size_t)batch * m) + pad256((size_t)batch * steps * d) +
-                      pad256((size_t)batch * steps * p);
-  const bool small = need <= SMALL_STAGE_LIMIT && !is_device_ptr(K) && !is_device_ptr(phi0) && !is_device_ptr(phi_ref) &&
-                     !is_device_ptr(out_x) && !is_device_ptr(out_u);
-  SmallStage st;
-  st.ctx = ctx;
+  CallStage st(ctx);
   MatIn k, f0, fr;
   MatOut ox, ou;
-  double *xdev = nullptr, *udev = nullptr;
-  int64_t ldxo = d, lduo = p;
-  if (small) {
-    NK_TRY(small_reserve(ctx, need));
-    k.ptr = small_in(st, K, m, p, m); k.ld = m;
-    f0.ptr = small_in(st, phi0, m, batch, m); f0.ld = m;
-    fr.ptr = small_in(st, phi_ref, m, batch, m); fr.ld = m;
-    xdev = small_out(st, out_x, d, (int64_t)batch * steps, d);
-    udev = small_out(st, out_u, p, (int64_t)batch * steps, p);
-  } else {
-    NK_TRY(stage_in(ctx, K, m, p, m, &k));
-    NK_TRY(stage_in(ctx, phi0, m, batch, m, &f0));
-    NK_TRY(stage_in(ctx, phi_ref, m, batch, m, &fr));
-    NK_TRY(stage_out(ctx, out_x, d, (int64_t)batch * steps, d, &ox));
-    NK_TRY(stage_out(ctx, out_u, p, (int64_t)batch * steps, p, &ou));
-    xdev = ox.dev; udev = ou.dev; ldxo = ox.ld; lduo = ou.ld;
-  }
+  st.in(&k, K, m, p, m);
+  st.in(&f0, phi0, m, batch, m);
+  st.in(&fr, phi_ref, m, batch, m);
+  st.out(&ox, out_x, d, (int64_t)batch * steps, d);
+  st.out(&ou, out_u, p, (int64_t)batch * steps, p);
+  NK_TRY(st.commit());
   // phi_{t+1} = A phi_t + B K (phi_ref - phi_t) = (A - B K) phi_t + B K phi_ref: one matrix-vector step per time step
   // (algebraically the loop of benchmark_lqr_cloth.py:79-84; the controls u_t = K (phi_ref - phi_t) are recovered for all
   // steps at once afterwards)
@@ -463,24 +422,14 @@ int nk_closed_loop_batch(nk_ctx* ctx, const nk_model* mdl, const double* K, cons
     NK_TRY(launch_copy2d(ctx, f0.ptr, f0.ld, Phi, ch.z_stride, batch, m));
     z0_in_place = true;
   }
-  const bool try_mw = chain_mw_wanted(ctx, ch);
-  std::unique_lock<std::mutex> mw_lock(g_chain_mw_mutex, std::defer_lock);
-  if (try_mw) mw_lock.lock();
-  for (int attempt = 0; attempt < 2; ++attempt) {
-    const bool mw = try_mw && attempt == 0;
-    NK_TRY(rollout_steps(ctx, ch, z0_in_place, mw));
+  NK_TRY(run_chain(ctx, ch, z0_in_place, /*batch_invariant=*/false, [&]() -> int {
     // u_t = K (phi_ref - phi_t) for all t: D = 1 phi_ref^T - Phi, U = D K^T
     NK_TRY(launch_ref_minus_traj(ctx, fr.ptr, fr.ld, Phi, ch.z_stride, Dm, ch.z_stride, steps, m, batch));
-    NK_TRY(launch_gemm(ctx, false, true, (int64_t)batch * steps, p, m, 1.0, Dm, m, k.ptr, k.ld, 0.0, udev, lduo));
-    NK_TRY(launch_gemm(ctx, false, true, (int64_t)batch * steps, d, m, 1.0, Phi, m, mdl->C, m, 0.0, xdev, ldxo));  // x_t = C phi_t
-    if (!small) {
-      NK_TRY(finish_out(ctx, ox));
-      NK_TRY(finish_out(ctx, ou));
-    }
-    NK_HIP(hipStreamSynchronize(ctx->stream));
-    if (!(mw && chain_mw_gave_up(ctx))) break;  // see rollout_impl
-  }
-  if (small) small_finish(st);
+    NK_TRY(launch_gemm(ctx, false, true, (int64_t)batch * steps, p, m, 1.0, Dm, m, k.ptr, k.ld, 0.0, ou.dev, ou.ld));
+    NK_TRY(launch_gemm(ctx, false, true, (int64_t)batch * steps, d, m, 1.0, Phi, m, mdl->C, m, 0.0, ox.dev, ox.ld));  // x_t = C phi_t
+    return st.queue_outputs();
+  }));
+  st.deliver();
   return NK_OK;
 }
 

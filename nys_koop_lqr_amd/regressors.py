@@ -145,32 +145,21 @@ def _fetched(name):
     return property(get, set_)
 
 
-class KoopmanNystromRegressor(KoopmanRegressor):
-    """regressors.py:114-178, MI355X-native.
-
-    Differences a caller can observe (all additive): `lift`/`predict` reuse K_mm^{-1/2} computed at fit time instead
-    of re-running sqrtm per call (regressors.py:174-175); `fit` accepts `row_ranges` (training rows of a K-fold split
-    without copying) and device-resident inputs; `rollout`, `score_neg_rmse`, `closed_loop` and `solve_lqr` expose
-    the callers' inner loops (benchmark_lqr_cloth.py:18-36, 52-57, 69-104, 238-263) as single calls.
-    """
+class _DeviceModelRegressor(KoopmanRegressor):
+    """What the estimators with a device model (nk_model) share: the asynchronous operator fetch, pickling through host
+    copies, the model's lifetime, and lift / predict / rollout / closed loops on it.  An estimator names the attribute that
+    holds its landmarks (`_landmarks_attr`, d x m), creates its model from host copies (`_create_model`) and fits."""
 
     A = _fetched("A")
     B = _fetched("B")
     C = _fetched("C")
     weights = _fetched("weights")
-    # Arithmetic of the O(n m d) kernel blocks and O(n m^2) Gram contractions of `fit`: "f64" (the only mode that meets the
-    # 1e-6 operator bar) or "f32" (BASELINE.json's stress configuration; include/nyskoop.h, nk_set_compute_dtype).  An
-    # attribute, not a constructor argument: the constructor mirrors the reference's (sklearn clone / get_params), and a
-    # clone starts from the default.
-    compute_dtype = "f64"
+    _landmarks_attr = None
+    _no_landmarks = "regressor has no landmarks: call fit first"
 
-    def __init__(self, n_inputs, kernel=None, gamma=None, m=None):
+    def __init__(self, n_inputs, gamma, m):
         self._fetching = False
         super().__init__(n_inputs, gamma, m)
-        self.kernel = kernel
-        self.nystrom_centers_input = None
-        self.nystrom_centers_output = None
-        self.jitter = 1e-6
         self._model = None
         self._model_key = None
         self._stats = None
@@ -181,6 +170,7 @@ class KoopmanNystromRegressor(KoopmanRegressor):
         """Forget the device copy of landmarks and operators (rebuilt from the host attributes at the next use)."""
         self._wait_fetch()
         self._drop_model()
+
     def _wait_fetch(self):
         if self.__dict__.get("_fetching"):
             self.__dict__["_fetching"] = False
@@ -225,64 +215,40 @@ class KoopmanNystromRegressor(KoopmanRegressor):
             self._model = None
             self._model_key = None
 
+    def _create_model(self, ctx, Z, p, pa, pb, pc, pw):
+        """Handle of a new device model with landmarks Z (m x d) and the operators behind the four pointers (or None)."""
+        raise NotImplementedError
+
     def _ensure_model(self):
-        """Device model for lift/predict/rollout; rebuilt from host copies after un-pickling or when a caller
+        """Device model for lift / predict / rollout; rebuilt from host copies after un-pickling or when a caller
         replaced the landmarks / operators by hand."""
-        if self.nystrom_centers_output is None:
-            raise RuntimeError("regressor has no landmarks: call fit first")
+        landmarks = self._landmarks()
+        if landmarks is None:
+            raise RuntimeError(self._no_landmarks)
         key = self._ops_key()
         if self._model is not None and self._model_key == key:
             return self._model
         self._wait_fetch()
         self._drop_model()
         ctx = _lib.get_context()
-        Z = np.ascontiguousarray(np.asarray(self.nystrom_centers_output, dtype=np.float64).T)  # m x d
+        Z = np.ascontiguousarray(np.asarray(landmarks, dtype=np.float64).T)  # m x d
         m, d = Z.shape
-        kd, keep = self.kernel.kernel.desc(d)
         p = int(self.n_inputs)
+        keep = []
 
         def ptr(a, shape):
             if a is None:
-                return None, None
+                return None
             a = np.ascontiguousarray(a, dtype=np.float64)
             if a.shape != shape:
                 raise ValueError(f"operator has shape {a.shape}, expected {shape}")
-            return a.ctypes.data, a
+            keep.append(a)
+            return a.ctypes.data
 
-        pa, ka = ptr(self.A, (m, m))
-        pb, kb = ptr(self.B, (m, p))
-        pc, kc = ptr(self.C, (d, m))
-        pw, kw = ptr(self.weights, (d, m + p))
-        h = C.c_void_p()
-        rc = ctx.lib.nk_model_create(ctx.handle, C.byref(kd), Z.ctypes.data, d, m, d, p, float(self.jitter),
-                                     pa, pb, pc, pw, C.byref(h))
-        if rc == -1:
-            raise ValueError(ctx.lib.nk_last_error().decode())
-        _lib.check(rc)
+        h = self._create_model(ctx, Z, p, ptr(self.A, (m, m)), ptr(self.B, (m, p)), ptr(self.C, (d, m)),
+                               ptr(self.weights, (d, m + p)))
         self._model, self._model_key = h, key
         return h
-
-    # ------------------------------------------------------------------------------------------------ fit
-    def _prepare(self, n, d, Y=None):
-        """Landmarks (regressors.py:129-134) and kernel descriptor for a fit on d-dimensional states."""
-        if self.nystrom_centers_output is None:  # regressors.py:129-132: global legacy NumPy RNG, n = #samples
-            if Y is None:
-                raise RuntimeError("landmarks must be set before a fit from Gram blocks")
-            idx = np.random.choice(np.arange(0, n), size=self.m, replace=False)
-            if _is_device_tensor(Y):
-                rows = Y[idx.tolist()]
-                self.nystrom_centers_output = np.ascontiguousarray(rows.cpu().numpy().T)
-            else:
-                self.nystrom_centers_output = np.asarray(Y).T[:, idx]
-        if self.nystrom_centers_input is None:  # regressors.py:133-134
-            self.nystrom_centers_input = self.nystrom_centers_output
-        Zo = np.ascontiguousarray(np.asarray(self.nystrom_centers_output, dtype=np.float64).T)
-        if Zo.shape[1] != d:
-            raise ValueError(f"landmarks have dimension {Zo.shape[1]}, data has {d}")
-        same = self.nystrom_centers_input is self.nystrom_centers_output
-        Zi = Zo if same else np.ascontiguousarray(np.asarray(self.nystrom_centers_input, dtype=np.float64).T)
-        kd, keep = self.kernel.kernel.desc(d)
-        return Zo, Zi, same, kd, keep
 
     @staticmethod
     def _ranges(row_ranges):
@@ -290,14 +256,6 @@ class KoopmanNystromRegressor(KoopmanRegressor):
             return None, 0, None
         flat = np.ascontiguousarray(np.asarray(row_ranges, dtype=np.int64).reshape(-1))
         return flat.ctypes.data_as(C.POINTER(C.c_int64)), flat.size // 2, flat
-
-    @staticmethod
-    def _raise(ctx, rc):
-        if rc == -1:
-            raise ValueError(ctx.lib.nk_last_error().decode())
-        if rc == -3:
-            raise np.linalg.LinAlgError(ctx.lib.nk_last_error().decode())
-        _lib.check(rc)
 
     def _adopt(self, ctx, h, stats, m, d, p, t_host, fetch=True):
         """Take over a freshly fitted device model: queue the copies of the operators into page-locked arrays
@@ -323,114 +281,17 @@ class KoopmanNystromRegressor(KoopmanRegressor):
                            host_ms_fetch=(t_host3 - t_host2) * 1e3, host_ms_pinned=(t_host2b - t_host2) * 1e3)
         self._model_key = self._ops_key()
 
-    def fit(self, X, Y, row_ranges=None, fetch=True):
-        """regressors.py:122-169.  X: n x (d+p) rows [state | input], Y: n x d (NumPy arrays, or float64 device
-        tensors already resident in HBM).  Returns None, like the reference."""
-        ctx = _lib.get_context()
-        Xm, Ym = _lib.Mat(X), _lib.Mat(Y)
-        n, d = Ym.shape
-        p = int(self.n_inputs)
-        if Xm.shape != (n, d + p):
-            raise ValueError(f"X has shape {Xm.shape}, expected {(n, d + p)}")
-        Zo, Zi, same, kd, keep = self._prepare(n, d, Y)
-        m = Zo.shape[0]
-        rr, n_rr, keep_rr = self._ranges(row_ranges)
-        stats = _lib.FitStats()
-        h = C.c_void_p()
-        t_host0 = time.perf_counter()
-        self._drop_model()
-        t_host1 = time.perf_counter()
-        ctx.wait_for(X, Y)  # device tensors: whatever torch still has queued for them comes first
-        ctx.set_compute_dtype(self.compute_dtype)
-        try:
-            rc = ctx.lib.nk_nystrom_fit(ctx.handle, C.byref(kd), Xm.ptr, Xm.ld, Ym.ptr, Ym.ld, n, d, p, rr, n_rr,
-                                        None if same else Zi.ctypes.data, d, Zo.ctypes.data, d, m,
-                                        float(self.gamma), float(self.jitter), C.byref(h), C.byref(stats))
-        finally:
-            if self.compute_dtype != "f64":
-                ctx.set_compute_dtype("f64")
-        self._raise(ctx, rc)
-        self._adopt(ctx, h, stats, m, d, p, (t_host0, t_host1), fetch)
-
-    # ------------------------------------------------------------------------- sample-sharded fit (SURVEY 8e(2))
-    def gram_size(self, d):
-        """Number of float64 entries of the packed Gram accumulator for d-dimensional states."""
-        m = np.asarray(self.nystrom_centers_output).shape[1] if self.nystrom_centers_output is not None else int(self.m)
-        cnt = C.c_int64()
-        _lib.check(_lib.load_library().nk_gram_doubles(m, d, int(self.n_inputs), C.byref(cnt)))
-        return int(cnt.value)
-
-    def gram_partial(self, X, Y, row_ranges=None, out=None):
-        """The four Gram blocks of regressors.py:151,153,162,164 (without the regularisers) over the given rows only,
-        packed into one flat float64 buffer `out` (a NumPy array, or a 1-D device tensor which is then filled in
-        place without leaving the GPU).  Landmarks must be set: every shard of a sharded fit uses the same ones."""
-        ctx = _lib.get_context()
-        Xm, Ym = _lib.Mat(X), _lib.Mat(Y)
-        n, d = Ym.shape
-        p = int(self.n_inputs)
-        if Xm.shape != (n, d + p):
-            raise ValueError(f"X has shape {Xm.shape}, expected {(n, d + p)}")
-        if self.nystrom_centers_output is None:
-            raise RuntimeError("landmarks must be set before gram_partial (all shards share them)")
-        Zo, Zi, same, kd, keep = self._prepare(n, d)
-        m = Zo.shape[0]
-        cnt = self.gram_size(d)
-        if out is None:
-            out = np.empty(cnt)
-        if _is_device_tensor(out):
-            if out.dim() != 1 or out.numel() != cnt or not out.is_contiguous() or "float64" not in str(out.dtype):
-                raise ValueError(f"out must be a contiguous float64 tensor with {cnt} entries")
-            optr = out.data_ptr()
-        else:
-            if out.shape != (cnt,) or out.dtype != np.float64 or not out.flags.c_contiguous:
-                raise ValueError(f"out must be a contiguous float64 array with {cnt} entries")
-            optr = out.ctypes.data
-        rr, n_rr, keep_rr = self._ranges(row_ranges)
-        stats = _lib.FitStats()
-        ctx.wait_for(X, Y, out)
-        rc = ctx.lib.nk_nystrom_gram(ctx.handle, C.byref(kd), Xm.ptr, Xm.ld, Ym.ptr, Ym.ld, n, d, p, rr, n_rr,
-                                     None if same else Zi.ctypes.data, d, Zo.ctypes.data, d, m, optr, C.byref(stats))
-        self._raise(ctx, rc)
-        self._gram_stats = stats.as_dict()
-        return out
-
-    def fit_from_gram(self, gram, n_total, d):
-        """Finish the fit from accumulated Gram blocks (the sum of gram_partial over all shards); n_total = number of
-        training rows over all shards (the `n` of regressors.py:127)."""
-        ctx = _lib.get_context()
-        p = int(self.n_inputs)
-        Zo, Zi, same, kd, keep = self._prepare(n_total, d)
-        m = Zo.shape[0]
-        cnt = self.gram_size(d)
-        if _is_device_tensor(gram):
-            if gram.numel() != cnt or not gram.is_contiguous() or "float64" not in str(gram.dtype):
-                raise ValueError(f"gram must be a contiguous float64 tensor with {cnt} entries")
-            gptr = gram.data_ptr()
-        else:
-            gram = np.ascontiguousarray(gram, dtype=np.float64).reshape(-1)
-            if gram.size != cnt:
-                raise ValueError(f"gram must have {cnt} entries")
-            gptr = gram.ctypes.data
-        stats = _lib.FitStats()
-        h = C.c_void_p()
-        t_host0 = time.perf_counter()
-        self._drop_model()
-        t_host1 = time.perf_counter()
-        ctx.wait_for(gram)  # e.g. the output of an all-reduce still running on torch's (RCCL's) stream
-        rc = ctx.lib.nk_nystrom_solve(ctx.handle, C.byref(kd), None if same else Zi.ctypes.data, d, Zo.ctypes.data, d, m,
-                                      d, p, gptr, int(n_total), float(self.gamma), float(self.jitter), C.byref(h),
-                                      C.byref(stats))
-        self._raise(ctx, rc)
-        self._adopt(ctx, h, stats, m, d, p, (t_host0, t_host1))
+    def _landmarks(self):
+        return getattr(self, self._landmarks_attr)
 
     def _landmark_shape(self):
         """(d, m) of the landmarks the device model lifts with."""
-        return np.asarray(self.nystrom_centers_output).shape
+        return np.asarray(self._landmarks()).shape
 
     def _ops_key(self):
         # landmarks are a plain attribute (the reference's callers assign them): identity + shape; operators: the
         # version counter bumped by every assignment (ids alone could be reused by a new array after a free)
-        z = self.nystrom_centers_output
+        z = self._landmarks()
         return (id(z), None if z is None else np.shape(z), self.__dict__.get("_ops_version", 0))
 
     # ------------------------------------------------------------------------------------------------ lift / predict
@@ -519,7 +380,7 @@ class KoopmanNystromRegressor(KoopmanRegressor):
         ptr = out.ctypes.data_as(C.POINTER(C.c_double))
         rc = ctx.lib.nk_rollout_err(ctx.handle, h, tr.ctypes.data, None if U is None else U.ctypes.data, T, k,
                                     None if relative else ptr, ptr if relative else None)
-        self._raise(ctx, rc)
+        _lib.check_mapped(rc)
         return out
 
     def closed_loop(self, K, phi0, phi_ref, num_steps):
@@ -585,7 +446,7 @@ class KoopmanNystromRegressor(KoopmanRegressor):
         ox, ou = np.empty((batch, max(num_steps, 0) + 1, d)), np.empty((batch, max(num_steps, 0), 1))
         rc = ctx.lib.nk_plant_loop(ctx.handle, h, int(plant_id), float(Ts), K.ctypes.data, xb.ctypes.data, xr.ctypes.data,
                                    num_steps, batch, ox.ctypes.data, ou.ctypes.data)
-        self._raise(ctx, rc)
+        _lib.check_mapped(rc)
         if single:
             return ox[0].T, ou[0].T
         return ox, ou
@@ -615,6 +476,161 @@ class KoopmanNystromRegressor(KoopmanRegressor):
     @property
     def fit_stats_(self):
         return self._stats
+
+
+class KoopmanNystromRegressor(_DeviceModelRegressor):
+    """regressors.py:114-178, MI355X-native.
+
+    Differences a caller can observe (all additive): `lift`/`predict` reuse K_mm^{-1/2} computed at fit time instead
+    of re-running sqrtm per call (regressors.py:174-175); `fit` accepts `row_ranges` (training rows of a K-fold split
+    without copying) and device-resident inputs; `rollout`, `score_neg_rmse`, `closed_loop` and `solve_lqr` expose
+    the callers' inner loops (benchmark_lqr_cloth.py:18-36, 52-57, 69-104, 238-263) as single calls.
+    """
+
+    # Arithmetic of the O(n m d) kernel blocks and O(n m^2) Gram contractions of `fit`: "f64" (the only mode that meets the
+    # 1e-6 operator bar) or "f32" (BASELINE.json's stress configuration; include/nyskoop.h, nk_set_compute_dtype).  An
+    # attribute, not a constructor argument: the constructor mirrors the reference's (sklearn clone / get_params), and a
+    # clone starts from the default.
+    compute_dtype = "f64"
+    _landmarks_attr = "nystrom_centers_output"
+
+    def __init__(self, n_inputs, kernel=None, gamma=None, m=None):
+        super().__init__(n_inputs, gamma, m)
+        self.kernel = kernel
+        self.nystrom_centers_input = None
+        self.nystrom_centers_output = None
+        self.jitter = 1e-6
+
+    def _create_model(self, ctx, Z, p, pa, pb, pc, pw):
+        m, d = Z.shape
+        kd, keep = self.kernel.kernel.desc(d)
+        h = C.c_void_p()
+        rc = ctx.lib.nk_model_create(ctx.handle, C.byref(kd), Z.ctypes.data, d, m, d, p, float(self.jitter),
+                                     pa, pb, pc, pw, C.byref(h))
+        _lib.check_mapped(rc)
+        return h
+
+    # ------------------------------------------------------------------------------------------------ fit
+    def _prepare(self, n, d, Y=None):
+        """Landmarks (regressors.py:129-134) and kernel descriptor for a fit on d-dimensional states."""
+        if self.nystrom_centers_output is None:  # regressors.py:129-132: global legacy NumPy RNG, n = #samples
+            if Y is None:
+                raise RuntimeError("landmarks must be set before a fit from Gram blocks")
+            idx = np.random.choice(np.arange(0, n), size=self.m, replace=False)
+            if _is_device_tensor(Y):
+                rows = Y[idx.tolist()]
+                self.nystrom_centers_output = np.ascontiguousarray(rows.cpu().numpy().T)
+            else:
+                self.nystrom_centers_output = np.asarray(Y).T[:, idx]
+        if self.nystrom_centers_input is None:  # regressors.py:133-134
+            self.nystrom_centers_input = self.nystrom_centers_output
+        Zo = np.ascontiguousarray(np.asarray(self.nystrom_centers_output, dtype=np.float64).T)
+        if Zo.shape[1] != d:
+            raise ValueError(f"landmarks have dimension {Zo.shape[1]}, data has {d}")
+        same = self.nystrom_centers_input is self.nystrom_centers_output
+        Zi = Zo if same else np.ascontiguousarray(np.asarray(self.nystrom_centers_input, dtype=np.float64).T)
+        kd, keep = self.kernel.kernel.desc(d)
+        return Zo, Zi, same, kd, keep
+
+    def fit(self, X, Y, row_ranges=None, fetch=True):
+        """regressors.py:122-169.  X: n x (d+p) rows [state | input], Y: n x d (NumPy arrays, or float64 device
+        tensors already resident in HBM).  Returns None, like the reference."""
+        ctx = _lib.get_context()
+        Xm, Ym = _lib.Mat(X), _lib.Mat(Y)
+        n, d = Ym.shape
+        p = int(self.n_inputs)
+        if Xm.shape != (n, d + p):
+            raise ValueError(f"X has shape {Xm.shape}, expected {(n, d + p)}")
+        Zo, Zi, same, kd, keep = self._prepare(n, d, Y)
+        m = Zo.shape[0]
+        rr, n_rr, keep_rr = self._ranges(row_ranges)
+        stats = _lib.FitStats()
+        h = C.c_void_p()
+        t_host0 = time.perf_counter()
+        self._drop_model()
+        t_host1 = time.perf_counter()
+        ctx.wait_for(X, Y)  # device tensors: whatever torch still has queued for them comes first
+        ctx.set_compute_dtype(self.compute_dtype)
+        try:
+            rc = ctx.lib.nk_nystrom_fit(ctx.handle, C.byref(kd), Xm.ptr, Xm.ld, Ym.ptr, Ym.ld, n, d, p, rr, n_rr,
+                                        None if same else Zi.ctypes.data, d, Zo.ctypes.data, d, m,
+                                        float(self.gamma), float(self.jitter), C.byref(h), C.byref(stats))
+        finally:
+            if self.compute_dtype != "f64":
+                ctx.set_compute_dtype("f64")
+        _lib.check_mapped(rc)
+        self._adopt(ctx, h, stats, m, d, p, (t_host0, t_host1), fetch)
+
+    # ------------------------------------------------------------------------- sample-sharded fit (SURVEY 8e(2))
+    def gram_size(self, d):
+        """Number of float64 entries of the packed Gram accumulator for d-dimensional states."""
+        m = np.asarray(self.nystrom_centers_output).shape[1] if self.nystrom_centers_output is not None else int(self.m)
+        cnt = C.c_int64()
+        _lib.check(_lib.load_library().nk_gram_doubles(m, d, int(self.n_inputs), C.byref(cnt)))
+        return int(cnt.value)
+
+    def gram_partial(self, X, Y, row_ranges=None, out=None):
+        """The four Gram blocks of regressors.py:151,153,162,164 (without the regularisers) over the given rows only,
+        packed into one flat float64 buffer `out` (a NumPy array, or a 1-D device tensor which is then filled in
+        place without leaving the GPU).  Landmarks must be set: every shard of a sharded fit uses the same ones."""
+        ctx = _lib.get_context()
+        Xm, Ym = _lib.Mat(X), _lib.Mat(Y)
+        n, d = Ym.shape
+        p = int(self.n_inputs)
+        if Xm.shape != (n, d + p):
+            raise ValueError(f"X has shape {Xm.shape}, expected {(n, d + p)}")
+        if self.nystrom_centers_output is None:
+            raise RuntimeError("landmarks must be set before gram_partial (all shards share them)")
+        Zo, Zi, same, kd, keep = self._prepare(n, d)
+        m = Zo.shape[0]
+        cnt = self.gram_size(d)
+        if out is None:
+            out = np.empty(cnt)
+        if _is_device_tensor(out):
+            if out.dim() != 1 or out.numel() != cnt or not out.is_contiguous() or "float64" not in str(out.dtype):
+                raise ValueError(f"out must be a contiguous float64 tensor with {cnt} entries")
+            optr = out.data_ptr()
+        else:
+            if out.shape != (cnt,) or out.dtype != np.float64 or not out.flags.c_contiguous:
+                raise ValueError(f"out must be a contiguous float64 array with {cnt} entries")
+            optr = out.ctypes.data
+        rr, n_rr, keep_rr = self._ranges(row_ranges)
+        stats = _lib.FitStats()
+        ctx.wait_for(X, Y, out)
+        rc = ctx.lib.nk_nystrom_gram(ctx.handle, C.byref(kd), Xm.ptr, Xm.ld, Ym.ptr, Ym.ld, n, d, p, rr, n_rr,
+                                     None if same else Zi.ctypes.data, d, Zo.ctypes.data, d, m, optr, C.byref(stats))
+        _lib.check_mapped(rc)
+        self._gram_stats = stats.as_dict()
+        return out
+
+    def fit_from_gram(self, gram, n_total, d):
+        """Finish the fit from accumulated Gram blocks (the sum of gram_partial over all shards); n_total = number of
+        training rows over all shards (the `n` of regressors.py:127)."""
+        ctx = _lib.get_context()
+        p = int(self.n_inputs)
+        Zo, Zi, same, kd, keep = self._prepare(n_total, d)
+        m = Zo.shape[0]
+        cnt = self.gram_size(d)
+        if _is_device_tensor(gram):
+            if gram.numel() != cnt or not gram.is_contiguous() or "float64" not in str(gram.dtype):
+                raise ValueError(f"gram must be a contiguous float64 tensor with {cnt} entries")
+            gptr = gram.data_ptr()
+        else:
+            gram = np.ascontiguousarray(gram, dtype=np.float64).reshape(-1)
+            if gram.size != cnt:
+                raise ValueError(f"gram must have {cnt} entries")
+            gptr = gram.ctypes.data
+        stats = _lib.FitStats()
+        h = C.c_void_p()
+        t_host0 = time.perf_counter()
+        self._drop_model()
+        t_host1 = time.perf_counter()
+        ctx.wait_for(gram)  # e.g. the output of an all-reduce still running on torch's (RCCL's) stream
+        rc = ctx.lib.nk_nystrom_solve(ctx.handle, C.byref(kd), None if same else Zi.ctypes.data, d, Zo.ctypes.data, d, m,
+                                      d, p, gptr, int(n_total), float(self.gamma), float(self.jitter), C.byref(h),
+                                      C.byref(stats))
+        _lib.check_mapped(rc)
+        self._adopt(ctx, h, stats, m, d, p, (t_host0, t_host1))
 
 
 class KoopmanKernelRegressor(KoopmanRegressor):
@@ -784,7 +800,7 @@ class KoopmanKernelRegressor(KoopmanRegressor):
         return self._gemm(ctx, self.Kout_sqrt_inv, Kout_test)
 
 
-class KoopmanSplineRegressor(KoopmanRegressor):
+class KoopmanSplineRegressor(_DeviceModelRegressor):
     """regressors.py:181-233 (the Korda-Mezic thin-plate-spline baseline), MI355X-native: the two n x m spline blocks, the
     three Gram products, the regularised pseudo-inverse and the operator products run on the device (nk_spline_fit).
 
@@ -792,42 +808,16 @@ class KoopmanSplineRegressor(KoopmanRegressor):
     from NumPy's global legacy RNG the first time `lift` needs them (in `fit`: from the training states) and are reused
     by every later fit.  Additive, as for the Nystrom class: `fit` accepts `row_ranges` and device tensors; `rollout`,
     `score_neg_rmse`, `closed_loop` and `solve_lqr` run the callers' loops on the device.  The device-model plumbing
-    (asynchronous operator fetch, pickling through host copies, lift / predict / rollout / closed loop) is the Nystrom
-    class's, shared method by method below."""
+    (asynchronous operator fetch, pickling through host copies, lift / predict / rollout / closed loop) is the base
+    class's, shared with the Nystrom estimator."""
 
-    A = _fetched("A")
-    B = _fetched("B")
-    C = _fetched("C")
-    weights = _fetched("weights")
+    _landmarks_attr = "centers"
+    _no_landmarks = "regressor has no centres: call fit (or lift) first"
 
     def __init__(self, n_inputs, state_bounds_params=None, m=None, gamma=None):
-        self._fetching = False
         super().__init__(n_inputs, gamma, m)
         self.state_bounds_params = state_bounds_params
         self.centers = None
-        self._model = None
-        self._model_key = None
-        self._stats = None
-        self._ops_version = 0
-
-    # shared with the Nystrom class: operator fetch, pickling, device-model lifetime, the callers' loops
-    invalidate_device_model = KoopmanNystromRegressor.invalidate_device_model
-    _wait_fetch = KoopmanNystromRegressor._wait_fetch
-    __getstate__ = KoopmanNystromRegressor.__getstate__
-    __setstate__ = KoopmanNystromRegressor.__setstate__
-    __del__ = KoopmanNystromRegressor.__del__
-    _drop_model = KoopmanNystromRegressor._drop_model
-    _ranges = staticmethod(KoopmanNystromRegressor._ranges)
-    _raise = staticmethod(KoopmanNystromRegressor._raise)
-    _adopt = KoopmanNystromRegressor._adopt
-    predict = KoopmanNystromRegressor.predict
-    score_neg_rmse = KoopmanNystromRegressor.score_neg_rmse
-    rollout = KoopmanNystromRegressor.rollout
-    open_loop_errors = KoopmanNystromRegressor.open_loop_errors
-    closed_loop = KoopmanNystromRegressor.closed_loop
-    closed_loop_plant = KoopmanNystromRegressor.closed_loop_plant
-    solve_lqr = KoopmanNystromRegressor.solve_lqr
-    fit_stats_ = KoopmanNystromRegressor.fit_stats_
 
     def compute_centers(self, X):
         """regressors.py:187-197, draw for draw: X is d x n (the array `lift` sees first)."""
@@ -840,43 +830,11 @@ class KoopmanSplineRegressor(KoopmanRegressor):
             return np.ascontiguousarray(X[:, centers_indices.tolist()].cpu().numpy())
         return np.asarray(X)[:, centers_indices]
 
-    def _landmark_shape(self):
-        return np.asarray(self.centers).shape
-
-    def _ops_key(self):
-        z = self.centers
-        return (id(z), None if z is None else np.shape(z), self.__dict__.get("_ops_version", 0))
-
-    def _ensure_model(self):
-        """Device model for lift / predict / rollout, rebuilt from host copies after un-pickling or when a caller replaced
-        the centres / operators (an unfitted regressor gets a model that can only lift)."""
-        if self.centers is None:
-            raise RuntimeError("regressor has no centres: call fit (or lift) first")
-        key = self._ops_key()
-        if self._model is not None and self._model_key == key:
-            return self._model
-        self._wait_fetch()
-        self._drop_model()
-        ctx = _lib.get_context()
-        Z = np.ascontiguousarray(np.asarray(self.centers, dtype=np.float64).T)  # m x d
-        m, d = Z.shape
-        p = int(self.n_inputs)
-        keep = []
-
-        def ptr(a, shape):
-            if a is None:
-                return None
-            a = np.ascontiguousarray(a, dtype=np.float64)
-            if a.shape != shape:
-                raise ValueError(f"operator has shape {a.shape}, expected {shape}")
-            keep.append(a)
-            return a.ctypes.data
-
-        pa, pb, pc, pw = ptr(self.A, (m, m)), ptr(self.B, (m, p)), ptr(self.C, (d, m)), ptr(self.weights, (d, m + p))
+    def _create_model(self, ctx, Z, p, pa, pb, pc, pw):
+        m, d = Z.shape  # (an unfitted regressor gets a model that can only lift)
         h = C.c_void_p()
         rc = ctx.lib.nk_spline_model_create(ctx.handle, Z.ctypes.data, d, m, d, p, pa, pb, pc, pw, C.byref(h))
-        self._raise(ctx, rc)
-        self._model, self._model_key = h, key
+        _lib.check_mapped(rc)
         return h
 
     def fit(self, X, Y, row_ranges=None, fetch=True):
@@ -910,7 +868,7 @@ class KoopmanSplineRegressor(KoopmanRegressor):
         ctx.wait_for(X, Y)
         rc = ctx.lib.nk_spline_fit(ctx.handle, Xm.ptr, Xm.ld, Ym.ptr, Ym.ld, n, d, p, rr, n_rr, Z.ctypes.data, d, m,
                                    float(self.gamma), C.byref(h), C.byref(stats))
-        self._raise(ctx, rc)
+        _lib.check_mapped(rc)
         self._adopt(ctx, h, stats, m, d, p, (t_host0, t_host1), fetch)
 
     def lift(self, X):
@@ -918,12 +876,4 @@ class KoopmanSplineRegressor(KoopmanRegressor):
         there are none yet, as the reference does."""
         if self.centers is None:
             self.centers = self.compute_centers(X)
-        ctx = _lib.get_context()
-        h = self._ensure_model()
-        Xq = _lib.Mat(X.t() if _is_device_tensor(X) else np.asarray(X, dtype=np.float64).T)
-        nq = Xq.shape[0]
-        m = self._landmark_shape()[1]
-        out = np.empty((nq, m))
-        ctx.wait_for(X)
-        _lib.check(ctx.lib.nk_lift(ctx.handle, h, Xq.ptr, Xq.ld, nq, out.ctypes.data, m))
-        return out.T
+        return super().lift(X)
