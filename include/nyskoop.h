@@ -424,6 +424,44 @@ typedef struct nk_plant_unit {
 } nk_plant_unit;
 int nk_plant_loop_multi(nk_ctx* ctx, int plant, double Ts, int32_t steps, const nk_plant_unit* units, int32_t n_units,
                         const double* u_opt, int32_t n_uopt, double* out_x, double* out_u, double* scores);
+/* ---- the multi-model form of the lifted closed loop, scored on the device: the control branch of the cloth sweep
+ *   (benchmark_lqr_cloth.py:213-270: per seed and estimator fit, gain, lqr_control) in ONE call after the fits and gains.
+ *   Every unit has its own model, gain, lifted initial state and lifted reference; the units of a call share `steps` and
+ *   `c` and may differ in everything else (model kind, m, p, d).  Unit u runs the loop of benchmark_lqr_cloth.py:79-84 in
+ *   the reference's order of operations, for t = 0 .. steps-1:
+ *     u_t = K (phi_ref - phi_t),   x_t = C phi_t,   phi_{t+1} = A phi_t + B u_t
+ *   (not the (A - B K) form of nk_closed_loop_batch: the results agree with it to rounding, not bit for bit).
+ *   Outputs, each dense with the units back to back (unit u owns the rows of its own width after those of the units before
+ *   it; with equal shapes these are plain 3-D arrays), host or device memory, EACH MAY BE NULL and is then never written on
+ *   the device either:
+ *     out_x:    n_units x steps x d        x_t
+ *     out_u:    n_units x steps x p        u_t
+ *     out_ucum: n_units x (steps + 1) x p  the cumulative input sequence of benchmark_lqr_cloth.py:76-81: row 0 = u_init,
+ *               row t+1 = row t + u_t, one rounded addition per entry in step order (u_s[:, -1] + u_op, not u0 + cumsum)
+ *     out_err:  n_units x steps            e_t = sqrt(sum_k (x_{t,k} - target_k)^2 / d)  (plot_reg_error_cloth.py:24)
+ *   scores: HOST, n_units x 4, may be NULL:  scores[u] = {J, err_final, u_sumsq, u_absmax},
+ *     J = sum_t (c sum_k (x_{t,k} - target_k)^2 + sum_j u_{t,j}^2),  err_final = e_{steps-1},
+ *     u_sumsq = sum_t sum_j u_{t,j}^2,  u_absmax = max_{t,j} |u_{t,j}|, NaN from the first NaN control on.
+ *     All sums are taken in an order fixed by (m, p, d, steps).
+ *   Not all five outputs may be NULL.  Everything is checked before anything is queued; a bad unit is NK_ERR_BAD_ARG with
+ *   its index in nk_last_error(), and no output is written.  Per unit: a Nystrom or spline model WITH fitted operators on
+ *   the context's device, 1 <= m <= 128, 1 <= p <= 8, d >= 1; K, phi0, phi_ref, target, u_init are HOST memory.  steps >= 1,
+ *   c finite and non-negative.  Ordinary contexts only (not lock-step members); models need not belong to ctx (models
+ *   fitted by lock-step members are accepted).
+ *   Device side: one 1024-thread workgroup owns one unit from its first to its last step ([A B] in registers, phi_t and u_t in
+ *   LDS, then x_t = C phi_t from the stored phi_t by the same workgroup); blockIdx.x selects a record of a table staged with
+ *   one copy, all gains, lifted states, targets and seeds are staged with one more, and the whole call is one launch.  A
+ *   unit's outputs depend on that unit alone: the same bits whatever else the call holds, in whatever order. */
+typedef struct nk_loop_unit {
+  const nk_model* model;   /* Nystrom or spline model WITH fitted operators; 1 <= m <= 128, 1 <= p <= 8, d >= 1 */
+  const double* K;         /* HOST, p x m, dense */
+  const double* phi0;      /* HOST, m: lifted initial state   (nk_lift of x0)    */
+  const double* phi_ref;   /* HOST, m: lifted reference state (nk_lift of x_ref) */
+  const double* target;    /* HOST, d: the state the loop is scored against (callers pass x_ref); NULL only if out_err and scores are NULL */
+  const double* u_init;    /* HOST, p: seed of the cumulative input sequence (benchmark_lqr_cloth.py:78); NULL = zeros */
+} nk_loop_unit;
+int nk_closed_loop_multi(nk_ctx* ctx, int32_t steps, double c, const nk_loop_unit* units, int32_t n_units,
+                         double* out_x, double* out_u, double* out_ucum, double* out_err, double* scores);
 /* ---- the gains of the sweep: K = dlqr(A, B, Q, R) (benchmark_lqr_hjb.py:293,356, benchmark_lqr_classic.py:288,
  *   benchmark_lqr_cloth.py:262: control.dlqr) for MANY independent problems in one call.  P solves the discrete algebraic
  *   Riccati equation A'PA - P - A'PB (R + B'PB)^-1 B'PA + Q = 0 by the structure-preserving doubling iteration

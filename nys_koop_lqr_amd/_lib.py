@@ -52,6 +52,13 @@ class PlantUnit(C.Structure):
                 ("uopt", C.c_int32), ("reserved", C.c_int32)]
 
 
+class LoopUnit(C.Structure):
+    """nk_loop_unit (include/nyskoop.h), one unit of nk_closed_loop_multi: six pointers (model, K, phi0, phi_ref, target,
+    u_init): 48 bytes, no padding."""
+    _fields_ = [("model", C.c_void_p), ("K", C.c_void_p), ("phi0", C.c_void_p), ("phi_ref", C.c_void_p),
+                ("target", C.c_void_p), ("u_init", C.c_void_p)]
+
+
 class DareProblem(C.Structure):
     """nk_dare_problem (include/nyskoop.h), one problem of nk_dare_batch."""
     _fields_ = [("m", C.c_int32), ("p", C.c_int32), ("A", C.c_void_p), ("lda", C.c_int64), ("B", C.c_void_p),
@@ -135,6 +142,7 @@ SIGNATURES = {
     "nk_plant_step": (C.c_int, [C.c_int, _D, _P, _P, _P]),
     "nk_plant_loop": (C.c_int, [_P, _P, C.c_int, _D, _P, _P, _P, _I32, _I32, _P, _P]),
     "nk_plant_loop_multi": (C.c_int, [_P, C.c_int, _D, _I32, C.POINTER(PlantUnit), _I32, _P, _I32, _P, _P, _P]),
+    "nk_closed_loop_multi": (C.c_int, [_P, _I32, _D, C.POINTER(LoopUnit), _I32, _P, _P, _P, _P, _P]),
     "nk_dare_batch": (C.c_int, [_P, C.POINTER(DareProblem), _I32, _D, _I32, C.POINTER(_I32), C.POINTER(_I32)]),
     "nk_model_lqr_gain_batch": (C.c_int, [_P, C.POINTER(_P), _I32, _D, _P, _D, _I32, _P, C.POINTER(_I32),
                                           C.POINTER(_I32)]),
@@ -378,6 +386,66 @@ class Context:
                                           ptr(ou), ptr(sc))
         check_mapped(rc)
         return sc, ox, ou
+
+    def closed_loop_multi(self, steps, c, models, dims, gains, phi0s, phi_refs, targets=None, u_inits=None, want_x=False,
+                          want_u=False, want_ucum=False, want_err=True, want_scores=True):
+        """nk_closed_loop_multi: one lifted closed loop per unit (u_t = K (phi_ref - phi_t), x_t = C phi_t, phi_{t+1} =
+        A phi_t + B u_t), all units in one call and one launch, scored on the device.  models: device-model handles; dims:
+        their (m, p, d); gains: one (p, m) array per unit; phi0s, phi_refs: one (m,) array per unit; targets: one (d,) array
+        per unit (None: nothing is scored); u_inits: one (p,) array per unit, None entries (or None) = zeros.
+        Returns (scores (n_units, 4) = J, err_final, u_sumsq, u_absmax or None, err (n_units, steps) or None, and three lists
+        of per-unit arrays or None: states (steps, d), controls (steps, p), cum_controls (steps + 1, p))."""
+        n = len(models)
+        steps = int(steps)
+        if not (len(dims) == len(gains) == len(phi0s) == len(phi_refs) == n):
+            raise ValueError("models, dims, gains, phi0s and phi_refs must have the same length")
+        if targets is None and (want_err or want_scores):
+            raise ValueError("scores and errors need a target per unit")
+        arr = (LoopUnit * max(n, 1))()
+        keep = []
+
+        def vec(a, size, what, i):
+            a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+            if a.size != size:
+                raise ValueError(f"unit {i}: {what} has {a.size} entries, expected {size}")
+            keep.append(a)
+            return a.ctypes.data
+
+        for i in range(n):
+            m, p, d = (int(v) for v in dims[i])
+            h = models[i]
+            arr[i].model = h.value if isinstance(h, C.c_void_p) else h
+            arr[i].K = vec(gains[i], p * m, "the gain", i)
+            arr[i].phi0 = vec(phi0s[i], m, "phi0", i)
+            arr[i].phi_ref = vec(phi_refs[i], m, "phi_ref", i)
+            if targets is not None:
+                arr[i].target = vec(targets[i], d, "the target", i)
+            if u_inits is not None and u_inits[i] is not None:
+                arr[i].u_init = vec(u_inits[i], p, "u_init", i)
+        T = max(steps, 0)
+        nx = sum(T * int(dm[2]) for dm in dims)
+        nu = sum(T * int(dm[1]) for dm in dims)
+        nc = sum((T + 1) * int(dm[1]) for dm in dims)
+        ox = np.empty(max(nx, 1)) if want_x else None
+        ou = np.empty(max(nu, 1)) if want_u else None
+        oc = np.empty(max(nc, 1)) if want_ucum else None
+        oe = np.full((n, T), np.nan) if want_err else None
+        sc = np.full((n, 4), np.nan) if want_scores else None
+        ptr = lambda a: None if a is None else a.ctypes.data
+        rc = self.lib.nk_closed_loop_multi(self.handle, steps, float(c), arr, n, ptr(ox), ptr(ou), ptr(oc), ptr(oe), ptr(sc))
+        check_mapped(rc)
+
+        def split(flat, rows, col):
+            if flat is None:
+                return None
+            out, off = [], 0
+            for dm in dims:
+                w = int(dm[col])
+                out.append(flat[off:off + rows * w].reshape(rows, w))
+                off += rows * w
+            return out
+
+        return sc, oe, split(ox, T, 2), split(ou, T, 1), split(oc, T + 1, 1)
 
     def dare_batch(self, As, Bs, Qs, Rs, tol=1e-13, max_iter=40, want_P=True):
         """nk_dare_batch: K = dlqr(A, B, Q, R) for every problem of the lists in one call, one workgroup per problem.

@@ -515,6 +515,33 @@ struct PlantLoopUnit {
 int launch_plant_loop_multi(nk_ctx* ctx, int plant, double Ts, int steps, PlantLoopUnit* units, const int* ktypes,
                             int n_units);
 
+// ---- lifted closed loops of many models in ONE launch, scored on the device (nk_loop_multi.hip): one 1024-thread workgroup
+// per unit, blockIdx.x = the record.  Every pointer is device memory.  Per step t < steps: u_t = K (phi_ref - phi_t),
+// x_t = C phi_t, phi_{t+1} = A phi_t + B u_t.  Phi / usq / sse: the unit's scratch (steps x m, steps, steps doubles).
+// Any of out_x / out_u / out_ucum / out_err / score may be null; target may be null when out_err and score are.
+constexpr int LOOP_MULTI_MAX_M = 128;
+constexpr int LOOP_MULTI_MAX_P = 8;
+struct LoopMultiUnit {
+  const double* G; int64_t ldg;  // [A | B]: m rows of m + p entries
+  const double* C;               // d x m, dense
+  const double* K;               // p x m, dense
+  const double* phi0;            // m
+  const double* phi_ref;         // m
+  const double* target;          // d, or nullptr
+  const double* u_init;          // p (zeros when the caller gave none)
+  double* Phi;                   // steps x m: phi_t
+  double* usq;                   // steps: sum_j u_{t,j}^2
+  double* sse;                   // steps: sum_k (x_{t,k} - target_k)^2
+  double* out_x; int64_t ldx;    // steps rows, or nullptr
+  double* out_u; int64_t ldu;    // steps rows, or nullptr
+  double* out_ucum; int64_t ldc; // steps + 1 rows, or nullptr
+  double* out_err;               // steps, or nullptr
+  double* score;                 // {J, err_final, u_sumsq, u_absmax}, or nullptr
+  int m, p, d, reserved;
+};
+// units: host records (read by the staging copy: alive until the stream has been synchronised)
+int launch_closed_loop_multi(nk_ctx* ctx, const LoopMultiUnit* units, int n_units, int steps, double c);
+
 // ---- batched Riccati solver (nk_dare.hip): one workgroup per problem, blockIdx.x = the record.  Every pointer is device
 // memory.  ws: the problem's workspace of dare_ws_doubles(M) doubles, M = m rounded up to 16.  Either Q (m x m) or C
 // (d x m: the cost is c sym(C'C), formed by the kernel's own product) is set.  R: p x p dense, nullptr = identity.
@@ -655,6 +682,23 @@ __device__ __forceinline__ double wave_sum64_dpp(double c) {
   a = c; b = c;
   swap32_f64(a, b);
   return a + b;
+}
+
+// Four values per lane, summed over the 32 lanes of a half wave: afterwards every lane holds the total of value
+// r = 2 * bit4(lane) + bit3(lane) (checked lane by lane on the device by tools/reduce_probe.hip).  Fixed order: the
+// result does not depend on anything but the inputs.
+__device__ __forceinline__ double reduce_4rows_32parts(double a0, double a1, double a2, double a3, int lane) {
+  swap16_f64(a0, a2);
+  const double e0 = a0 + a2;  // lanes with bit4 = 0: value 0, bit4 = 1: value 2 (each over parts {q, q + 16})
+  swap16_f64(a1, a3);
+  const double e1 = a1 + a3;  // value 1 / value 3
+  const bool hi8 = (lane & 8) != 0;
+  const double keep = hi8 ? e1 : e0, send = hi8 ? e0 : e1;
+  double c = keep + dpp_f64<0x140>(send);  // row_mirror: lane i <-> 15 - i
+  c += dpp_f64<0xB1>(c);                   // quad_perm [1,0,3,2]
+  c += dpp_f64<0x4E>(c);                   // quad_perm [2,3,0,1]
+  c += dpp_f64<0x141>(c);                  // row_half_mirror: lane i <-> 7 - i
+  return c;
 }
 
 // kernel value from the accumulated squared distance (RBF, Matern-5/2) or dot product (linear) of the pre-scaled

@@ -589,6 +589,117 @@ int nk_plant_loop_multi(nk_ctx* ctx, int plant, double Ts, int32_t steps, const 
   return NK_OK;
 }
 
+int nk_closed_loop_multi(nk_ctx* ctx, int32_t steps, double c, const nk_loop_unit* units, int32_t n_units, double* out_x,
+                         double* out_u, double* out_ucum, double* out_err, double* scores) {
+  NK_TRY(check_ctx(ctx));
+  NK_REQUIRE(!ctx_recording(ctx), "nk_closed_loop_multi: not available to the members of a lock-step group");
+  NK_REQUIRE(units != nullptr && n_units >= 1, "nk_closed_loop_multi: n_units = %d units at %p: at least one is needed",
+             n_units, (const void*)units);
+  NK_REQUIRE(steps >= 1, "nk_closed_loop_multi: steps = %d must be positive", steps);
+  NK_REQUIRE(std::isfinite(c) && c >= 0.0, "nk_closed_loop_multi: c must be finite and non-negative");
+  NK_REQUIRE(out_x || out_u || out_ucum || out_err || scores,
+             "nk_closed_loop_multi: out_x, out_u, out_ucum, out_err and scores are all null: nothing to return");
+  NK_REQUIRE(!is_device_ptr(scores), "nk_closed_loop_multi: scores must be host memory");
+  // every unit is checked before anything is queued; the staging block (slots start on 256 bytes) and the dense,
+  // unit-major output offsets are laid out on the way
+  auto slot = [](size_t doubles) { return (doubles + 31) & ~(size_t)31; };
+  const bool scored = out_err != nullptr || scores != nullptr;
+  std::vector<size_t> in_off((size_t)n_units), ws_off((size_t)n_units), x_off((size_t)n_units), u_off((size_t)n_units),
+      uc_off((size_t)n_units);
+  size_t in_doubles = 0, ws_doubles = 0, x_doubles = 0, u_doubles = 0, uc_doubles = 0;
+  for (int u = 0; u < n_units; ++u) {
+    const nk_loop_unit& un = units[u];
+    const nk_model* mdl = un.model;
+    NK_REQUIRE(mdl != nullptr, "nk_closed_loop_multi: unit %d: the model is null", u);
+    NK_REQUIRE(mdl->p >= 1 && mdl->p <= LOOP_MULTI_MAX_P, "nk_closed_loop_multi: unit %d: p = %d inputs must lie in 1 .. %d", u,
+               mdl->p, LOOP_MULTI_MAX_P);
+    NK_REQUIRE(mdl->m >= 1 && mdl->m <= LOOP_MULTI_MAX_M,
+               "nk_closed_loop_multi: unit %d: m = %d must lie in 1 .. %d (larger models: nk_closed_loop)", u, mdl->m,
+               LOOP_MULTI_MAX_M);
+    NK_REQUIRE(mdl->d >= 1, "nk_closed_loop_multi: unit %d: d = %d", u, mdl->d);
+    NK_REQUIRE(mdl->has_ops, "nk_closed_loop_multi: unit %d: the model holds no fitted operators", u);
+    NK_REQUIRE(mdl->device == ctx->device, "nk_closed_loop_multi: unit %d: the model lives on device %d, the context on %d", u,
+               mdl->device, ctx->device);
+    NK_REQUIRE(un.K && un.phi0 && un.phi_ref, "nk_closed_loop_multi: unit %d: null argument (K, phi0, phi_ref)", u);
+    NK_REQUIRE(un.target != nullptr || !scored,
+               "nk_closed_loop_multi: unit %d: target is null, but out_err or scores are requested", u);
+    NK_REQUIRE(!is_device_ptr(un.K) && !is_device_ptr(un.phi0) && !is_device_ptr(un.phi_ref) && !is_device_ptr(un.target) &&
+                   !is_device_ptr(un.u_init),
+               "nk_closed_loop_multi: unit %d: K, phi0, phi_ref, target and u_init must be host memory", u);
+    const size_t m = (size_t)mdl->m, p = (size_t)mdl->p, d = (size_t)mdl->d;
+    in_off[u] = in_doubles;
+    in_doubles += slot(p * m) + 2 * slot(m) + slot(d) + slot(p);  // K | phi0 | phi_ref | target | u_init
+    ws_off[u] = ws_doubles;
+    ws_doubles += slot((size_t)steps * m) + 2 * slot((size_t)steps);  // phi_t | sum u^2 | sum (x - target)^2, per step
+    x_off[u] = x_doubles;
+    x_doubles += (size_t)steps * d;
+    u_off[u] = u_doubles;
+    u_doubles += (size_t)steps * p;
+    uc_off[u] = uc_doubles;
+    uc_doubles += ((size_t)steps + 1) * p;
+  }
+  // one staging block for every gain, lifted state, target and seed: one copy
+  std::vector<double> h_in(in_doubles, 0.0);
+  for (int u = 0; u < n_units; ++u) {
+    const nk_loop_unit& un = units[u];
+    const size_t m = (size_t)un.model->m, p = (size_t)un.model->p, d = (size_t)un.model->d;
+    double* dst = h_in.data() + in_off[u];
+    std::copy(un.K, un.K + p * m, dst);
+    dst += slot(p * m);
+    std::copy(un.phi0, un.phi0 + m, dst);
+    dst += slot(m);
+    std::copy(un.phi_ref, un.phi_ref + m, dst);
+    dst += slot(m);
+    if (un.target) std::copy(un.target, un.target + d, dst);
+    dst += slot(d);
+    if (un.u_init) std::copy(un.u_init, un.u_init + p, dst);
+  }
+  double *d_in = nullptr, *d_ws = nullptr, *d_sc = nullptr;
+  NK_TRY(arena_alloc_t(ctx, in_doubles, &d_in));
+  NK_HIP(hipMemcpyAsync(d_in, h_in.data(), in_doubles * 8, hipMemcpyHostToDevice, ctx->stream));
+  NK_TRY(arena_alloc_t(ctx, ws_doubles, &d_ws));
+  if (scores) NK_TRY(arena_alloc_t(ctx, (size_t)n_units * 4, &d_sc));
+  // a dense output: the caller's device memory as it is, or an arena block that one copy brings back
+  struct Out { double* host; double* dev; size_t doubles; };
+  Out outs[4] = {{out_x, nullptr, x_doubles}, {out_u, nullptr, u_doubles}, {out_ucum, nullptr, uc_doubles},
+                 {out_err, nullptr, (size_t)n_units * steps}};
+  for (Out& o : outs) {
+    if (!o.host) continue;
+    if (is_device_ptr(o.host)) { o.dev = o.host; o.host = nullptr; }
+    else NK_TRY(arena_alloc_t(ctx, o.doubles, &o.dev));
+  }
+  std::vector<LoopMultiUnit> recs((size_t)n_units);
+  for (int u = 0; u < n_units; ++u) {
+    const nk_model* mdl = units[u].model;
+    const size_t m = (size_t)mdl->m, p = (size_t)mdl->p, d = (size_t)mdl->d;
+    LoopMultiUnit& r = recs[u];
+    r = LoopMultiUnit{};
+    r.G = mdl->A; r.ldg = mdl->m + mdl->p; r.C = mdl->C;
+    const double* in = d_in + in_off[u];
+    r.K = in; in += slot(p * m);
+    r.phi0 = in; in += slot(m);
+    r.phi_ref = in; in += slot(m);
+    r.target = units[u].target ? in : nullptr; in += slot(d);
+    r.u_init = in;
+    double* ws = d_ws + ws_off[u];
+    r.Phi = ws; ws += slot((size_t)steps * m);
+    r.usq = ws; ws += slot((size_t)steps);
+    r.sse = ws;
+    r.out_x = outs[0].dev ? outs[0].dev + x_off[u] : nullptr; r.ldx = mdl->d;
+    r.out_u = outs[1].dev ? outs[1].dev + u_off[u] : nullptr; r.ldu = mdl->p;
+    r.out_ucum = outs[2].dev ? outs[2].dev + uc_off[u] : nullptr; r.ldc = mdl->p;
+    r.out_err = outs[3].dev ? outs[3].dev + (size_t)u * steps : nullptr;
+    r.score = scores ? d_sc + 4 * (size_t)u : nullptr;
+    r.m = mdl->m; r.p = mdl->p; r.d = mdl->d;
+  }
+  NK_TRY(launch_closed_loop_multi(ctx, recs.data(), n_units, steps, c));
+  for (const Out& o : outs)
+    if (o.host) NK_HIP(hipMemcpyAsync(o.host, o.dev, o.doubles * 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (scores) NK_HIP(hipMemcpyAsync(scores, d_sc, (size_t)n_units * 32, hipMemcpyDeviceToHost, ctx->stream));
+  NK_HIP(hipStreamSynchronize(ctx->stream));  // (h_in and recs are read by the copies queued above)
+  return NK_OK;
+}
+
 int nk_dare_batch(nk_ctx* ctx, const nk_dare_problem* problems, int32_t n, double tol, int32_t max_iter,
                   int32_t* out_status, int32_t* out_iters) {
   NK_TRY(check_ctx(ctx));

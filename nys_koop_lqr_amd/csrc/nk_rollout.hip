@@ -92,23 +92,7 @@ constexpr int CHAIN_THREADS = 1024;
 constexpr int CHAIN_KPT = 5;                // columns of G per thread (stride 32)
 constexpr int CHAIN_ZU = 32 * CHAIN_KPT;    // padded length of [z ; u] in LDS (160)
 
-// Four values per lane, summed over the 32 lanes of a half wave: afterwards every lane holds the total of value
-// r = 2 * bit4(lane) + bit3(lane) (checked lane by lane on the device by tools/reduce_probe.hip).  Fixed order: the
-// result does not depend on anything but the inputs.
-__device__ __forceinline__ double reduce_4rows_32parts(double a0, double a1, double a2, double a3, int lane) {
-  swap16_f64(a0, a2);
-  const double e0 = a0 + a2;  // lanes with bit4 = 0: value 0, bit4 = 1: value 2 (each over parts {q, q + 16})
-  swap16_f64(a1, a3);
-  const double e1 = a1 + a3;  // value 1 / value 3
-  const bool hi8 = (lane & 8) != 0;
-  const double keep = hi8 ? e1 : e0, send = hi8 ? e0 : e1;
-  double c = keep + dpp_f64<0x140>(send);  // row_mirror: lane i <-> 15 - i
-  c += dpp_f64<0xB1>(c);                   // quad_perm [1,0,3,2]
-  c += dpp_f64<0x4E>(c);                   // quad_perm [2,3,0,1]
-  c += dpp_f64<0x141>(c);                  // row_half_mirror: lane i <-> 7 - i
-  return c;
-}
-
+// (the cross-lane reduction of a step, reduce_4rows_32parts, lives in nk_common.h: the closed loops of nk_loop_multi.hip share it)
 __global__ void __launch_bounds__(CHAIN_THREADS) lifted_chain_kernel(ChainParams P) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
   const int m = P.m, pu = P.pu, mpu = m + pu;

@@ -156,6 +156,27 @@ def sharded_lqr_sweep(X, Y, n_inputs, params, ms, seeds, plant, x0, x_ref, num_s
     return harness.lqr_result(units, flat, None, None, len(seeds), len(ms))
 
 
+def sharded_cloth_lqr_sweep(X, Y, n_inputs, params, m, seeds, x0, x_ref, num_steps=60, estimator="nystrom", c=0.0075,
+                            gain="host", batch=32, workers=4, control_nodes=(168, 169, 170, 189, 190, 191), centers=None,
+                            fit_fn=None, loop_fn=None, gain_batch_fn=None):
+    """Distributed counterpart of harness.cloth_lqr_sweep: every rank plans the same units with the same draws, the units
+    are dealt round-robin (shard_units), every rank fits, solves and runs its share on its own GPU (one closed_loop_multi
+    call per rank) and ONE all-gather assembles the four scores of every unit.  Per-step errors and trajectories stay on
+    their ranks.  Every rank returns the same dict of tables J, err_final, u_sumsq, u_absmax (harness.cloth_lqr_sweep
+    without `err`, `timing` and trajectories)."""
+    import torch.distributed as dist
+    rank, world = (dist.get_rank(), dist.get_world_size()) if dist.is_initialized() else (0, 1)
+    names, units = harness.cloth_lqr_plan(X, Y, n_inputs, params, m, seeds, estimator, centers)
+    mine = shard_units(len(units), rank, world)
+    local = harness.cloth_lqr_run_units(X, Y, n_inputs, [units[u] for u in mine], x0, x_ref, num_steps, c, gain, batch,
+                                        workers, control_nodes, False, fit_fn, loop_fn, gain_batch_fn)[0]
+    flat = all_gather_scores(local, len(units), rank, world) if world > 1 else local
+    out = harness.cloth_lqr_result(names, units, flat, np.full((len(units), 0), np.nan), len(seeds),
+                                   isinstance(estimator, str))
+    del out["err"]
+    return out
+
+
 def sample_sharded_fit(reg, X_local, Y_local, landmark_rows=None):
     """One LARGE fit over several GPUs: the samples are sharded, every rank holds all landmarks,
     accumulates the four Gram blocks of its own rows on its GPU (`reg.gram_partial`), ONE all-reduce sums the packed

@@ -634,16 +634,15 @@ def lqr_fit_unit(X, Y, n_inputs, params, unit, estimator="nystrom"):
     return reg
 
 
-def lqr_run_units(X, Y, n_inputs, params, units, plant, x0, x_ref, num_steps, estimator="nystrom", gain_fn=None, c=1.0,
-                  u_opt=None, batch=32, workers=4, return_trajectories=False, fit_fn=None, loop_fn=None, gain="host",
-                  gain_batch_fn=None):
-    """Scores of planned units, in their order: an (n_units, 4) array (SCORE_NAMES; NaN for a unit whose fit or gain
-    failed), the trajectories (or None, None) and the wall-clock split.  fit_fn / loop_fn stand in for lqr_fit_unit /
-    plant_loop_multi (rehearsals without a GPU; with a fit_fn the fits run as a plain loop).
-    gain="device": the gains of all fitted units come from ONE nk_model_lqr_gain_batch call after the fits (K =
-    dlqr(A, B, c sym(C'C), I) by the batched doubling solver; gain_fn is not used); a unit whose solve reports a non-zero
-    status gets NaN scores and is not run.  timing keeps its keys: gain_wait_s is that call, gain_cpu_s is 0.
-    gain_batch_fn(regs, c) -> (Ks, status, iterations) stands in for the device call."""
+def lqr_fit_and_gain(X, Y, n_inputs, params, units, estimator="nystrom", gain_fn=None, c=1.0, batch=32, workers=4,
+                     fit_fn=None, gain="host", gain_batch_fn=None, after_fit=None):
+    """The fits and gains of planned units -- what lqr_run_units and cloth_lqr_sweep share.  Fits: `batch` at a time through
+    the lock-step pool (a plain loop with batch <= 1 or a fit_fn); a unit may carry its own "estimator" and "params".
+    after_fit(reg, unit): called on the fitting thread right after a successful fit, inside the lock-step round (its result
+    is kept per unit).  Gains: gain="host": gain_fn(A, B, C) in `workers` host threads while later rounds fit;
+    gain="device": ONE nk_model_lqr_gain_batch call after the fits (gain_batch_fn(regs, c) stands in for it).
+    Returns (regs, gains, extras, timing): a unit whose fit failed has regs[i] None, one without a gain gains[i] None;
+    timing = dict(fit_s, gain_wait_s, gain_cpu_s)."""
     import time
     if gain not in ("host", "device"):
         raise ValueError(f"gain must be 'host' or 'device', got {gain!r}")
@@ -653,7 +652,6 @@ def lqr_run_units(X, Y, n_inputs, params, units, plant, x0, x_ref, num_steps, es
     X = np.ascontiguousarray(X, dtype=np.float64)
     Y = np.ascontiguousarray(Y, dtype=np.float64)
     gain_fn = gain_fn or lqr_default_gain(c)
-    loop_fn = loop_fn or plant_loop_multi
     n = len(units)
     gain_s = [0.0] * n
 
@@ -665,16 +663,24 @@ def lqr_run_units(X, Y, n_inputs, params, units, plant, x0, x_ref, num_steps, es
             gain_s[i] = time.perf_counter() - t0
 
     pool = _lib.worker_pool(max(1, int(workers)))
-    regs, futures = [None] * n, [None] * n
+    regs, futures, extras = [None] * n, [None] * n, [None] * n
     t0 = time.perf_counter()
     lockstep = fit_fn is None and batch > 1 and n > 1
-    fit = (lambda u: (fit_fn or lqr_fit_unit)(X, Y, n_inputs, params, u, estimator))
+
+    def fit(u):
+        reg = (fit_fn or lqr_fit_unit)(X, Y, n_inputs, u.get("params", params), u, u.get("estimator", estimator))
+        if after_fit is None:
+            return reg
+        return reg, (None if reg is None else after_fit(reg, u))
+
     step = int(batch) if lockstep else 1
     lpool = _lib.lockstep_pool(step) if lockstep else None
     for r in range(0, n, step):
         idx = list(range(r, min(r + step, n)))
         fitted = lpool.run_round(fit, [units[i] for i in idx]) if lockstep else [fit(units[i]) for i in idx]
         for i, reg in zip(idx, fitted):  # the gains of this round are solved on the host while the next round fits
+            if after_fit is not None:
+                reg, extras[i] = reg
             regs[i] = reg
             if reg is not None and not device_gain:
                 futures[i] = pool.submit(gain_of, i, reg)
@@ -695,6 +701,25 @@ def lqr_run_units(X, Y, n_inputs, params, units, plant, x0, x_ref, num_steps, es
             except Exception:  # noqa: BLE001 -- a unit without a gain scores NaN, like GridSearchCV's error_score=nan
                 gains[i] = None
     t2 = time.perf_counter()
+    return regs, gains, extras, dict(fit_s=t1 - t0, gain_wait_s=t2 - t1, gain_cpu_s=float(sum(gain_s)))
+
+
+def lqr_run_units(X, Y, n_inputs, params, units, plant, x0, x_ref, num_steps, estimator="nystrom", gain_fn=None, c=1.0,
+                  u_opt=None, batch=32, workers=4, return_trajectories=False, fit_fn=None, loop_fn=None, gain="host",
+                  gain_batch_fn=None):
+    """Scores of planned units, in their order: an (n_units, 4) array (SCORE_NAMES; NaN for a unit whose fit or gain
+    failed), the trajectories (or None, None) and the wall-clock split.  fit_fn / loop_fn stand in for lqr_fit_unit /
+    plant_loop_multi (rehearsals without a GPU; with a fit_fn the fits run as a plain loop).
+    gain="device": the gains of all fitted units come from ONE nk_model_lqr_gain_batch call after the fits (K =
+    dlqr(A, B, c sym(C'C), I) by the batched doubling solver; gain_fn is not used); a unit whose solve reports a non-zero
+    status gets NaN scores and is not run.  timing keeps its keys: gain_wait_s is that call, gain_cpu_s is 0.
+    gain_batch_fn(regs, c) -> (Ks, status, iterations) stands in for the device call."""
+    import time
+    loop_fn = loop_fn or plant_loop_multi
+    n = len(units)
+    regs, gains, _, tm = lqr_fit_and_gain(X, Y, n_inputs, params, units, estimator, gain_fn, c, batch, workers, fit_fn, gain,
+                                          gain_batch_fn)
+    t2 = time.perf_counter()
     live = [i for i in range(n) if gains[i] is not None]
     scores = np.full((n, len(SCORE_NAMES)), np.nan)
     states = controls = None
@@ -707,8 +732,9 @@ def lqr_run_units(X, Y, n_inputs, params, units, plant, x0, x_ref, num_steps, es
             states = np.full((n,) + np.shape(res["states"])[1:], np.nan)
             controls = np.full((n,) + np.shape(res["controls"])[1:], np.nan)
             states[live], controls[live] = res["states"], res["controls"]
-    t3 = time.perf_counter()
-    timing = dict(fit_s=t1 - t0, gain_wait_s=t2 - t1, loop_s=t3 - t2, gain_cpu_s=float(sum(gain_s)), total_s=t3 - t0)
+    loop_s = time.perf_counter() - t2
+    timing = dict(fit_s=tm["fit_s"], gain_wait_s=tm["gain_wait_s"], loop_s=loop_s, gain_cpu_s=tm["gain_cpu_s"],
+                  total_s=tm["fit_s"] + tm["gain_wait_s"] + loop_s)
     return scores, states, controls, timing
 
 
@@ -757,6 +783,249 @@ def lqr_result(units, scores, states, controls, n_seeds, n_ms, timing=None):
     out["units"], out["timing"] = units, timing
     if states is not None:
         out["states"], out["controls"] = lqr_table(units, states, n_seeds, n_ms), lqr_table(units, controls, n_seeds, n_ms)
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the CLOTH control sweep (benchmark_lqr_cloth.py:213-270): seeds x {Nystrom, splines}, lifted closed loop
+# ---------------------------------------------------------------------------------------------------------------
+LOOP_SCORE_NAMES = ("J", "err_final", "u_sumsq", "u_absmax")
+LOOP_MULTI_MAX_M = 128  # nk_closed_loop_multi keeps [A B] in the registers of one workgroup
+
+
+def closed_loop_scores(states, controls, target, c=0.0075, u_init=None):
+    """What nk_closed_loop_multi reduces on the device, on the host by the same formulas, from one loop's states
+    (steps, d), controls (steps, p) and the target (d,): e_t = sqrt(sum_k (x_{t,k} - target_k)^2 / d),
+    J = sum_t (c sum_k (x_{t,k} - target_k)^2 + sum_j u_{t,j}^2), err_final = e_{steps-1}, u_sumsq, u_absmax (NaN from the
+    first NaN control on) and the cumulative inputs s_0 = u_init (zeros), s_{t+1} = s_t + u_t.  Returns a dict.  Needs no GPU."""
+    xs = np.asarray(states, dtype=np.float64)
+    us = np.asarray(controls, dtype=np.float64)
+    steps, d = xs.shape
+    with np.errstate(all="ignore"):
+        sse = np.sum(np.square(xs - np.asarray(target, dtype=np.float64).reshape(1, d)), axis=1)
+        usq = np.sum(np.square(us), axis=1)
+        J = 0.0
+        for t in range(steps):
+            J = J + (c * sse[t] + usq[t])
+        au = np.abs(us)
+        cum = np.empty((steps + 1, us.shape[1]))
+        cum[0] = 0.0 if u_init is None else np.asarray(u_init, dtype=np.float64).reshape(-1)
+        for t in range(steps):
+            cum[t + 1] = cum[t] + us[t]
+        err = np.sqrt(sse / d)
+    return dict(J=float(J), err_final=float(err[-1]), u_sumsq=float(np.sum(usq)),
+                u_absmax=float("nan") if np.any(np.isnan(au)) else float(np.max(au)), err=err, cum_controls=cum)
+
+
+def closed_loop_multi_lifted(regressors, gains, lifts, targets, num_steps, c=0.0075, u_inits=None,
+                             return_trajectories=False):
+    """closed_loop_multi after the lifts: lifts[u] = (phi0, phi_ref), two (m,) vectors."""
+    regs = list(regressors)
+    n = len(regs)
+    num_steps = int(num_steps)
+    if not (len(gains) == len(lifts) == len(targets) == n):
+        raise ValueError("regressors, gains, lifts and targets must have the same length")
+    u_inits = [None] * n if u_inits is None else list(u_inits)
+    dims = []
+    for r, K in zip(regs, gains):
+        d, m = r._landmark_shape()
+        p = int(r.n_inputs)
+        if np.shape(K) != (p, m):
+            raise ValueError(f"gain has shape {np.shape(K)}, expected {(p, m)}")
+        dims.append((int(m), p, int(d)))
+    out = {name: np.full(n, np.nan) for name in LOOP_SCORE_NAMES}
+    out["err"] = np.full((n, num_steps), np.nan)
+    out["path"] = ["device" if dm[0] <= LOOP_MULTI_MAX_M else "single" for dm in dims]
+    states, controls, cums = [None] * n, [None] * n, [None] * n
+    dev = [i for i in range(n) if out["path"][i] == "device"]
+    if dev:
+        sc, err, ox, ou, oc = _lib.get_context().closed_loop_multi(
+            num_steps, c, [regs[i]._ensure_model() for i in dev], [dims[i] for i in dev], [gains[i] for i in dev],
+            [lifts[i][0] for i in dev], [lifts[i][1] for i in dev], [targets[i] for i in dev], [u_inits[i] for i in dev],
+            want_x=return_trajectories, want_u=return_trajectories, want_ucum=return_trajectories)
+        for k, name in enumerate(LOOP_SCORE_NAMES):
+            out[name][dev] = sc[:, k]
+        out["err"][dev] = err
+        if return_trajectories:
+            for k, i in enumerate(dev):
+                states[i], controls[i], cums[i] = ox[k], ou[k], oc[k]
+    for i in range(n):  # a model beyond one workgroup's registers: the single-model call, scored on the host
+        if out["path"][i] == "device":
+            continue
+        xs, us = regs[i].closed_loop(np.asarray(gains[i], dtype=np.float64), lifts[i][0], lifts[i][1], num_steps)
+        sc = closed_loop_scores(xs.T, us.T, targets[i], c, u_inits[i])
+        for name in LOOP_SCORE_NAMES:
+            out[name][i] = sc[name]
+        out["err"][i] = sc["err"]
+        states[i], controls[i], cums[i] = np.ascontiguousarray(xs.T), np.ascontiguousarray(us.T), sc["cum_controls"]
+    if return_trajectories:
+        same = len({dm[1:] for dm in dims}) == 1  # equal (p, d): plain 3-D arrays, otherwise lists of per-unit arrays
+        out["states"] = np.stack(states) if same else states
+        out["controls"] = np.stack(controls) if same else controls
+        out["cum_controls"] = np.stack(cums) if same else cums
+    return out
+
+
+def _per_unit(x, n, what):
+    """One state for all n units (a vector / column) or one per unit (a sequence of n, or an (n, d) array)."""
+    if isinstance(x, np.ndarray) and (x.ndim == 1 or (x.ndim == 2 and x.shape[1] == 1)):
+        return [x.reshape(-1)] * n
+    x = list(x)
+    if len(x) != n:
+        if all(np.ndim(v) == 0 for v in x):
+            return [np.asarray(x, dtype=np.float64)] * n
+        raise ValueError(f"{what}: {len(x)} entries for {n} units")
+    return [np.asarray(v, dtype=np.float64).reshape(-1) for v in x]
+
+
+def closed_loop_multi(regressors, gains, x0s, x_refs, num_steps, c=0.0075, u_inits=None, targets=None,
+                      return_trajectories=False):
+    """The lifted closed loop of lqr_control (benchmark_lqr_cloth.py:73-84) for every (regressor, gain, x0, x_ref) unit in
+    ONE device call (nk_closed_loop_multi), scored on the device: per step u_t = K (phi_ref - phi_t), x_t = C phi_t,
+    phi_{t+1} = A phi_t + B u_t.  The units may mix model kinds, m, p and d.  x0s, x_refs: one state for all units or one
+    per unit; each regressor lifts its [x0, x_ref] with one `lift` call.  targets: the state each loop is scored against
+    (default: its x_ref).  u_inits: per unit, the seed of the cumulative input sequence (None: zeros).
+    Returns a dict of (n_units,) arrays J, err_final, u_sumsq, u_absmax (include/nyskoop.h), err (n_units, num_steps) =
+    RMSE per step (plot_reg_error_cloth.py:24), and path: per unit "device" or "single" -- a regressor with m > 128 runs
+    through its own closed_loop call and is scored on the host by the same formulas.  With return_trajectories also states
+    (n_units, num_steps, d), controls (n_units, num_steps, p) and cum_controls (n_units, num_steps + 1, p) (lists of
+    per-unit arrays when the units differ in p or d).  Without them nothing but the scores and errors leaves the device."""
+    regs = list(regressors)
+    n = len(regs)
+    x0s, x_refs = _per_unit(x0s, n, "x0s"), _per_unit(x_refs, n, "x_refs")
+    targets = x_refs if targets is None else _per_unit(targets, n, "targets")
+    lifts = []
+    for r, x0, xr in zip(regs, x0s, x_refs):
+        phi = r.lift(np.stack((x0, xr), axis=1))  # one call for both lifts
+        lifts.append((np.ascontiguousarray(phi[:, 0]), np.ascontiguousarray(phi[:, 1])))
+    return closed_loop_multi_lifted(regs, list(gains), lifts, targets, num_steps, c, u_inits, return_trajectories)
+
+
+def cloth_control_layout(initial_state, states, cum_controls, simulator_order=(0, 3, 1, 4, 2, 5)):
+    """What lqr_control returns (benchmark_lqr_cloth.py:85-104), from one unit of closed_loop_multi: states (steps, d) and
+    cum_controls (steps + 1, p).  Returns (x_s, y_s, z_s, final_us) in the layout of harness.lqr_control."""
+    x0 = np.asarray(initial_state, dtype=np.float64).reshape(-1, 1)
+    visited = np.hstack((x0, np.asarray(states, dtype=np.float64).T))
+    final_us = np.asarray(cum_controls, dtype=np.float64).T[list(simulator_order), :]
+    return visited[0::3], visited[1::3], visited[2::3], final_us
+
+
+def cloth_lqr_plan(X, Y, n_inputs, params, m, seeds, estimator="nystrom", centers=None):
+    """The units of cloth_lqr_sweep: per estimator lqr_plan with the one landmark count `m` (np.random.seed(seed) in front
+    of every fit, benchmark_lqr_cloth.py:216-233), estimator-major; each unit carries its "estimator", "params" and "ei"
+    (position of the estimator).  estimator: a name or a sequence of names; with a sequence `params` (and `centers`) are
+    dicts keyed by the name.  Needs no GPU."""
+    names = [estimator] if isinstance(estimator, str) else list(estimator)
+    units = []
+    for ei, name in enumerate(names):
+        _check_estimator(name)
+        par = params if isinstance(estimator, str) else params[name]
+        cen = centers if isinstance(estimator, str) or centers is None else centers.get(name)
+        cen = None if cen is None else {(s, 0): v for s, v in cen.items()}
+        for u in lqr_plan(X, Y, n_inputs, par, [int(m)], seeds, name, cen):
+            units.append(dict(u, estimator=name, params=par, ei=ei))
+    return names, units
+
+
+def cloth_lqr_run_units(X, Y, n_inputs, units, x0, x_ref, num_steps=60, c=0.0075, gain="host", batch=32, workers=4,
+                        control_nodes=(168, 169, 170, 189, 190, 191), return_trajectories=False, fit_fn=None, loop_fn=None,
+                        gain_batch_fn=None):
+    """Planned units of the cloth sweep: fits (the lifts of x0 / x_ref inside the lock-step round, right after each
+    member's fit), gains (lqr_fit_and_gain) and ONE closed_loop_multi call over the units that have a gain.  Returns
+    (scores (n_units, 4) in LOOP_SCORE_NAMES order, err (n_units, num_steps), gains, result of the loop call or None,
+    indices of the units it held, timing); a unit whose fit or gain failed is NaN and is not submitted."""
+    import time
+    x0 = np.asarray(x0, dtype=np.float64).reshape(-1)
+    x_ref = np.asarray(x_ref, dtype=np.float64).reshape(-1)
+    both = np.stack((x0, x_ref), axis=1)
+    u_init = None if control_nodes is None else np.ascontiguousarray(x0[list(control_nodes)])
+    loop_fn = loop_fn or closed_loop_multi_lifted
+
+    def lifted(reg, unit):
+        phi = reg.lift(both)
+        return np.ascontiguousarray(phi[:, 0]), np.ascontiguousarray(phi[:, 1])
+
+    n = len(units)
+    regs, gains, lifts, tm = lqr_fit_and_gain(X, Y, n_inputs, None, units, "nystrom", None, c, batch, workers, fit_fn, gain,
+                                              gain_batch_fn, after_fit=lifted)
+    t2 = time.perf_counter()
+    live = [i for i in range(n) if gains[i] is not None]
+    scores = np.full((n, len(LOOP_SCORE_NAMES)), np.nan)
+    err = np.full((n, int(num_steps)), np.nan)
+    res = None
+    if live:
+        res = loop_fn([regs[i] for i in live], [gains[i] for i in live], [lifts[i] for i in live], [x_ref] * len(live),
+                      num_steps, c, [u_init] * len(live), return_trajectories)
+        for k, name in enumerate(LOOP_SCORE_NAMES):
+            scores[live, k] = res[name]
+        err[live] = res["err"]
+    loop_s = time.perf_counter() - t2
+    timing = dict(fit_s=tm["fit_s"], gain_wait_s=tm["gain_wait_s"], loop_s=loop_s, gain_cpu_s=tm["gain_cpu_s"],
+                  total_s=tm["fit_s"] + tm["gain_wait_s"] + loop_s)
+    return scores, err, gains, res, live, timing
+
+
+def cloth_lqr_result(names, units, scores, err, n_seeds, single, timing=None):
+    """The tables of cloth_lqr_sweep from per-unit values in plan order: (n_seeds,) for one estimator name, else
+    (len(names), n_seeds)."""
+    def table(values):
+        values = np.asarray(values, dtype=np.float64)
+        out = np.full((len(names), n_seeds) + values.shape[1:], np.nan)
+        for u, v in zip(units, values):
+            out[u["ei"], u["si"]] = v
+        return out[0] if single else out
+
+    out = {name: table(scores[:, k]) for k, name in enumerate(LOOP_SCORE_NAMES)}
+    out["err"] = table(err)
+    out["estimators"], out["units"], out["timing"] = names, units, timing
+    return out
+
+
+def cloth_lqr_sweep(X, Y, n_inputs, params, m, seeds, x0, x_ref, num_steps=60, estimator="nystrom", c=0.0075, gain="host",
+                    batch=32, workers=4, control_nodes=(168, 169, 170, 189, 190, 191), return_trajectories=False,
+                    centers=None, fit_fn=None, loop_fn=None, gain_batch_fn=None):
+    """The control branch of benchmark_lqr_cloth.py:213-270 as one call: for every seed (and every estimator) fit at `m`
+    landmarks -> K = dlqr(A, B, c C'C, I) -> `num_steps` steps of the lifted closed loop of lqr_control from x0 towards
+    x_ref, with its cumulative input sequence seeded by x0[control_nodes].
+      draws:  lqr_plan's per-seed protocol (one RandomState(seed) per seed and estimator); `centers` {seed: landmarks}
+              replaces them.  estimator: "nystrom", "spline", or a sequence of both with params = {name: params}: then
+              every table gets a leading estimator axis and all units still share the ONE loop call;
+      fits:   `batch` at a time through the lock-step pool (batch <= 1: a plain loop; same bits); each member lifts
+              [x0, x_ref] right after its fit, inside the round;
+      gains:  gain="host": regressor.solve_lqr's arithmetic in `workers` host threads while later rounds fit;
+              gain="device": ONE nk_model_lqr_gain_batch call after the fits; a unit without a gain is NaN and is not run;
+      loops:  ONE closed_loop_multi call over all surviving units, scored on the device against x_ref.
+    Returns a dict of per-seed tables J, err_final, u_sumsq, u_absmax (len(seeds),) and err (len(seeds), num_steps), the
+    planned `units`, `estimators` and the wall-clock split `timing` (fit_s, gain_wait_s, loop_s, gain_cpu_s, total_s).
+    With return_trajectories also x_s, y_s, z_s (len(seeds), d / 3, num_steps + 1) and final_us (len(seeds), p,
+    num_steps + 1) in the layout of harness.lqr_control, the raw states (len(seeds), num_steps, d) and controls
+    (len(seeds), num_steps, p) of the loop call, K (len(seeds), p, m) and K_sim, the gains with the rows in the
+    simulator's order (lqr.cloth_gain_for_simulator, benchmark_lqr_cloth.py:263); failed units are NaN.
+    fit_fn / loop_fn / gain_batch_fn stand in for lqr_fit_unit / closed_loop_multi_lifted / the device gain call."""
+    single = isinstance(estimator, str)
+    names, units = cloth_lqr_plan(X, Y, n_inputs, params, m, seeds, estimator, centers)
+    scores, err, gains, res, live, timing = cloth_lqr_run_units(X, Y, n_inputs, units, x0, x_ref, num_steps, c, gain, batch,
+                                                                workers, control_nodes, return_trajectories, fit_fn,
+                                                                loop_fn, gain_batch_fn)
+    out = cloth_lqr_result(names, units, scores, err, len(seeds), single, timing)
+    if return_trajectories:
+        from .lqr import cloth_gain_for_simulator
+        n_seeds, p, steps = len(seeds), int(n_inputs), int(num_steps)
+        d = np.asarray(x0).size
+        shape = (len(names), n_seeds)
+        tabs = dict(x_s=np.full(shape + (d // 3, steps + 1), np.nan), y_s=np.full(shape + (d // 3, steps + 1), np.nan),
+                    z_s=np.full(shape + (d // 3, steps + 1), np.nan), final_us=np.full(shape + (p, steps + 1), np.nan),
+                    K=np.full(shape + (p, int(m)), np.nan), K_sim=np.full(shape + (p, int(m)), np.nan),
+                    states=np.full(shape + (steps, d), np.nan), controls=np.full(shape + (steps, p), np.nan))
+        for k, i in enumerate(live):
+            at = (units[i]["ei"], units[i]["si"])
+            xs, ys, zs, fu = cloth_control_layout(x0, res["states"][k], res["cum_controls"][k])
+            tabs["x_s"][at], tabs["y_s"][at], tabs["z_s"][at], tabs["final_us"][at] = xs, ys, zs, fu
+            tabs["K"][at], tabs["states"][at] = gains[i], res["states"][k]
+            if "controls" in res:
+                tabs["controls"][at] = res["controls"][k]
+            tabs["K_sim"][at] = cloth_gain_for_simulator(np.asarray(gains[i])) if p == 6 else gains[i]
+        out.update({k: (v[0] if single else v) for k, v in tabs.items()})
     return out
 
 
