@@ -252,6 +252,45 @@ int nk_kernel_matrix(nk_ctx* ctx, const nk_kernel_desc* kd,
                      const double* B, int64_t ldb, int64_t nB,
                      double* out, int64_t ldo);
 
+/* ---- landmark selection (beyond the reference, which draws landmarks uniformly at random, regressors.py:129-132): m
+ *   steps of partial pivoted Cholesky of K(Y, Y) over the CANDIDATE rows -- all n rows, or the rows of row_ranges
+ *   concatenated in the order given, as the fits gather them ([begin,end) pairs as in nk_nystrom_fit; empty ranges are
+ *   dropped; n_c = number of candidates).  Y: n x d, host or device.  The state is the residual diagonal
+ *   dg_i = k(y_i, y_i) and a factor F (n_c x m, a dedicated HBM allocation of 8 n_c m bytes that is released before the
+ *   call returns, never part of the context's workspace; NK_ERR_OOM when it does not fit).  Step j = 0 .. m-1:
+ *     pick    NK_LANDMARK_GREEDY: the candidate with the largest dg; equal values go to the LOWEST candidate position
+ *             (ties are real: far-apart points leave many residuals at exactly 1).  NK_LANDMARK_RPCHOLESKY: with
+ *             T = sum dg, the smallest position whose inclusive prefix sum of dg exceeds u[j] * T (a position with
+ *             dg == 0 is never picked; should rounding let no prefix exceed it, the last position with dg > 0).
+ *     record  out_resid[j] = dg[piv] and out_trace[j] = T (the sum of dg before the step).
+ *     stop    if dg[piv] <= tol * dg0max (dg0max = the largest initial diagonal entry) or dg[piv] <= 0 the selection ends
+ *             with *m_selected = j: the residual at which a landmark is picked is the squared Cholesky pivot of K_mm at
+ *             that landmark, so tol > 0 stops before K_mm becomes singular to working precision.
+ *     column  c_i = k(y_i, y_piv) - sum_{l<j} F[i,l] F[piv,l], F[i,j] = c_i / sqrt(dg[piv]),
+ *             dg_i = max(dg_i - F[i,j]^2, 0), dg[piv] = 0 exactly.
+ *   Summation orders, all fixed by the inputs alone (no atomics; the result does not depend on the launch geometry):
+ *   kernel values from direct differences (dot products for LINEAR) of the pre-scaled coordinates, accumulated over
+ *   k in four partial sums (k mod 4) combined as (a0 + a1) + (a2 + a3); the sum over l < j likewise in four partial sums
+ *   (l mod 4) in increasing l; T and the prefix sums: blocks of 256 consecutive candidate positions are summed by a halving
+ *   tree (entry t + entry t + s for s = 128, 64, .. 1), the block sums are added in index order, and inside the block
+ *   that holds the pick dg is added in index order on top of the prefix before that block.
+ *   Kernel families: RBF (isotropic or anisotropic), MATERN52, LINEAR.  NK_KERNEL_TPS is rejected: the thin-plate spline
+ *   is not positive semi-definite (its diagonal is 0), so it has no Cholesky factor.
+ *   The selection is nested: the rows for m are the first m rows for any larger m (same u prefix, same tol).
+ *   out_rows (HOST, m): rows of Y in pick order, -1 from entry *m_selected on.  out_resid (HOST, m, may be NULL): entry
+ *   *m_selected, if there is one, is the residual that fired the stop rule, later entries are 0.  out_trace (HOST, m + 1,
+ *   may be NULL): entry *m_selected is the trace left, tr(K - K_nm K_mm^-1 K_mn) over the candidates; later entries are 0.
+ *   u: HOST, m numbers in [0, 1), read for NK_LANDMARK_RPCHOLESKY only (may be NULL for GREEDY).
+ *   Everything is checked before anything is queued: 1 <= m <= min(n_c, 4096), d <= 2048, tol finite and >= 0, the rule,
+ *   u, the kernel family and its dimension, the ranges inside [0, n]; a failed check is NK_ERR_BAD_ARG and no output is
+ *   written.  All 2m + 1 launches are queued without a host round trip and one copy brings the results back.  Ordinary
+ *   contexts only (not lock-step members). ------------------------------------------------------------------------- */
+#define NK_LANDMARK_GREEDY 0
+#define NK_LANDMARK_RPCHOLESKY 1
+int nk_select_landmarks(nk_ctx* ctx, const nk_kernel_desc* kd, const double* Y, int64_t ldy, int64_t n, int32_t d,
+                        const int64_t* row_ranges, int32_t n_ranges, int32_t rule, const double* u, int32_t m, double tol,
+                        int64_t* out_rows, double* out_resid, double* out_trace, int32_t* m_selected);
+
 /* ---- fit: replaces KoopmanNystromRegressor.fit given landmarks (regressors.py:136-169).
  *   X: n x (d+p) rows [state | input] (the array the reference's fit(X, Y) receives), Y: n x d.
  *   row_ranges: optional 2*n_ranges int64 [begin,end) pairs selecting the training rows (K-fold training

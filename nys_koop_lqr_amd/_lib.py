@@ -11,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 
 NK_KERNEL_RBF, NK_KERNEL_MATERN52, NK_KERNEL_LINEAR, NK_KERNEL_TPS = 0, 1, 2, 3
 NK_PLANT_DUFFING, NK_PLANT_DOUBLE_INTEGRATOR, NK_PLANT_HJB = 0, 1, 2
+NK_LANDMARK_GREEDY, NK_LANDMARK_RPCHOLESKY = 0, 1
 NK_OK = 0
 _ERR_NAMES = {-1: "NK_ERR_BAD_ARG", -2: "NK_ERR_HIP", -3: "NK_ERR_NOT_SPD", -4: "NK_ERR_OOM",
               -5: "NK_ERR_NO_CONVERGENCE", -6: "NK_ERR_NO_DEVICE"}
@@ -113,6 +114,8 @@ SIGNATURES = {
     "nk_host_alloc": (_P, [C.c_uint64]),
     "nk_host_free": (None, [_P]),
     "nk_kernel_matrix": (C.c_int, [_P, C.POINTER(KernelDesc), _P, _I64, _I64, _P, _I64, _I64, _P, _I64]),
+    "nk_select_landmarks": (C.c_int, [_P, C.POINTER(KernelDesc), _P, _I64, _I64, _I32, C.POINTER(_I64), _I32, _I32, _P,
+                                      _I32, _D, _P, _P, _P, C.POINTER(_I32)]),
     "nk_nystrom_fit": (C.c_int, [_P, C.POINTER(KernelDesc), _P, _I64, _P, _I64, _I64, _I32, _I32,
                                  C.POINTER(_I64), _I32, _P, _I64, _P, _I64, _I32, _D, _D,
                                  C.POINTER(_P), C.POINTER(FitStats)]),

@@ -708,6 +708,74 @@ int nk_kernel_matrix(nk_ctx* ctx, const nk_kernel_desc* kd, const double* A, int
   return NK_OK;
 }
 
+int nk_select_landmarks(nk_ctx* ctx, const nk_kernel_desc* kd, const double* Y, int64_t ldy, int64_t n, int32_t d,
+                        const int64_t* row_ranges, int32_t n_ranges, int32_t rule, const double* u, int32_t m, double tol,
+                        int64_t* out_rows, double* out_resid, double* out_trace, int32_t* m_selected) {
+  NK_TRY(check_ctx(ctx));
+  NK_REQUIRE(!ctx_recording(ctx), "nk_select_landmarks: not available to the members of a lock-step group");
+  NK_REQUIRE(kd && Y && out_rows && m_selected, "nk_select_landmarks: null argument");
+  NK_REQUIRE(n >= 1 && d >= 1 && ldy >= d, "nk_select_landmarks: bad sizes (n = %lld, d = %d, ldy = %lld)", (long long)n, d,
+             (long long)ldy);
+  NK_REQUIRE(d <= LANDMARKS_MAX_D, "nk_select_landmarks: d = %d is beyond the column kernel's range (%d)", d, LANDMARKS_MAX_D);
+  NK_REQUIRE(kd->type != NK_KERNEL_TPS,
+             "nk_select_landmarks: the thin-plate spline is not positive semi-definite and has no Cholesky factor");
+  NK_REQUIRE(kd->type == NK_KERNEL_RBF || kd->type == NK_KERNEL_MATERN52 || kd->type == NK_KERNEL_LINEAR,
+             "nk_select_landmarks: unknown kernel type %d", kd->type);
+  NK_REQUIRE(rule == NK_LANDMARK_GREEDY || rule == NK_LANDMARK_RPCHOLESKY, "nk_select_landmarks: unknown rule %d", rule);
+  NK_REQUIRE(std::isfinite(tol) && tol >= 0.0, "nk_select_landmarks: tol must be finite and non-negative");
+  NK_REQUIRE(n_ranges >= 0 && (n_ranges == 0 || row_ranges != nullptr), "nk_select_landmarks: bad row ranges");
+  std::vector<int64_t> rng;  // the candidates as [begin, end) pairs, in the order given
+  int64_t nc = 0;
+  if (n_ranges > 0) {
+    for (int i = 0; i < n_ranges; ++i) {
+      const int64_t b = row_ranges[2 * i], e = row_ranges[2 * i + 1];
+      NK_REQUIRE(0 <= b && b <= e && e <= n, "nk_select_landmarks: row range %d = [%lld,%lld) outside [0,%lld)", i, (long long)b,
+                 (long long)e, (long long)n);
+      if (e > b) { rng.push_back(b); rng.push_back(e); nc += e - b; }
+    }
+  } else {
+    rng.push_back(0); rng.push_back(n); nc = n;
+  }
+  NK_REQUIRE(m >= 1 && m <= LANDMARKS_MAX_M && m <= nc, "nk_select_landmarks: m = %d must lie in 1 .. min(%lld candidates, %d)",
+             m, (long long)nc, LANDMARKS_MAX_M);
+  if (rule == NK_LANDMARK_RPCHOLESKY) {
+    NK_REQUIRE(u != nullptr, "nk_select_landmarks: the RPCholesky rule needs m uniforms in u");
+    for (int j = 0; j < m; ++j) NK_REQUIRE(u[j] >= 0.0 && u[j] < 1.0, "nk_select_landmarks: u[%d] = %g is outside [0, 1)", j, u[j]);
+  }
+  NK_REQUIRE(!is_device_ptr(out_rows) && !is_device_ptr(out_resid) && !is_device_ptr(out_trace) && !is_device_ptr(u),
+             "nk_select_landmarks: u and the outputs must be host memory");
+  double* winv = nullptr;
+  NK_TRY(arena_alloc_t(ctx, (size_t)d, &winv));
+  NK_TRY(make_winv(ctx, kd, d, winv));  // (checks the descriptor's dimension and length scales before its one copy)
+  CallStage st(ctx);
+  MatIn y;
+  st.in(&y, Y, ldy, n, d);
+  NK_TRY(st.commit());
+  NK_TRY(st.resident(&y, d));  // every workgroup of the preparation reads it: HBM, not the page-locked block
+  std::vector<int64_t> pos;
+  std::vector<double> resid, trace;
+  int count = 0;
+  NK_TRY(select_landmarks_device(ctx, kd->type, y.ptr, y.ld, rng, nc, d, winv, kd->sigma0, rule, u, m, tol, &pos, &resid, &trace,
+                                 &count));
+  // candidate positions -> rows of Y
+  for (int j = 0; j < m; ++j) {
+    int64_t row = -1;
+    if (j < count) {
+      int64_t p = pos[j];
+      for (size_t r = 0; r < rng.size(); r += 2) {
+        const int64_t len = rng[r + 1] - rng[r];
+        if (p < len) { row = rng[r] + p; break; }
+        p -= len;
+      }
+    }
+    out_rows[j] = row;
+  }
+  if (out_resid) std::copy(resid.begin(), resid.end(), out_resid);
+  if (out_trace) std::copy(trace.begin(), trace.end(), out_trace);
+  *m_selected = count;
+  return NK_OK;
+}
+
 int nk_model_create(nk_ctx* ctx, const nk_kernel_desc* kd, const double* Zout, int64_t ldz, int32_t m, int32_t d,
                     int32_t p, double jitter, const double* A, const double* B, const double* C, const double* W,
                     nk_model** model) {

@@ -568,6 +568,17 @@ inline int dare_pad(int m) { return (m + 15) & ~15; }
 inline size_t dare_ws_doubles(int M) { return (size_t)7 * M * M; }
 int launch_dare(nk_ctx* ctx, const DareRec* table_dev, int count, double tol, int max_iter);
 
+// ---- landmark selection (nk_landmarks.hip): partial pivoted Cholesky of K(Y, Y) over the candidate rows rng ([begin, end)
+// pairs of rows of the device matrix Y, nc rows in all), m steps queued without a host round trip.  positions: the
+// m_selected candidate positions in pick order; resid: m entries, trace: m + 1 entries (zero past the stop).  The factor
+// is a dedicated allocation released before the call returns (NK_ERR_OOM when it does not fit).
+constexpr int LANDMARKS_MAX_M = 4096;
+constexpr int LANDMARKS_MAX_D = 2048;  // (m + d) doubles of LDS per workgroup of the column launch
+int select_landmarks_device(nk_ctx* ctx, int ktype, const double* Y, int64_t ldy, const std::vector<int64_t>& rng, int64_t nc,
+                            int d, const double* winv, double sigma0, int rule, const double* u_host, int m, double tol,
+                            std::vector<int64_t>* positions, std::vector<double>* resid, std::vector<double>* trace,
+                            int* m_selected);
+
 }  // namespace nk
 
 namespace nk {

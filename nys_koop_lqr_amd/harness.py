@@ -313,6 +313,40 @@ def sysid_plan(X, Y, n_inputs, params, ms, seeds, test_index, train_ranges=None,
     return units
 
 
+def landmark_centers(Y, kernel, ms, seeds, test_index, train_ranges=None, rule="greedy", tol=0.0, select_fn=None):
+    """The `centers=` dictionary of sysid_plan / sysid_sweep from pivoted-Cholesky landmark selection on the device
+    (landmarks.select_landmarks) instead of uniform draws: {(seed, test, k): the first ms[k] selected landmarks, as
+    indices in the reference's training-row numbering}.  The selection is nested, so ONE selection of max(ms) per distinct
+    training-row set serves every m.  rule="greedy": all seeds with the same training rows share it; "rpcholesky": every
+    seed draws its own max(ms) uniforms from np.random.RandomState(seed).  A tolerance that stops the selection before
+    max(ms) landmarks is an error (sysid_plan wants ms[k] landmarks per unit).  select_fn: stands in for
+    select_landmarks (tests without a GPU)."""
+    if select_fn is None:
+        from .landmarks import select_landmarks as select_fn
+    n = np.shape(Y)[0]
+    m_max = max(int(m) for m in ms)
+    shared, out = {}, {}
+    for si, seed in enumerate(seeds):
+        seed = int(seed)
+        ranges = _per_seed(train_ranges, si, seed)
+        key = None if ranges is None else tuple(np.asarray(ranges, dtype=np.int64).reshape(-1).tolist())
+        if rule != "greedy":
+            key = (seed, key)
+        if key not in shared:
+            u = None if rule == "greedy" else np.random.RandomState(seed).uniform(size=m_max)
+            rows = np.asarray(select_fn(Y, kernel, m_max, rule=rule, row_ranges=ranges, tol=tol, u=u), dtype=np.int64)
+            if len(rows) < m_max:
+                raise ValueError(f"the selection stopped after {len(rows)} landmarks (tol = {tol}), ms asks for {m_max}")
+            rowmap = train_row_map(ranges, n)
+            position = np.full(n, -1, dtype=np.int64)
+            position[rowmap[::-1]] = np.arange(len(rowmap) - 1, -1, -1)  # data-set row -> its first training-row index
+            shared[key] = position[rows]
+        for ti, _ in enumerate(_per_seed(test_index, si, seed)):
+            for k, m in enumerate(ms):
+                out[(seed, ti, k)] = shared[key][:int(m)].copy()
+    return out
+
+
 def sysid_unit_error(X, Y, n_inputs, params, unit, tr, U, estimator="nystrom", relative=False):
     """One unit of the sweep on the calling thread's context: fit on the unit's rows with its landmarks, operators left on
     the device, then the open-loop error of its test trajectory reduced on the device (reg.open_loop_errors).

@@ -492,6 +492,12 @@ class KoopmanNystromRegressor(_DeviceModelRegressor):
     # attribute, not a constructor argument: the constructor mirrors the reference's (sklearn clone / get_params), and a
     # clone starts from the default.
     compute_dtype = "f64"
+    # How `fit` chooses landmarks when none are set: "uniform" (the reference's draw, regressors.py:129-132), or "greedy" /
+    # "rpcholesky": pivoted-Cholesky selection on the device over the fit's training rows (landmarks.select_landmarks),
+    # stopped early by landmark_tol (the fit then has fewer than m landmarks).  Attributes like compute_dtype: not
+    # constructor arguments, and a clone starts from the defaults.
+    landmark_rule = "uniform"
+    landmark_tol = 0.0
     _landmarks_attr = "nystrom_centers_output"
 
     def __init__(self, n_inputs, kernel=None, gamma=None, m=None):
@@ -511,12 +517,17 @@ class KoopmanNystromRegressor(_DeviceModelRegressor):
         return h
 
     # ------------------------------------------------------------------------------------------------ fit
-    def _prepare(self, n, d, Y=None):
+    def _prepare(self, n, d, Y=None, row_ranges=None):
         """Landmarks (regressors.py:129-134) and kernel descriptor for a fit on d-dimensional states."""
         if self.nystrom_centers_output is None:  # regressors.py:129-132: global legacy NumPy RNG, n = #samples
             if Y is None:
                 raise RuntimeError("landmarks must be set before a fit from Gram blocks")
-            idx = np.random.choice(np.arange(0, n), size=self.m, replace=False)
+            if self.landmark_rule != "uniform":
+                from .landmarks import select_landmarks
+                idx = select_landmarks(Y, self.kernel, self.m, rule=self.landmark_rule, row_ranges=row_ranges,
+                                       tol=self.landmark_tol)
+            else:
+                idx = np.random.choice(np.arange(0, n), size=self.m, replace=False)
             if _is_device_tensor(Y):
                 rows = Y[idx.tolist()]
                 self.nystrom_centers_output = np.ascontiguousarray(rows.cpu().numpy().T)
@@ -541,7 +552,7 @@ class KoopmanNystromRegressor(_DeviceModelRegressor):
         p = int(self.n_inputs)
         if Xm.shape != (n, d + p):
             raise ValueError(f"X has shape {Xm.shape}, expected {(n, d + p)}")
-        Zo, Zi, same, kd, keep = self._prepare(n, d, Y)
+        Zo, Zi, same, kd, keep = self._prepare(n, d, Y, row_ranges)
         m = Zo.shape[0]
         rr, n_rr, keep_rr = self._ranges(row_ranges)
         stats = _lib.FitStats()
