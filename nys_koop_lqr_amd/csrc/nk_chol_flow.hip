@@ -1,7 +1,7 @@
 // Blocked Cholesky of up to two augmented systems (cholesky_aug_pair_async's contract: an m x m SPD block plus `extra`
 // right-hand-side rows) in ONE launch: a tile-dataflow factorisation.
 //
-// The launch-per-step chain (nk_linalg.hip) runs 32 dependent block steps at m = 2000, each a diagonal factor, a panel launch
+// The launch-per-step chain (nk_chol.hip) runs 32 dependent block steps at m = 2000, each a diagonal factor, a panel launch
 // and a trailing update that ends only when its slowest tile is done -- about 97 us per step against a few us of arithmetic.
 // Here the work is the set of 64 x 64 tiles (i, k), i >= k, of the factor, each owned by one workgroup from start to end,
 // LEFT-LOOKING:

@@ -68,7 +68,7 @@ enum {
   EV_LANDMARKS = 8,      // landmark matrices built (main or preparation stream) / the preparation stream, and the main
                          // stream where it assembles the systems
   EV_SQRT_PREPARED = 9,  // sqrtm_prepare's chain, preparation stream / the side stream in front of the iteration
-  EV_SQRT_RESID = 10,    // residual copy of the synchronous square-root iteration (nk_linalg.hip) / the host, same place
+  EV_SQRT_RESID = 10,    // residual copy of the host-checked square-root iteration (nk_sqrtm.hip) / the host, same place
   EV_SQRT_SCALARS = 11,  // sqrtm_prepare's schedule scalars on their way to the host / the host in sqrtm_finish
   EV_FORK = 12,          // scratch fork point, recorded on the main stream and waited for at once by the stream that
                          // branches off: the landmark matrices aside, the pipelined upload, the Y rows' preparation
@@ -76,6 +76,33 @@ enum {
   EV_GEMM_T0 = 14,       // recorded by the GEMM engines (nk_gemm*.hip) around a timed launch; read there, or by the
   EV_GEMM_T1 = 15,       // fits after their own synchronisation when the launch was timed without one (sync_timing = false)
   EV_COUNT = 16
+};
+
+// Regions of nk_ctx::h_scalars, the pinned host mirror of small device results.  Who writes (by a copy queued on its
+// stream) / who reads.  Two owners may be in flight on different streams during a fit, so the regions do not overlap.
+enum {
+  HS_SCRATCH = 0,             // [0..3] read back right behind a synchronisation of the writer's own stream: the synchronous
+                              // form of the square root (c, ||P||_F^2, trace, ||L^-1||_F^2 in SqrtPlan::d_sc's order), its
+                              // residuals, the coupled iteration, the pseudo-inverse (nk_pinv.hip) / the same function
+  HS_SQRT_FLAG = 8,           // verdict of the queued square-root iteration, sqrtm_finish (in a fit: side stream) / sqrtm_verdict:
+  HS_SQRT_RESID_AT_FLAG = 9,  //   step + 1 of the first step below the residual bar (0: none), the residual there,
+  HS_SQRT_RESID_LAST = 10,    //   the last residual seen
+  HS_SQRT_C = 12,             // schedule scalars of the square root, sqrtm_prepare (in a fit: preparation stream) /
+  HS_SQRT_SUMSQ = 13,         //   the early form of sqrtm_finish behind EV_SQRT_SCALARS: ||P||_inf, ||P||_F^2,
+  HS_SQRT_TRACE = 14,         //   trace(P)
+  HS_REFINE = 16,             // [16..23] refinement verdicts, four per system, nk_fit.hip (main stream) / read_refinement
+  HS_COUNT = 64               // length of h_scalars (and of d_scalars)
+};
+// Device scalars of SqrtPlan::d_sc.  sqrtm_prepare writes the first four, the queued iteration of sqrtm_finish the state.
+enum {
+  SQ_C = 0,              // c = ||P||_inf
+  SQ_SUMSQ = 1,          // ||P||_F^2
+  SQ_TRACE = 2,          // trace(P)
+  SQ_LINV2 = 3,          // ||L^-1||_F^2
+  SQ_FLAG = 5,           // iteration state (ns_flag_kernel): step + 1 of the first step below the residual bar (0: not yet),
+  SQ_RESID_AT_FLAG = 6,  //   the residual at that step,
+  SQ_RESID_LAST = 7,     //   the last residual seen
+  SQ_COUNT = 8
 };
 
 struct nk_member_state;
@@ -99,8 +126,8 @@ struct nk_ctx {
   int* d_info = nullptr;       // device flags for factorisation failures (one int per paired system)
   unsigned long long* d_piv = nullptr;  // [min, max] Cholesky pivot per system slot (bit patterns), behind d_info's 4 slots
   unsigned long long* h_piv = nullptr;  // pinned host mirror
-  double* d_scalars = nullptr; // small device scratch for reductions (64 doubles)
-  double* h_scalars = nullptr; // pinned host mirror
+  double* d_scalars = nullptr; // small device scratch for reductions (HS_COUNT doubles)
+  double* h_scalars = nullptr; // pinned host mirror, HS_COUNT doubles in the HS_* regions above
   int* h_info = nullptr;       // pinned host mirror of d_info (kept apart from h_scalars: both streams may be in flight)
   double* d_zeros = nullptr;   // 4 KiB zero page (K-tail rows of the LDS-DMA GEMM)
   hipEvent_t ev[EV_COUNT];  // indexed by the EV_* slots above
@@ -317,7 +344,14 @@ struct GemmCall {
 int launch_gemm_pair(nk_ctx* ctx, bool transA, bool transB, const GemmCall* calls, int ncalls);
 
 struct TnSkip;  // device-side launch control, defined with the TN engine below
-// elementwise / reductions
+// elementwise / reductions (nk_elementwise.hip)
+// workgroups of a grid-stride launch over `total` elements; it also fixes the number of per-block partials of the
+// reductions and with it their summation order
+static inline int grid_for(int64_t total, int num_cu) {
+  int64_t b = (total + 255) / 256;
+  const int64_t cap = (int64_t)num_cu * 8;
+  return (int)(b < 1 ? 1 : (b > cap ? cap : b));
+}
 int launch_add_diag(nk_ctx* ctx, double* A, int64_t lda, int n, double v);
 int launch_copy2d(nk_ctx* ctx, const double* src, int64_t lds, double* dst, int64_t ldd, int64_t rows, int64_t cols);
 int launch_axpby2d(nk_ctx* ctx, double a, const double* X, int64_t ldx, double b, double* Y, int64_t ldy,
@@ -327,7 +361,11 @@ int launch_scale_add_identity(nk_ctx* ctx, double a, const double* X, int64_t ld
 int launch_fill(nk_ctx* ctx, double* A, int64_t lda, int64_t rows, int64_t cols, double v);
 int launch_frob_minus_identity(nk_ctx* ctx, const double* M, int64_t ldm, int n, double* d_out,
                                const TnSkip* skip = nullptr);  // sum (M-I)^2
+// the per-block partials of sum (M-I)^2 alone, grid_for(n * n) of them (*count), for a caller that sums them itself
+int launch_frob_mi_partials(nk_ctx* ctx, const double* M, int64_t ldm, int n, double* partial, int* count, const TnSkip* skip);
 int launch_max_abs_rowsum(nk_ctx* ctx, const double* M, int64_t ldm, int n, double* d_out);
+// d_sumsq[0] = sum of squares of M (n x n), d_trace[0] = its trace (nullptr: the sum of squares only)
+int launch_sumsq_trace(nk_ctx* ctx, const double* M, int64_t ldm, int n, double* d_sumsq, double* d_trace);
 int launch_colsum_sqdiff(nk_ctx* ctx, const double* P, int64_t ldp, const double* Y, int64_t ldy, int64_t rows,
                          int cols, double* d_colsum);  // colsum[j] = sum_i (P[i][j]-Y[i][j])^2
 
@@ -344,10 +382,9 @@ struct SqrtPlan {
   double* Linv = nullptr;  // inverted diagonal blocks
   double* X0 = nullptr;    // L^T / sqrt(c)   (c = ||P||_inf)
   double* X0t = nullptr;   // L / sqrt(c)
-  double* d_sc = nullptr;  // device scalars: c, ||P||_F^2, trace(P), ||L^-1||_F^2; then the iteration state
-                           // [5] convergence flag (step + 1), [6] residual at that step, [7] last residual
+  double* d_sc = nullptr;  // SQ_COUNT device scalars, the SQ_* slots above
   ArenaMark mark{0, 0};
-  // verdict of sqrtm_finish: known at once for the synchronous forms, otherwise in ctx->h_scalars[8..10] once the
+  // verdict of sqrtm_finish: known at once for the synchronous forms, otherwise in ctx->h_scalars[HS_SQRT_FLAG ..] once the
   // stream has been synchronised (sqrtm_verdict)
   bool deferred = false;
   int rc = 0, iters = 0, kmax = 0;
@@ -659,6 +696,11 @@ int launch_kmat_gram(nk_ctx* ctx, int ktype, const double* At, int64_t ldat, con
 //      v_permlane32_swap between rows and half waves (checked lane by lane on the device by tools/reduce_probe.hip)
 #if defined(__HIPCC__)
 namespace nk {
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+  return v;
+}
 typedef unsigned chain_u2 __attribute__((ext_vector_type(2)));
 template <int CTRL> __device__ __forceinline__ double dpp_f64(double v) {
   int lo = __double2loint(v), hi = __double2hiint(v);

@@ -770,10 +770,10 @@ int NystromFit::refine() {
       // X += dX while the corrections contract (a numerically singular system that happened to factor is left alone)
       NK_TRY(launch_refine_apply(ctx, Res, mq, Xq, mq, nr, mq, step, refine_state + 4 * q, partial));
     }
-    NK_HIP(hipMemcpyAsync(ctx->h_scalars + 16 + 4 * q, refine_state + 4 * q, 4 * sizeof(double), hipMemcpyDeviceToHost,
+    NK_HIP(hipMemcpyAsync(ctx->h_scalars + HS_REFINE + 4 * q, refine_state + 4 * q, 4 * sizeof(double), hipMemcpyDeviceToHost,
                           ctx->stream));
     arena_release(ctx, mk);
-    refined[q] = -1;  // verdict in h_scalars[16 + 4 q ..] after the synchronisation that follows (read_refinement)
+    refined[q] = -1;  // verdict in h_scalars[HS_REFINE + 4 q ..] after the synchronisation that follows (read_refinement)
     redo_products = true;
   }
   return NK_OK;
@@ -820,8 +820,8 @@ int NystromFit::settle_sqrt() {
 void NystromFit::read_refinement() {
   for (int q = 0; q < 2; ++q)
     if (refined[q] < 0) {
-      refined[q] = (int)ctx->h_scalars[16 + 4 * q + 2];  // steps accepted by the contraction guard
-      refine_ratio[q] = ctx->h_scalars[16 + 4 * q + 3];
+      refined[q] = (int)ctx->h_scalars[HS_REFINE + 4 * q + 2];  // steps accepted by the contraction guard
+      refine_ratio[q] = ctx->h_scalars[HS_REFINE + 4 * q + 3];
     }
   if (refined[0] > 0 || refined[1] > 0) count_event(CNT_REFINED);
 }

@@ -408,7 +408,7 @@ static bool ctx_pinned_mirror(const nk_ctx* c, const void* p, size_t bytes) {
   const char* q = static_cast<const char*>(p);
   const char* hs = reinterpret_cast<const char*>(c->h_scalars);
   const char* hi = reinterpret_cast<const char*>(c->h_info);
-  return (hs && q >= hs && q + bytes <= hs + 64 * sizeof(double)) || (hi && q >= hi && q + bytes <= hi + 64 * sizeof(int));
+  return (hs && q >= hs && q + bytes <= hs + HS_COUNT * sizeof(double)) || (hi && q >= hi && q + bytes <= hi + 64 * sizeof(int));
 }
 
 hipError_t x_memcpy_async(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s) {

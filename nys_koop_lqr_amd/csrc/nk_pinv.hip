@@ -1,6 +1,6 @@
 // Rank-revealing fallback of the two regularised solves (regressors.py:155,165): the reference calls
 // scipy.linalg.lstsq, i.e. LAPACK gelsd, which returns the MINIMUM-NORM solution with every singular value below a
-// cut-off relative to the largest one treated as zero.  The fast path (blocked Cholesky, nk_linalg.hip) has no such
+// cut-off relative to the largest one treated as zero.  The fast path (blocked Cholesky, nk_chol.hip) has no such
 // notion: on a numerically rank-deficient system it meets a non-positive (or rounding-level) pivot.  This file provides
 // the truncated pseudo-inverse for that case, entirely on the device:
 //
@@ -575,9 +575,9 @@ int pinv_right_divide(nk_ctx* ctx, const double* P, int64_t ldp, int m, const do
   NK_TRY(launch_add_diag(ctx, V, m, m, 1.0));
   hipLaunchKernelGGL(sumsq_all_kernel, dim3(1), dim3(256), 0, ctx->stream, P, ldp, m, d_out);
   NK_HIP(hipGetLastError());
-  NK_HIP(hipMemcpyAsync(ctx->h_scalars, d_out, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  NK_HIP(hipMemcpyAsync(ctx->h_scalars + HS_SCRATCH, d_out, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   NK_HIP(hipStreamSynchronize(ctx->stream));
-  const double fro = std::sqrt(ctx->h_scalars[0]);
+  const double fro = std::sqrt(ctx->h_scalars[HS_SCRATCH]);
   if (!std::isfinite(fro)) {
     set_error("pseudo-inverse fallback: the system matrix is not finite");
     arena_release(ctx, mk);
@@ -665,13 +665,13 @@ int pinv_right_divide(nk_ctx* ctx, const double* P, int64_t ldp, int m, const do
     NK_HIP(hipGetLastError());
     NK_TRY(launch_gemm(ctx, false, false, rows, m, m, 1.0, T, m, W, m, 0.0, E_out, ldeo));  // (T diag) W, rows of W = u_j
   }
-  NK_HIP(hipMemcpyAsync(ctx->h_scalars, d_out, 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  NK_HIP(hipMemcpyAsync(ctx->h_scalars + HS_SCRATCH, d_out, 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
   NK_HIP(hipStreamSynchronize(ctx->stream));
   if (info) {
-    info->rank = (int)ctx->h_scalars[0];
-    info->sigma_max = ctx->h_scalars[1];
-    info->sigma_min_kept = ctx->h_scalars[2];
-    info->sigma_min = ctx->h_scalars[3];
+    info->rank = (int)ctx->h_scalars[HS_SCRATCH];
+    info->sigma_max = ctx->h_scalars[HS_SCRATCH + 1];
+    info->sigma_min_kept = ctx->h_scalars[HS_SCRATCH + 2];
+    info->sigma_min = ctx->h_scalars[HS_SCRATCH + 3];
     info->sweeps = sweeps;
     info->converged = last_rot == 0 || m <= 1;
   }

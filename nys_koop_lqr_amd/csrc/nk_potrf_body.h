@@ -1,4 +1,4 @@
-// Diagonal-block Cholesky of the blocked factorisation (nk_linalg.hip), in its own translation unit (fully unrolled).  Replaces the LAPACK potrf inside lstsq's role
+// Diagonal-block Cholesky of the blocked factorisation (nk_chol.hip), in its own translation unit (fully unrolled).  Replaces the LAPACK potrf inside lstsq's role
 // (regressors.py:155,165).
 #pragma once
 #include "nk_common.h"

@@ -1,4 +1,4 @@
-// Trailing update of one step of the blocked Cholesky (nk_linalg.hip: cholesky_aug_pair_async):
+// Trailing update of one step of the blocked Cholesky (nk_chol.hip: cholesky_aug_pair_async):
 //     C[tm, tn] -= P[tm] P[tn]^T      P = the 64-column panel of this step (rows x 64, row-major, k contiguous),
 // lower tiles of the square part plus full tiles for the extra (right-hand-side) rows, for up to two systems in one
 // launch.  The generic engine (nk_gemm.hip) walks K in register-staged, barrier-separated steps of 16 -- with K = 64 it

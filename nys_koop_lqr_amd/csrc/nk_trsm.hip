@@ -1,4 +1,4 @@
-// Backward substitution of the augmented blocked Cholesky (nk_linalg.hip: cholesky_aug_pair_async) in ONE launch.
+// Backward substitution of the augmented blocked Cholesky (nk_chol.hip: cholesky_aug_pair_async) in ONE launch.
 //
 // After the factorisation the extra rows hold E = R^T L^-T; the solution of the regularised systems of
 // regressors.py:155,165 is X^T = E L^-1, i.e. every ROW x of the result solves x L = e on its own.  The blocked

@@ -475,6 +475,27 @@ def test_sqrtm_fast_path_vs_scipy(nk, m):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("m", [1022, 1024])
+def test_sqrtm_at_the_boundary_between_the_two_iterations(nk, m):
+    """m = 1022 is the largest even size on the host-checked iteration, m = 1024 the smallest on the queued one (the whole
+    iteration queued from the step schedule, verdict read afterwards).  Well-conditioned family of test_sqrtm_same_bits; the
+    bars are that test's (S S^-1), the figure documented for the full-size fit (S S = P) and the iteration's own."""
+    from nys_koop_lqr_amd import _lib
+    ctx = nk.get_context()
+    rng = np.random.default_rng(m)
+    Q = rng.standard_normal((m, 2 * m))
+    P = Q @ Q.T / (2 * m) + 1e-3 * np.eye(m)
+    S, Si = np.empty((m, m)), np.empty((m, m))
+    it, res = C.c_int32(), C.c_double()
+    _lib.check(ctx.lib.nk_sqrtm_spd(ctx.handle, P.ctypes.data, m, m, S.ctypes.data, Si.ctypes.data, C.byref(it), C.byref(res)))
+    inv_err, sq_err = float(np.linalg.norm(S @ Si - np.eye(m)) / np.sqrt(m)), relf(S @ S, P)
+    print(f"\n[sqrtm m={m}] iters {it.value} residual {res.value:.3e} |S Sinv - I|_F/sqrt(m) {inv_err:.3e} relf(S S, P) {sq_err:.3e}")
+    assert inv_err < 1e-8
+    assert sq_err < 1e-11
+    assert res.value < 1e-7 and 3 <= it.value < 40
+
+
+@pytest.mark.gpu
 def test_sqrtm_numerically_singular_input_is_handled(nk):
     """A kernel matrix without jitter is numerically singular: the Cholesky route of the square root meets a
     non-positive pivot and the coupled iteration takes over; either it delivers a square root or a clean error comes

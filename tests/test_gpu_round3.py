@@ -183,7 +183,7 @@ h = hashlib.sha256(np.ascontiguousarray(reg.A).tobytes() + np.ascontiguousarray(
 print("HASH", h)
 ''' % ROOT
     hashes = []
-    for la in ("1", "0"):  # (off by default: nk_linalg.hip)
+    for la in ("1", "0"):  # (off by default: nk_chol.hip)
         env = dict(os.environ, NYSKOOP_CHOL_LOOKAHEAD=la)
         out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, env=env)
         assert out.returncode == 0, (out.stdout[-300:], out.stderr[-1500:])
