@@ -12,8 +12,9 @@ namespace nk {
 
 // ---------------------------------------------------------------------------------------------------------------
 // matrix square root: coupled Newton-Schulz  Y <- Y T, Z <- T Z, T = (3I - ZY)/2,  Y0 = P/c, Z0 = I
-//   Y -> (P/c)^{1/2}, Z -> (P/c)^{-1/2}.  Only M = ZY is symmetrised (mirrored upper tiles); symmetrising Y and Z as
-//   well was observed to destabilise the iteration, the plain products are stable.
+//   Y -> (P/c)^{1/2}, Z -> (P/c)^{-1/2}.  Only M = ZY is symmetrised (mirrored upper tiles, diagonal tiles averaged with their
+//   transposes); symmetrising Y and Z as well was observed to destabilise the iteration, the plain products are stable (see
+//   DESIGN.md).
 // ---------------------------------------------------------------------------------------------------------------
 static int read_scalar(nk_ctx* ctx, const double* d_ptr, double* out) {
   NK_HIP(hipMemcpyAsync(ctx->h_scalars + HS_SCRATCH, d_ptr, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -102,6 +103,12 @@ int sqrtm_spd_coupled(nk_ctx* ctx, const double* P, int64_t ldp, int m, double* 
       NK_TRY(launch_axpby2d(ctx, 0.5, b.Yt, m, 0.5, b.M, m, m, m));
     } else {
       NK_TRY(launch_gemm(ctx, true, false, m, m, m, 1.0, b.Zt, m, b.Y, m, 0.0, b.M, m, sym));
+      // The mirrored mode copies whole tiles across the diagonal and leaves the 128 x 128 diagonal tiles as computed.  Those
+      // are symmetric to the last bit for a product X^T X, but for Z Y only up to rounding -- and Z <- T Z below is issued as
+      // T^T Z, which a T that is not exactly symmetric turns into another iteration (3 to 8 times the error of the intended
+      // one at cond 1e6, tests/test_gpu_sqrtm.py).  Average M with its transpose; T is free until the step is formed.
+      NK_TRY(launch_transpose(ctx, b.M, m, b.T, m, m, m));
+      NK_TRY(launch_axpby2d(ctx, 0.5, b.T, m, 0.5, b.M, m, m, m));
     }
     // a_lo over-estimates the smallest eigenvalue of M: while it is below 1/2 the iteration cannot have converged
     // (||M - I||_F / sqrt(m) >= (1 - lambda_min) / sqrt(m)), so the residual reduction and its host round trip are
@@ -475,7 +482,9 @@ int sqrtm_finish(nk_ctx* ctx, SqrtPlan* plan, double* S, double* Sinv) {
   if (!plan->early) {
     NK_TRY(scalars_synchronous(ctx, plan, ib, &sc));
     if (ctx->h_info[ib] == CHOL_FLOW_GIVEUP) return sqrtm_again_on_chain(ctx, plan, S, Sinv);
-    if (ctx->h_info[ib] != 0 || !(sc.c > 0.0) || !std::isfinite(sc.c) || !(sc.linv2 > 0.0) || !std::isfinite(sc.linv2))
+    const char* hook = getenv("NYSKOOP_SQRT_FORCE_COUPLED");  // test hook, read per call: take the fallback (tests/)
+    const bool forced = hook && hook[0] == '1';
+    if (forced || ctx->h_info[ib] != 0 || !(sc.c > 0.0) || !std::isfinite(sc.c) || !(sc.linv2 > 0.0) || !std::isfinite(sc.linv2))
       return sqrtm_coupled_fallback(ctx, plan, S, Sinv);
   }
   PolarIter it;

@@ -74,6 +74,7 @@ def schedule_program(tmp_path_factory):
             out.append((kmax, s2, check))
         return out
 
+    run.exe = exe  # (tests/test_sqrtm_reference_host.py runs the program's other modes)
     return run
 
 
