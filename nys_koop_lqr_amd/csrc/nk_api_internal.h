@@ -1,7 +1,8 @@
-// Helpers shared by the translation units behind the C ABI (nk_api.hip, nk_fit.hip, nk_sweep.hip, nk_control.hip);
-// defined in nk_api.hip unless noted.
+// Helpers shared by the translation units behind the C ABI (nk_api.hip, nk_api_compute.hip, nk_fit.hip, nk_sweep.hip,
+// nk_control.hip, nk_api_loops.hip, nk_api_dare.hip); defined in nk_api.hip unless noted.
 #pragma once
 #include "nk_common.h"
+#include "nk_unit_pack.h"
 
 #include <chrono>
 #include <cstdio>
@@ -33,6 +34,7 @@ int make_winv(nk_ctx* ctx, const nk_kernel_desc* kd, int d, double* dst_dev);
 int model_alloc(nk_ctx* ctx, int m, int d, int p, nk_model** out, int kind = NK_MODEL_NYSTROM);
 
 // phi (nq x m, ld ldo) = k(Xq, Z) * Sinv, processed in row chunks; a spline model's lift is the raw block k(Xq, Z)
+// (this and predict_device: nk_api_compute.hip)
 int lift_device(nk_ctx* ctx, const nk_model* mdl, const double* Xq, int64_t ldx, int64_t nq, double* out, int64_t ldo);
 // out (nq x d) = [phi(X) | U] W^T
 int predict_device(nk_ctx* ctx, const nk_model* mdl, const double* Xaug, int64_t ldx, int64_t nq, double* out, int64_t ldo);
@@ -79,6 +81,10 @@ class CallStage {
   bool pinned = false;
   std::vector<Operand> ops;
 };
+
+// the staging block of a unit-table call (nk_unit_pack.h) in the arena: its one host-to-device copy.  The pack must outlive
+// the synchronisation that ends the call: the copy reads its block.
+int stage_pack(nk_ctx* ctx, UnitPack& pack, double** dev);
 
 // the body of nk_rollout_err for a context whose arena the caller has prepared (check_ctx): the sweep gathers a unit's
 // trajectories into the arena first (nk_control.hip)

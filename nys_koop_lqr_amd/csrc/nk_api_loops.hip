@@ -1,0 +1,233 @@
+// Closed loops that run as one launch behind the C ABI: the plant loops (nk_plant_step, nk_plant_loop, nk_plant_loop_multi;
+// nk_plant_loop.hip) and the lifted loop of many models (nk_closed_loop_multi; nk_loop_multi.hip).  The unit-table calls
+// check every unit, lay its host operands out in one staging block (nk_unit_pack.h), move it with one copy, build the
+// table of device records, launch, and bring the results back behind one synchronisation.
+#include "nk_common.h"
+#include "nk_api_internal.h"
+#include "nk_plant.h"
+
+#include <cmath>
+#include <string>
+#include <vector>
+
+using namespace nk;
+
+// One model against a plant, for both plant-loop entries.  unit < 0: the single-model call (no "unit %d: " in the text).
+static int check_plant_model(nk_ctx* ctx, const char* who, int unit, const nk_model* mdl, int plant) {
+  auto at = [unit] { return unit >= 0 ? "unit " + std::to_string(unit) + ": " : std::string(); };  // (a failed check only)
+  NK_REQUIRE(mdl->device == ctx->device, "%s: %sthe model lives on device %d, the context on %d", who, at().c_str(),
+             mdl->device, ctx->device);
+  NK_REQUIRE(mdl->p == 1, "%s: %sthe plants have one input, the model has %d", who, at().c_str(), mdl->p);
+  NK_REQUIRE(mdl->d == plant_dim(plant), "%s: %sthe %s has %d states, the model has %d", who, at().c_str(),
+             plant_name(plant), plant_dim(plant), mdl->d);
+  NK_REQUIRE(mdl->m >= 1 && mdl->m <= plant_loop_max_m(), "%s: %sm = %d landmarks, at most %d fit one workgroup", who,
+             at().c_str(), mdl->m, plant_loop_max_m());
+  NK_REQUIRE(mdl->kind == NK_MODEL_SPLINE
+                 ? mdl->ktype == NK_KERNEL_TPS
+                 : (mdl->ktype == NK_KERNEL_RBF || mdl->ktype == NK_KERNEL_MATERN52 || mdl->ktype == NK_KERNEL_LINEAR),
+             "%s: %skernel type %d is not supported for this model", who, at().c_str(), mdl->ktype);
+  return NK_OK;
+}
+
+extern "C" {
+
+int nk_plant_step(int plant, double Ts, const double* x, const double* u, double* x_next) {
+  NK_REQUIRE(plant_dim(plant) > 0, "nk_plant_step: unknown plant %d", plant);
+  NK_REQUIRE(x && u && x_next, "nk_plant_step: null argument");
+  plant_step_host(plant, Ts, x, u[0], x_next);
+  return NK_OK;
+}
+
+int nk_plant_loop(nk_ctx* ctx, const nk_model* mdl, int plant, double Ts, const double* K, const double* x0,
+                  const double* x_ref, int32_t steps, int32_t batch, double* out_x, double* out_u) {
+  NK_TRY(check_ctx(ctx));
+  NK_REQUIRE(!ctx_recording(ctx), "nk_plant_loop: not available to the members of a lock-step group");
+  NK_REQUIRE(mdl && K && x0 && x_ref && out_x && out_u, "nk_plant_loop: null argument");
+  NK_REQUIRE(plant_dim(plant) > 0, "nk_plant_loop: unknown plant %d", plant);
+  NK_TRY(check_plant_model(ctx, "nk_plant_loop", -1, mdl, plant));
+  NK_REQUIRE(steps >= 1 && batch >= 1, "nk_plant_loop: steps = %d and batch = %d must be positive", steps, batch);
+  NK_REQUIRE(std::isfinite(Ts), "nk_plant_loop: Ts is not finite");
+  const int m = mdl->m, d = mdl->d;
+  MatIn k, xi, xr;
+  MatOut ox, ou;
+  NK_TRY(stage_in(ctx, K, m, 1, m, &k));
+  NK_TRY(stage_in(ctx, x0, d, batch, d, &xi));
+  NK_TRY(stage_in(ctx, x_ref, d, batch, d, &xr));
+  NK_TRY(stage_out(ctx, out_x, d, (int64_t)batch * (steps + 1), d, &ox));
+  NK_TRY(stage_out(ctx, out_u, 1, (int64_t)batch * steps, 1, &ou));
+  // u = K phi = K (k S^-1)^T = (S^-1 K^T) . k: the product nk_lift forms, contracted with the gain first
+  const double* w = k.ptr;
+  if (mdl->kind != NK_MODEL_SPLINE) {
+    double* wf = nullptr;
+    NK_TRY(arena_alloc_t(ctx, (size_t)m + 2, &wf));
+    NK_TRY(launch_gemm(ctx, false, true, m, 1, m, 1.0, mdl->Sinv, m, k.ptr, k.ld, 0.0, wf, 1));
+    w = wf;
+  }
+  NK_TRY(launch_plant_loop(ctx, mdl, plant, Ts, w, xi.ptr, xi.ld, xr.ptr, xr.ld, steps, batch, ox.dev, ox.ld, ou.dev,
+                           ou.ld));
+  NK_TRY(finish_out(ctx, ox));
+  NK_TRY(finish_out(ctx, ou));
+  NK_HIP(hipStreamSynchronize(ctx->stream));
+  return NK_OK;
+}
+
+int nk_plant_loop_multi(nk_ctx* ctx, int plant, double Ts, int32_t steps, const nk_plant_unit* units, int32_t n_units,
+                        const double* u_opt, int32_t n_uopt, double* out_x, double* out_u, double* scores) {
+  NK_TRY(check_ctx(ctx));
+  NK_REQUIRE(!ctx_recording(ctx), "nk_plant_loop_multi: not available to the members of a lock-step group");
+  NK_REQUIRE(plant_dim(plant) > 0, "nk_plant_loop_multi: unknown plant %d", plant);
+  NK_REQUIRE(units != nullptr && n_units >= 1, "nk_plant_loop_multi: n_units = %d units at %p: at least one is needed",
+             n_units, (const void*)units);
+  NK_REQUIRE(steps >= 1, "nk_plant_loop_multi: steps = %d must be positive", steps);
+  NK_REQUIRE(std::isfinite(Ts), "nk_plant_loop_multi: Ts is not finite");
+  NK_REQUIRE(out_x || out_u || scores, "nk_plant_loop_multi: out_x, out_u and scores are all null: nothing to return");
+  NK_REQUIRE(n_uopt >= 0 && (n_uopt == 0 || u_opt != nullptr), "nk_plant_loop_multi: n_uopt = %d rows of a null u_opt",
+             n_uopt);
+  NK_REQUIRE(!is_device_ptr(scores), "nk_plant_loop_multi: scores must be host memory");
+  const int d = plant_dim(plant);
+  // every unit is checked before anything is queued; its gain, initial state and reference are laid out on the way
+  UnitPack in, folds;
+  std::vector<PlantUnitOffsets> off((size_t)n_units);
+  for (int u = 0; u < n_units; ++u) {
+    const nk_plant_unit& un = units[u];
+    NK_REQUIRE(un.model && un.K && un.x0 && un.x_ref, "nk_plant_loop_multi: unit %d: null argument", u);
+    NK_TRY(check_plant_model(ctx, "nk_plant_loop_multi", u, un.model, plant));
+    NK_REQUIRE(un.uopt >= -1 && un.uopt < n_uopt, "nk_plant_loop_multi: unit %d: uopt = %d, u_opt has %d rows", u, un.uopt,
+               n_uopt);
+    NK_REQUIRE(!is_device_ptr(un.K) && !is_device_ptr(un.x0) && !is_device_ptr(un.x_ref),
+               "nk_plant_loop_multi: unit %d: K, x0 and x_ref must be host memory", u);
+    off[u] = pack_plant_unit(in, folds, un.K, un.x0, un.x_ref, (size_t)un.model->m, (size_t)d,
+                             un.model->kind != NK_MODEL_SPLINE);
+  }
+  double *d_in = nullptr, *d_w = nullptr, *d_sc = nullptr;
+  NK_TRY(stage_pack(ctx, in, &d_in));
+  if (folds.doubles()) NK_TRY(arena_alloc_t(ctx, folds.doubles(), &d_w));
+  if (scores) NK_TRY(arena_alloc_t(ctx, (size_t)n_units * 4, &d_sc));
+  MatIn uo;
+  MatOut ox, ou;
+  if (n_uopt > 0) NK_TRY(stage_in(ctx, u_opt, steps, n_uopt, steps, &uo));
+  if (out_x) NK_TRY(stage_out(ctx, out_x, d, (int64_t)n_units * (steps + 1), d, &ox));
+  if (out_u) NK_TRY(stage_out(ctx, out_u, 1, (int64_t)n_units * steps, 1, &ou));
+  std::vector<PlantLoopUnit> recs((size_t)n_units);
+  std::vector<int> ktypes((size_t)n_units);
+  for (int u = 0; u < n_units; ++u) {
+    const nk_plant_unit& un = units[u];
+    const nk_model* mdl = un.model;
+    const int m = mdl->m;
+    // u = K phi = K (k S^-1)^T = (S^-1 K^T) . k, the fold of nk_plant_loop by the same call on the same operands (the gain
+    // row has its leading dimension there); the folds of all units are queued back to back, nothing waits between them
+    const double* w = d_in + off[u].K;
+    if (mdl->kind != NK_MODEL_SPLINE) {
+      double* wf = d_w + off[u].w;
+      NK_TRY(launch_gemm(ctx, false, true, m, 1, m, 1.0, mdl->Sinv, m, w, (int64_t)gain_row_reserve((size_t)m), 0.0, wf,
+                         1));
+      w = wf;
+    }
+    PlantLoopUnit& r = recs[u];
+    r.Z = mdl->Z; r.winv = mdl->winv; r.w = w; r.x0 = d_in + off[u].x0; r.xref = d_in + off[u].x_ref;
+    r.out_x = out_x ? ox.dev + (int64_t)u * (steps + 1) * ox.ld : nullptr; r.ldx = out_x ? ox.ld : 0;
+    r.out_u = out_u ? ou.dev + (int64_t)u * steps * ou.ld : nullptr; r.ldu = out_u ? ou.ld : 0;
+    r.u_opt = un.uopt >= 0 ? uo.ptr + (int64_t)un.uopt * uo.ld : nullptr;
+    r.score = scores ? d_sc + 4 * (size_t)u : nullptr;
+    r.sigma0sq = mdl->sigma0 * mdl->sigma0; r.m = m; r.reserved = 0;
+    ktypes[u] = mdl->ktype;
+  }
+  NK_TRY(launch_plant_loop_multi(ctx, plant, Ts, steps, recs.data(), ktypes.data(), n_units));
+  if (out_x) NK_TRY(finish_out(ctx, ox));
+  if (out_u) NK_TRY(finish_out(ctx, ou));
+  if (scores) NK_HIP(hipMemcpyAsync(scores, d_sc, (size_t)n_units * 32, hipMemcpyDeviceToHost, ctx->stream));
+  NK_HIP(hipStreamSynchronize(ctx->stream));  // (the staging block and recs are read by the copies queued above)
+  return NK_OK;
+}
+
+// every unit of nk_closed_loop_multi is checked before anything is queued
+static int check_loop_unit(nk_ctx* ctx, int u, const nk_loop_unit& un, bool scored) {
+  const nk_model* mdl = un.model;
+  NK_REQUIRE(mdl != nullptr, "nk_closed_loop_multi: unit %d: the model is null", u);
+  NK_REQUIRE(mdl->p >= 1 && mdl->p <= LOOP_MULTI_MAX_P, "nk_closed_loop_multi: unit %d: p = %d inputs must lie in 1 .. %d", u,
+             mdl->p, LOOP_MULTI_MAX_P);
+  NK_REQUIRE(mdl->m >= 1 && mdl->m <= LOOP_MULTI_MAX_M,
+             "nk_closed_loop_multi: unit %d: m = %d must lie in 1 .. %d (larger models: nk_closed_loop)", u, mdl->m,
+             LOOP_MULTI_MAX_M);
+  NK_REQUIRE(mdl->d >= 1, "nk_closed_loop_multi: unit %d: d = %d", u, mdl->d);
+  NK_REQUIRE(mdl->has_ops, "nk_closed_loop_multi: unit %d: the model holds no fitted operators", u);
+  NK_REQUIRE(mdl->device == ctx->device, "nk_closed_loop_multi: unit %d: the model lives on device %d, the context on %d", u,
+             mdl->device, ctx->device);
+  NK_REQUIRE(un.K && un.phi0 && un.phi_ref, "nk_closed_loop_multi: unit %d: null argument (K, phi0, phi_ref)", u);
+  NK_REQUIRE(un.target != nullptr || !scored,
+             "nk_closed_loop_multi: unit %d: target is null, but out_err or scores are requested", u);
+  NK_REQUIRE(!is_device_ptr(un.K) && !is_device_ptr(un.phi0) && !is_device_ptr(un.phi_ref) && !is_device_ptr(un.target) &&
+                 !is_device_ptr(un.u_init),
+             "nk_closed_loop_multi: unit %d: K, phi0, phi_ref, target and u_init must be host memory", u);
+  return NK_OK;
+}
+
+int nk_closed_loop_multi(nk_ctx* ctx, int32_t steps, double c, const nk_loop_unit* units, int32_t n_units, double* out_x,
+                         double* out_u, double* out_ucum, double* out_err, double* scores) {
+  NK_TRY(check_ctx(ctx));
+  NK_REQUIRE(!ctx_recording(ctx), "nk_closed_loop_multi: not available to the members of a lock-step group");
+  NK_REQUIRE(units != nullptr && n_units >= 1, "nk_closed_loop_multi: n_units = %d units at %p: at least one is needed",
+             n_units, (const void*)units);
+  NK_REQUIRE(steps >= 1, "nk_closed_loop_multi: steps = %d must be positive", steps);
+  NK_REQUIRE(std::isfinite(c) && c >= 0.0, "nk_closed_loop_multi: c must be finite and non-negative");
+  NK_REQUIRE(out_x || out_u || out_ucum || out_err || scores,
+             "nk_closed_loop_multi: out_x, out_u, out_ucum, out_err and scores are all null: nothing to return");
+  NK_REQUIRE(!is_device_ptr(scores), "nk_closed_loop_multi: scores must be host memory");
+  // the staging block (gains, lifted states, targets, seeds), the workspace and the dense, unit-major output offsets are
+  // laid out while the units are checked
+  UnitPack in, ws;
+  std::vector<LoopUnitOffsets> off((size_t)n_units);
+  std::vector<size_t> x_off((size_t)n_units), u_off((size_t)n_units), uc_off((size_t)n_units);
+  size_t x_doubles = 0, u_doubles = 0, uc_doubles = 0;
+  for (int u = 0; u < n_units; ++u) {
+    const nk_loop_unit& un = units[u];
+    NK_TRY(check_loop_unit(ctx, u, un, out_err != nullptr || scores != nullptr));
+    const size_t m = (size_t)un.model->m, p = (size_t)un.model->p, d = (size_t)un.model->d;
+    off[u] = pack_loop_unit(in, ws, un.K, un.phi0, un.phi_ref, un.target, un.u_init, m, p, d, (size_t)steps);
+    x_off[u] = x_doubles;
+    x_doubles += (size_t)steps * d;
+    u_off[u] = u_doubles;
+    u_doubles += (size_t)steps * p;
+    uc_off[u] = uc_doubles;
+    uc_doubles += ((size_t)steps + 1) * p;
+  }
+  double *d_in = nullptr, *d_ws = nullptr, *d_sc = nullptr;
+  NK_TRY(stage_pack(ctx, in, &d_in));
+  NK_TRY(arena_alloc_t(ctx, ws.doubles(), &d_ws));
+  if (scores) NK_TRY(arena_alloc_t(ctx, (size_t)n_units * 4, &d_sc));
+  // a dense output: the caller's device memory as it is, or an arena block that one copy brings back
+  struct Out { double* host; double* dev; size_t doubles; };
+  Out outs[4] = {{out_x, nullptr, x_doubles}, {out_u, nullptr, u_doubles}, {out_ucum, nullptr, uc_doubles},
+                 {out_err, nullptr, (size_t)n_units * steps}};
+  for (Out& o : outs) {
+    if (!o.host) continue;
+    if (is_device_ptr(o.host)) { o.dev = o.host; o.host = nullptr; }
+    else NK_TRY(arena_alloc_t(ctx, o.doubles, &o.dev));
+  }
+  std::vector<LoopMultiUnit> recs((size_t)n_units);
+  for (int u = 0; u < n_units; ++u) {
+    const nk_model* mdl = units[u].model;
+    const LoopUnitOffsets& o = off[u];
+    LoopMultiUnit& r = recs[u];
+    r = LoopMultiUnit{};
+    r.G = mdl->A; r.ldg = mdl->m + mdl->p; r.C = mdl->C;
+    r.K = d_in + o.K; r.phi0 = d_in + o.phi0; r.phi_ref = d_in + o.phi_ref;
+    r.target = units[u].target ? d_in + o.target : nullptr;
+    r.u_init = d_in + o.u_init;
+    r.Phi = d_ws + o.Phi; r.usq = d_ws + o.usq; r.sse = d_ws + o.sse;
+    r.out_x = outs[0].dev ? outs[0].dev + x_off[u] : nullptr; r.ldx = mdl->d;
+    r.out_u = outs[1].dev ? outs[1].dev + u_off[u] : nullptr; r.ldu = mdl->p;
+    r.out_ucum = outs[2].dev ? outs[2].dev + uc_off[u] : nullptr; r.ldc = mdl->p;
+    r.out_err = outs[3].dev ? outs[3].dev + (size_t)u * steps : nullptr;
+    r.score = scores ? d_sc + 4 * (size_t)u : nullptr;
+    r.m = mdl->m; r.p = mdl->p; r.d = mdl->d;
+  }
+  NK_TRY(launch_closed_loop_multi(ctx, recs.data(), n_units, steps, c));
+  for (const Out& o : outs)
+    if (o.host) NK_HIP(hipMemcpyAsync(o.host, o.dev, o.doubles * 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (scores) NK_HIP(hipMemcpyAsync(scores, d_sc, (size_t)n_units * 32, hipMemcpyDeviceToHost, ctx->stream));
+  NK_HIP(hipStreamSynchronize(ctx->stream));  // (the staging block and recs are read by the copies queued above)
+  return NK_OK;
+}
+
+}  // extern "C"

@@ -529,6 +529,7 @@ bool lifted_chain_mw_timed_out(nk_ctx* ctx, int* row, int* step, int* traj);  //
 // (nk_plant_loop.hip): w = the gain folded into the lift (m entries, p = 1), u_t = sum_j w_j (k(z_j, x_ref) - k(z_j, x_t)),
 // x_{t+1} = plant(x_t, u_t); out_x rows b * (steps + 1) + t (row 0 = x_0), out_u rows b * steps + t
 int plant_loop_max_m();
+void plant_step_host(int plant, double Ts, const double* x, double u, double* x_next);  // nk_plant_step; plant id checked
 int launch_plant_loop(nk_ctx* ctx, const nk_model* mdl, int plant, double Ts, const double* w, const double* x0,
                       int64_t x0_stride, const double* xref, int64_t xref_stride, int steps, int batch, double* out_x,
                       int64_t ldx, double* out_u, int64_t ldu);

@@ -20,6 +20,7 @@
 #include "nk_plant.h"
 
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 namespace nk {
@@ -216,26 +217,52 @@ __global__ void __launch_bounds__(LPT == 1 ? 64 : 64 * PLANT_LOOP_MAX_WAVES)
 
 bool plant_loop_ok(int m) { return m >= 1 && m <= PLANT_LOOP_MAX_M; }
 
-template <int PLANT, int KTYPE>
-static void plant_loop_launch(nk_ctx* ctx, const PlantLoopParams& P, int batch) {
-  if (P.m <= 64) {
-    hipLaunchKernelGGL((plant_loop_kernel<PLANT, KTYPE, 1>), dim3(batch), dim3(64), 0, ctx->stream, P);
+// The workgroup shape of a model of m landmarks: one wave with one landmark per lane up to 64, PLANT_LOOP_LPT per lane beyond.
+static void plant_loop_class(int m, int* lpt, int* waves) {
+  if (m <= 64) {
+    *lpt = 1;
+    *waves = 1;
   } else {
-    const int waves = (P.m + 64 * PLANT_LOOP_LPT - 1) / (64 * PLANT_LOOP_LPT);
-    hipLaunchKernelGGL((plant_loop_kernel<PLANT, KTYPE, PLANT_LOOP_LPT>), dim3(batch), dim3(64 * waves), 0, ctx->stream, P);
+    *lpt = PLANT_LOOP_LPT;
+    *waves = (m + 64 * PLANT_LOOP_LPT - 1) / (64 * PLANT_LOOP_LPT);
   }
 }
-template <int PLANT>
-static int plant_loop_ktype(nk_ctx* ctx, int ktype, const PlantLoopParams& P, int batch) {
+
+// ---- dispatch: a run-time id becomes a template argument, handed to f as a std::integral_constant
+template <class F>
+static auto with_plant(int plant, F&& f) {  // (the id has been checked: plant_dim(plant) > 0)
+  if (plant == NK_PLANT_DUFFING) return f(std::integral_constant<int, NK_PLANT_DUFFING>{});
+  if (plant == NK_PLANT_DOUBLE_INTEGRATOR) return f(std::integral_constant<int, NK_PLANT_DOUBLE_INTEGRATOR>{});
+  return f(std::integral_constant<int, NK_PLANT_HJB>{});
+}
+template <class F>
+static int with_kernel_family(const char* who, int ktype, F&& f) {
   switch (ktype) {
-    case NK_KERNEL_RBF: plant_loop_launch<PLANT, NK_KERNEL_RBF>(ctx, P, batch); break;
-    case NK_KERNEL_MATERN52: plant_loop_launch<PLANT, NK_KERNEL_MATERN52>(ctx, P, batch); break;
-    case NK_KERNEL_LINEAR: plant_loop_launch<PLANT, NK_KERNEL_LINEAR>(ctx, P, batch); break;
-    case NK_KERNEL_TPS: plant_loop_launch<PLANT, NK_KERNEL_TPS>(ctx, P, batch); break;
-    default: set_error("plant_loop: unknown kernel type %d", ktype); return NK_ERR_BAD_ARG;
+    case NK_KERNEL_RBF: f(std::integral_constant<int, NK_KERNEL_RBF>{}); break;
+    case NK_KERNEL_MATERN52: f(std::integral_constant<int, NK_KERNEL_MATERN52>{}); break;
+    case NK_KERNEL_LINEAR: f(std::integral_constant<int, NK_KERNEL_LINEAR>{}); break;
+    case NK_KERNEL_TPS: f(std::integral_constant<int, NK_KERNEL_TPS>{}); break;
+    default: set_error("%s: unknown kernel type %d", who, ktype); return NK_ERR_BAD_ARG;
   }
   NK_HIP(hipGetLastError());
   return NK_OK;
+}
+// launch(plant, kernel family, landmarks per lane) for a launch whose workgroups have `lpt` landmarks per lane
+template <class F>
+static int plant_loop_dispatch(const char* who, int plant, int ktype, int lpt, F&& launch) {
+  return with_plant(plant, [&](auto pl) {
+    return with_kernel_family(who, ktype, [&](auto kt) {
+      if (lpt == 1) launch(pl, kt, std::integral_constant<int, 1>{});
+      else launch(pl, kt, std::integral_constant<int, PLANT_LOOP_LPT>{});
+    });
+  });
+}
+
+// nk_plant_step: one step of the plant in the host build of nk_plant.h (x_next may be x)
+void plant_step_host(int plant, double Ts, const double* x, double u, double* x_next) {
+  double xn[PLANT_MAX_D];
+  with_plant(plant, [&](auto pl) { plant_step<decltype(pl)::value>(Ts, x, u, xn); });
+  for (int k = 0; k < plant_dim(plant); ++k) x_next[k] = xn[k];
 }
 
 // all pointers device memory; w: the folded gain (m entries); out_x: batch * (steps + 1) rows of d, out_u: batch * steps
@@ -248,46 +275,16 @@ int launch_plant_loop(nk_ctx* ctx, const nk_model* mdl, int plant, double Ts, co
   P.Z = mdl->Z; P.winv = mdl->winv; P.w = w; P.m = mdl->m; P.sigma0sq = mdl->sigma0 * mdl->sigma0; P.Ts = Ts;
   P.x0 = x0; P.x0_stride = x0_stride; P.xref = xref; P.xref_stride = xref_stride;
   P.out_x = out_x; P.ldx = ldx; P.out_u = out_u; P.ldu = ldu; P.steps = steps;
-  if (plant == NK_PLANT_DUFFING) return plant_loop_ktype<NK_PLANT_DUFFING>(ctx, mdl->ktype, P, batch);
-  if (plant == NK_PLANT_DOUBLE_INTEGRATOR) return plant_loop_ktype<NK_PLANT_DOUBLE_INTEGRATOR>(ctx, mdl->ktype, P, batch);
-  return plant_loop_ktype<NK_PLANT_HJB>(ctx, mdl->ktype, P, batch);
+  int lpt = 0, waves = 0;
+  plant_loop_class(mdl->m, &lpt, &waves);
+  return plant_loop_dispatch("plant_loop", plant, mdl->ktype, lpt, [&](auto pl, auto kt, auto lp) {
+    hipLaunchKernelGGL((plant_loop_kernel<decltype(pl)::value, decltype(kt)::value, decltype(lp)::value>), dim3(batch),
+                       dim3(64 * waves), 0, ctx->stream, P);
+  });
 }
 int plant_loop_max_m() { return PLANT_LOOP_MAX_M; }
 
 // ---- multi-model form ------------------------------------------------------------------------------------------------
-static void plant_loop_class(int m, int* lpt, int* waves) {  // the workgroup shape nk_plant_loop gives a model of m landmarks
-  if (m <= 64) {
-    *lpt = 1;
-    *waves = 1;
-  } else {
-    *lpt = PLANT_LOOP_LPT;
-    *waves = (m + 64 * PLANT_LOOP_LPT - 1) / (64 * PLANT_LOOP_LPT);
-  }
-}
-
-template <int PLANT, int KTYPE>
-static void plant_loop_multi_launch(nk_ctx* ctx, const PlantLoopUnit* table, int count, int lpt, int waves, double Ts,
-                                    int steps) {
-  if (lpt == 1)
-    hipLaunchKernelGGL((plant_loop_multi_kernel<PLANT, KTYPE, 1>), dim3(count), dim3(64), 0, ctx->stream, table, Ts, steps);
-  else
-    hipLaunchKernelGGL((plant_loop_multi_kernel<PLANT, KTYPE, PLANT_LOOP_LPT>), dim3(count), dim3(64 * waves), 0,
-                       ctx->stream, table, Ts, steps);
-}
-template <int PLANT>
-static int plant_loop_multi_ktype(nk_ctx* ctx, int ktype, const PlantLoopUnit* table, int count, int lpt, int waves,
-                                  double Ts, int steps) {
-  switch (ktype) {
-    case NK_KERNEL_RBF: plant_loop_multi_launch<PLANT, NK_KERNEL_RBF>(ctx, table, count, lpt, waves, Ts, steps); break;
-    case NK_KERNEL_MATERN52: plant_loop_multi_launch<PLANT, NK_KERNEL_MATERN52>(ctx, table, count, lpt, waves, Ts, steps); break;
-    case NK_KERNEL_LINEAR: plant_loop_multi_launch<PLANT, NK_KERNEL_LINEAR>(ctx, table, count, lpt, waves, Ts, steps); break;
-    case NK_KERNEL_TPS: plant_loop_multi_launch<PLANT, NK_KERNEL_TPS>(ctx, table, count, lpt, waves, Ts, steps); break;
-    default: set_error("plant_loop_multi: unknown kernel type %d", ktype); return NK_ERR_BAD_ARG;
-  }
-  NK_HIP(hipGetLastError());
-  return NK_OK;
-}
-
 // units: host records holding device pointers, ktypes: the kernel family of each.  The records are sorted into classes of
 // (kernel family, landmarks per lane, waves) -- stable, so the order inside a class is the caller's --, staged with ONE
 // copy and run with one launch per class.  `units` is reordered in place and must stay alive until the stream has been
@@ -321,12 +318,11 @@ int launch_plant_loop_multi(nk_ctx* ctx, int plant, double Ts, int steps, PlantL
     int e = b + 1;
     while (e < n_units && !less(keys[b], keys[e])) ++e;
     const Key& k = keys[b];
-    if (plant == NK_PLANT_DUFFING)
-      NK_TRY(plant_loop_multi_ktype<NK_PLANT_DUFFING>(ctx, k.ktype, table + b, e - b, k.lpt, k.waves, Ts, steps));
-    else if (plant == NK_PLANT_DOUBLE_INTEGRATOR)
-      NK_TRY(plant_loop_multi_ktype<NK_PLANT_DOUBLE_INTEGRATOR>(ctx, k.ktype, table + b, e - b, k.lpt, k.waves, Ts, steps));
-    else
-      NK_TRY(plant_loop_multi_ktype<NK_PLANT_HJB>(ctx, k.ktype, table + b, e - b, k.lpt, k.waves, Ts, steps));
+    const PlantLoopUnit* first = table + b;
+    NK_TRY(plant_loop_dispatch("plant_loop_multi", plant, k.ktype, k.lpt, [&](auto pl, auto kt, auto lp) {
+      hipLaunchKernelGGL((plant_loop_multi_kernel<decltype(pl)::value, decltype(kt)::value, decltype(lp)::value>), dim3(e - b),
+                         dim3(64 * k.waves), 0, ctx->stream, first, Ts, steps);
+    }));
     b = e;
   }
   return NK_OK;

@@ -22,17 +22,20 @@ struct CvData {  // what a unit sees: the data set in HBM, a host copy of Y (onl
   int64_t ldxd = 0, ldyd = 0, ldyh = 0, n = 0;
   int32_t d = 0, p = 0;
 };
-// fit_score(member, unit, data, scratch, &score): fit + score of one unit on a member that is inside its unit of work;
-// set_phase(member, k, phase) for member k of `members`: 1 = stop at a system that needs the rank-truncating branch (NK_ERR_NOT_SPD: the unit is run again
-// in phase 2), 2 = take the branch, 0 = back to what the caller had set.
+// fit_score(member, unit, data, scratch, &score): fit + score of one unit on a member that is inside its unit of work.
+// Phases: 1 = stop at a system that needs the rank-truncating branch (NK_ERR_NOT_SPD: the unit is run again in phase 2),
+// 2 = take the branch, 0 = back to what the caller had set.  strict_phases: the members' strict mode follows the phases
+// (1 = strict: the factorisation reports a rank-deficient system and the unit stops there, 2 = the fallback);
+// set_phase(member, phase), may be empty: what else the estimator switches.
 // A unit may produce several numbers (the trajectories of a system-identification unit): fit_score writes up to `max_vals`
 // of them and store(unit, rc, vals) files them -- or NaN when rc != NK_OK -- with the unit's status.
 using CvFitScore = std::function<int(nk_ctx*, int, const CvData&, std::vector<double>&, double*)>;
-using CvSetPhase = std::function<void(nk_ctx*, int, int)>;
+using CvSetPhase = std::function<void(nk_ctx*, int)>;
 using CvStore = std::function<void(int, int, const double*)>;
 static int cv_grid_run(const char* what, nk_ctx* const* members, int32_t n_members, const double* X, int64_t ldx,
                        const double* Y, int64_t ldy, int64_t n, int32_t d, int32_t p, int32_t n_units, bool want_host_y,
-                       const CvFitScore& fit_score, const CvSetPhase& set_phase, const CvStore& store, int max_vals) {
+                       const CvFitScore& fit_score, bool strict_phases, const CvSetPhase& set_phase, const CvStore& store,
+                       int max_vals) {
   if (n_units == 0) return NK_OK;
   nk_ctx* lead = members[0];
   NK_HIP(hipSetDevice(lead->device));
@@ -134,23 +137,52 @@ static int cv_grid_run(const char* what, nk_ctx* const* members, int32_t n_membe
     run_units(all, false);
     return NK_OK;
   }
+  std::vector<int> saved_strict((size_t)B);
+  for (int k = 0; k < B; ++k) saved_strict[(size_t)k] = members[k]->strict_spd;
+  auto enter_phase = [&](int phase) {
+    for (int k = 0; k < B; ++k) {
+      if (strict_phases) members[k]->strict_spd = phase == 1 ? 1 : (phase == 2 ? 0 : saved_strict[(size_t)k]);
+      if (set_phase) set_phase(members[k], phase);
+    }
+  };
   const bool cv_trace = getenv("NYSKOOP_CV_TRACE") != nullptr;
   const auto t_start = std::chrono::steady_clock::now();
-  for (int k = 0; k < B; ++k) set_phase(members[k], k, 1);
+  enter_phase(1);
   run_units(all, true);
-  for (int k = 0; k < B; ++k) set_phase(members[k], k, 0);
+  enter_phase(0);
   const auto t_mid = std::chrono::steady_clock::now();
   if (!deferred.empty()) {
     std::sort(deferred.begin(), deferred.end());
-    for (int k = 0; k < B; ++k) set_phase(members[k], k, 2);
+    enter_phase(2);
     run_units(deferred, false);
-    for (int k = 0; k < B; ++k) set_phase(members[k], k, 0);
+    enter_phase(0);
   }
   if (cv_trace)
     fprintf(stderr, "[nyskoop] %s: %d units in %.3f s, %zu rank-deficient units again in %.3f s (%d members)\n", what, n_units,
             std::chrono::duration<double>(t_mid - t_start).count(), deferred.size(),
             std::chrono::duration<double>(std::chrono::steady_clock::now() - t_mid).count(), B);
   return NK_OK;
+}
+
+// ---- what the sweeps' entry points share
+// a unit's test fold [begin, end) inside the n rows
+static int check_test_fold(const char* who, int u, int64_t begin, int64_t end, int64_t n) {
+  NK_REQUIRE(0 <= begin && begin < end && end <= n, "%s: unit %d: bad test fold", who, u);
+  return NK_OK;
+}
+// a unit's landmarks: rows of the host copy of Y, gathered densely (m x d)
+static void gather_landmarks(const CvData& dt, const int64_t* rows, int m, int d, std::vector<double>& Z) {
+  Z.resize((size_t)m * d);
+  for (int j = 0; j < m; ++j) memcpy(&Z[(size_t)j * d], dt.Yh + rows[j] * dt.ldyh, (size_t)d * 8);
+}
+// phase 1 stops a spline unit where nk_spline_fit would enter the pseudo-inverse, the other phases let it go on
+static void spline_defer_phase(nk_ctx* ctx, int phase) { ctx->spline_defer_svd = phase == 1; }
+// one score per unit, NaN for a unit that failed, with the unit's status
+static CvStore scalar_store(double* scores, int32_t* status) {
+  return [=](int u, int rc, const double* v) {
+    scores[u] = rc == NK_OK ? v[0] : std::nan("");
+    if (status) status[u] = rc;
+  };
 }
 
 extern "C" {
@@ -163,14 +195,13 @@ int nk_cv_grid(nk_ctx* const* members, int32_t n_members, const double* X, int64
   for (int u = 0; u < n_units; ++u) {
     const nk_cv_unit& cu = units[u];
     NK_REQUIRE(cu.kernel && cu.landmark_rows && cu.m > 0, "nk_cv_grid: unit %d: null kernel / landmarks", u);
-    NK_REQUIRE(0 <= cu.test_begin && cu.test_begin < cu.test_end && cu.test_end <= n, "nk_cv_grid: unit %d: bad test fold", u);
+    NK_TRY(check_test_fold("nk_cv_grid", u, cu.test_begin, cu.test_end, n));
     for (int j = 0; j < cu.m; ++j)
       NK_REQUIRE(cu.landmark_rows[j] >= 0 && cu.landmark_rows[j] < n, "nk_cv_grid: unit %d: landmark row out of range", u);
   }
   auto fit_score = [&](nk_ctx* ctx, int u, const CvData& dt, std::vector<double>& Z, double* sc) -> int {
     const nk_cv_unit& cu = units[u];
-    Z.resize((size_t)cu.m * d);
-    for (int j = 0; j < cu.m; ++j) memcpy(&Z[(size_t)j * d], dt.Yh + cu.landmark_rows[j] * dt.ldyh, (size_t)d * 8);
+    gather_landmarks(dt, cu.landmark_rows, cu.m, d, Z);
     const int64_t rr[4] = {0, cu.test_begin, cu.test_end, n};
     nk_model* mdl = nullptr;
     int rc = nk_nystrom_fit(ctx, cu.kernel, dt.Xd, dt.ldxd, dt.Yd, dt.ldyd, n, d, p, rr, 2, nullptr, 0, Z.data(), d, cu.m,
@@ -181,17 +212,8 @@ int nk_cv_grid(nk_ctx* const* members, int32_t n_members, const double* X, int64
     if (mdl) nk_model_destroy(mdl);
     return rc;
   };
-  // phase 1 = strict mode (the factorisation reports a rank-deficient system and the unit stops there), phase 2 = the fallback
-  std::vector<int> saved_strict((size_t)n_members);
-  for (int k = 0; k < n_members; ++k) saved_strict[(size_t)k] = members[k]->strict_spd;
-  auto set_phase = [&](nk_ctx* ctx, int k, int phase) {
-    ctx->strict_spd = phase == 1 ? 1 : (phase == 2 ? 0 : saved_strict[(size_t)k]);
-  };
-  auto store = [&](int u, int rc, const double* v) {
-    scores[u] = rc == NK_OK ? v[0] : std::nan("");
-    if (status) status[u] = rc;
-  };
-  return cv_grid_run("cv_grid", members, n_members, X, ldx, Y, ldy, n, d, p, n_units, true, fit_score, set_phase, store, 1);
+  return cv_grid_run("cv_grid", members, n_members, X, ldx, Y, ldy, n, d, p, n_units, true, fit_score, true, nullptr,
+                     scalar_store(scores, status), 1);
 }
 
 // The spline sweep (regressors.py:181-221 under GridSearchCV, benchmark_lqr_classic.py:55-60): same rounds, same two phases.
@@ -207,8 +229,7 @@ int nk_spline_cv_grid(nk_ctx* const* members, int32_t n_members, const double* X
     const nk_spline_cv_unit& cu = units[u];
     NK_REQUIRE(cu.centers && cu.m > 0, "nk_spline_cv_grid: unit %d: null centres / m <= 0", u);
     NK_REQUIRE(!is_device_ptr(cu.centers), "nk_spline_cv_grid: unit %d: centres must be a host pointer", u);
-    NK_REQUIRE(0 <= cu.test_begin && cu.test_begin < cu.test_end && cu.test_end <= n,
-               "nk_spline_cv_grid: unit %d: bad test fold", u);
+    NK_TRY(check_test_fold("nk_spline_cv_grid", u, cu.test_begin, cu.test_end, n));
   }
   auto fit_score = [&](nk_ctx* ctx, int u, const CvData& dt, std::vector<double>&, double* sc) -> int {
     const nk_spline_cv_unit& cu = units[u];
@@ -221,13 +242,8 @@ int nk_spline_cv_grid(nk_ctx* const* members, int32_t n_members, const double* X
     if (mdl) nk_model_destroy(mdl);
     return rc;
   };
-  auto set_phase = [&](nk_ctx* ctx, int, int phase) { ctx->spline_defer_svd = phase == 1; };
-  auto store = [&](int u, int rc, const double* v) {
-    scores[u] = rc == NK_OK ? v[0] : std::nan("");
-    if (status) status[u] = rc;
-  };
-  return cv_grid_run("spline_cv_grid", members, n_members, X, ldx, Y, ldy, n, d, p, n_units, false, fit_score, set_phase,
-                     store, 1);
+  return cv_grid_run("spline_cv_grid", members, n_members, X, ldx, Y, ldy, n, d, p, n_units, false, fit_score, false,
+                     spline_defer_phase, scalar_store(scores, status), 1);
 }
 
 // The multi-seed system-identification sweep (benchmark_lqr_classic.py:211-255, benchmark_lqr_cloth.py:163-211) as one call:
@@ -292,8 +308,7 @@ int nk_sysid_grid(nk_ctx* const* members, int32_t n_members, const double* X, in
     nk_model* mdl = nullptr;
     int rc;
     if (su.kernel) {
-      Z.resize((size_t)su.m * d);
-      for (int j = 0; j < su.m; ++j) memcpy(&Z[(size_t)j * d], dt.Yh + su.landmark_rows[j] * dt.ldyh, (size_t)d * 8);
+      gather_landmarks(dt, su.landmark_rows, su.m, d, Z);
       rc = nk_nystrom_fit(ctx, su.kernel, dt.Xd, dt.ldxd, dt.Yd, dt.ldyd, n, d, p, su.row_ranges, su.n_ranges, nullptr, 0,
                           Z.data(), d, su.m, su.gamma, su.jitter, &mdl, nullptr);
     } else {
@@ -322,12 +337,6 @@ int nk_sysid_grid(nk_ctx* const* members, int32_t n_members, const double* X, in
     return rc;
   };
   // phase 1: both estimators stop where they would enter the rank-truncating branch, phase 2: they take it
-  std::vector<int> saved_strict((size_t)n_members);
-  for (int k = 0; k < n_members; ++k) saved_strict[(size_t)k] = members[k]->strict_spd;
-  auto set_phase = [&](nk_ctx* ctx, int k, int phase) {
-    ctx->strict_spd = phase == 1 ? 1 : (phase == 2 ? 0 : saved_strict[(size_t)k]);
-    ctx->spline_defer_svd = phase == 1;
-  };
   auto store = [&](int u, int rc, const double* v) {
     const nk_sysid_unit& su = units[u];
     for (int i = 0; i < su.n_traj; ++i) {
@@ -336,8 +345,8 @@ int nk_sysid_grid(nk_ctx* const* members, int32_t n_members, const double* X, in
     }
     if (status) status[u] = rc;
   };
-  return cv_grid_run("sysid_grid", members, n_members, X, ldx, Y, ldy, n, d, p, n_units, any_nystrom, fit_score, set_phase,
-                     store, 2 * max_traj);
+  return cv_grid_run("sysid_grid", members, n_members, X, ldx, Y, ldy, n, d, p, n_units, any_nystrom, fit_score, true,
+                     spline_defer_phase, store, 2 * max_traj);
 }
 
 }  // extern "C"

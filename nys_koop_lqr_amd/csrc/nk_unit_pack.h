@@ -1,0 +1,92 @@
+// Staging layout of the unit-table calls (nk_plant_loop_multi, nk_closed_loop_multi; nk_api_loops.hip): host only, no HIP
+// include, so that a plain C++17 compiler builds it (tests/unit_pack_main.cpp).
+//
+// A call lays the operands of all its units out in ONE block of doubles that a single host-to-device copy moves; the
+// device records then point into the copy.  Every piece starts on a slot boundary (32 doubles = 256 bytes) and what a
+// piece reserves beyond the doubles copied into it is +0.0.  A region that only the device writes (a workspace, the
+// folded gains) is laid out with the same offsets and never asks for the block: no host bytes exist for it.
+#pragma once
+#include <cassert>
+#include <cstddef>
+#include <cstring>
+#include <vector>
+
+namespace nk {
+
+// the slot rule: sizes round up to 32 doubles
+inline size_t unit_slot(size_t doubles) { return (doubles + 31) & ~(size_t)31; }
+
+// Reserved length of a gain row of m entries (p = 1): the even leading dimension that stage_in gives the 1 x m gain of
+// nk_plant_loop, so that the fold of a unit sees the operands of the single call.
+inline size_t gain_row_reserve(size_t m) { return m + (m & 1); }
+
+class UnitPack {
+ public:
+  // slot(doubles) zero doubles at the end of the layout; the offset of the first
+  size_t reserve(size_t doubles) {
+    const size_t at = total_;
+    total_ += unit_slot(doubles);
+    return at;
+  }
+  // `count` doubles from `src` go to offset `at` of a reserved piece (a null source leaves the zeros); `src` is read by
+  // block() and must stay alive until then
+  void copy(size_t at, const double* src, size_t count) {
+    assert(at + count <= total_);
+    if (src && count) pieces_.push_back(Piece{src, at, count});
+  }
+  size_t append(const double* src, size_t count, size_t reserve_doubles) {
+    assert(count <= reserve_doubles);
+    const size_t at = reserve(reserve_doubles);
+    copy(at, src, count);
+    return at;
+  }
+  size_t append(const double* src, size_t count) { return append(src, count, count); }
+  size_t doubles() const { return total_; }
+  // the finished block for the one copy: doubles() doubles, valid while the pack lives and nothing is added
+  const double* block() {
+    block_.assign(total_, 0.0);
+    for (const Piece& p : pieces_) memcpy(block_.data() + p.at, p.src, p.count * sizeof(double));
+    return block_.data();
+  }
+
+ private:
+  struct Piece { const double* src; size_t at, count; };
+  size_t total_ = 0;
+  std::vector<Piece> pieces_;
+  std::vector<double> block_;
+};
+
+// ---- the two layouts ---------------------------------------------------------------------------------------------------
+// A plant unit (nk_plant_loop_multi).  `in`: K (reserved as a gain row) | x0, x_ref together in one piece of 2 d.
+// `folds` (device only): the folded gain of a unit that has one, m + 2 doubles.
+struct PlantUnitOffsets { size_t K = 0, x0 = 0, x_ref = 0, w = 0; };
+inline PlantUnitOffsets pack_plant_unit(UnitPack& in, UnitPack& folds, const double* K, const double* x0, const double* x_ref,
+                                        size_t m, size_t d, bool fold) {
+  PlantUnitOffsets o;
+  o.K = in.append(K, m, gain_row_reserve(m));
+  o.x0 = in.reserve(2 * d);
+  o.x_ref = o.x0 + d;
+  in.copy(o.x0, x0, d);
+  in.copy(o.x_ref, x_ref, d);
+  if (fold) o.w = folds.reserve(m + 2);
+  return o;
+}
+
+// A loop unit (nk_closed_loop_multi).  `in`: K (p x m) | phi0 | phi_ref | target (d, may be null) | u_init (p, may be null).
+// `ws` (device only): phi_t of every step | sum u^2 per step | sum (x - target)^2 per step.
+struct LoopUnitOffsets { size_t K = 0, phi0 = 0, phi_ref = 0, target = 0, u_init = 0, Phi = 0, usq = 0, sse = 0; };
+inline LoopUnitOffsets pack_loop_unit(UnitPack& in, UnitPack& ws, const double* K, const double* phi0, const double* phi_ref,
+                                      const double* target, const double* u_init, size_t m, size_t p, size_t d, size_t steps) {
+  LoopUnitOffsets o;
+  o.K = in.append(K, p * m);
+  o.phi0 = in.append(phi0, m);
+  o.phi_ref = in.append(phi_ref, m);
+  o.target = in.append(target, d);
+  o.u_init = in.append(u_init, p);
+  o.Phi = ws.reserve(steps * m);
+  o.usq = ws.reserve(steps);
+  o.sse = ws.reserve(steps);
+  return o;
+}
+
+}  // namespace nk

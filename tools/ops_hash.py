@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """SHA-256 of the operators of a few fits, of square roots and SPD solves through the C-ABI, and of one lock-step round of
-small fits (library given by NYSKOOP_LIB): two builds that compute the same bits print the same lines."""
+small fits, and of the unit-table calls (plant loops, lifted loops, Riccati gains) on models rebuilt from host copies
+(library given by NYSKOOP_LIB): two builds that compute the same bits print the same lines."""
 import ctypes as C, hashlib, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -90,3 +91,56 @@ delta = {k: after[k] - before[k] for k in after}
 print("lockstep grouping:", delta, "member launches", delta["member_launches_merged"] + delta["single_launches"],
       file=sys.stderr, flush=True)
 pool.close()
+
+
+# ---- models rebuilt from host copies (nk_model_create, nk_spline_model_create) and the unit-table calls on them
+def rebuilt(kind, m, p, d, seed, scale=1.0):
+    """Random stable operators on random landmarks: A = 0.9 x orthogonal, B and C of order one."""
+    r = np.random.default_rng(seed)
+    if kind == "spline":
+        reg = nk.KoopmanSplineRegressor(p, m=m, gamma=1e-6)
+        reg.centers = scale * r.standard_normal((d, m))
+    else:
+        reg = nk.KoopmanNystromRegressor(p, kernel=nk.KernelWrapper(np.ones(d)), gamma=1e-6, m=m)
+        reg.nystrom_centers_output = scale * r.standard_normal((d, m))
+    Q, _ = np.linalg.qr(r.standard_normal((m, m)))
+    reg.A, reg.B, reg.C = 0.9 * Q, 0.3 * r.standard_normal((m, p)) / np.sqrt(m), r.standard_normal((d, m))
+    return reg, r
+
+
+for kind in ("nystrom", "spline"):
+    reg, r = rebuilt(kind, 50, 2, 3, 11)
+    print("rebuilt", kind, "lift of 5 points", h(reg.lift(r.standard_normal((3, 5)))), flush=True)
+
+plant = nk.DuffingOscillator(Ts=0.01)
+units = [rebuilt("nystrom", 40, 1, 2, 21), rebuilt("spline", 64, 1, 2, 22), rebuilt("nystrom", 300, 1, 2, 23)]
+gains = [0.1 * r.standard_normal(reg._landmark_shape()[1]) for reg, r in units]
+x0s = np.array([[0.5, -0.2], [0.1, 0.3], [-0.4, 0.2]])
+sc, ox, ou = ctx.plant_loop_multi(plant.plant_id, plant.Ts, 20, [reg._ensure_model() for reg, _ in units], gains, x0s,
+                                  np.zeros((3, 2)), u_opt=np.linspace(-1.0, 1.0, 20), want_x=True, want_u=True)
+print("plant_loop_multi m = 40, 64, 300, 20 steps: states", h(ox), "controls", h(ou), "scores", h(sc),
+      "finite", bool(np.all(np.isfinite(ox))), flush=True)
+
+for steps in (16, 17):
+    units = [rebuilt("nystrom", 20, 1, 2, 31), rebuilt("nystrom", 100, 6, 192, 32), rebuilt("spline", 128, 8, 5, 33)]
+    dims = [(20, 1, 2), (100, 6, 192), (128, 8, 5)]
+    K = [0.2 * r.standard_normal((p, m)) / np.sqrt(m) for (reg, r), (m, p, d) in zip(units, dims)]
+    vec = lambda k: [r.standard_normal(dm[k]) for (reg, r), dm in zip(units, dims)]
+    phi0, phi_ref, target, u_init = vec(0), vec(0), vec(2), vec(1)
+    sc, err, ox, ou, oc = ctx.closed_loop_multi(steps, 0.0075, [reg._ensure_model() for reg, _ in units], dims, K, phi0, phi_ref,
+                                                target, u_init, want_x=True, want_u=True, want_ucum=True)
+    print("closed_loop_multi", steps, "steps: x", h(*ox), "u", h(*ou), "ucum", h(*oc), "err", h(err), "scores", h(sc),
+          "finite", bool(np.all(np.isfinite(sc))), flush=True)
+
+As, Bs, Qs, Rs = [], [], [], []
+for m, p in ((3, 1), (64, 2), (100, 6)):
+    r = np.random.default_rng(40 + m)
+    Q, _ = np.linalg.qr(r.standard_normal((m, m)))
+    Cm = r.standard_normal((p + 1, m))
+    As.append(0.95 * Q); Bs.append(r.standard_normal((m, p)) / np.sqrt(m)); Qs.append(Cm.T @ Cm); Rs.append(np.eye(p))
+Ks, Ps, status, iters, deltas = ctx.dare_batch(As, Bs, Qs, Rs)
+print("dare_batch m = 3, 64, 100: status", list(status), "iters", list(iters), "K", h(*Ks), "P", h(*Ps), "delta", h(deltas),
+      flush=True)
+regs = [rebuilt("nystrom", 40, 2, 3, 51)[0], rebuilt("spline", 64, 2, 4, 52)[0]]
+Ks, status, iters = ctx.model_lqr_gain_batch([reg._ensure_model() for reg in regs], 0.5)
+print("model_lqr_gain_batch m = 40, 64: status", list(status), "iters", list(iters), "K", h(*Ks), flush=True)
