@@ -8,6 +8,7 @@
 
 #include "nyskoop.h"
 #include "nk_lockstep.h"
+#include "nk_gemm_plan.h"
 
 namespace nk {
 
@@ -316,14 +317,49 @@ inline int arena_alloc_t(nk_ctx* ctx, size_t count, T** out) {
 }
 bool is_device_ptr(const void* p);
 
+// ---- dynamic-LDS opt-in of a list of kernels.  Use as a function-local static, whose initialisation runs once and is
+// safe when several threads make their first launch together:
+//   static const hipError_t e = dynamic_lds_register(BYTES, kernel_a, kernel_b<1>, ...);  NK_TRY(dynamic_lds_status(e));
+template <typename... Fn>
+inline hipError_t dynamic_lds_register(int bytes, Fn*... kernels) {
+  hipError_t e = hipSuccess;
+  for (const void* f : {reinterpret_cast<const void*>(kernels)...})
+    if (e == hipSuccess) e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  return e;
+}
+inline int dynamic_lds_status(hipError_t e) {  // a failed registration fails every launch that needs it
+  if (e == hipSuccess) return NK_OK;
+  set_error("hipFuncSetAttribute(hipFuncAttributeMaxDynamicSharedMemorySize) failed: %s", hipGetErrorString(e));
+  return NK_ERR_HIP;
+}
+
+// ---- timing bracket of the GEMM engines: begin() and end() record EV_GEMM_T0 / EV_GEMM_T1 around the timed launch when the
+// caller gave ms; read(sync) waits for the launch and stores the elapsed time (sync = false: the caller reads the two
+// events after its own synchronisation)
+struct GemmTimer {
+  nk_ctx* ctx;
+  float* ms;
+  int mark(int slot) const {
+    if (ms) NK_HIP(hipEventRecord(ctx->ev[slot], ctx->stream));
+    return NK_OK;
+  }
+  int begin() const { return mark(EV_GEMM_T0); }
+  int end() const { return mark(EV_GEMM_T1); }
+  int read(bool sync) const {
+    if (!ms || !sync) return NK_OK;
+    NK_HIP(hipEventSynchronize(ctx->ev[EV_GEMM_T1]));
+    NK_HIP(hipEventElapsedTime(ms, ctx->ev[EV_GEMM_T0], ctx->ev[EV_GEMM_T1]));
+    return NK_OK;
+  }
+};
+
 // ---- device launchers (all asynchronous on ctx->stream; device pointers only) ---------------------------------
 // kernel matrix out[i][j] = k(A[i,:], B[j,:]); winv = 1/lengthscale (d entries, device)
 int launch_kmat(nk_ctx* ctx, int ktype, const double* A, int64_t lda, int64_t nA, const double* B, int64_t ldb,
                 int64_t nB, int d, const double* winv, double sigma0, double* out, int64_t ldo);
 
-enum { TRI_FULL = 0, TRI_UPPER_MIRROR = 1, TRI_LOWER = 2 };
 struct GemmOpts {
-  int tri = TRI_FULL;  // TRI_UPPER_MIRROR: compute tiles with tn >= tm and mirror; TRI_LOWER: tiles tn <= tm only
+  int tri = TRI_FULL;  // TRI_* (nk_gemm_plan.h)
   int splitk = 0;      // 0 = choose automatically
 };
 // C = alpha*op(A)*op(B) + beta*C ; transA: A stored KxM ; transB: B stored NxK
@@ -343,7 +379,7 @@ struct GemmCall {
 // up to two independent problems with the same transposition flags in one launch (no split-K)
 int launch_gemm_pair(nk_ctx* ctx, bool transA, bool transB, const GemmCall* calls, int ncalls);
 
-struct TnSkip;  // device-side launch control, defined with the TN engine below
+struct TnSkip;  // device-side launch control of the TN engine (nk_tn.h)
 // elementwise / reductions (nk_elementwise.hip)
 // workgroups of a grid-stride launch over `total` elements; it also fixes the number of per-block partials of the
 // reductions and with it their summation order
@@ -617,64 +653,6 @@ int select_landmarks_device(nk_ctx* ctx, int ktype, const double* Y, int64_t ldy
                             std::vector<int64_t>* positions, std::vector<double>* resid, std::vector<double>* trace,
                             int* m_selected);
 
-}  // namespace nk
-
-namespace nk {
-// ---- fast TN multi-problem GEMM (LDS-DMA staged), see nk_gemm_tn.hip -------------------------------------------
-// C_p[M_p x N_p] = alpha_p * A_p^T B_p + beta_p * C_p for up to 4 problems that share the contraction length K:
-// A_p stored K x M_p (lda), B_p stored K x N_p (ldb).  One launch covers every 128x128 tile of every problem.
-enum { KTRIM_NONE = 0, KTRIM_B_UPPER = 1 /* B (K x N) upper triangular */, KTRIM_A_LOWER = 2 /* A (K x M) lower triangular */ };
-struct TnProblem {
-  const double* A = nullptr;
-  const double* B = nullptr;
-  double* C = nullptr;
-  int64_t lda = 0, ldb = 0, ldc = 0;
-  int M = 0, N = 0;
-  int tri = TRI_FULL;  // TRI_UPPER_MIRROR for symmetric products (A == B)
-  int ktrim = 0;       // KTRIM_B_UPPER / KTRIM_A_LOWER: a triangular operand, the k range where it is zero is skipped
-  double alpha = 1.0, beta = 0.0;
-  double* Ct = nullptr;  // optional: also store the transpose, Ct[col][row] = C[row][col] (N x M, leading dim ldct)
-  int64_t ldct = 0;
-  const double* A_even = nullptr;  // operand selection (TnSkip::select): alternatives of A / B for an even step count
-  const double* B_even = nullptr;
-  double* Caff = nullptr;  // optional second output Caff = aff_a * C + aff_c * I (same leading dimension as C)
-  double aff_a = 0.0, aff_c = 0.0;
-};
-// Device-side control of a launch, so that an iteration with a data-dependent length can be queued in full without host
-// round trips.  state: the launch returns at once when state[0] != 0 && state[0] <= step (state[0] = number of steps after
-// which the iteration converged, written on the device).  select: the parity of select[0] picks A/B (odd) or
-// A_even/B_even (even) -- the buffer of a ping-pong iteration that holds the final iterate.
-struct TnSkip {
-  const double* state = nullptr;
-  int step = 0;
-  const double* select = nullptr;
-  // single symmetric product C: the reduce kernel also leaves per-workgroup partial sums of (C - I)^2 here (at least
-  // 8 * tiles entries); *resid_count receives how many
-  double* resid_partials = nullptr;
-  int* resid_count = nullptr;
-};
-bool tn_fast_ok(const TnProblem& p);  // alignment / leading-dimension requirements of the LDS-DMA path
-// fp32 engine (nk_gemm_tn_f32.hip): operands fp32 contraction-major, results fp64
-struct TnProblemF {
-  const float* A = nullptr;
-  const float* B = nullptr;
-  double* C = nullptr;
-  int64_t lda = 0, ldb = 0, ldc = 0;
-  int M = 0, N = 0;
-  int tri = TRI_FULL;
-  double beta = 0.0;
-};
-bool tnf_fast_ok(const TnProblemF& p);
-int launch_gemm_tn_f32_multi(nk_ctx* ctx, const TnProblemF* probs, int nprob, int64_t K, int splitk /*0=auto*/,
-                             float* ms_kernel = nullptr, bool sync_timing = true);
-int prep_rows_f32(nk_ctx* ctx, const double* X, int64_t ldx, int64_t rows, int d, const double* winv, const double* center,
-                  float* Xt, int64_t ldt, float* sq);
-int launch_cvt_f64_f32(nk_ctx* ctx, const double* src, int64_t lds_, float* dst, int64_t ldd, int64_t rows, int cols);
-int launch_kmat_gram_f32(nk_ctx* ctx, int ktype, const float* At, int64_t ldat, const float* sqa, int64_t nA, const float* Bt,
-                         int64_t ldbt, const float* sqb, int64_t nB, int d, double sigma0, float* out, int64_t ldo);
-int launch_gemm_tn_multi(nk_ctx* ctx, const TnProblem* probs, int nprob, int64_t K, int splitk /*0=auto*/,
-                         float* ms_kernel = nullptr, bool sync_timing = true, const TnSkip* skip = nullptr);
-int launch_transpose(nk_ctx* ctx, const double* src, int64_t lds, double* dst, int64_t ldd, int rows, int cols);
 // X += dX if the refinement still contracts (verdict on the device, in state[4]: alive, |dX|^2 last accepted, accepted
 // steps, |dX_0| / |X|); no host synchronisation
 constexpr int refine_partial_blocks() { return 512; }
@@ -683,14 +661,6 @@ int launch_refine_apply(nk_ctx* ctx, const double* dX, int64_t ldd, double* X, i
 // Res (nr x mq) = R - X P, dot products in doubled precision (compensated): the residual of the refinement steps
 int launch_resid_dd(nk_ctx* ctx, const double* X, int64_t ldx, const double* P, int64_t ldp, const double* R, int64_t ldr,
                     double* Res, int64_t ldres, int nr, int mq);
-// Gram-form kernel matrix on the MFMA engine (nk_gemm_tn.hip): prep_rows centres/scales/transposes rows to
-// contraction-major and returns their squared norms; launch_kmat_gram evaluates k() in the GEMM epilogue
-int launch_colmean(nk_ctx* ctx, const double* Z, int64_t ldz, int rows, int d, double* mean);
-int prep_rows(nk_ctx* ctx, const double* X, int64_t ldx, int64_t rows, int d, const double* winv, const double* center,
-              double* Xt, int64_t ldt, double* sq);
-int launch_kmat_gram(nk_ctx* ctx, int ktype, const double* At, int64_t ldat, const double* sqa, int64_t nA,
-                     const double* Bt, int64_t ldbt, const double* sqb, int64_t nB, int d, double sigma0, double* out,
-                     int64_t ldo);
 }  // namespace nk
 
 // ---- cross-lane helpers for fp64 on gfx950 (no LDS traffic): DPP moves inside a 16-lane row, v_permlane16_swap /

@@ -3,6 +3,7 @@
 // order), the column sums of the RMSE scorer, and the doubled-precision residual and contraction guard of the refinement
 // of the regularised solves.
 #include "nk_common.h"
+#include "nk_tn.h"
 
 #include <algorithm>
 

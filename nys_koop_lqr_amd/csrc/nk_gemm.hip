@@ -20,6 +20,7 @@
 // share the same operand panels through the XCD's L2.  Partial tiles go to a slab and a second kernel reduces
 // them in a fixed order (deterministic, no float atomics).
 #include "nk_common.h"
+#include "nk_tn.h"
 
 namespace nk {
 
@@ -279,104 +280,68 @@ __device__ __forceinline__ void gemm_reduce_kernel_body(const double* __restrict
 __global__ void __launch_bounds__(256) gemm_reduce_kernel(const double* __restrict__ slab, int splitk, int M, int N, double alpha, double beta, double* __restrict__ C, int64_t ldc, int tri) { gemm_reduce_kernel_body(slab, splitk, M, N, alpha, beta, C, ldc, tri); }
 NK_BATCHED_TWIN(gemm_reduce_kernel, (256), const double*, int, int, int, double, double, double*, int64_t, int)
 
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+static_assert(BM == TBM && BN == TBM, "the launch plan (nk_gemm_plan.h) counts 128 x 128 tiles");
 
 // Fill the device parameters of one problem (no split-K slab handling: splitk must resolve to 1 for batched use).
-static int gemm_prepare(nk_ctx* ctx, bool transA, bool transB, int64_t M, int64_t N, int64_t K, double alpha,
-                        const double* A, int64_t lda, const double* B, int64_t ldb, double beta, double* C, int64_t ldc,
-                        const GemmOpts& opts, GemmParams* out, int* ntiles_out) {
+static int gemm_prepare(nk_ctx* ctx, int64_t M, int64_t N, int64_t K, double alpha, const double* A, int64_t lda,
+                        const double* B, int64_t ldb, double beta, double* C, int64_t ldc, const GemmOpts& opts,
+                        GemmParams* out) {
   NK_REQUIRE(M < (1 << 30) && N < (1 << 30) && K < (1LL << 31) && K >= 0, "nk_gemm: dimension out of range");
-  GemmParams& p = *out;
+  if (opts.tri == TRI_UPPER_MIRROR) NK_REQUIRE(M == N, "nk_gemm: the mirrored mode needs a square C");
+  if (opts.tri == TRI_LOWER) NK_REQUIRE(M >= N, "nk_gemm: the lower mode needs M >= N");
+  GemmParams p{};
   p.A = A; p.B = B; p.C = C; p.slab = nullptr;
   p.lda = lda; p.ldb = ldb; p.ldc = ldc;
   p.M = (int)M; p.N = (int)N; p.K = (int)K;
-  p.tiles_m = (int)((M + BM - 1) / BM);
-  p.tiles_n = (int)((N + BN - 1) / BN);
+  p.tiles_m = plan_tiles(M);
+  p.tiles_n = plan_tiles(N);
   p.tri = opts.tri;
-  if (p.tri == TRI_UPPER_MIRROR) NK_REQUIRE(M == N, "nk_gemm: the mirrored mode needs a square C");
-  if (p.tri == TRI_LOWER) NK_REQUIRE(M >= N, "nk_gemm: the lower mode needs M >= N");
   p.alpha = alpha; p.beta = beta;
   p.vecA = aligned16(A) && (lda % 2 == 0);
   p.vecB = aligned16(B) && (ldb % 2 == 0);
-  int ntiles = p.tiles_m * p.tiles_n;
-  if (p.tri == TRI_UPPER_MIRROR) ntiles = p.tiles_m * (p.tiles_m + 1) / 2;
-  if (p.tri == TRI_LOWER) ntiles = p.tiles_n * (p.tiles_n + 1) / 2 + (p.tiles_m - p.tiles_n) * p.tiles_n;
-  const int ktiles_total = (int)((K + BK - 1) / BK);
-  int splitk = opts.splitk;
-  if (splitk <= 0) {
-    const int target = 4 * ctx->num_cu;  // two resident workgroups per CU, two rounds
-    splitk = ntiles >= target / 2 ? 1 : (target + ntiles - 1) / ntiles;
-    if (splitk >= 6) splitk = ((splitk + 7) / 8) * 8;  // align slices with the 8 XCDs
-    const int max_split = ktiles_total / 8 > 0 ? ktiles_total / 8 : 1;  // at least 8 k-steps per slice
-    if (splitk > max_split) splitk = max_split;
-    if (splitk > 64) splitk = 64;
-    if (splitk < 1) splitk = 1;
-  }
-  p.splitk = splitk;
-  p.klen = ((ktiles_total + splitk - 1) / splitk) * BK;
-  if (p.klen == 0) p.klen = BK;
-  p.nblocks = ntiles * splitk;
-  *ntiles_out = ntiles;
+  const int ntiles = plan_tile_count(p.tri, p.tiles_m, p.tiles_n);
+  const int ktiles_total = plan_ktiles(K, BK);
+  p.splitk = opts.splitk > 0 ? opts.splitk : plan_splitk_generic(ntiles, ktiles_total, ctx->num_cu);
+  p.klen = plan_slice_len(ktiles_total, p.splitk, BK);
+  p.nblocks = ntiles * p.splitk;
+  *out = p;
   return NK_OK;
 }
 
 static int gemm_set_attrs() {
-  static bool attr_set = false;
-  if (!attr_set) {
-    NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f64_kernel<false, false>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-    NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f64_kernel<false, true>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-    NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f64_kernel<true, false>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-    NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f64_kernel_batched<false, false>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-    NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f64_kernel_batched<false, true>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-    NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f64_kernel_batched<true, false>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-    NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f64_kernel_batched<true, true>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-    NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_f64_kernel<true, true>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-    attr_set = true;
-  }
-  return NK_OK;
+  static const hipError_t e = dynamic_lds_register(
+      LDS_BYTES, gemm_f64_kernel<false, false>, gemm_f64_kernel<false, true>, gemm_f64_kernel<true, false>,
+      gemm_f64_kernel<true, true>, gemm_f64_kernel_batched<false, false>, gemm_f64_kernel_batched<false, true>,
+      gemm_f64_kernel_batched<true, false>, gemm_f64_kernel_batched<true, true>);
+  return dynamic_lds_status(e);
 }
 
-static void gemm_dispatch(nk_ctx* ctx, bool transA, bool transB, dim3 grid, const GemmBatch& b) {
-  dim3 block(GEMM_THREADS);
-  if (transA && transB) hipLaunchKernelGGL((gemm_f64_kernel<true, true>), grid, block, LDS_BYTES, ctx->stream, b);
-  else if (transA) hipLaunchKernelGGL((gemm_f64_kernel<true, false>), grid, block, LDS_BYTES, ctx->stream, b);
-  else if (transB) hipLaunchKernelGGL((gemm_f64_kernel<false, true>), grid, block, LDS_BYTES, ctx->stream, b);
-  else hipLaunchKernelGGL((gemm_f64_kernel<false, false>), grid, block, LDS_BYTES, ctx->stream, b);
+static int gemm_dispatch(nk_ctx* ctx, bool transA, bool transB, dim3 grid, const GemmBatch& b) {
+  void (*const kernels[2][2])(GemmBatch) = {{gemm_f64_kernel<false, false>, gemm_f64_kernel<false, true>},
+                                            {gemm_f64_kernel<true, false>, gemm_f64_kernel<true, true>}};
+  hipLaunchKernelGGL(kernels[transA][transB], grid, dim3(GEMM_THREADS), LDS_BYTES, ctx->stream, b);
+  NK_HIP(hipGetLastError());
+  return NK_OK;
 }
 
 // Two independent small problems with the same transposition flags in ONE launch (blockIdx.y = problem).  Used by the
 // paired Cholesky factorisations / triangular solves of the fit, whose per-step kernels are latency bound.
 int launch_gemm_pair(nk_ctx* ctx, bool transA, bool transB, const GemmCall* calls, int ncalls) {
   NK_REQUIRE(ncalls >= 1 && ncalls <= GEMM_MAX_BATCH, "gemm_pair: 1..2 problems");
-  GemmBatch b;
+  GemmBatch b{};  // a slot without a problem has nblocks = 0
   int maxblocks = 0, live = 0;
-  for (int q = 0; q < GEMM_MAX_BATCH; ++q) {
-    if (q < ncalls && calls[q].M > 0 && calls[q].N > 0) {
-      GemmOpts o = calls[q].opts;
-      o.splitk = 1;
-      int nt = 0;
-      NK_TRY(gemm_prepare(ctx, transA, transB, calls[q].M, calls[q].N, calls[q].K, calls[q].alpha, calls[q].A,
-                          calls[q].lda, calls[q].B, calls[q].ldb, calls[q].beta, calls[q].C, calls[q].ldc, o, &b.p[q], &nt));
-      if (b.p[q].nblocks > maxblocks) maxblocks = b.p[q].nblocks;
-      ++live;
-    } else {
-      b.p[q] = GemmParams{};
-      b.p[q].nblocks = 0;
-    }
+  for (int q = 0; q < ncalls; ++q) {
+    const GemmCall& c = calls[q];
+    if (c.M <= 0 || c.N <= 0) continue;
+    GemmOpts o = c.opts;
+    o.splitk = 1;
+    NK_TRY(gemm_prepare(ctx, c.M, c.N, c.K, c.alpha, c.A, c.lda, c.B, c.ldb, c.beta, c.C, c.ldc, o, &b.p[q]));
+    if (b.p[q].nblocks > maxblocks) maxblocks = b.p[q].nblocks;
+    ++live;
   }
   if (live == 0) return NK_OK;
   NK_TRY(gemm_set_attrs());
-  gemm_dispatch(ctx, transA, transB, dim3((unsigned)maxblocks, (unsigned)GEMM_MAX_BATCH), b);
-  NK_HIP(hipGetLastError());
-  return NK_OK;
+  return gemm_dispatch(ctx, transA, transB, dim3((unsigned)maxblocks, (unsigned)GEMM_MAX_BATCH), b);
 }
 
 // Small products (lift of a few states, the product with C after a rollout, p-column blocks): the 128 x 128 engine
@@ -455,38 +420,25 @@ int launch_gemm(nk_ctx* ctx, bool transA, bool transB, int64_t M, int64_t N, int
     tp.tri = opts.tri; tp.alpha = alpha; tp.beta = beta;
     if (tn_fast_ok(tp) && (opts.tri == TRI_FULL || M == N)) return launch_gemm_tn_multi(ctx, &tp, 1, K, 0, ms_kernel);
   }
-  GemmBatch b;
-  b.p[1] = GemmParams{};
-  b.p[1].nblocks = 0;
-  int ntiles = 0;
-  NK_TRY(gemm_prepare(ctx, transA, transB, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, opts, &b.p[0], &ntiles));
+  GemmBatch b{};  // the second slot stays empty (nblocks = 0)
   GemmParams& p = b.p[0];
-  const int splitk = p.splitk;
+  NK_TRY(gemm_prepare(ctx, M, N, K, alpha, A, lda, B, ldb, beta, C, ldc, opts, &p));
   const ArenaMark mark = arena_mark(ctx);
-  if (splitk > 1) {
-    double* slab = nullptr;
-    NK_TRY(arena_alloc_t(ctx, (size_t)splitk * M * N, &slab));
-    p.slab = slab;
-  }
+  if (p.splitk > 1) NK_TRY(arena_alloc_t(ctx, (size_t)p.splitk * M * N, &p.slab));
   NK_TRY(gemm_set_attrs());
-  if (ms_kernel) NK_HIP(hipEventRecord(ctx->ev[EV_GEMM_T0], ctx->stream));
-  gemm_dispatch(ctx, transA, transB, dim3((unsigned)p.nblocks, 1), b);
-  NK_HIP(hipGetLastError());
-  if (ms_kernel) {
-    NK_HIP(hipEventRecord(ctx->ev[EV_GEMM_T1], ctx->stream));
-  }
-  if (splitk > 1) {
+  const GemmTimer timer{ctx, ms_kernel};
+  NK_TRY(timer.begin());
+  NK_TRY(gemm_dispatch(ctx, transA, transB, dim3((unsigned)p.nblocks, 1), b));
+  NK_TRY(timer.end());
+  if (p.splitk > 1) {
     const int64_t total = M * N;
     int blocks = (int)((total + 255) / 256);
     if (blocks > ctx->num_cu * 16) blocks = ctx->num_cu * 16;
-    hipLaunchKernelGGL(gemm_reduce_kernel, dim3(blocks), dim3(256), 0, ctx->stream, p.slab, splitk, p.M, p.N, alpha,
+    hipLaunchKernelGGL(gemm_reduce_kernel, dim3(blocks), dim3(256), 0, ctx->stream, p.slab, p.splitk, p.M, p.N, alpha,
                        beta, C, ldc, p.tri);
     NK_HIP(hipGetLastError());
   }
-  if (ms_kernel) {
-    NK_HIP(hipEventSynchronize(ctx->ev[EV_GEMM_T1]));
-    NK_HIP(hipEventElapsedTime(ms_kernel, ctx->ev[EV_GEMM_T0], ctx->ev[EV_GEMM_T1]));
-  }
+  NK_TRY(timer.read(true));
   arena_release(ctx, mark);  // stream order makes the slab reusable by later launches
   return NK_OK;
 }

@@ -16,7 +16,7 @@
 //     applies alpha/beta, bounds and the symmetric mirror (deterministic; no float atomics).
 #include "nk_common.h"
 #include "nk_tn_kstep.inc"
-#include "nk_tn_shared.h"
+#include "nk_tn.h"
 
 #include <cstdlib>
 #include <cstring>
@@ -504,17 +504,13 @@ int launch_transpose(nk_ctx* ctx, const double* src, int64_t lds_, double* dst, 
   return NK_OK;
 }
 
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-bool tn_fast_ok(const TnProblem& p) {
-  return p.M >= 2 && p.N >= 2 && aligned16(p.A) && aligned16(p.B) && p.lda % 2 == 0 && p.ldb % 2 == 0 &&
-         p.lda >= ((p.M + 1) & ~1) && p.ldb >= ((p.N + 1) & ~1);
-}
-
-static bool g_tn_attr_set = false;
-static int tn_use_asm() {
-  const char* e = getenv("NYSKOOP_TN_ASM");  // read per launch: A/B runs flip it inside one process
-  return (e && e[0] == '0') ? 0 : 1;
+static int tn_attrs() {
+  static const hipError_t e = dynamic_lds_register(
+      TN_LDS_BYTES, gemm_tn_f64_kernel<0>, gemm_tn_f64_kernel<1>, gemm_tn_f64_kernel<2>, gemm_tn_f64_kernel<3>,
+      gemm_tn_f64_kernel<4>, gram_fused_f64_kernel, gemm_tn_f64_kernel_batched<0>, gemm_tn_f64_kernel_batched<1>,
+      gemm_tn_f64_kernel_batched<2>, gemm_tn_f64_kernel_batched<3>, gemm_tn_f64_kernel_batched<4>,
+      gram_fused_f64_kernel_batched);
+  return dynamic_lds_status(e);
 }
 
 int tn_ensure_zero_page(nk_ctx* ctx) {
@@ -524,74 +520,78 @@ int tn_ensure_zero_page(nk_ctx* ctx) {
   return NK_OK;
 }
 
-int launch_gemm_tn_multi(nk_ctx* ctx, const TnProblem* probs, int nprob, int64_t K, int splitk, float* ms_kernel,
-                         bool sync_timing, const TnSkip* skip) {
-  NK_REQUIRE(nprob >= 1 && nprob <= TN_MAXP, "gemm_tn_multi: 1..4 problems");
-  NK_REQUIRE(K >= 0 && K < (1LL << 31), "gemm_tn_multi: K out of range");
+// Experiment switches of the engine, read once at the top of every launch: A/B runs flip them inside one
+// process.
+struct TnEnv {
+  int use_asm;         // NYSKOOP_TN_ASM=0: the compiler-scheduled form of the k steps instead of the hand-scheduled one
+  int kmask = -1;      // NYSKOOP_TN_KMASK (product launches): operand rows are fetched from k & kmask
+  int splitk = -1;     // NYSKOOP_TN_SPLITK (the fit's fused Gram launch): its number of K slices; -1 = the plan's
+  TnEnv(bool fused_gram, bool kmat) {
+    const char* e = getenv("NYSKOOP_TN_ASM");
+    use_asm = (e && e[0] == '0') ? 0 : 1;
+    if (!kmat && (e = getenv("NYSKOOP_TN_KMASK")) != nullptr) kmask = (int)strtol(e, nullptr, 0);
+    if (fused_gram && (e = getenv("NYSKOOP_TN_SPLITK")) != nullptr) splitk = atoi(e);
+  }
+};
+
+// one problem slot of the product kernel and of the reduce kernel
+static void tn_fill_slot(const TnProblem& s, int tiles_n, int tile_begin, TnDev& d, TnRed& r) {
+  d.A = s.A; d.B = s.B; d.lda = s.lda; d.ldb = s.ldb; d.M = s.M; d.N = s.N;
+  d.tiles_n = tiles_n; d.tri = s.tri; d.ktrim = s.ktrim; d.tile_begin = tile_begin;
+  d.C = s.C; d.ldc = s.ldc; d.alpha = s.alpha; d.beta = s.beta; d.Ct = s.Ct; d.ldct = s.ldct;
+  d.A_even = s.A_even; d.B_even = s.B_even;
+  d.Caff = s.Caff; d.aff_a = s.aff_a; d.aff_c = s.aff_c;
+  r.Caff = s.Caff; r.aff_a = s.aff_a; r.aff_c = s.aff_c;
+  r.Ct = s.Ct; r.ldct = s.ldct;
+  r.C = s.C; r.ldc = s.ldc; r.M = s.M; r.N = s.N; r.tiles_n = tiles_n; r.tri = s.tri; r.tile_begin = tile_begin;
+  r.alpha = s.alpha; r.beta = s.beta;
+}
+
+// fused kernel-matrix epilogue of a launch: out[i][j] = k(sqa[i] + sqb[j] - 2 acc)
+struct TnKmatEpi {
+  const double* sqa;
+  const double* sqb;
+  double* out;
+  int64_t ldo;
+  int ktype;
+  double sigma0sq;
+};
+using TnKernel = void (*)(TnParams);
+static TnKernel tn_kernel(int nprob, const TnKmatEpi* epi) {
+  if (!epi) return nprob >= 3 ? gram_fused_f64_kernel : gemm_tn_f64_kernel<0>;  // >= 3: the fit's fused Gram launch
+  switch (epi->ktype) {
+    case NK_KERNEL_RBF: return gemm_tn_f64_kernel<1>;
+    case NK_KERNEL_MATERN52: return gemm_tn_f64_kernel<2>;
+    case NK_KERNEL_TPS: return gemm_tn_f64_kernel<4>;
+    default: return gemm_tn_f64_kernel<3>;
+  }
+}
+
+// The one launcher of the engine: probs[0..nprob) checked by the caller.  epi: a kernel-matrix launch (one problem, one K
+// slice, its own grid order) instead of a product launch.
+static int tn_launch(nk_ctx* ctx, const TnProblem* probs, int nprob, int64_t K, int splitk, float* ms_kernel,
+                     bool sync_timing, const TnSkip* skip, const TnKmatEpi* epi) {
   NK_TRY(tn_ensure_zero_page(ctx));
-  TnParams P;
-  TnRedParams R;
-  int ntiles = 0;
-  for (int q = 0; q < nprob; ++q) {
-    const TnProblem& s = probs[q];
-    NK_REQUIRE(tn_fast_ok(s), "gemm_tn_multi: problem %d violates the alignment contract", q);
-    NK_REQUIRE(s.tri == TRI_FULL || (s.tri == TRI_UPPER_MIRROR && s.M == s.N), "gemm_tn_multi: bad tri mode");
-    const int tmn = (s.M + TBM - 1) / TBM, tnn = (s.N + TBM - 1) / TBM;
-    TnDev& d = P.p[q];
-    d.A = s.A; d.B = s.B; d.lda = s.lda; d.ldb = s.ldb; d.M = s.M; d.N = s.N;
-    d.tiles_n = tnn; d.tri = s.tri; d.ktrim = s.ktrim; d.tile_begin = ntiles;
-    d.C = s.C; d.ldc = s.ldc; d.alpha = s.alpha; d.beta = s.beta; d.Ct = s.Ct; d.ldct = s.ldct;
-    d.A_even = s.A_even; d.B_even = s.B_even;
-    d.Caff = s.Caff; d.aff_a = s.aff_a; d.aff_c = s.aff_c;
-    TnRed& r = R.p[q];
-    r.Caff = s.Caff; r.aff_a = s.aff_a; r.aff_c = s.aff_c;
-    r.Ct = s.Ct; r.ldct = s.ldct;
-    r.C = s.C; r.ldc = s.ldc; r.M = s.M; r.N = s.N; r.tiles_n = tnn; r.tri = s.tri; r.tile_begin = ntiles;
-    r.alpha = s.alpha; r.beta = s.beta;
-    ntiles += s.tri == TRI_FULL ? tmn * tnn : tmn * (tmn + 1) / 2;
+  const TnEnv env(nprob >= 3, epi != nullptr);
+  const TileLayout L = plan_layout(probs, nprob);
+  const int ntiles = L.ntiles;
+  TnParams P{};
+  TnRedParams R{};
+  for (int q = 0; q < TN_MAXP; ++q) {  // unused slots: problem 0 again, at a tile_begin that no tile index reaches
+    const int src = q < nprob ? q : 0;
+    tn_fill_slot(probs[src], L.tiles_n[src], L.tile_begin[q], P.p[q], R.p[q]);
   }
-  for (int q = nprob; q < TN_MAXP; ++q) {
-    P.p[q] = P.p[0];
-    P.p[q].tile_begin = 1 << 30;
-    R.p[q] = R.p[0];
-    R.p[q].tile_begin = 1 << 30;
-  }
-  const int ktiles_total = (int)((K + TBK - 1) / TBK);
-  const bool want_resid = skip && skip->resid_partials != nullptr;
-  if (splitk <= 0) {
-    // Pick the number of K slices with a small cost model calibrated on MI355X (profiles/r01_*): a k-step costs
-    // 1.22 units per workgroup when two workgroups share a CU and 2.35 when a workgroup is alone on its CU (one wave
-    // per SIMD cannot hide the barrier + DMA latency); workgroups beyond 2/CU run as further rounds.  The slab
-    // round trip (write + read of ntiles*splitk tiles) is charged at ~4 TB/s.  Multiples of 8 keep one K range per
-    // XCD (panels shared through that XCD's L2) and get a small bonus.
-    const int slots = 2 * ctx->num_cu;
-    const int max_split = ktiles_total / 8 > 1 ? ktiles_total / 8 : 1;
-    double best = 1e300;
-    splitk = 1;
-    for (int c = 1; c <= 64 && c <= max_split; ++c) {
-      const int64_t wgs = (int64_t)ntiles * c;
-      const double steps = (double)((ktiles_total + c - 1) / c);
-      const int64_t full = wgs / slots, rem = wgs % slots;
-      double t = full * 2.44 * steps;
-      if (rem > 0) t += (rem <= ctx->num_cu ? 2.35 : 2.44) * steps;
-      t *= 4096.0;                                                      // cycles of MFMA per k-step and wave
-      if (c > 1) t += (double)wgs * (TBM * TBM * 8.0 * 2.0) / 4.0e12 * 2.4e9;  // slab write + read, in cycles
-      t += 2000.0 * c / 8.0;                                            // mild preference for fewer slices
-      if (c % 8 == 0) t *= 0.97;
-      if (t < best) { best = t; splitk = c; }
-    }
-  }
-  if (want_resid && splitk < 2) splitk = 2;  // the residual partials come out of the reduce kernel
-  if (nprob >= 3 && getenv("NYSKOOP_TN_SPLITK")) splitk = atoi(getenv("NYSKOOP_TN_SPLITK"));  // experiments
-  P.kmask = getenv("NYSKOOP_TN_KMASK") ? (int)strtol(getenv("NYSKOOP_TN_KMASK"), nullptr, 0) : -1;
-  P.use_asm = tn_use_asm();
+  const int ktiles_total = plan_ktiles(K, TBK);
+  if (splitk <= 0) splitk = plan_splitk_tn_f64(ntiles, ktiles_total, ctx->num_cu);
+  splitk = plan_splitk_with_resid(splitk, skip && skip->resid_partials != nullptr);
+  if (env.splitk != -1) splitk = env.splitk;  // experiments
   P.nprob = nprob; P.ntiles = ntiles; P.K = (int)K; P.splitk = splitk;
-  P.klen = ((ktiles_total + splitk - 1) / splitk) * TBK;
-  if (P.klen == 0) P.klen = TBK;
+  P.klen = plan_slice_len(ktiles_total, splitk, TBK);
+  P.kmask = env.kmask; P.use_asm = env.use_asm;
   P.zeros = ctx->d_zeros;
   const ArenaMark mark = arena_mark(ctx);
   double* slab = nullptr;
-  if (splitk > 1) NK_TRY(arena_alloc_t(ctx, (size_t)ntiles * splitk * TBM * TBM, &slab));
+  if (splitk > 1) NK_TRY(arena_alloc_t(ctx, plan_slab_elems(ntiles, splitk), &slab));
   P.slab = slab;
   R.nprob = nprob; R.splitk = splitk; R.slab = slab;
   P.skip_state = R.skip_state = skip ? skip->state : nullptr;
@@ -599,51 +599,33 @@ int launch_gemm_tn_multi(nk_ctx* ctx, const TnProblem* probs, int nprob, int64_t
   P.select_state = skip ? skip->select : nullptr;
   R.resid_partials = (skip && splitk > 1 && nprob == 1) ? skip->resid_partials : nullptr;
   if (skip && skip->resid_count) *skip->resid_count = R.resid_partials ? ntiles * RPARTS : 0;
-  if (!g_tn_attr_set) {
-    NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_f64_kernel<0>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
-    NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gram_fused_f64_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
-    NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_f64_kernel<1>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
-    NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_f64_kernel<2>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
-    NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_f64_kernel<3>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
-    NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_f64_kernel<4>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
-    NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_f64_kernel_batched<0>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
-    NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_f64_kernel_batched<1>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
-    NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_f64_kernel_batched<2>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
-    NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_f64_kernel_batched<3>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
-    NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_f64_kernel_batched<4>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
-    NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gram_fused_f64_kernel_batched),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
-    g_tn_attr_set = true;
+  if (epi) {
+    P.sqa = epi->sqa; P.sqb = epi->sqb; P.out = epi->out; P.ldo = epi->ldo; P.ktype = epi->ktype;
+    P.sigma0sq = epi->sigma0sq;
   }
-  if (ms_kernel) NK_HIP(hipEventRecord(ctx->ev[EV_GEMM_T0], ctx->stream));
-  P.sqa = P.sqb = nullptr; P.out = nullptr; P.ldo = 0; P.ktype = 0; P.sigma0sq = 0.0;
-  if (nprob >= 3)  // the fit's fused Gram launch
-    hipLaunchKernelGGL(gram_fused_f64_kernel, dim3((unsigned)(ntiles * splitk)), dim3(256), TN_LDS_BYTES, ctx->stream, P);
-  else
-    hipLaunchKernelGGL(gemm_tn_f64_kernel<0>, dim3((unsigned)(ntiles * splitk)), dim3(256), TN_LDS_BYTES, ctx->stream, P);
+  const unsigned grid = epi ? plan_kmat_grid(plan_tiles(probs[0].M), L.tiles_n[0]) : (unsigned)(ntiles * splitk);
+  NK_TRY(tn_attrs());
+  const GemmTimer timer{ctx, ms_kernel};
+  NK_TRY(timer.begin());
+  hipLaunchKernelGGL(tn_kernel(nprob, epi), dim3(grid), dim3(256), TN_LDS_BYTES, ctx->stream, P);
   NK_HIP(hipGetLastError());
-  if (ms_kernel) NK_HIP(hipEventRecord(ctx->ev[EV_GEMM_T1], ctx->stream));
-  if (splitk > 1) {
-    hipLaunchKernelGGL(gemm_tn_reduce_kernel, dim3((unsigned)ntiles * RPARTS), dim3(256), 0, ctx->stream, R);
-    NK_HIP(hipGetLastError());
-  }
-  if (ms_kernel && sync_timing) {  // otherwise the caller reads EV_GEMM_T0 -> EV_GEMM_T1 after its own synchronisation
-    NK_HIP(hipEventSynchronize(ctx->ev[EV_GEMM_T1]));
-    NK_HIP(hipEventElapsedTime(ms_kernel, ctx->ev[EV_GEMM_T0], ctx->ev[EV_GEMM_T1]));
-  }
+  NK_TRY(timer.end());
+  if (splitk > 1) NK_TRY(launch_tn_reduce(ctx, R, ntiles));
+  NK_TRY(timer.read(sync_timing));  // sync_timing = false: the caller reads the two events after its own synchronisation
   arena_release(ctx, mark);
   return NK_OK;
+}
+
+int launch_gemm_tn_multi(nk_ctx* ctx, const TnProblem* probs, int nprob, int64_t K, int splitk, float* ms_kernel,
+                         bool sync_timing, const TnSkip* skip) {
+  NK_REQUIRE(nprob >= 1 && nprob <= TN_MAXP, "gemm_tn_multi: 1..4 problems");
+  NK_REQUIRE(K >= 0 && K < (1LL << 31), "gemm_tn_multi: K out of range");
+  for (int q = 0; q < nprob; ++q) {
+    const TnProblem& s = probs[q];
+    NK_REQUIRE(tn_fast_ok(s), "gemm_tn_multi: problem %d violates the alignment contract", q);
+    NK_REQUIRE(s.tri == TRI_FULL || (s.tri == TRI_UPPER_MIRROR && s.M == s.N), "gemm_tn_multi: bad tri mode");
+  }
+  return tn_launch(ctx, probs, nprob, K, splitk, ms_kernel, sync_timing, skip, nullptr);
 }
 
 
@@ -743,60 +725,11 @@ int prep_rows(nk_ctx* ctx, const double* X, int64_t ldx, int64_t rows, int d, co
 int launch_kmat_gram(nk_ctx* ctx, int ktype, const double* At, int64_t ldat, const double* sqa, int64_t nA,
                      const double* Bt, int64_t ldbt, const double* sqb, int64_t nB, int d, double sigma0, double* out,
                      int64_t ldo) {
-  NK_TRY(tn_ensure_zero_page(ctx));
-  TnProblem tp;
+  TnProblem tp;  // the Gram-form launch is a one-problem, one-slice launch of the engine with k() as its epilogue
   tp.A = At; tp.B = Bt; tp.lda = ldat; tp.ldb = ldbt; tp.M = (int)nA; tp.N = (int)nB;
   NK_REQUIRE(tn_fast_ok(tp), "kmat_gram: operands violate the alignment contract");
-  TnParams P;
-  P.skip_state = nullptr; P.skip_step = 0; P.select_state = nullptr;
-  const int tmn = (int)((nA + TBM - 1) / TBM), tnn = (int)((nB + TBM - 1) / TBM);
-  TnDev& dv = P.p[0];
-  dv.A = At; dv.B = Bt; dv.lda = ldat; dv.ldb = ldbt; dv.M = (int)nA; dv.N = (int)nB; dv.tiles_n = tnn; dv.tri = TRI_FULL;
-  dv.tile_begin = 0; dv.ktrim = KTRIM_NONE; dv.A_even = dv.B_even = nullptr; dv.Caff = nullptr; dv.aff_a = dv.aff_c = 0.0;
-  dv.C = nullptr; dv.ldc = 0; dv.alpha = 1.0; dv.beta = 0.0; dv.Ct = nullptr; dv.ldct = 0;
-  for (int q = 1; q < TN_MAXP; ++q) { P.p[q] = P.p[0]; P.p[q].tile_begin = 1 << 30; }
-  P.nprob = 1; P.ntiles = tmn * tnn; P.K = d; P.splitk = 1; P.kmask = -1; P.use_asm = tn_use_asm();
-  P.klen = ((d + TBK - 1) / TBK) * TBK;
-  P.zeros = ctx->d_zeros; P.slab = nullptr;
-  P.sqa = sqa; P.sqb = sqb; P.out = out; P.ldo = ldo; P.ktype = ktype; P.sigma0sq = sigma0 * sigma0;
-  if (!g_tn_attr_set) {
-    NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_f64_kernel<0>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
-    NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gram_fused_f64_kernel),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
-    NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_f64_kernel<1>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
-    NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_f64_kernel<2>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
-    NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_f64_kernel<3>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
-    NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_f64_kernel<4>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
-    NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_f64_kernel_batched<0>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
-    NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_f64_kernel_batched<1>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
-    NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_f64_kernel_batched<2>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
-    NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_f64_kernel_batched<3>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
-    NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_f64_kernel_batched<4>),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
-    NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gram_fused_f64_kernel_batched),
-                               hipFuncAttributeMaxDynamicSharedMemorySize, TN_LDS_BYTES));
-    g_tn_attr_set = true;
-  }
-  const unsigned grid = 8u * (unsigned)tmn * (unsigned)((tnn + 7) / 8);
-  if (ktype == NK_KERNEL_RBF)
-    hipLaunchKernelGGL(gemm_tn_f64_kernel<1>, dim3(grid), dim3(256), TN_LDS_BYTES, ctx->stream, P);
-  else if (ktype == NK_KERNEL_MATERN52)
-    hipLaunchKernelGGL(gemm_tn_f64_kernel<2>, dim3(grid), dim3(256), TN_LDS_BYTES, ctx->stream, P);
-  else if (ktype == NK_KERNEL_TPS)
-    hipLaunchKernelGGL(gemm_tn_f64_kernel<4>, dim3(grid), dim3(256), TN_LDS_BYTES, ctx->stream, P);
-  else
-    hipLaunchKernelGGL(gemm_tn_f64_kernel<3>, dim3(grid), dim3(256), TN_LDS_BYTES, ctx->stream, P);
-  NK_HIP(hipGetLastError());
-  return NK_OK;
+  const TnKmatEpi epi = {sqa, sqb, out, ldo, ktype, sigma0 * sigma0};
+  return tn_launch(ctx, &tp, 1, d, 1, nullptr, true, nullptr, &epi);
 }
 
 }  // namespace nk

@@ -12,7 +12,7 @@
 // k, lanes 32-63 row k + 1: 2 x 512 B, contiguous in the unpadded LDS image) -- operand fragments fetched one k-pair
 // ahead of the MFMAs that use them, one barrier per step.
 #include "nk_common.h"
-#include "nk_tn_shared.h"
+#include "nk_tn.h"
 #include "nk_tnf_kstep.inc"
 
 #include <cstdlib>
@@ -60,6 +60,79 @@ __device__ __forceinline__ void dma2_rows(const float* lane_src, uint32_t lds_ad
                : "m0");
 }
 __device__ __forceinline__ void dma_wait_all_f() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+
+// ---- epilogues, shared by the compiled bodies and the assembly ones.  Element (block i, j; register v) of a wave's
+// 64 x 64 sub-tile: row = i*32 + 8*(v/4) + 4*half + v%4, col = j*32 + l32; val(i, j, v) is its accumulated product. ----
+struct TnfLane {
+  int tm, tn;         // tile
+  int wm, wn;         // wave within the tile
+  int half, l32;      // lane
+};
+// Gram launches: the raw partial tile to the slab, or (one K slice) the finished tile to C with beta and the mirror
+template <class Val>
+__device__ __forceinline__ void tnf_store_gram(const TnParamsF& P, const TnDevF pr, int gt, int split, const TnfLane L,
+                                               Val val) {
+  const bool direct = P.splitk == 1;
+  const bool mirror = direct && pr.tri == TRI_UPPER_MIRROR && L.tm != L.tn;
+  double* out = direct ? nullptr : P.slab + ((int64_t)gt * P.splitk + split) * (TBM * TBM);
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int v = 0; v < 16; ++v) {
+        const int r = L.wm * 64 + i * 32 + 8 * (v >> 2) + 4 * L.half + (v & 3);
+        const int c = L.wn * 64 + j * 32 + L.l32;
+        const double x = val(i, j, v);
+        if (!direct) {
+          out[r * TBM + c] = x;
+        } else {
+          const int row = L.tm * TBM + r, col = L.tn * TBM + c;
+          if (row < pr.M && col < pr.N) {
+            double w = x;
+            if (pr.beta != 0.0) w += pr.beta * pr.C[(int64_t)row * pr.ldc + col];
+            pr.C[(int64_t)row * pr.ldc + col] = w;
+            if (mirror) pr.C[(int64_t)col * pr.ldc + row] = w;
+          }
+        }
+      }
+}
+// kernel-matrix launches (EPI = 1 RBF, 2 Matern-5/2, 3 linear), in fp32
+template <int EPI, class Val>
+__device__ __forceinline__ void tnf_store_kmat(const TnParamsF& P, const TnDevF pr, const TnfLane L, Val val) {
+  float sbv[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int col = L.tn * TBM + L.wn * 64 + j * 32 + L.l32;
+    sbv[j] = (EPI != 3 && col < pr.N) ? P.sqb[col] : 0.f;
+  }
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int v = 0; v < 16; ++v) {
+      const int row = L.tm * TBM + L.wm * 64 + i * 32 + 8 * (v >> 2) + 4 * L.half + (v & 3);
+      if (row >= pr.M) continue;
+      const float sav = EPI != 3 ? P.sqa[row] : 0.f;
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int col = L.tn * TBM + L.wn * 64 + j * 32 + L.l32;
+        const float dot = val(i, j, v);
+        float out;
+        if (EPI == 3) {
+          out = dot + P.sigma0sq;
+        } else {
+          const float D = fmaxf(sav + sbv[j] - 2.f * dot, 0.f);
+          if (EPI == 1) {
+            out = expf(-0.5f * D);
+          } else {
+            const float t = sqrtf(D) * 2.2360679774997896f;
+            out = (1.f + t + t * t * (1.f / 3.f)) * expf(-t);
+          }
+        }
+        if (col < pr.N) P.out[(int64_t)row * P.ldo + col] = out;
+      }
+    }
+}
 
 template <int EPI>
 __device__ __forceinline__ void tnf_body(const TnParamsF& P) {
@@ -186,67 +259,11 @@ __device__ __forceinline__ void tnf_body(const TnParamsF& P) {
     }
   }
 
-  // element (block i, j; register v) of a wave's 64 x 64 sub-tile: row = i*32 + 8*(v/4) + 4*half + v%4, col = j*32 + l32
-  if (EPI == 0) {
-    const bool direct = P.splitk == 1;
-    const bool mirror = direct && pr.tri == TRI_UPPER_MIRROR && tm != tn;
-    double* out = direct ? nullptr : P.slab + ((int64_t)gt * P.splitk + split) * (TBM * TBM);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j)
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-          const int r = wm * 64 + i * 32 + 8 * (v >> 2) + 4 * half + (v & 3);
-          const int c = wn * 64 + j * 32 + l32;
-          const double val = sh[i][j][v] + (double)acc[i][j][v];
-          if (!direct) {
-            out[r * TBM + c] = val;
-          } else {
-            const int row = tm * TBM + r, col = tn * TBM + c;
-            if (row < pr.M && col < pr.N) {
-              double w = val;
-              if (pr.beta != 0.0) w += pr.beta * pr.C[(int64_t)row * pr.ldc + col];
-              pr.C[(int64_t)row * pr.ldc + col] = w;
-              if (mirror) pr.C[(int64_t)col * pr.ldc + row] = w;
-            }
-          }
-        }
-  } else {
-    // kernel-matrix epilogue (EPI = 1 RBF, 2 Matern-5/2, 3 linear) in fp32
-    float sbv[2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int col = tn * TBM + wn * 64 + j * 32 + l32;
-      sbv[j] = (EPI != 3 && col < pr.N) ? P.sqb[col] : 0.f;
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int v = 0; v < 16; ++v) {
-        const int row = tm * TBM + wm * 64 + i * 32 + 8 * (v >> 2) + 4 * half + (v & 3);
-        if (row >= pr.M) continue;
-        const float sav = EPI != 3 ? P.sqa[row] : 0.f;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const int col = tn * TBM + wn * 64 + j * 32 + l32;
-          const float dot = acc[i][j][v];
-          float val;
-          if (EPI == 3) {
-            val = dot + P.sigma0sq;
-          } else {
-            const float D = fmaxf(sav + sbv[j] - 2.f * dot, 0.f);
-            if (EPI == 1) {
-              val = expf(-0.5f * D);
-            } else {
-              const float t = sqrtf(D) * 2.2360679774997896f;
-              val = (1.f + t + t * t * (1.f / 3.f)) * expf(-t);
-            }
-          }
-          if (col < pr.N) P.out[(int64_t)row * P.ldo + col] = val;
-        }
-      }
-  }
+  const TnfLane L = {tm, tn, wm, wn, half, l32};
+  if (EPI == 0)
+    tnf_store_gram(P, pr, gt, split, L, [&](int i, int j, int v) { return sh[i][j][v] + (double)acc[i][j][v]; });
+  else
+    tnf_store_kmat<EPI>(P, pr, L, [&](int i, int j, int v) { return acc[i][j][v]; });
 }
 
 template <int EPI>
@@ -261,6 +278,52 @@ __global__ void __launch_bounds__(256, 2) gemm_tn_f32_kernel(TnParamsF P) {
 // launcher): K a multiple of 32, so that every K range consists of full steps.
 // ---------------------------------------------------------------------------------------------------------------
 typedef double d16v __attribute__((ext_vector_type(16)));
+
+// Operands of the assembly k loop (nk_tnf_kstep.inc) for the K range that begins at row kbeg and has nfull >= 1 full steps;
+// the first stage is loaded here (per-lane addresses; the block uses scalar row pointers) and the barrier behind it passed.
+struct TnfAsmOps {
+  uint32_t ard, brd;    // LDS read addresses of this lane's fragments
+  uint32_t voa, vob;    // this lane's row of a pair, its four columns, as a byte offset
+  uint32_t stra, strb;  // 8 rows, in bytes
+  uint32_t dst0;        // LDS address of this wave's first row pair
+  uint32_t cnt, flags;  // pairs of steady steps; bit 0: an odd one left over
+  uint64_t rowa, rowb;  // row pointers of this wave's first pair of the second step
+};
+#define NK_TNF_IN_OPERANDS(o)                                                                                          \
+  [ard] "v"(o.ard), [brd] "v"(o.brd), [voa] "v"(o.voa), [vob] "v"(o.vob), [rowa] "s"(o.rowa), [rowb] "s"(o.rowb),      \
+      [stra] "s"(o.stra), [strb] "s"(o.strb), [dst0] "s"(o.dst0), [flags] "s"(o.flags)
+__device__ __forceinline__ TnfAsmOps tnf_asm_setup(const TnDevF pr, int kbeg, int nfull, const TnfLane L, int wave,
+                                                   uint32_t lds0) {
+  const int ca = min(L.tm * TBM + L.l32 * 4, (pr.M - 1) & ~3);
+  const int cb = min(L.tn * TBM + L.l32 * 4, (pr.N - 1) & ~3);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {  // row pairs wave, wave + 4, ... of both panels
+    const int rp = wave + 4 * q;
+    const int k = kbeg + 2 * rp + L.half;
+    dma2_rows(pr.A + (int64_t)k * pr.lda + ca, lds0 + (uint32_t)(2 * rp * FROW) * 4u);
+    dma2_rows(pr.B + (int64_t)k * pr.ldb + cb, lds0 + (uint32_t)(FPANEL + 2 * rp * FROW) * 4u);
+  }
+  dma_wait_all_f();
+  __syncthreads();
+  TnfAsmOps o;
+  o.ard = lds0 + (uint32_t)(L.half * FROW + L.l32 + L.wm * 64) * 4u;
+  o.brd = lds0 + (uint32_t)(FPANEL + L.half * FROW + L.l32 + L.wn * 64) * 4u;
+  o.voa = (uint32_t)(L.half * pr.lda + ca) * 4u;
+  o.vob = (uint32_t)(L.half * pr.ldb + cb) * 4u;
+  o.stra = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(pr.lda * 32));
+  o.strb = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(pr.ldb * 32));
+  o.dst0 = (uint32_t)__builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(wave * 2 * FROW) * 4u);
+  const int steady = nfull - 1;
+  o.cnt = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(steady / 2));
+  o.flags = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(steady & 1));
+  const uint64_t ra = (uint64_t)(uintptr_t)(pr.A + (int64_t)(kbeg + FBK + 2 * wave) * pr.lda);
+  const uint64_t rb = (uint64_t)(uintptr_t)(pr.B + (int64_t)(kbeg + FBK + 2 * wave) * pr.ldb);
+  o.rowa = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(ra >> 32)) << 32) |
+           (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)ra);
+  o.rowb = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(rb >> 32)) << 32) |
+           (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)rb);
+  return o;
+}
 
 __device__ __forceinline__ void tnf_gram_asm_body(const TnParamsF& P) {
   extern __shared__ __attribute__((aligned(16))) float fsmem[];
@@ -280,70 +343,19 @@ __device__ __forceinline__ void tnf_gram_asm_body(const TnParamsF& P) {
   const int kbeg = split * P.klen;
   const int kend = min(P.K, kbeg + P.klen);
   const int nfull = kend > kbeg ? (kend - kbeg) / FBK : 0;
-  const int ca = min(tm * TBM + l32 * 4, (pr.M - 1) & ~3);
-  const int cb = min(tn * TBM + l32 * 4, (pr.N - 1) & ~3);
-  const uint32_t lds0 = (uint32_t)(uintptr_t)fsmem;
+  const TnfLane L = {tm, tn, wm, wn, half, l32};
   d16v s00, s01, s10, s11;
 #pragma unroll
   for (int v = 0; v < 16; ++v) { s00[v] = 0.0; s01[v] = 0.0; s10[v] = 0.0; s11[v] = 0.0; }
   if (nfull > 0) {
-    // first stage: row pairs wave, wave + 4, ... of both panels (per-lane addresses; the block uses scalar row pointers)
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int rp = wave + 4 * q;
-      const int k = kbeg + 2 * rp + half;
-      dma2_rows(pr.A + (int64_t)k * pr.lda + ca, lds0 + (uint32_t)(2 * rp * FROW) * 4u);
-      dma2_rows(pr.B + (int64_t)k * pr.ldb + cb, lds0 + (uint32_t)(FPANEL + 2 * rp * FROW) * 4u);
-    }
-    dma_wait_all_f();
-    __syncthreads();
-    const uint32_t ard = lds0 + (uint32_t)(half * FROW + l32 + wm * 64) * 4u;
-    const uint32_t brd = lds0 + (uint32_t)(FPANEL + half * FROW + l32 + wn * 64) * 4u;
-    const uint32_t voa = (uint32_t)(half * pr.lda + ca) * 4u;  // this lane's row of a pair, its four columns
-    const uint32_t vob = (uint32_t)(half * pr.ldb + cb) * 4u;
-    const uint32_t stra = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(pr.lda * 32));  // 8 rows, in bytes
-    const uint32_t strb = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(pr.ldb * 32));
-    const uint32_t dst0 = (uint32_t)__builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(wave * 2 * FROW) * 4u);
-    const int steady = nfull - 1;
-    uint32_t cnt = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(steady / 2));
-    const uint32_t flags = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(steady & 1));
-    const uint64_t ra = (uint64_t)(uintptr_t)(pr.A + (int64_t)(kbeg + FBK + 2 * wave) * pr.lda);
-    const uint64_t rb = (uint64_t)(uintptr_t)(pr.B + (int64_t)(kbeg + FBK + 2 * wave) * pr.ldb);
-    const uint64_t rowa = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(ra >> 32)) << 32) |
-                          (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)ra);
-    const uint64_t rowb = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(rb >> 32)) << 32) |
-                          (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)rb);
+    TnfAsmOps o = tnf_asm_setup(pr, kbeg, nfull, L, wave, (uint32_t)(uintptr_t)fsmem);
     asm volatile(NK_TNF_KLOOP_ASM
-                 : "+{v[128:159]}"(s00), "+{v[160:191]}"(s01), "+{v[192:223]}"(s10), "+{v[224:255]}"(s11), [cnt] "+s"(cnt)
-                 : [ard] "v"(ard), [brd] "v"(brd), [voa] "v"(voa), [vob] "v"(vob), [rowa] "s"(rowa), [rowb] "s"(rowb),
-                   [stra] "s"(stra), [strb] "s"(strb), [dst0] "s"(dst0), [flags] "s"(flags)
+                 : "+{v[128:159]}"(s00), "+{v[160:191]}"(s01), "+{v[192:223]}"(s10), "+{v[224:255]}"(s11), [cnt] "+s"(o.cnt)
+                 : NK_TNF_IN_OPERANDS(o)
                  : NK_TNF_CLOBBERS);
   }
-  // element (block i, j; register v) of a wave's 64 x 64 sub-tile: row = i*32 + 8*(v/4) + 4*half + v%4, col = j*32 + l32
-  const bool direct = P.splitk == 1;
-  const bool mirror = direct && pr.tri == TRI_UPPER_MIRROR && tm != tn;
-  double* out = direct ? nullptr : P.slab + ((int64_t)gt * P.splitk + split) * (TBM * TBM);
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int v = 0; v < 16; ++v) {
-        const int r = wm * 64 + i * 32 + 8 * (v >> 2) + 4 * half + (v & 3);
-        const int c = wn * 64 + j * 32 + l32;
-        const double val = i == 0 ? (j == 0 ? s00[v] : s01[v]) : (j == 0 ? s10[v] : s11[v]);
-        if (!direct) {
-          out[r * TBM + c] = val;
-        } else {
-          const int row = tm * TBM + r, col = tn * TBM + c;
-          if (row < pr.M && col < pr.N) {
-            double w = val;
-            if (pr.beta != 0.0) w += pr.beta * pr.C[(int64_t)row * pr.ldc + col];
-            pr.C[(int64_t)row * pr.ldc + col] = w;
-            if (mirror) pr.C[(int64_t)col * pr.ldc + row] = w;
-          }
-        }
-      }
+  tnf_store_gram(P, pr, gt, split, L,
+                 [&](int i, int j, int v) { return i == 0 ? (j == 0 ? s00[v] : s01[v]) : (j == 0 ? s10[v] : s11[v]); });
 }
 __global__ void __launch_bounds__(256, 2) gram_fused_f32_asm_kernel(TnParamsF P) { tnf_gram_asm_body(P); }
 
@@ -364,78 +376,17 @@ __device__ __forceinline__ void tnf_kmat_asm_body(const TnParamsF& P) {
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int half = lane >> 5, l32 = lane & 31;
   const int wm = wave >> 1, wn = wave & 1;
-  const int nfull = P.K / FBK;
-  const int ca = min(tm * TBM + l32 * 4, (pr.M - 1) & ~3);
-  const int cb = min(tn * TBM + l32 * 4, (pr.N - 1) & ~3);
-  const uint32_t lds0 = (uint32_t)(uintptr_t)fsmem;
+  const TnfLane L = {tm, tn, wm, wn, half, l32};
   f16v c00, c01, c10, c11;
 #pragma unroll
   for (int v = 0; v < 16; ++v) { c00[v] = 0.f; c01[v] = 0.f; c10[v] = 0.f; c11[v] = 0.f; }
-  {
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int rp = wave + 4 * q;
-      const int k = 2 * rp + half;
-      dma2_rows(pr.A + (int64_t)k * pr.lda + ca, lds0 + (uint32_t)(2 * rp * FROW) * 4u);
-      dma2_rows(pr.B + (int64_t)k * pr.ldb + cb, lds0 + (uint32_t)(FPANEL + 2 * rp * FROW) * 4u);
-    }
-    dma_wait_all_f();
-    __syncthreads();
-    const uint32_t ard = lds0 + (uint32_t)(half * FROW + l32 + wm * 64) * 4u;
-    const uint32_t brd = lds0 + (uint32_t)(FPANEL + half * FROW + l32 + wn * 64) * 4u;
-    const uint32_t voa = (uint32_t)(half * pr.lda + ca) * 4u;
-    const uint32_t vob = (uint32_t)(half * pr.ldb + cb) * 4u;
-    const uint32_t stra = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(pr.lda * 32));
-    const uint32_t strb = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(pr.ldb * 32));
-    const uint32_t dst0 = (uint32_t)__builtin_amdgcn_readfirstlane(lds0 + (uint32_t)(wave * 2 * FROW) * 4u);
-    const int steady = nfull - 1;
-    uint32_t cnt = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(steady / 2));
-    const uint32_t flags = (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(steady & 1));
-    const uint64_t ra = (uint64_t)(uintptr_t)(pr.A + (int64_t)(FBK + 2 * wave) * pr.lda);
-    const uint64_t rb = (uint64_t)(uintptr_t)(pr.B + (int64_t)(FBK + 2 * wave) * pr.ldb);
-    const uint64_t rowa = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(ra >> 32)) << 32) |
-                          (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)ra);
-    const uint64_t rowb = ((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(rb >> 32)) << 32) |
-                          (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)rb);
-    asm volatile(NK_TNF_KLOOP_PLAIN_ASM
-                 : "+{v[0:15]}"(c00), "+{v[16:31]}"(c01), "+{v[32:47]}"(c10), "+{v[48:63]}"(c11), [cnt] "+s"(cnt)
-                 : [ard] "v"(ard), [brd] "v"(brd), [voa] "v"(voa), [vob] "v"(vob), [rowa] "s"(rowa), [rowb] "s"(rowb),
-                   [stra] "s"(stra), [strb] "s"(strb), [dst0] "s"(dst0), [flags] "s"(flags)
-                 : NK_TNF_PLAIN_CLOBBERS);
-  }
-  // kernel-matrix epilogue (EPI = 1 RBF, 2 Matern-5/2, 3 linear) in fp32, as in tnf_body
-  float sbv[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    const int col = tn * TBM + wn * 64 + j * 32 + l32;
-    sbv[j] = (EPI != 3 && col < pr.N) ? P.sqb[col] : 0.f;
-  }
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int v = 0; v < 16; ++v) {
-      const int row = tm * TBM + wm * 64 + i * 32 + 8 * (v >> 2) + 4 * half + (v & 3);
-      if (row >= pr.M) continue;
-      const float sav = EPI != 3 ? P.sqa[row] : 0.f;
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int col = tn * TBM + wn * 64 + j * 32 + l32;
-        const float dot = i == 0 ? (j == 0 ? c00[v] : c01[v]) : (j == 0 ? c10[v] : c11[v]);
-        float val;
-        if (EPI == 3) {
-          val = dot + P.sigma0sq;
-        } else {
-          const float D = fmaxf(sav + sbv[j] - 2.f * dot, 0.f);
-          if (EPI == 1) {
-            val = expf(-0.5f * D);
-          } else {
-            const float t = sqrtf(D) * 2.2360679774997896f;
-            val = (1.f + t + t * t * (1.f / 3.f)) * expf(-t);
-          }
-        }
-        if (col < pr.N) P.out[(int64_t)row * P.ldo + col] = val;
-      }
-    }
+  TnfAsmOps o = tnf_asm_setup(pr, 0, P.K / FBK, L, wave, (uint32_t)(uintptr_t)fsmem);
+  asm volatile(NK_TNF_KLOOP_PLAIN_ASM
+               : "+{v[0:15]}"(c00), "+{v[16:31]}"(c01), "+{v[32:47]}"(c10), "+{v[48:63]}"(c11), [cnt] "+s"(o.cnt)
+               : NK_TNF_IN_OPERANDS(o)
+               : NK_TNF_PLAIN_CLOBBERS);
+  tnf_store_kmat<EPI>(P, pr, L,
+                      [&](int i, int j, int v) { return i == 0 ? (j == 0 ? c00[v] : c01[v]) : (j == 0 ? c10[v] : c11[v]); });
 }
 template <int EPI>
 __global__ void __launch_bounds__(256, 2) kmat_f32_asm_kernel(TnParamsF P) { tnf_kmat_asm_body<EPI>(P); }
@@ -443,25 +394,95 @@ __global__ void __launch_bounds__(256, 2) kmat_f32_asm_kernel(TnParamsF P) { tnf
 // the fit's fused Gram launch in fp32, under its own name for the profiler
 __global__ void __launch_bounds__(256, 2) gram_fused_f32_kernel(TnParamsF P) { tnf_body<0>(P); }
 
-bool tnf_fast_ok(const TnProblemF& p) {
-  auto al = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-  return p.M >= 4 && p.N >= 4 && al(p.A) && al(p.B) && p.lda % 4 == 0 && p.ldb % 4 == 0 && p.lda >= ((p.M + 3) & ~3) &&
-         p.ldb >= ((p.N + 3) & ~3);
+static int tnf_attrs() {
+  static const hipError_t e = dynamic_lds_register(
+      F32_LDS_BYTES, gemm_tn_f32_kernel<0>, gemm_tn_f32_kernel<1>, gemm_tn_f32_kernel<2>, gemm_tn_f32_kernel<3>,
+      gram_fused_f32_kernel, gram_fused_f32_asm_kernel, kmat_f32_asm_kernel<1>, kmat_f32_asm_kernel<2>,
+      kmat_f32_asm_kernel<3>);
+  return dynamic_lds_status(e);
 }
 
-static int tnf_attrs() {
-  static bool done = false;
-  if (done) return NK_OK;
-  NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_f32_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, F32_LDS_BYTES));
-  NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_f32_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, F32_LDS_BYTES));
-  NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_f32_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, F32_LDS_BYTES));
-  NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_f32_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, F32_LDS_BYTES));
-  NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gram_fused_f32_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, F32_LDS_BYTES));
-  NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(gram_fused_f32_asm_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, F32_LDS_BYTES));
-  NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kmat_f32_asm_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, F32_LDS_BYTES));
-  NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kmat_f32_asm_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, F32_LDS_BYTES));
-  NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kmat_f32_asm_kernel<3>), hipFuncAttributeMaxDynamicSharedMemorySize, F32_LDS_BYTES));
-  done = true;
+// Experiment switches of the engine, read once at the top of every launch: A/B runs and the bit-identity
+// test flip them inside one process.
+struct TnfEnv {
+  bool asm_on;  // NYSKOOP_F32_ASM=0: the compiler-scheduled kernels instead of the assembly k loop
+  int flush;    // NYSKOOP_F32_FLUSH: k-steps between two flushes of the fp32 accumulators into the fp64 shadow (default 1)
+  TnfEnv() {
+    const char* e = getenv("NYSKOOP_F32_ASM");
+    asm_on = !(e && e[0] == '0');
+    e = getenv("NYSKOOP_F32_FLUSH");
+    flush = e ? atoi(e) : 1;
+  }
+};
+
+// fused kernel-matrix epilogue of a launch: out[i][j] = k(sqa[i] + sqb[j] - 2 acc), fp32
+struct TnfKmatEpi {
+  const float* sqa;
+  const float* sqb;
+  float* out;
+  int64_t ldo;
+  int ktype;
+  float sigma0sq;
+};
+using TnfKernel = void (*)(TnParamsF);
+static TnfKernel tnf_kernel(int nprob, bool use_asm, const TnfKmatEpi* epi) {
+  if (!epi) return use_asm ? gram_fused_f32_asm_kernel : nprob >= 3 ? gram_fused_f32_kernel : gemm_tn_f32_kernel<0>;
+  switch (epi->ktype) {
+    case NK_KERNEL_RBF: return use_asm ? kmat_f32_asm_kernel<1> : gemm_tn_f32_kernel<1>;
+    case NK_KERNEL_MATERN52: return use_asm ? kmat_f32_asm_kernel<2> : gemm_tn_f32_kernel<2>;
+    default: return use_asm ? kmat_f32_asm_kernel<3> : gemm_tn_f32_kernel<3>;
+  }
+}
+
+// The one launcher of the engine: probs[0..nprob) checked by the caller.  epi: a kernel-matrix launch (one problem, one K
+// slice, its own grid order, no fp64 shadow) instead of a product launch.
+static int tnf_launch(nk_ctx* ctx, const TnProblemF* probs, int nprob, int64_t K, int splitk, float* ms_kernel,
+                      bool sync_timing, const TnfKmatEpi* epi) {
+  NK_TRY(tn_ensure_zero_page(ctx));
+  NK_TRY(tnf_attrs());
+  const TnfEnv env;
+  const TileLayout L = plan_layout(probs, nprob);
+  const int ntiles = L.ntiles;
+  TnParamsF P{};
+  TnRedParams R{};
+  for (int q = 0; q < TN_MAXP; ++q) {  // unused slots: problem 0 again, at a tile_begin that no tile index reaches
+    const int src = q < nprob ? q : 0;
+    const TnProblemF& s = probs[src];
+    TnDevF& d = P.p[q];
+    d.A = s.A; d.B = s.B; d.lda = s.lda; d.ldb = s.ldb; d.M = s.M; d.N = s.N; d.tiles_n = L.tiles_n[src]; d.tri = s.tri;
+    d.tile_begin = L.tile_begin[q]; d.C = s.C; d.ldc = s.ldc; d.beta = s.beta;
+    TnRed& r = R.p[q];  // (value-initialised: no transposed copy, no affine second output)
+    r.C = s.C; r.ldc = s.ldc; r.M = s.M; r.N = s.N;
+    r.tiles_n = d.tiles_n; r.tri = s.tri; r.tile_begin = d.tile_begin; r.alpha = 1.0; r.beta = s.beta;
+  }
+  const int ktiles_total = plan_ktiles(K, FBK);
+  // the assembly k loop (one workgroup per CU): every K range must consist of full steps, the flush interval must be 1
+  const bool use_asm = env.asm_on && K % FBK == 0 && K >= FBK && (epi || env.flush <= 1);
+  if (splitk <= 0) splitk = plan_splitk_tn_f32(ntiles, ktiles_total, ctx->num_cu);
+  P.nprob = nprob; P.ntiles = ntiles; P.K = (int)K; P.splitk = splitk;
+  P.klen = plan_slice_len(ktiles_total, splitk, FBK);
+  // fp32 partial sums run over ONE k-step (32 rows) before they are added to the fp64 shadow: the conversions hide in the
+  // shadow of the MFMAs (3.72 against 3.58 ms per launch with 32 steps on the C5 twin) and the operators of an
+  // ill-conditioned fit feel every lost bit (tools/f32_diag.py)
+  P.flush_steps = epi ? 1 << 30 : env.flush < 1 ? 1 : env.flush;
+  P.zeros = reinterpret_cast<const float*>(ctx->d_zeros);
+  const ArenaMark mark = arena_mark(ctx);
+  double* slab = nullptr;
+  if (splitk > 1) NK_TRY(arena_alloc_t(ctx, plan_slab_elems(ntiles, splitk), &slab));
+  P.slab = slab;
+  R.nprob = nprob; R.splitk = splitk; R.slab = slab;
+  if (epi) {
+    P.sqa = epi->sqa; P.sqb = epi->sqb; P.out = epi->out; P.ldo = epi->ldo; P.sigma0sq = epi->sigma0sq;
+  }
+  const unsigned grid = epi ? plan_kmat_grid(plan_tiles(probs[0].M), L.tiles_n[0]) : (unsigned)(ntiles * splitk);
+  const GemmTimer timer{ctx, ms_kernel};
+  NK_TRY(timer.begin());
+  hipLaunchKernelGGL(tnf_kernel(nprob, use_asm, epi), dim3(grid), dim3(256), F32_LDS_BYTES, ctx->stream, P);
+  NK_HIP(hipGetLastError());
+  NK_TRY(timer.end());
+  if (splitk > 1) NK_TRY(launch_tn_reduce(ctx, R, ntiles));
+  NK_TRY(timer.read(sync_timing));
+  arena_release(ctx, mark);
   return NK_OK;
 }
 
@@ -471,79 +492,12 @@ int launch_gemm_tn_f32_multi(nk_ctx* ctx, const TnProblemF* probs, int nprob, in
   NK_REQUIRE(nprob >= 1 && nprob <= TN_MAXP, "gemm_tn_f32_multi: 1..4 problems");
   NK_REQUIRE(K >= 0 && K < (1LL << 31), "gemm_tn_f32_multi: K out of range");
   NK_REQUIRE(!ctx_recording(ctx), "gemm_tn_f32_multi: the fp32 engine is not available inside a lock-step group");
-  NK_TRY(tn_ensure_zero_page(ctx));
-  NK_TRY(tnf_attrs());
-  TnParamsF P;
-  TnRedParams R;
-  int ntiles = 0;
   for (int q = 0; q < nprob; ++q) {
     const TnProblemF& s = probs[q];
     NK_REQUIRE(tnf_fast_ok(s), "gemm_tn_f32_multi: problem %d violates the alignment contract", q);
     NK_REQUIRE(s.tri == TRI_FULL || (s.tri == TRI_UPPER_MIRROR && s.M == s.N), "gemm_tn_f32_multi: bad tri mode");
-    const int tmn = (s.M + TBM - 1) / TBM, tnn = (s.N + TBM - 1) / TBM;
-    TnDevF& d = P.p[q];
-    d.A = s.A; d.B = s.B; d.lda = s.lda; d.ldb = s.ldb; d.M = s.M; d.N = s.N; d.tiles_n = tnn; d.tri = s.tri;
-    d.tile_begin = ntiles; d.C = s.C; d.ldc = s.ldc; d.beta = s.beta;
-    TnRed& r = R.p[q];
-    r.C = s.C; r.Ct = nullptr; r.Caff = nullptr; r.aff_a = r.aff_c = 0.0; r.ldc = s.ldc; r.ldct = 0; r.M = s.M; r.N = s.N;
-    r.tiles_n = tnn; r.tri = s.tri; r.tile_begin = ntiles; r.alpha = 1.0; r.beta = s.beta;
-    ntiles += s.tri == TRI_FULL ? tmn * tnn : tmn * (tmn + 1) / 2;
   }
-  for (int q = nprob; q < TN_MAXP; ++q) {
-    P.p[q] = P.p[0]; P.p[q].tile_begin = 1 << 30;
-    R.p[q] = R.p[0]; R.p[q].tile_begin = 1 << 30;
-  }
-  const int ktiles_total = (int)((K + FBK - 1) / FBK);
-  // the assembly k loop (one workgroup per CU): every K range must consist of full steps, the flush interval must be 1
-  const int flush_req = getenv("NYSKOOP_F32_FLUSH") ? atoi(getenv("NYSKOOP_F32_FLUSH")) : 1;
-  const char* fa = getenv("NYSKOOP_F32_ASM");  // read per launch: 0 = the compiler-scheduled kernel (A/B runs, bit-identity test)
-  const bool use_asm = !(fa && fa[0] == '0') && K % FBK == 0 && K >= FBK && flush_req <= 1;
-  if (splitk <= 0) {
-    // K slices: the fewest (1, 2, 4, then multiples of 8: one K range per XCD) that fill at least 95 % of the workgroup
-    // slots of the rounds they need, while a slice keeps at least 8 k-steps
-    const int64_t slots = 2 * ctx->num_cu;
-    splitk = 1;
-    double best_eff = 0.0;
-    for (int c : {1, 2, 4, 8, 16, 24, 32, 40, 48, 56, 64}) {
-      if (c > 1 && ktiles_total / c < 8) break;
-      const int64_t wgs = (int64_t)ntiles * c;
-      const int64_t rounds = (wgs + slots - 1) / slots;
-      const double eff = (double)wgs / (double)(rounds * slots);
-      if (eff > best_eff + 1e-9) { best_eff = eff; splitk = c; }
-      if (eff >= 0.95) break;
-    }
-  }
-  P.nprob = nprob; P.ntiles = ntiles; P.K = (int)K; P.splitk = splitk;
-  P.klen = ((ktiles_total + splitk - 1) / splitk) * FBK;
-  if (P.klen == 0) P.klen = FBK;
-  // fp32 partial sums run over ONE k-step (32 rows) before they are added to the fp64 shadow: the conversions hide in the
-  // shadow of the MFMAs (3.72 against 3.58 ms per launch with 32 steps on the C5 twin) and the operators of an
-  // ill-conditioned fit feel every lost bit (tools/f32_diag.py)
-  P.flush_steps = getenv("NYSKOOP_F32_FLUSH") ? atoi(getenv("NYSKOOP_F32_FLUSH")) : 1;
-  if (P.flush_steps < 1) P.flush_steps = 1;
-  P.zeros = reinterpret_cast<const float*>(ctx->d_zeros);
-  const ArenaMark mark = arena_mark(ctx);
-  double* slab = nullptr;
-  if (splitk > 1) NK_TRY(arena_alloc_t(ctx, (size_t)ntiles * splitk * TBM * TBM, &slab));
-  P.slab = slab;
-  P.sqa = P.sqb = nullptr; P.out = nullptr; P.ldo = 0; P.sigma0sq = 0.f;
-  R.nprob = nprob; R.splitk = splitk; R.slab = slab; R.skip_state = nullptr; R.skip_step = 0; R.resid_partials = nullptr;
-  if (ms_kernel) NK_HIP(hipEventRecord(ctx->ev[EV_GEMM_T0], ctx->stream));
-  if (use_asm)
-    hipLaunchKernelGGL(gram_fused_f32_asm_kernel, dim3((unsigned)(ntiles * splitk)), dim3(256), F32_LDS_BYTES, ctx->stream, P);
-  else if (nprob >= 3)
-    hipLaunchKernelGGL(gram_fused_f32_kernel, dim3((unsigned)(ntiles * splitk)), dim3(256), F32_LDS_BYTES, ctx->stream, P);
-  else
-    hipLaunchKernelGGL(gemm_tn_f32_kernel<0>, dim3((unsigned)(ntiles * splitk)), dim3(256), F32_LDS_BYTES, ctx->stream, P);
-  NK_HIP(hipGetLastError());
-  if (ms_kernel) NK_HIP(hipEventRecord(ctx->ev[EV_GEMM_T1], ctx->stream));
-  if (splitk > 1) NK_TRY(launch_tn_reduce(ctx, R, ntiles));
-  if (ms_kernel && sync_timing) {
-    NK_HIP(hipEventSynchronize(ctx->ev[EV_GEMM_T1]));
-    NK_HIP(hipEventElapsedTime(ms_kernel, ctx->ev[EV_GEMM_T0], ctx->ev[EV_GEMM_T1]));
-  }
-  arena_release(ctx, mark);
-  return NK_OK;
+  return tnf_launch(ctx, probs, nprob, K, splitk, ms_kernel, sync_timing, nullptr);
 }
 
 // ---- preparation of the rows for the Gram-form kernel blocks: centred, scaled by 1 / lengthscale, rounded to fp32 and
@@ -611,39 +565,11 @@ int launch_cvt_f64_f32(nk_ctx* ctx, const double* src, int64_t lds_, float* dst,
 int launch_kmat_gram_f32(nk_ctx* ctx, int ktype, const float* At, int64_t ldat, const float* sqa, int64_t nA, const float* Bt,
                          int64_t ldbt, const float* sqb, int64_t nB, int d, double sigma0, float* out, int64_t ldo) {
   NK_REQUIRE(!ctx_recording(ctx), "kmat_gram_f32: the fp32 engine is not available inside a lock-step group");
-  NK_TRY(tn_ensure_zero_page(ctx));
-  NK_TRY(tnf_attrs());
-  TnProblemF tp;
+  TnProblemF tp;  // a one-problem, one-slice launch of the engine with k() as its epilogue
   tp.A = At; tp.B = Bt; tp.lda = ldat; tp.ldb = ldbt; tp.M = (int)nA; tp.N = (int)nB;
   NK_REQUIRE(tnf_fast_ok(tp), "kmat_gram_f32: operands violate the alignment contract");
-  TnParamsF P;
-  const int tmn = (int)((nA + TBM - 1) / TBM), tnn = (int)((nB + TBM - 1) / TBM);
-  TnDevF& dv = P.p[0];
-  dv.A = At; dv.B = Bt; dv.lda = ldat; dv.ldb = ldbt; dv.M = (int)nA; dv.N = (int)nB; dv.tiles_n = tnn; dv.tri = TRI_FULL;
-  dv.tile_begin = 0; dv.C = nullptr; dv.ldc = 0; dv.beta = 0.0;
-  for (int q = 1; q < TN_MAXP; ++q) { P.p[q] = P.p[0]; P.p[q].tile_begin = 1 << 30; }
-  P.nprob = 1; P.ntiles = tmn * tnn; P.K = d; P.splitk = 1;
-  P.klen = ((d + FBK - 1) / FBK) * FBK;
-  P.flush_steps = 1 << 30;
-  P.zeros = reinterpret_cast<const float*>(ctx->d_zeros); P.slab = nullptr;
-  P.sqa = sqa; P.sqb = sqb; P.out = out; P.ldo = ldo; P.sigma0sq = (float)(sigma0 * sigma0);
-  const unsigned grid = 8u * (unsigned)tmn * (unsigned)((tnn + 7) / 8);
-  const char* fa = getenv("NYSKOOP_F32_ASM");  // read per launch: 0 = the compiler-scheduled kernels
-  const bool use_asm = !(fa && fa[0] == '0') && d % FBK == 0 && d >= FBK;
-  if (use_asm && ktype == NK_KERNEL_RBF)
-    hipLaunchKernelGGL(kmat_f32_asm_kernel<1>, dim3(grid), dim3(256), F32_LDS_BYTES, ctx->stream, P);
-  else if (use_asm && ktype == NK_KERNEL_MATERN52)
-    hipLaunchKernelGGL(kmat_f32_asm_kernel<2>, dim3(grid), dim3(256), F32_LDS_BYTES, ctx->stream, P);
-  else if (use_asm)
-    hipLaunchKernelGGL(kmat_f32_asm_kernel<3>, dim3(grid), dim3(256), F32_LDS_BYTES, ctx->stream, P);
-  else if (ktype == NK_KERNEL_RBF)
-    hipLaunchKernelGGL(gemm_tn_f32_kernel<1>, dim3(grid), dim3(256), F32_LDS_BYTES, ctx->stream, P);
-  else if (ktype == NK_KERNEL_MATERN52)
-    hipLaunchKernelGGL(gemm_tn_f32_kernel<2>, dim3(grid), dim3(256), F32_LDS_BYTES, ctx->stream, P);
-  else
-    hipLaunchKernelGGL(gemm_tn_f32_kernel<3>, dim3(grid), dim3(256), F32_LDS_BYTES, ctx->stream, P);
-  NK_HIP(hipGetLastError());
-  return NK_OK;
+  const TnfKmatEpi epi = {sqa, sqb, out, ldo, ktype, (float)(sigma0 * sigma0)};
+  return tnf_launch(ctx, &tp, 1, d, 1, nullptr, true, &epi);
 }
 
 }  // namespace nk

@@ -305,7 +305,6 @@ __global__ void __launch_bounds__(256) kmat_small_kernel_batched(
       "kmat_small_kernel<" #K ">");
 NK_KSMALL_TWIN(0) NK_KSMALL_TWIN(1) NK_KSMALL_TWIN(2) NK_KSMALL_TWIN(3)
 
-static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 int launch_kmat(nk_ctx* ctx, int ktype, const double* A, int64_t lda, int64_t nA, const double* B, int64_t ldb,
                 int64_t nB, int d, const double* winv, double sigma0, double* out, int64_t ldo) {

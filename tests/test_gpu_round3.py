@@ -90,6 +90,72 @@ def test_tn_engine_products_vs_numpy(nk, M, N, K):
     assert relf(C, ref) < 5e-15
 
 
+@pytest.mark.parametrize("M,N,K", [(128, 128, 64), (130, 258, 17), (2, 2, 3), (128, 128, 2048)])
+def test_tn_engine_assembly_k_steps_give_the_bits_of_the_compiled_steps(nk, monkeypatch, M, N, K):
+    """The hand-scheduled k steps of the fp64 TN engine (the default) against the compiler-scheduled form of the same steps
+    (NYSKOOP_TN_ASM=0, read per launch): the same MFMAs in the same order, so the same bits, and both within the bar of the
+    engine's products.  Four full steps in one slice; edge tiles with one full step and a one-row tail; less than a step;
+    one tile whose K range is cut into 16 slices, so that the reduce kernel runs."""
+    from nys_koop_lqr_amd import _lib
+    rng = np.random.default_rng(M + 7 * N + 13 * K)
+    A = rng.standard_normal((K, M)); B = rng.standard_normal((K, N))
+    ctx = nk.get_context()
+
+    def product():
+        C = np.empty((M, N))
+        _lib.check(ctx.lib.nk_gemm(ctx.handle, 1, 0, M, N, K, 1.0, A.ctypes.data, M, B.ctypes.data, N, 0.0, C.ctypes.data, N))
+        return C
+    Ca = product()
+    monkeypatch.setenv("NYSKOOP_TN_ASM", "0")
+    Cc = product()
+    monkeypatch.delenv("NYSKOOP_TN_ASM")
+    ref = A.T @ B
+    print(f"({M}, {N}, {K}): assembly {relf(Ca, ref):.3e}, compiled {relf(Cc, ref):.3e}, max |difference| {np.abs(Ca - Cc).max():.3e}")
+    assert relf(Ca, ref) < 5e-15 and relf(Cc, ref) < 5e-15
+    assert np.array_equal(Ca, Cc), float(np.abs(Ca - Cc).max())
+
+
+def test_first_launches_of_the_engines_from_four_threads_at_once():
+    """The engines register their kernels' dynamic LDS on first use.  In a fresh process four threads, each with its own
+    context, make their first call at the same moment -- two on the fp64 TN engine, two on the fp32 one -- and every product
+    is right."""
+    code = r'''
+import sys, threading
+import numpy as np
+sys.path.insert(0, %r)
+import nys_koop_lqr_amd as nk
+from nys_koop_lqr_amd import _lib
+M = N = 128; K = 64
+barrier = threading.Barrier(4)
+errs = [None] * 4
+def work(i):
+    rng = np.random.default_rng(i)
+    ctx = nk.get_context()
+    C = np.empty((M, N))
+    if i < 2:
+        A = rng.standard_normal((K, M)); B = rng.standard_normal((K, N))
+        barrier.wait()
+        _lib.check(ctx.lib.nk_gemm(ctx.handle, 1, 0, M, N, K, 1.0, A.ctypes.data, M, B.ctypes.data, N, 0.0, C.ctypes.data, N))
+        ref = A.T @ B
+        errs[i] = float(np.linalg.norm(C - ref) / np.linalg.norm(ref))
+    else:
+        A = rng.standard_normal((K, M)).astype(np.float32); B = rng.standard_normal((K, N)).astype(np.float32)
+        barrier.wait()
+        _lib.check(ctx.lib.nk_gemm_f32(ctx.handle, M, N, K, A.ctypes.data, M, B.ctypes.data, N, C.ctypes.data, N))
+        ref = A.astype(np.float64).T @ B.astype(np.float64)
+        errs[i] = float(np.abs(C - ref).max() / np.abs(ref).max())
+threads = [threading.Thread(target=work, args=(i,)) for i in range(4)]
+for t in threads: t.start()
+for t in threads: t.join()
+print("ERRS", *errs)
+''' % ROOT
+    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, (out.returncode, out.stdout[-300:], out.stderr[-2000:])
+    errs = [float(v) for v in [l for l in out.stdout.splitlines() if l.startswith("ERRS")][0].split()[1:]]
+    print("relative errors of the four first products:", errs)
+    assert len(errs) == 4 and max(errs[:2]) < 5e-15 and max(errs[2:]) < 2e-6, errs
+
+
 @pytest.mark.parametrize("M,N,K", [(128, 128, 64), (2006, 2000, 4100), (384, 2000, 777), (132, 260, 33), (4, 4, 5)])
 def test_fp32_engine_gram_products_vs_numpy(nk, M, N, K):
     """C (fp64) = A^T B with fp32 operands through the fp32 engine's Gram entry (nk_bench-free path: a fit-shaped call is
@@ -111,12 +177,13 @@ def test_fp32_engine_gram_products_vs_numpy(nk, M, N, K):
 
 
 @pytest.mark.parametrize("M,N,K", [(128, 128, 32), (128, 128, 64), (132, 260, 96), (200, 72, 160), (384, 2000, 800),
-                                   (2006, 2000, 4096), (2006, 2000, 12288)])
+                                   (2006, 2000, 4096), (2006, 2000, 12288), (128, 128, 2048)])
 def test_fp32_engine_assembly_k_loop_gives_the_bits_of_the_compiled_loop(nk, monkeypatch, M, N, K):
     """The fp32 Gram launches with the whole k loop as one hand-scheduled assembly block (accumulators double buffered in the
     accumulation registers, the fp64 flush in the gaps between the matrix instructions; K a multiple of 32) against the
     compiler-scheduled kernel (NYSKOOP_F32_ASM=0, read per launch): same products, same flush order -- the same bits; K from
-    one step (final step only) over odd and even step counts to split-K ranges."""
+    one step (final step only) over odd and even step counts to split-K ranges (two slices at K = 4096 and 12288, eight for
+    the single tile with K = 2048: the slices are chosen before the kernel is, nk_gemm_plan.h, so both kernels get the same)."""
     from nys_koop_lqr_amd import _lib
     rng = np.random.default_rng(M + 3 * N + 11 * K)
     lda, ldb = (M + 3) & ~3, (N + 3) & ~3
@@ -134,10 +201,7 @@ def test_fp32_engine_assembly_k_loop_gives_the_bits_of_the_compiled_loop(nk, mon
     monkeypatch.delenv("NYSKOOP_F32_ASM")
     ref = Ap[:, :M].astype(np.float64).T @ Bp[:, :N].astype(np.float64)
     assert np.abs(Cc - ref).max() / np.abs(ref).max() < 2e-6
-    if K <= 4096:
-        assert np.array_equal(Ca, Cc), float(np.abs(Ca - Cc).max())
-    else:  # the two kernels split K differently (one against two workgroups per CU): the fp64 sums of the slices differ in order
-        assert np.abs(Ca - Cc).max() / np.abs(ref).max() < 1e-15
+    assert np.array_equal(Ca, Cc), float(np.abs(Ca - Cc).max())
 
 
 def test_fp32_engine_fit_with_assembly_k_loops_gives_the_bits_of_the_compiled_loops(nk, monkeypatch):

@@ -144,3 +144,26 @@ print("dare_batch m = 3, 64, 100: status", list(status), "iters", list(iters), "
 regs = [rebuilt("nystrom", 40, 2, 3, 51)[0], rebuilt("spline", 64, 2, 4, 52)[0]]
 Ks, status, iters = ctx.model_lqr_gain_batch([reg._ensure_model() for reg in regs], 0.5)
 print("model_lqr_gain_batch m = 40, 64: status", list(status), "iters", list(iters), "K", h(*Ks), flush=True)
+
+# ---- the matrix-product engines on their own: the fp64 TN engine through nk_gemm(transA = 1) (one slice, edge tiles with a
+# K tail, less than a k-step, one tile in 16 slices), the fp32 engine through nk_gemm_f32, a fit on the fp32 engine, and the
+# Gram-form kernel matrix (thin-plate spline, d >= 32)
+for (M, N, K) in ((128, 128, 64), (130, 258, 17), (2, 2, 3), (128, 128, 2048)):
+    r = np.random.default_rng(M + 7 * N + 13 * K)
+    A, B, Cm = r.standard_normal((K, M)), r.standard_normal((K, N)), np.empty((M, N))
+    _lib.check(ctx.lib.nk_gemm(ctx.handle, 1, 0, M, N, K, 1.0, A.ctypes.data, M, B.ctypes.data, N, 0.0, Cm.ctypes.data, N))
+    print("nk_gemm transA", M, N, K, h(Cm), flush=True)
+for (M, N, K) in ((132, 260, 96), (128, 128, 2048)):
+    r = np.random.default_rng(M + 3 * N + 11 * K)
+    A, B, Cm = r.standard_normal((K, M)).astype(np.float32), r.standard_normal((K, N)).astype(np.float32), np.empty((M, N))
+    _lib.check(ctx.lib.nk_gemm_f32(ctx.handle, M, N, K, A.ctypes.data, M, B.ctypes.data, N, Cm.ctypes.data, N))
+    print("nk_gemm_f32", M, N, K, h(Cm), flush=True)
+X, Y = data(4096, 64, 3)
+reg = nk.KoopmanNystromRegressor(3, kernel=nk.ThreeDimensionalKernel(6., 6., 6., 64), gamma=1e-4, m=256)
+reg.compute_dtype = "f32"
+reg.nystrom_centers_output = np.ascontiguousarray(Y[:256].T)
+reg.fit(X, Y)
+print("fp32 fit 4096 64 3 256", h(reg.A, reg.B, reg.C), "finite", bool(np.all(np.isfinite(reg.A))), flush=True)
+r = np.random.default_rng(77)
+Kt = nk.kernels.DeviceKernel(_lib.NK_KERNEL_TPS)(r.standard_normal((300, 40)), r.standard_normal((260, 40)))
+print("nk_kernel_matrix tps 300 260 40", h(Kt), "finite", bool(np.all(np.isfinite(Kt))), flush=True)
