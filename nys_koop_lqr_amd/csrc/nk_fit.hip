@@ -109,8 +109,10 @@ struct KernelBlocks {
     return NK_OK;
   }
   // one piece of `len` rows (xs, ys) into the feature rows at Fo
+  // (a piece of ONE row -- a one-row fit, or the one-row tail of the last pass -- is below the two rows the engine's
+  // operand contract asks for: direct differences for that piece)
   int piece(nk_ctx* ctx, const double* xs, int64_t ldx, const double* ys, int64_t ldy, int64_t len, double* Fo) const {
-    if (gram_form) {
+    if (gram_form && len >= 2) {
       NK_TRY(prep_rows(ctx, xs, ldx, len, d, winv, center, Rt, ldt, sqr));
       NK_TRY(launch_kmat_gram(ctx, ktype, Rt, ldt, sqr, len, Zti, ldzt, sqzi, m, d, sigma0, Fo, ldf));
       NK_TRY(prep_rows(ctx, ys, ldy, len, d, winv, center, Rt, ldt, sqr));
@@ -354,12 +356,12 @@ int NystromFit::prepare_features() {
   f_rows = passes.size() > 1 ? pass_rows : n_eff;
   NK_TRY(arena_alloc_t(ctx, f32 ? ((size_t)f_rows * ldf + 1) / 2 + 64 : (size_t)f_rows * ldf + 64, &F));
   kb.ktype = kd->type; kb.sigma0 = kd->sigma0; kb.d = d; kb.p = p; kb.m = m; kb.winv = mdl->winv; kb.zi = zi; kb.zo = zo;
-  kb.gram_form = ctx->kmat_mode == 0 && d >= 32;
+  kb.gram_form = ctx->kmat_mode == 0 && d >= 32 && m >= 2;  // (one landmark is below the engine's two operand columns)
   // Gram-form kernel blocks (MFMA engine): rows centred on the landmark mean, scaled by 1/l, transposed
   for (auto& ps : passes) for (auto& pc : ps) maxlen = std::max(maxlen, pc.len);
   kb.ldt = (maxlen + 1) & ~(int64_t)1;
   kb.ldzt = (m + 1) & ~1;
-  overlap_prep = kb.gram_form && passes.size() == 1 && passes[0].size() == 1;
+  overlap_prep = kb.gram_form && passes.size() == 1 && passes[0].size() == 1 && maxlen >= 2;
   if (kb.gram_form) {
     NK_TRY(arena_alloc_t(ctx, (size_t)d, &kb.center));
     if (!f32) {
@@ -527,7 +529,8 @@ int NystromFit::pass_f64(size_t ip) {
     if (multi_pass) ms_gram_kernel += ms1; else gram_deferred = timed;
     gram_launches += 1;
     y_done = np == 4;
-  } else {  // unaligned operands (odd m+p): generic engine
+  } else {  // m = 1, below the contract's two columns: generic engine.  (An odd m + p does not come here: F is padded to
+            // even columns, off_out and ldf are even, so its operands meet the contract; only ldc = m + p is odd.)
     GemmOpts sym;
     sym.tri = TRI_UPPER_MIRROR;
     float t3[3] = {0.f, 0.f, 0.f};
@@ -1005,7 +1008,7 @@ int nk_spline_fit(nk_ctx* ctx, const double* X, int64_t ldx, const double* Y, in
   KernelBlocks kb;
   kb.ktype = NK_KERNEL_TPS; kb.sigma0 = 0.0; kb.d = d; kb.p = p; kb.m = m; kb.winv = mdl->winv; kb.zi = kb.zo = zc;
   kb.ldf = ldf; kb.off_out = off_out;
-  kb.gram_form = ctx->kmat_mode == 0 && d >= 32;
+  kb.gram_form = ctx->kmat_mode == 0 && d >= 32 && m >= 2;  // (one landmark is below the engine's two operand columns)
   int64_t maxlen = 0;
   for (auto& ps : passes) for (auto& pc : ps) maxlen = std::max(maxlen, pc.len);
   kb.ldt = (maxlen + 1) & ~(int64_t)1;

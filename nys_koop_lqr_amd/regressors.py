@@ -487,8 +487,8 @@ class KoopmanNystromRegressor(_DeviceModelRegressor):
     the callers' inner loops (benchmark_lqr_cloth.py:18-36, 52-57, 69-104, 238-263) as single calls.
     """
 
-    # Arithmetic of the O(n m d) kernel blocks and O(n m^2) Gram contractions of `fit`: "f64" (the only mode that meets the
-    # 1e-6 operator bar) or "f32" (BASELINE.json's stress configuration; include/nyskoop.h, nk_set_compute_dtype).  An
+    # Arithmetic of the O(n m d) kernel blocks and O(n m^2) Gram contractions of `fit` and `gram_partial`: "f64" (the only
+    # mode that meets the 1e-6 operator bar) or "f32" (BASELINE.json's stress configuration; include/nyskoop.h, nk_set_compute_dtype).  An
     # attribute, not a constructor argument: the constructor mirrors the reference's (sklearn clone / get_params), and a
     # clone starts from the default.
     compute_dtype = "f64"
@@ -608,8 +608,13 @@ class KoopmanNystromRegressor(_DeviceModelRegressor):
         rr, n_rr, keep_rr = self._ranges(row_ranges)
         stats = _lib.FitStats()
         ctx.wait_for(X, Y, out)
-        rc = ctx.lib.nk_nystrom_gram(ctx.handle, C.byref(kd), Xm.ptr, Xm.ld, Ym.ptr, Ym.ld, n, d, p, rr, n_rr,
-                                     None if same else Zi.ctypes.data, d, Zo.ctypes.data, d, m, optr, C.byref(stats))
+        ctx.set_compute_dtype(self.compute_dtype)  # as in `fit`: the shards of a sharded fit use the engine the attribute names
+        try:
+            rc = ctx.lib.nk_nystrom_gram(ctx.handle, C.byref(kd), Xm.ptr, Xm.ld, Ym.ptr, Ym.ld, n, d, p, rr, n_rr,
+                                         None if same else Zi.ctypes.data, d, Zo.ctypes.data, d, m, optr, C.byref(stats))
+        finally:
+            if self.compute_dtype != "f64":
+                ctx.set_compute_dtype("f64")
         _lib.check_mapped(rc)
         self._gram_stats = stats.as_dict()
         return out

@@ -316,7 +316,8 @@ def _synth(n, d, p, seed):
 def test_fit_variants_vs_oracle(nk, O, case):
     """Shapes and options the golden fixtures do not reach, against the oracle on the same seeded inputs: the Matern
     epilogue of the Gram-form (MFMA) kernel blocks (d >= 32), separate input / output landmarks (regressors.py:133-134
-    only aliases them by default), n_inputs = 0, odd m / d / p (unaligned operands -> generic engine), linear kernel."""
+    only aliases them by default), n_inputs = 0, odd m / d / p (odd leading dimensions of the accumulators; the padded
+    feature matrix still takes the fused launch), linear kernel."""
     if case == "matern_gram_form":
         n, d, p, m, gamma = 900, 40, 2, 48, 1e-3
         nkk, okk = nk.KernelWrapper(np.full(d, 6.0)), O.KernelWrapper(np.full(d, 6.0))

@@ -160,7 +160,8 @@ print("ERRS", *errs)
 def test_fp32_engine_gram_products_vs_numpy(nk, M, N, K):
     """C (fp64) = A^T B with fp32 operands through the fp32 engine's Gram entry (nk_bench-free path: a fit-shaped call is
     not needed, the engine is reachable through nk_gemm_f32): products of fp32 numbers accumulated in fp32 for at most
-    1024 rows at a time, then in fp64 -- compared with the fp64 product of the same rounded operands."""
+    32 rows at a time (one k-step: nk_gemm_tn_f32.hip, FBK and flush_steps), then in fp64 -- compared with the fp64 product
+    of the same rounded operands."""
     from nys_koop_lqr_amd import _lib
     rng = np.random.default_rng(M + 3 * N + 11 * K)
     A = rng.standard_normal((K, M)).astype(np.float32)
