@@ -9,6 +9,7 @@
 #include "nyskoop.h"
 #include "nk_lockstep.h"
 #include "nk_gemm_plan.h"
+#include "nk_chain_plan.h"
 
 namespace nk {
 
@@ -529,6 +530,7 @@ int cholesky_fail_flags(nk_ctx* ctx, const CholSys* sys, int nsys, int* failed /
 int launch_lifted_step(nk_ctx* ctx, const double* G, int64_t ldg, int m, int mz, int pu, const double* z, int64_t zstride,
                        const double* u, int64_t ustride, const double* bias, double* out, int64_t ostride, int batch);
 
+// (which kernel advances a recursion, and all its size classes: nk_chain_plan.h)
 // the whole recursion z_{t+1} = G [z_t; u_t] + bias for a batch of trajectories in ONE launch, G resident in LDS (m <= 128);
 // optionally preceded by the lift of the initial states by the same workgroups (nk_rollout.hip)
 struct ChainArgs {
@@ -545,17 +547,14 @@ struct ChainArgs {
 };
 int launch_ref_minus_traj(nk_ctx* ctx, const double* ref, int64_t ref_stride, const double* Phi, int64_t phi_stride,
                           double* D, int64_t d_stride, int steps, int m, int batch);
-bool lifted_chain_ok(int m, int pu, int d_lift);
 // open-loop forecast error reduced on the device (nk_traj_err.hip): out[b] = (sum (x_true - C z)^2, sum (C z)^2) over the T
 // steps of trajectory b, from the lifted states Zall [b][t][m]; the product C z is never stored.  m <= 4096.
-int traj_err_tile(int m);  // time steps per workgroup (0: m out of range)
+// (traj_err_tile, the time steps per workgroup, is in nk_chain_plan.h)
 int launch_traj_err(nk_ctx* ctx, const double* Zall, int64_t z_stride, const double* Cop, int64_t ldc, const double* Xtrue,
                     int64_t x_stride, int m, int d, int T, int batch, double* out);
 int launch_lifted_chain(nk_ctx* ctx, const ChainArgs& a);
 // m > 128: multi-workgroup recursion, one launch per group of trajectories that is resident at once (nk_rollout.hip)
 bool lifted_chain_mw_ok(const nk_ctx* ctx, int m, int pu);
-int chain_mw_workgroups(int m);
-int chain_mw_group(int m, int batch);  // trajectories one workgroup advances together
 int launch_lifted_chain_mw(nk_ctx* ctx, const ChainArgs& a);
 int lifted_chain_mw_reset(nk_ctx* ctx);                                       // clears the device status words
 int lifted_chain_mw_fetch_status(nk_ctx* ctx);                                // queues their copy to the host

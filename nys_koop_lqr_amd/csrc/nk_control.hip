@@ -27,12 +27,9 @@ static std::mutex g_chain_mw_mutex;
 // other unless they are few (<= 16: chunks of launches still beat a launch per step; beyond that the per-step GEMM
 // amortises its launches over the batch).
 static bool chain_mw_wanted(nk_ctx* ctx, const ChainArgs& chain) {
-  if (!chain_mw_enabled() || ctx_recording(ctx) || chain.T < 3) return false;
-  if (lifted_chain_ok(chain.m, chain.pu, chain.lift ? chain.d : 0)) return false;
-  if (!lifted_chain_mw_ok(ctx, chain.m, chain.U ? chain.pu : 0)) return false;
-  const int nt = chain_mw_group(chain.m, chain.batch);
-  const int64_t groups = (chain.batch + nt - 1) / nt;
-  return groups <= 16 || groups * chain_mw_workgroups(chain.m) <= ctx->num_cu;
+  const bool allowed = chain_mw_enabled() && !ctx_recording(ctx);
+  return chain_mw_wanted_plan(chain.m, chain.pu, chain.U ? chain.pu : 0, chain.lift ? chain.d : 0, chain.T, chain.batch,
+                              ctx->num_cu, allowed);
 }
 
 static bool chain_mw_gave_up(nk_ctx* ctx) {
@@ -52,14 +49,16 @@ static bool chain_mw_gave_up(nk_ctx* ctx) {
 
 static int rollout_steps(nk_ctx* ctx, ChainArgs chain, bool z0_in_place, bool use_mw) {
   const int m = chain.m, p = chain.pu, T = chain.T, batch = chain.batch;
-  if (lifted_chain_ok(m, p, chain.lift ? chain.d : 0)) return launch_lifted_chain(ctx, chain);
+  // the branch is the plan's (nk_chain_plan.h: what the tests mirror and assert); use_mw carries the conditions that are
+  // no arithmetic (the switch, a recording context, the repeat after a give-up) and chain_mw_wanted's verdict
+  const ChainPlan plan = chain_plan(m, p, chain.lift ? chain.d : 0, T, batch, ctx->num_cu, /*batch_invariant=*/false,
+                                    chain.bias != nullptr && chain.bias_stride != 0, use_mw);
+  if (plan.route == ROUTE_CHAIN) return launch_lifted_chain(ctx, chain);
   NK_REQUIRE(!chain.lift && z0_in_place, "rollout_steps: internal: the stepwise path needs z_0 in place");
-  if (use_mw) {
+  NK_REQUIRE((plan.route == ROUTE_MW) == use_mw, "rollout_steps: internal: the plan and the caller disagree on the route");
+  if (plan.route == ROUTE_MW) {
     // trajectories that are resident side by side: (CUs / workgroups per trajectory group) groups of `nt`
-    const int nt = chain_mw_group(m, batch);
-    int nb = ctx->num_cu / chain_mw_workgroups(m);
-    if (nb < 1) nb = 1;
-    nb *= nt;
+    const int nb = chain_mw_chunk(m, batch, ctx->num_cu);
     NK_TRY(lifted_chain_mw_reset(ctx));
     for (int b0 = 0; b0 < batch; b0 += nb) {
       ChainArgs sub = chain;
@@ -74,9 +73,9 @@ static int rollout_steps(nk_ctx* ctx, ChainArgs chain, bool z0_in_place, bool us
   double* Zall = chain.Zall;
   const int64_t ldz = chain.z_stride;
   for (int t = 0; t + 1 < T; ++t) {
-    if (batch <= 16) {  // matrix-vector chain: one wave per row of G, trajectories in groups of 8
-      for (int b0 = 0; b0 < batch; b0 += 8) {
-        const int nb = batch - b0 < 8 ? batch - b0 : 8;
+    if (plan.route == ROUTE_STEP) {  // matrix-vector chain: one wave per row of G, trajectories in groups of 8
+      for (int b0 = 0; b0 < batch; b0 += STEP_MAX_BATCH) {
+        const int nb = batch - b0 < STEP_MAX_BATCH ? batch - b0 : STEP_MAX_BATCH;
         // the kernel takes one bias vector: trajectories with their own bias go one by one
         if (chain.bias && chain.bias_stride != 0) {
           for (int b = b0; b < b0 + nb; ++b)
@@ -122,9 +121,9 @@ static int run_chain(nk_ctx* ctx, const ChainArgs& ch, bool z0_in_place, bool ba
   for (int attempt = 0; attempt < 2; ++attempt) {
     const bool mw = try_mw && attempt == 0;
     if (batch_invariant && !lifted_chain_ok(ch.m, ch.pu, ch.lift ? ch.d : 0)) {
-      for (int b0 = 0; b0 < ch.batch; b0 += 16) {
+      for (int b0 = 0; b0 < ch.batch; b0 += STEP_INVARIANT_CHUNK) {
         ChainArgs sub = ch;
-        sub.batch = ch.batch - b0 < 16 ? ch.batch - b0 : 16;
+        sub.batch = ch.batch - b0 < STEP_INVARIANT_CHUNK ? ch.batch - b0 : STEP_INVARIANT_CHUNK;
         sub.Zall = ch.Zall + (int64_t)b0 * ch.z_stride;
         if (ch.U) sub.U = ch.U + (int64_t)b0 * ch.u_stride;
         NK_TRY(rollout_steps(ctx, sub, z0_in_place, false));

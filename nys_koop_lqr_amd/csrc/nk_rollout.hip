@@ -8,8 +8,6 @@
 
 namespace nk {
 
-constexpr int STEP_MAX_BATCH = 8;
-
 __device__ __forceinline__ double wave_sum64(double v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
@@ -88,10 +86,7 @@ struct ChainParams {
   int d_pad;                                         // LDS doubles reserved for the scaled x0 (lift)
 };
 
-constexpr int CHAIN_THREADS = 1024;
-constexpr int CHAIN_KPT = 5;                // columns of G per thread (stride 32)
-constexpr int CHAIN_ZU = 32 * CHAIN_KPT;    // padded length of [z ; u] in LDS (160)
-
+// (CHAIN_THREADS, CHAIN_KPT, CHAIN_ZU and the LDS budget: nk_chain_plan.h)
 // (the cross-lane reduction of a step, reduce_4rows_32parts, lives in nk_common.h: the closed loops of nk_loop_multi.hip share it)
 __global__ void __launch_bounds__(CHAIN_THREADS) lifted_chain_kernel(ChainParams P) {
   extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -100,7 +95,7 @@ __global__ void __launch_bounds__(CHAIN_THREADS) lifted_chain_kernel(ChainParams
   double* zu1 = zu0 + CHAIN_ZU;
   double* kv = zu1 + CHAIN_ZU;               // m kernel values (lift), zero padded to CHAIN_ZU
   double* biasS = kv + CHAIN_ZU;             // m
-  double* xw = biasS + 128;                  // d scaled coordinates of x0 (lift)
+  double* xw = biasS + CHAIN_BIAS_DOUBLES;   // d scaled coordinates of x0 (lift)
   double* Ublk = xw + P.d_pad;               // P.tb x pu
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = CHAIN_THREADS / 64;
   const int part = tid & 31, row0 = (tid >> 5) * 4;
@@ -230,8 +225,7 @@ __global__ void __launch_bounds__(CHAIN_THREADS) lifted_chain_kernel(ChainParams
 // it raises *status and publishes NaN, which releases everybody behind it -- the grid always drains, and the caller
 // repeats the recursion with one launch per step.
 // ---------------------------------------------------------------------------------------------------------------
-constexpr int MW_KPT = 32;                                     // most 64-wide chunks of the state per lane: m <= 2048
-constexpr int MW_ROWS = 16;                                    // rows (waves) per workgroup
+// (MW_KPT chunks of the state per lane at most, MW_ROWS rows per workgroup: nk_chain_plan.h)
 constexpr unsigned long long MW_SENTINEL = 0x7FF4A5C3E1D2B697ull;  // exponent all ones, quiet bit clear: signalling NaN
 constexpr unsigned long long MW_QNAN = 0x7FF8000000000000ull;
 constexpr int MW_POLL_LIMIT = 1 << 19;
@@ -339,17 +333,7 @@ __global__ void __launch_bounds__(64 * MW_ROWS) lifted_chain_mw_kernel(ChainMwPa
   }
 }
 
-// trajectories per workgroup for a batch: NT * ceil(m / 64) <= 32 (the LDS image of the NT state vectors, two buffers)
-int chain_mw_group(int m, int batch) {
-  const int kpt = (m + 63) / 64;
-  int nt = 1;
-  while (nt < 4 && 2 * nt * (kpt <= 4 ? 4 : kpt <= 8 ? 8 : kpt <= 16 ? 16 : 32) <= 32 && 2 * nt <= batch) nt *= 2;
-  return nt;
-}
-int chain_mw_workgroups(int m) { return (m + MW_ROWS - 1) / MW_ROWS; }
-bool lifted_chain_mw_ok(const nk_ctx* ctx, int m, int pu) {
-  return m >= 1 && m <= 64 * MW_KPT && pu >= 0 && pu <= 64 && chain_mw_workgroups(m) <= ctx->num_cu;
-}
+bool lifted_chain_mw_ok(const nk_ctx* ctx, int m, int pu) { return chain_mw_fits(m, pu, ctx->num_cu); }
 
 // Zall row 0 of every trajectory holds z_0; U (if any) and bias are in DEVICE memory; batch * workgroups <= CUs.  The
 // verdict (a wave gave up waiting) lands in ctx->h_info[12..15] with the caller's next synchronisation of ctx->stream:
@@ -373,11 +357,12 @@ int launch_lifted_chain_mw(nk_ctx* ctx, const ChainArgs& a) {
                      a.T, a.batch);
   const dim3 grid((unsigned)chain_mw_workgroups(a.m), (unsigned)groups), block(64 * MW_ROWS);
 #define NK_MW_LAUNCH(K, N) hipLaunchKernelGGL((lifted_chain_mw_kernel<K, N>), grid, block, 0, ctx->stream, P)
-  if (P.kpt <= 4) {
+  const int kclass = chain_mw_kpt_class(P.kpt);
+  if (kclass == 4) {
     if (nt == 4) NK_MW_LAUNCH(4, 4); else if (nt == 2) NK_MW_LAUNCH(4, 2); else NK_MW_LAUNCH(4, 1);
-  } else if (P.kpt <= 8) {
+  } else if (kclass == 8) {
     if (nt == 4) NK_MW_LAUNCH(8, 4); else if (nt == 2) NK_MW_LAUNCH(8, 2); else NK_MW_LAUNCH(8, 1);
-  } else if (P.kpt <= 16) {
+  } else if (kclass == 16) {
     if (nt == 2) NK_MW_LAUNCH(16, 2); else NK_MW_LAUNCH(16, 1);
   } else {
     NK_MW_LAUNCH(MW_KPT, 1);
@@ -425,15 +410,6 @@ int launch_ref_minus_traj(nk_ctx* ctx, const double* ref, int64_t ref_stride, co
   return NK_OK;
 }
 
-static inline int chain_d_pad(int d_lift) { return d_lift > 0 ? d_lift + (d_lift & 1) : 0; }
-// LDS doubles without the control block
-static size_t chain_fixed_doubles(int d_lift) { return 3 * (size_t)CHAIN_ZU + 128 + (size_t)chain_d_pad(d_lift) + 2; }
-constexpr size_t CHAIN_LDS_MAX = 64 * 1024;
-bool lifted_chain_ok(int m, int pu, int d_lift) {
-  if (!(m >= 1 && m <= 128 && pu >= 0 && m + pu <= CHAIN_ZU)) return false;
-  return (chain_fixed_doubles(d_lift) + (size_t)pu * 16) * sizeof(double) <= CHAIN_LDS_MAX;  // >= 16 steps of controls per block
-}
-
 static bool g_chain_attr_set = false;
 
 int launch_lifted_chain(nk_ctx* ctx, const ChainArgs& a) {
@@ -441,14 +417,8 @@ int launch_lifted_chain(nk_ctx* ctx, const ChainArgs& a) {
   NK_REQUIRE(lifted_chain_ok(a.m, a.pu, dl), "lifted_chain: operators do not fit in LDS");
   NK_REQUIRE(a.batch >= 1 && a.T >= 1, "lifted_chain: bad sizes");
   const int pu = a.U ? a.pu : 0;
-  const size_t fixed = chain_fixed_doubles(dl) * sizeof(double);
-  int tb = a.T > 1 ? a.T - 1 : 1;
-  if (pu > 0) {
-    const size_t room = (CHAIN_LDS_MAX - fixed) / (sizeof(double) * (size_t)pu);
-    if ((size_t)tb > room) tb = (int)room;
-    if (tb > 1024) tb = 1024;
-  }
-  const size_t bytes = fixed + (size_t)tb * (size_t)pu * sizeof(double);
+  const int tb = chain_tb(pu, dl, a.T);
+  const size_t bytes = chain_lds_bytes(pu, dl, tb);
   if (!g_chain_attr_set) {
     NK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(lifted_chain_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                (int)CHAIN_LDS_MAX));

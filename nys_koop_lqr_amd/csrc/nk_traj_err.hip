@@ -15,15 +15,8 @@
 
 namespace nk {
 
-constexpr int TERR_TT = 8;            // most time steps per tile
-constexpr int TERR_LDS_DOUBLES = 4096;  // 32 KB of z rows per workgroup
+// (TERR_TT steps per tile at most, TERR_LDS_DOUBLES of z rows per workgroup, traj_err_tile: nk_chain_plan.h)
 constexpr int TERR_WAVES = 4;
-
-int traj_err_tile(int m) {
-  if (m < 1 || m > TERR_LDS_DOUBLES) return 0;
-  const int tt = TERR_LDS_DOUBLES / m;
-  return tt < TERR_TT ? tt : TERR_TT;
-}
 
 __device__ __forceinline__ void traj_err_partial_kernel_body(const double* __restrict__ Zall, int64_t z_stride,
                                                              const double* __restrict__ Cop, int64_t ldc,

@@ -167,7 +167,7 @@ def _fitted(nk, O, n=500, d=12, p=2, m=48, seed=3, ls=4.0, gamma=1e-4):
 @pytest.mark.parametrize("m,p", [(48, 2), (100, 6), (128, 6), (129, 3), (200, 1), (33, 0), (300, 2), (520, 6), (1100, 2)])
 def test_rollout_single_launch_and_stepwise_paths(nk, O, m, p):
     """m <= 128: the whole recursion (and the lift) in one launch with [A | B] resident in the registers of one workgroup;
-    larger m: one launch as well, [A | B] spread over ceil(m / 8) workgroups that exchange the state through memory
+    larger m: one launch as well, [A | B] spread over ceil(m / 16) workgroups that exchange the state through memory
     (lifted_chain_mw_kernel).  Both against the oracle's loop on the SAME operators (so that only the recursion is under
     test), single and batched, with and without the lifted trajectory."""
     reg, ref, X, Y, rng = _fitted(nk, O, n=max(4 * m, 300), d=9, p=p, m=m, seed=m + p)
@@ -197,7 +197,11 @@ def test_rollout_single_launch_and_stepwise_paths(nk, O, m, p):
     # T = 1: only the lifted initial state
     one = reg.rollout(X[3, :d], Useq[:, :1])
     assert relf(one, reg.C @ z0) < 1e-12
-    if m in (129, 200):  # more trajectories than the single-launch recursion takes: one GEMM per step
+    if m in (129, 200):
+        # 70 trajectories are 18 groups of four: more than the 16 groups that are chunked unconditionally, so the multi-workgroup
+        # recursion takes them only where 18 x ceil(m / 16) workgroups are resident at once (on 256 compute units they are: one
+        # launch), and one GEMM per step advances them elsewhere (csrc/nk_chain_plan.h).  The GEMM per step itself is held
+        # entry by entry in test_gpu_rollout_steps.py::test_one_launch_per_step[gemm-*], which asserts its route.
         nb = 70
         Ubig = rng.standard_normal((nb, 12, p))
         big = reg.rollout(X[:nb, :d], Ubig)
@@ -253,7 +257,8 @@ def test_closed_loop_batch(nk, O):
     # one shared reference broadcast over the batch
     xs2, _ = reg.closed_loop(K, phi0, phir[:1], 30)
     assert np.array_equal(xs2[0], xs[0])
-    # m > 128: stepwise path
+    # m > 128: the multi-workgroup recursion with a bias per trajectory (the stepwise paths of the closed loop, which this
+    # call only reaches after a give-up, are run in test_gpu_rollout_steps.py::test_closed_loop[loop-step-*, loop-gemm-*])
     reg2, _, X2, Y2, _ = _fitted(nk, O, n=600, d=6, p=2, m=150, seed=12)
     K2 = reg2.solve_lqr(c=0.5)
     f0 = reg2.lift(X2[:3, :6].T).T

@@ -8,8 +8,9 @@
 import numpy as np
 import pytest
 
+from rollout_reference import score_reference, score_sums
+
 pytestmark = pytest.mark.gpu
-EPS = np.finfo(float).eps
 NK_ERR_BAD_ARG = -1
 
 
@@ -18,10 +19,6 @@ def nk():
     import nys_koop_lqr_amd as nk
     nk.get_context()
     return nk
-
-
-def gamma_k(k):
-    return k * EPS / (1.0 - k * EPS)
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -86,21 +83,14 @@ def check_fused(tag, got, trajs):
     squares and adds dT of them (any order: at most dT roundings on a path).  Same for ssim with sqrt(ssim).  The device
     hands back sqrt(sse / dT) and 100 sqrt(sse) / sqrt(ssim): recovering the two sums from them costs a square root, a
     division, a square and a product each (gamma_8 on sse; ssim is recovered from both numbers: gamma_16).  The host side
-    of the comparison is evaluated in extended precision from the same lifted states, so it adds nothing."""
+    of the comparison is evaluated in extended precision from the same lifted states, so it adds nothing.  The bound itself
+    is rollout_reference.score_reference (shared with test_gpu_rollout_steps.py)."""
     Z, C = got["Z"], got["C"]
     k, T, m = Z.shape
     d = C.shape[0]
-    true = np.transpose(trajs, (0, 2, 1)).astype(np.longdouble)
-    sim = Z.astype(np.longdouble) @ C.T.astype(np.longdouble)
-    sse = np.sum((true - sim) ** 2, axis=(1, 2))
-    ssim = np.sum(sim ** 2, axis=(1, 2))
-    e = gamma_k(m + 2) * (np.abs(Z) @ np.abs(C).T)
-    e_norm = np.sqrt(np.sum(e.astype(np.longdouble) ** 2, axis=(1, 2)))
-    bound_sse = 2 * np.sqrt(sse) * e_norm + e_norm ** 2 + gamma_k(d * T) * sse + gamma_k(8) * sse
-    bound_ssim = 2 * np.sqrt(ssim) * e_norm + e_norm ** 2 + gamma_k(d * T) * ssim + gamma_k(16) * ssim
+    sse, ssim, bound_sse, bound_ssim = score_reference(Z, C, np.transpose(trajs, (0, 2, 1)))
     assert np.all(np.isfinite(got["abs17"])) and np.all(np.isfinite(got["rel17"]))
-    sse_dev = got["abs17"].astype(np.longdouble) ** 2 * (d * T)
-    ssim_dev = sse_dev * (np.longdouble(100.0) / got["rel17"].astype(np.longdouble)) ** 2
+    sse_dev, ssim_dev = score_sums(got["abs17"], got["rel17"], d, T)
     r_sse, r_ssim = np.abs(sse_dev - sse) / bound_sse, np.abs(ssim_dev - ssim) / bound_ssim
     print(f"\n[{tag}] m = {m}, d = {d}, T = {T}: |d sse| / bound max {float(r_sse.max()):.3e}, |d ssim| / bound max "
           f"{float(r_ssim.max()):.3e}; rel. deviation of sse max {float((np.abs(sse_dev - sse) / sse).max()):.2e}")
