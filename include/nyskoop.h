@@ -540,6 +540,32 @@ int nk_dare_batch(nk_ctx* ctx, const nk_dare_problem* problems, int32_t n, doubl
 int nk_model_lqr_gain_batch(nk_ctx* ctx, const nk_model* const* models, int32_t n, double c, const double* R_or_NULL,
                             double tol, int32_t max_iter, double* out_K, int32_t* out_status, int32_t* out_iters);
 int nk_model_lqr_cost(nk_ctx* ctx, const nk_model* model, double c, double* Q, int64_t ldq);
+/* ---- ONE problem past the batched solver's limits: the same doubling steps, stopping rule, status codes and NaN outputs as
+ *   nk_dare_batch, run as a chain of ordinary launches on the context's stream: every m x m product on the fp64 GEMM engine,
+ *   W = I + G H solved by a blocked LU with partial row pivoting (column blocks of 64; panel, row exchanges, row block and
+ *   trailing update are separate launches).  No kernel waits for another workgroup, and the results are the same bits from
+ *   call to call.  The host synchronises once per doubling step to read the status and the two norms of the stopping test.
+ *   Limits: 1 <= m <= NK_DARE_LARGE_MAX_M, 1 <= p <= NK_DARE_LARGE_MAX_P.  Workspace: about 9 M^2 doubles (M = m rounded up
+ *   to 16; 1.2 GB at m = 4096), a dedicated device allocation made for the call and freed before it returns; when it is
+ *   refused the call returns NK_ERR_OOM and writes nothing.
+ *   A, B, Q, R and out_K (p x m, dense), out_P (m x m, dense; may be NULL) are HOST or DEVICE memory, each on its own.
+ *   out_delta (may be NULL): the last relative step; out_iters may be NULL.  Everything is checked before anything is
+ *   queued or allocated: a bad argument is NK_ERR_BAD_ARG and no output is touched.  Ordinary contexts only. */
+#define NK_DARE_LARGE_MAX_M 10240
+#define NK_DARE_LARGE_MAX_P 32
+int nk_dare_large(nk_ctx* ctx, int32_t m, int32_t p, const double* A, int64_t lda, const double* B, int64_t ldb,
+                  const double* Q, int64_t ldq, const double* R, int64_t ldr, double tol, int32_t max_iter, double* out_K,
+                  double* out_P, double* out_delta, int32_t* out_status, int32_t* out_iters);
+/* The gain of one fitted model, K = dlqr(A, B, c sym(C'C), R), by the solver of nk_dare_large whatever m is: [A B] and C are
+ * read from the model's device allocation, the cost is formed on the device (fp64 GEMM engine).  R: p x p dense, host or
+ * device, or NULL for the identity.  out_K: p x m dense, host or device.  out_iters may be NULL. */
+int nk_model_lqr_gain(nk_ctx* ctx, const nk_model* model, double c, const double* R_or_NULL, double tol, int32_t max_iter,
+                      double* out_K, int32_t* out_status, int32_t* out_iters);
+/* Diagnostics: host wall clock of the calling thread's last nk_dare_large / nk_model_lqr_gain in milliseconds,
+ * out[0] = the solver in all, and -- only when NYSKOOP_DARE_TIMING is set in the environment, which synchronises the stream
+ * around every phase -- out[1] = the LU launches, out[2] = the products and elementwise kernels of the steps, out[3] = the
+ * per-step synchronisation; out[4] = steps taken. */
+int nk_dare_large_times(double out[5]);
 /* ---- rollout of explicit operators without a model (any estimator that exposes A, B, C: the exact-kernel comparator of
  *   benchmark_lqr_hjb.py:334-381, un-pickled gains): z0: batch x m lifted initial states; A: m x m, B: m x p, C: d x m
  *   (row-major, host or device); U, out_x, out_z as in nk_rollout. --------------------------------------------------- */

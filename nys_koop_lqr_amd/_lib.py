@@ -150,6 +150,10 @@ SIGNATURES = {
     "nk_model_lqr_gain_batch": (C.c_int, [_P, C.POINTER(_P), _I32, _D, _P, _D, _I32, _P, C.POINTER(_I32),
                                           C.POINTER(_I32)]),
     "nk_model_lqr_cost": (C.c_int, [_P, _P, _D, _P, _I64]),
+    "nk_dare_large": (C.c_int, [_P, _I32, _I32, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _D, _I32, _P, _P, C.POINTER(_D),
+                                C.POINTER(_I32), C.POINTER(_I32)]),
+    "nk_model_lqr_gain": (C.c_int, [_P, _P, _D, _P, _D, _I32, _P, C.POINTER(_I32), C.POINTER(_I32)]),
+    "nk_dare_large_times": (C.c_int, [C.POINTER(_D)]),
     "nk_linear_rollout": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P]),
     "nk_gemm_f32": (C.c_int, [_P, _I64, _I64, _I64, _P, _I64, _P, _I64, _P, _I64]),
     "nk_gemm": (C.c_int, [_P, C.c_int, C.c_int, _I64, _I64, _I64, _D, _P, _I64, _P, _I64, _D, _P, _I64]),
@@ -516,6 +520,51 @@ class Context:
             Ks.append(out[off:off + sz].reshape(int(p), int(m)).copy())
             off += sz
         return Ks, status[:n], iters[:n]
+
+    def dare_large(self, A, B, Q, R, tol=1e-13, max_iter=40, want_P=True):
+        """nk_dare_large: K = dlqr(A, B, Q, R) for ONE problem of any size (m <= 10240, p <= 32) by the launch-chain solver.
+        A, B, Q, R: NumPy arrays or float64 device tensors (2-D, unit inner stride), each on its own.  Returns
+        (K (p, m), P (m, m) or None, status, iterations, delta) with host arrays; status 0 = converged, 1 = max_iter
+        reached, 2 = non-finite / singular (outputs NaN)."""
+        a = Mat(A)
+        m = a.shape[0]
+        if a.shape != (m, m):
+            raise ValueError(f"A must be square, got {a.shape}")
+        if not (hasattr(B, "data_ptr") and hasattr(B, "stride")):
+            B = np.asarray(B, dtype=np.float64).reshape(m, -1) if m else np.zeros((0, 1))
+        b = Mat(B)
+        p = b.shape[1]
+        q, r = Mat(Q, m, m), Mat(R, p, p)
+        if b.shape[0] != m:
+            raise ValueError(f"B has {b.shape[0]} rows, A {m}")
+        K = np.full((p, m), np.nan)
+        P = np.full((m, m), np.nan) if want_P else None
+        status, iters, delta = _I32(-1), _I32(0), _D(np.nan)
+        self.wait_for(A, B, Q, R)
+        rc = self.lib.nk_dare_large(self.handle, m, p, a.ptr, a.ld, b.ptr, b.ld, q.ptr, q.ld, r.ptr, r.ld, float(tol),
+                                    int(max_iter), K.ctypes.data, P.ctypes.data if want_P else None, C.byref(delta),
+                                    C.byref(status), C.byref(iters))
+        check_mapped(rc)
+        return K, P, int(status.value), int(iters.value), float(delta.value)
+
+    def model_lqr_gain(self, model, m, p, c, R=None, tol=1e-13, max_iter=40):
+        """nk_model_lqr_gain: K = dlqr(A, B, c sym(C'C), R) of one device model by the launch-chain solver, whatever m is
+        (R = None: the identity).  Returns (K (p, m), status, iterations); a status other than 0 has a NaN gain."""
+        h = model.value if isinstance(model, C.c_void_p) else model
+        K = np.full((int(p), int(m)), np.nan)
+        Rm = None if R is None else np.ascontiguousarray(np.asarray(R, dtype=np.float64).reshape(int(p), int(p)))
+        status, iters = _I32(-1), _I32(0)
+        rc = self.lib.nk_model_lqr_gain(self.handle, h, float(c), None if Rm is None else Rm.ctypes.data, float(tol),
+                                        int(max_iter), K.ctypes.data, C.byref(status), C.byref(iters))
+        check_mapped(rc)
+        return K, int(status.value), int(iters.value)
+
+    def dare_large_times(self):
+        """nk_dare_large_times: dict(ms_total, ms_lu, ms_products, ms_sync, steps) of this thread's last nk_dare_large /
+        nk_model_lqr_gain; the split is taken only with NYSKOOP_DARE_TIMING set in the environment."""
+        v = (_D * 5)()
+        check(self.lib.nk_dare_large_times(v))
+        return dict(ms_total=v[0], ms_lu=v[1], ms_products=v[2], ms_sync=v[3], steps=int(v[4]))
 
     def model_lqr_cost(self, model, m, c):
         """nk_model_lqr_cost: the cost matrix c sym(C'C) (m x m) exactly as nk_model_lqr_gain_batch forms it."""

@@ -1,5 +1,6 @@
 // The Riccati entry points behind the C ABI (nk_dare_batch, nk_model_lqr_gain_batch, nk_model_lqr_cost): checks, staging of
-// the problems and one launch of the batched solver (nk_dare.hip) per workspace-capped group.
+// the problems and one launch of the batched solver (nk_dare.hip) per workspace-capped group; and the two entries of the
+// launch-chain solver for one problem of any size (nk_dare_large, nk_model_lqr_gain: nk_dare_large.hip).
 #include "nk_common.h"
 #include "nk_api_internal.h"
 
@@ -191,6 +192,82 @@ int nk_model_lqr_cost(nk_ctx* ctx, const nk_model* model, double c, double* Q, i
   int32_t st = 0;
   NK_TRY(dare_run(ctx, items, 0.0, 1, &st, nullptr));
   for (int i = 0; i < m; ++i) std::copy(q.begin() + (size_t)i * m, q.begin() + (size_t)(i + 1) * m, Q + (int64_t)i * ldq);
+  return NK_OK;
+}
+
+// The two entries of the launch-chain solver (nk_dare_large.hip): operands staged as nk_gemm stages its own (host memory is
+// copied into the arena, device memory is used in place), one solver call, the results copied back.
+static int dare_large_run(nk_ctx* ctx, DareLargeArgs& a, double* out_K, double* out_P, double* out_delta,
+                          int32_t* out_status, int32_t* out_iters) {
+  MatOut k, pm;
+  NK_TRY(stage_out(ctx, out_K, a.m, a.p, a.m, &k));
+  a.outK = k.dev; a.ldk = k.ld;
+  if (out_P) {
+    NK_TRY(stage_out(ctx, out_P, a.m, a.m, a.m, &pm));
+    a.outP = pm.dev; a.ldp = pm.ld;
+  }
+  DareLargeResult res;
+  NK_TRY(launch_dare_large(ctx, a, &res));
+  NK_TRY(finish_out(ctx, k));
+  if (out_P) NK_TRY(finish_out(ctx, pm));
+  NK_HIP(hipStreamSynchronize(ctx->stream));
+  *out_status = res.status;
+  if (out_iters) *out_iters = res.iters;
+  if (out_delta) *out_delta = res.delta;
+  return NK_OK;
+}
+
+int nk_dare_large(nk_ctx* ctx, int32_t m, int32_t p, const double* A, int64_t lda, const double* B, int64_t ldb,
+                  const double* Q, int64_t ldq, const double* R, int64_t ldr, double tol, int32_t max_iter, double* out_K,
+                  double* out_P, double* out_delta, int32_t* out_status, int32_t* out_iters) {
+  NK_TRY(check_ctx(ctx));
+  NK_TRY(dare_check_common(ctx, "nk_dare_large", tol, max_iter));
+  NK_REQUIRE(m >= 1 && m <= NK_DARE_LARGE_MAX_M, "nk_dare_large: m = %d must lie in 1 .. %d", m, NK_DARE_LARGE_MAX_M);
+  NK_REQUIRE(p >= 1 && p <= NK_DARE_LARGE_MAX_P, "nk_dare_large: p = %d must lie in 1 .. %d", p, NK_DARE_LARGE_MAX_P);
+  NK_REQUIRE(A && B && Q && R && out_K && out_status, "nk_dare_large: null argument");
+  NK_REQUIRE(lda >= m && ldq >= m && ldb >= p && ldr >= p, "nk_dare_large: leading dimension too small");
+  DareLargeArgs a;
+  a.m = m; a.p = p; a.tol = tol; a.max_iter = max_iter;
+  MatIn ma, mb, mq, mr;
+  NK_TRY(stage_in(ctx, A, lda, m, m, &ma));
+  NK_TRY(stage_in(ctx, B, ldb, m, p, &mb));
+  NK_TRY(stage_in(ctx, Q, ldq, m, m, &mq));
+  NK_TRY(stage_in(ctx, R, ldr, p, p, &mr));
+  a.A = ma.ptr; a.lda = ma.ld; a.B = mb.ptr; a.ldb = mb.ld; a.Q = mq.ptr; a.ldq = mq.ld; a.R = mr.ptr; a.ldr = mr.ld;
+  return dare_large_run(ctx, a, out_K, out_P, out_delta, out_status, out_iters);
+}
+
+int nk_model_lqr_gain(nk_ctx* ctx, const nk_model* model, double c, const double* R, double tol, int32_t max_iter,
+                      double* out_K, int32_t* out_status, int32_t* out_iters) {
+  NK_TRY(check_ctx(ctx));
+  NK_TRY(dare_check_common(ctx, "nk_model_lqr_gain", tol, max_iter));
+  NK_REQUIRE(model != nullptr, "nk_model_lqr_gain: the model is null");
+  NK_REQUIRE(model->device == ctx->device, "nk_model_lqr_gain: the model lives on device %d, the context on %d", model->device,
+             ctx->device);
+  NK_REQUIRE(model->has_ops, "nk_model_lqr_gain: the model has no fitted operators");
+  NK_REQUIRE(model->m >= 1 && model->m <= NK_DARE_LARGE_MAX_M, "nk_model_lqr_gain: m = %d must lie in 1 .. %d", model->m,
+             NK_DARE_LARGE_MAX_M);
+  NK_REQUIRE(model->p >= 1 && model->p <= NK_DARE_LARGE_MAX_P, "nk_model_lqr_gain: p = %d must lie in 1 .. %d", model->p,
+             NK_DARE_LARGE_MAX_P);
+  NK_REQUIRE(out_K != nullptr && out_status != nullptr, "nk_model_lqr_gain: null output");
+  NK_REQUIRE(std::isfinite(c) && c >= 0.0, "nk_model_lqr_gain: c must be finite and non-negative");
+  DareLargeArgs a;
+  a.m = model->m; a.p = model->p; a.d = model->d; a.tol = tol; a.max_iter = max_iter;
+  a.A = model->A; a.B = model->B; a.lda = a.ldb = model->m + model->p;
+  a.C = model->C; a.ldc = model->m; a.c = c;
+  if (R) {
+    MatIn mr;
+    NK_TRY(stage_in(ctx, R, model->p, model->p, model->p, &mr));
+    a.R = mr.ptr; a.ldr = mr.ld;
+  }
+  return dare_large_run(ctx, a, out_K, nullptr, nullptr, out_status, out_iters);
+}
+
+int nk_dare_large_times(double out[5]) {
+  NK_REQUIRE(out != nullptr, "nk_dare_large_times: out is null");
+  DareLargeTimes t;
+  dare_large_last_times(&t);
+  out[0] = t.ms_total; out[1] = t.ms_lu; out[2] = t.ms_products; out[3] = t.ms_sync; out[4] = (double)t.steps;
   return NK_OK;
 }
 

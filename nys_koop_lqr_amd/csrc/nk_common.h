@@ -641,6 +641,39 @@ inline int dare_pad(int m) { return (m + 15) & ~15; }
 inline size_t dare_ws_doubles(int M) { return (size_t)7 * M * M; }
 int launch_dare(nk_ctx* ctx, const DareRec* table_dev, int count, double tol, int max_iter);
 
+// ---- one Riccati problem of any size m <= NK_DARE_LARGE_MAX_M, p <= NK_DARE_LARGE_MAX_P as a chain of launches
+// (nk_dare_large.hip): the same doubling steps, the products through launch_gemm, the solve a blocked LU whose block steps
+// are separate kernels.  Every pointer is device memory.  Either Q (m x m) or C (d x m: the cost is c sym(C'C)) is set.
+// R: p x p, or nullptr = identity.  outK: p x m, outP: m x m or nullptr; both are NaN for a status other than 0.  The
+// workspace (dare_large_ws_bytes) is a dedicated allocation released before the call returns (NK_ERR_OOM when it does not
+// fit, nothing written).  Synchronises the stream once per doubling step.
+struct DareLargeArgs {
+  int m = 0, p = 0, d = 0;
+  const double* A = nullptr; int64_t lda = 0;
+  const double* B = nullptr; int64_t ldb = 0;
+  const double* Q = nullptr; int64_t ldq = 0;
+  const double* C = nullptr; int64_t ldc = 0;
+  double c = 0.0;
+  const double* R = nullptr; int64_t ldr = 0;
+  double tol = 1e-13;
+  int max_iter = 40;
+  double* outK = nullptr; int64_t ldk = 0;
+  double* outP = nullptr; int64_t ldp = 0;
+};
+struct DareLargeResult {
+  int status = 0, iters = 0;  // status as in DareRec
+  double delta = 0.0;         // last relative step (NaN when no step was taken)
+};
+size_t dare_large_ws_bytes(int m);
+int launch_dare_large(nk_ctx* ctx, const DareLargeArgs& args, DareLargeResult* res);
+// host wall clock of the calling thread's last launch_dare_large.  The split (LU launches, products, the per-step
+// synchronisation) is taken only with NYSKOOP_DARE_TIMING set, which synchronises the stream around every phase.
+struct DareLargeTimes {
+  double ms_total = 0.0, ms_lu = 0.0, ms_products = 0.0, ms_sync = 0.0;
+  int steps = 0;
+};
+void dare_large_last_times(DareLargeTimes* out);
+
 // ---- landmark selection (nk_landmarks.hip): partial pivoted Cholesky of K(Y, Y) over the candidate rows rng ([begin, end)
 // pairs of rows of the device matrix Y, nc rows in all), m steps queued without a host round trip.  positions: the
 // m_selected candidate positions in pick order; resid: m entries, trace: m + 1 entries (zero past the stop).  The factor

@@ -1,6 +1,7 @@
 """Discrete LQR.  dlqr is the host Riccati solve (scipy) and the default everywhere; dare_doubling is the NumPy statement
 of the structure-preserving doubling iteration that the batched device solver runs (csrc/nk_dare.hip, one workgroup per
-problem), and dlqr_batch hands a list of problems to that solver in one call.
+problem), and dlqr_batch hands a list of problems to that solver in one call.  dlqr_device solves one problem of any
+size with the launch-chain form of the same iteration (csrc/nk_dare_large.hip).
 
 Stands in for `control.dlqr(A, B, Q, R)` used at benchmark_lqr_cloth.py:262, benchmark_lqr_classic.py:288 and
 benchmark_lqr_hjb.py:293,356 (python-control is not a dependency here): K = (B'PB + R)^-1 B'PA with P the
@@ -89,6 +90,19 @@ def dlqr_batch(As, Bs, Qs, Rs, tol=1e-13, max_iter=40):
     from . import _lib
     Ks, Ps, status, iters, _ = _lib.get_context().dare_batch(As, Bs, Qs, Rs, tol=tol, max_iter=max_iter)
     return Ks, Ps, status, iters
+
+
+def dlqr_device(A, B, Q, R, tol=1e-13, max_iter=40):
+    """(K, P) = dlqr(A, B, Q, R) on the device for ONE problem of any size (nk_dare_large: the steps of dare_doubling as a
+    chain of launches, products on the fp64 GEMM engine, W solved by a blocked pivoted LU; m <= 10240, p <= 32).  The
+    operands are NumPy arrays or float64 device tensors.  Raises np.linalg.LinAlgError when the iteration does not
+    converge or breaks down, as scipy does."""
+    from . import _lib
+    K, P, status, _, _ = _lib.get_context().dare_large(A, B, Q, R, tol=tol, max_iter=max_iter, want_P=True)
+    if status != 0:
+        raise np.linalg.LinAlgError(f"device Riccati solve failed with status {status} "
+                                    "(1: max_iter reached, 2: non-finite values or a singular pivot)")
+    return K, P
 
 
 def cloth_gain_for_simulator(K):

@@ -1,7 +1,8 @@
 """Host-side mirror of the reference's estimator surface (regressors.py:32-55, 114-178): same constructor, same
 public attributes, same fit / lift / predict shapes and error behaviour, so that the reference's drivers
 (GridSearchCV, validate_dyn_sys, lqr_control, pickling) run unchanged -- with the arithmetic done by the HIP
-kernels of libnyskoop.so through ctypes.  The DARE (control.dlqr in the reference) stays on the host.
+kernels of libnyskoop.so through ctypes.  The DARE (control.dlqr in the reference) stays on the host by default;
+solve_lqr(device=True) runs it on the device (the batched solver up to m = 256, the launch-chain solver beyond).
 """
 import ctypes as C
 import time
@@ -16,13 +17,31 @@ from .lqr import dlqr
 
 
 def _lqr_gain_batch(regs, c, R=None, tol=1e-13, max_iter=40):
-    """(Ks, status, iterations) of nk_model_lqr_gain_batch for fitted regressors (one device call, chunked by the
-    library).  A module-level seam: tests without a GPU replace it."""
+    """(Ks, status, iterations) of the device Riccati solvers for fitted regressors, in the callers' order.  The models
+    within the batched solver's limits (m <= 256, p <= 8) go through nk_model_lqr_gain_batch together (one device call,
+    chunked by the library; a model's result does not depend on what else the call holds); every other model goes through
+    nk_model_lqr_gain, the launch-chain solver, one call each.  A module-level seam: tests without a GPU replace it."""
     ctx = _lib.get_context()
     handles = [r._ensure_model() for r in regs]
     dims = [(int(r._landmark_shape()[1]), int(r.n_inputs)) for r in regs]
-    return ctx.model_lqr_gain_batch(handles, c, R, tol=tol, max_iter=max_iter, dims=dims)
+    small = [u for u, (m, p) in enumerate(dims) if m <= DARE_BATCH_MAX_M and p <= DARE_BATCH_MAX_P]
+    if len(small) == len(regs):
+        return ctx.model_lqr_gain_batch(handles, c, R, tol=tol, max_iter=max_iter, dims=dims)
+    Ks = [None] * len(regs)
+    status = np.full(len(regs), -1, dtype=np.int32)
+    iters = np.zeros(len(regs), dtype=np.int32)
+    if small:
+        Kb, sb, ib = ctx.model_lqr_gain_batch([handles[u] for u in small], c, R, tol=tol, max_iter=max_iter,
+                                              dims=[dims[u] for u in small])
+        for k, u in enumerate(small):
+            Ks[u], status[u], iters[u] = Kb[k], sb[k], ib[k]
+    for u, (m, p) in enumerate(dims):
+        if Ks[u] is None:
+            Ks[u], status[u], iters[u] = ctx.model_lqr_gain(handles[u], m, p, c, R, tol=tol, max_iter=max_iter)
+    return Ks, status, iters
 
+
+DARE_BATCH_MAX_M, DARE_BATCH_MAX_P = 256, 8  # limits of nk_dare_batch (include/nyskoop.h)
 
 
 def _is_device_tensor(x):
@@ -454,9 +473,10 @@ class _DeviceModelRegressor(KoopmanRegressor):
     def solve_lqr(self, Q=None, R=None, c=0.0075, device=False):
         """Host DARE, standing in for control.dlqr(A, B, Q, R) (benchmark_lqr_cloth.py:238-240,262): by default
         Q = c * C^T C symmetrised and R = I.  Returns the gain K (p x m).
-        device=True: the batched device solver with this one model (nk_model_lqr_gain_batch: Q = c sym(C'C) formed on the
-        device from the model's own operators, so Q must be None; m <= 256, p <= 8); raises np.linalg.LinAlgError when
-        the iteration does not converge or breaks down, as scipy does."""
+        device=True: the device solvers with this one model (Q = c sym(C'C) formed on the device from the model's own
+        operators, so Q must be None): the batched solver for m <= 256, p <= 8 (nk_model_lqr_gain_batch), the
+        launch-chain solver beyond (nk_model_lqr_gain; m <= 10240, p <= 32); raises np.linalg.LinAlgError when the
+        iteration does not converge or breaks down, as scipy does."""
         if device:
             if Q is not None:
                 raise ValueError("solve_lqr(device=True) forms Q = c sym(C'C) on the device: pass c, not Q")
@@ -754,7 +774,8 @@ class KoopmanKernelRegressor(KoopmanRegressor):
         self.weights = Wd.cpu().numpy()
         self.Kout = Kout.cpu().numpy()
         self.Kout_sqrt_inv = Sinv.cpu().numpy()
-        self._dev_cache = dict(Sinv=Sinv, Ys=Ys_d, device=ctx.device)  # lift() multiplies from HBM
+        # lift() multiplies from HBM; solve_lqr(device=True) reads the operators there
+        self._dev_cache = dict(Sinv=Sinv, Ys=Ys_d, G_ls=G_ls, Cd=Cd, device=ctx.device)
 
     def __getstate__(self):
         state = dict(self.__dict__)
@@ -814,6 +835,45 @@ class KoopmanKernelRegressor(KoopmanRegressor):
             return out.cpu().numpy()
         Kout_test = self.kernel.kernel(np.ascontiguousarray(self.training_outputs.T), Xq)
         return self._gemm(ctx, self.Kout_sqrt_inv, Kout_test)
+
+    def solve_lqr(self, Q=None, R=None, c=1.0, device=False):
+        """The gain of the exact model (benchmark_lqr_hjb.py:356: control.dlqr on the N x N operators): by default
+        Q = c * C^T C symmetrised and R = I.  Returns K (p x N).  On the host it is lqr.dlqr (scipy); device=True runs
+        the launch-chain Riccati solver (nk_dare_large) on the operators, read from HBM where the fit left them there
+        (nothing N x N crosses PCIe again) and from the host attributes after a host-composed fit or un-pickling.
+        Raises np.linalg.LinAlgError when the device iteration does not converge or breaks down."""
+        p = int(self.n_inputs)
+        if not device:
+            if Q is None:
+                S = self.C.T @ self.C
+                Q = c * ((S + S.T) / 2)
+            if R is None:
+                R = np.eye(p)
+            K, _ = dlqr(self.A, self.B, Q, R)
+            return K
+        ctx = _lib.get_context()
+        N = self.A.shape[0]
+        if R is None:
+            R = np.eye(p)
+        cache = self.__dict__.get("_dev_cache")
+        if cache is not None and cache["device"] == ctx.device and "G_ls" in cache:
+            import torch
+            G_ls, Cd = cache["G_ls"], cache["Cd"]
+            A_op, B_op = G_ls[:, :N], G_ls[:, N:]
+            if Q is None:
+                Qd = self._dgemm(ctx, Cd, Cd, torch.empty((N, N), dtype=torch.float64, device=G_ls.device), tA=1)
+                Q = (Qd + Qd.T).mul_(0.5 * c)
+            torch.cuda.synchronize(G_ls.device)
+        else:
+            A_op, B_op = np.asarray(self.A), np.asarray(self.B).reshape(N, p)
+            if Q is None:
+                S = self.C.T @ self.C
+                Q = c * ((S + S.T) / 2)
+        K, _, status, _, _ = ctx.dare_large(A_op, B_op, Q, R, want_P=False)
+        if status != 0:
+            raise np.linalg.LinAlgError(f"device Riccati solve failed with status {status} "
+                                        "(1: max_iter reached, 2: non-finite values or a singular pivot)")
+        return K
 
 
 class KoopmanSplineRegressor(_DeviceModelRegressor):
