@@ -463,6 +463,51 @@ typedef struct nk_plant_unit {
 } nk_plant_unit;
 int nk_plant_loop_multi(nk_ctx* ctx, int plant, double Ts, int32_t steps, const nk_plant_unit* units, int32_t n_units,
                         const double* u_opt, int32_t n_uopt, double* out_x, double* out_u, double* scores);
+/* ---- the same loops around a plant the CALLER describes: a polynomial vector field as a table of monomials, up to four
+ *   states and four inputs, under one Runge-Kutta step of length Ts.
+ *     f_row(x, u) = sum over the row's terms of coef * prod_k x_k^ex[k] * prod_j u_j^eu[j]
+ *   The order of operations is part of the interface; the host build, the device build and the Python class
+ *   PolynomialSystem give the same bits (plain IEEE operations, no fused multiply-add):
+ *     term:  v = coef; for k = 0 .. d-1: v = v * x_k, ex[k] times; then for j = 0 .. p-1: v = v * u_j, eu[j] times;
+ *     row:   f[row] starts at 0.0 and receives f[row] = f[row] + v in table order;
+ *     step:  k2 = f(x + k1 Ts / 2.0), k3 = f(x + k2 Ts / 2.0), x + (Ts / 6.0) (((k1 + 2.0 k2) + 2.0 k3) + k4) with
+ *            k4 = f(x + k3 Ts) (k4_at_k1 = 0: classical RK4) or f(x + k1 Ts) (k4_at_k1 = 1: the reference's variant, with
+ *            which NK_PLANT_DUFFING, _DOUBLE_INTEGRATOR and _HJB can be written as tables).
+ *   A description is checked by every entry point before anything is queued; NK_ERR_BAD_ARG with the field or the term
+ *   index in the message for: d or p outside 1..4, n_terms outside 1..32, a row outside 0..d-1, an exponent set for
+ *   k >= d or j >= p, a term of degree above 5, a non-finite coef, a non-finite or non-positive Ts, k4_at_k1 not 0 or 1.
+ *   The step function: x_next = plant(x, u) on the HOST (x, x_next: d doubles, u: p doubles; no context, no GPU needed).
+ *   The loop: the contract of nk_plant_loop with K: p x m, out_u: batch x steps x p; the model's d and p must equal the
+ *   plant's.  u_j = sum_l W[l][j] (k(z_l, x_ref) - k(z_l, x_t)) with W = K_mm^{-1/2} K^T folded once per call.
+ *   The multi form: the contract of nk_plant_loop_multi with nk_plant_unit.K: p x m, u_opt: n_uopt x steps x p, and the
+ *   sums of the scores extended over the inputs in index order:
+ *     sse_u = sum_t sum_j (u_tj - uopt_tj)^2,  ss_opt = sum_t sum_j uopt_tj^2  (both in (t, j) order),
+ *     J = sum_k x0_k^2, then per step J = (J + sx) + su with sx = sum_k x_{t+1,k}^2 and su = sum_j u_tj^2 (rounded
+ *     squares, index order),  u_absmax over t and j, NaN from the first NaN control on.
+ *   Limit on m per class of (states, inputs) -- the landmarks, their reference values and p weights each stay in the
+ *   registers of one workgroup of 16 waves:  d = 1, 2: m <= 4096 for p = 1, 2 and m <= 2048 for p = 3, 4;
+ *   d = 3, 4: m <= 2048 for p = 1, 2 and m <= 1024 for p = 3, 4.  Beyond its class limit a call is NK_ERR_BAD_ARG. */
+#define NK_POLY_MAX_D 4
+#define NK_POLY_MAX_P 4
+#define NK_POLY_MAX_TERMS 32
+#define NK_POLY_MAX_DEGREE 5 /* sum of a term's exponents */
+typedef struct nk_poly_term {
+  int32_t row;   /* the state whose derivative the term belongs to */
+  uint8_t ex[4]; /* exponents of the states */
+  uint8_t eu[4]; /* exponents of the inputs */
+  double coef;
+} nk_poly_term;
+typedef struct nk_poly_plant {
+  int32_t d, p, n_terms, k4_at_k1;
+  double Ts;
+  nk_poly_term terms[NK_POLY_MAX_TERMS];
+} nk_poly_plant;
+int nk_poly_plant_step(const nk_poly_plant* plant, const double* x, const double* u, double* x_next);
+int nk_poly_plant_loop(nk_ctx* ctx, const nk_model* model, const nk_poly_plant* plant, const double* K, const double* x0,
+                       const double* x_ref, int32_t steps, int32_t batch, double* out_x, double* out_u);
+int nk_poly_plant_loop_multi(nk_ctx* ctx, const nk_poly_plant* plant, int32_t steps, const nk_plant_unit* units,
+                             int32_t n_units, const double* u_opt, int32_t n_uopt, double* out_x, double* out_u,
+                             double* scores);
 /* ---- the multi-model form of the lifted closed loop, scored on the device: the control branch of the cloth sweep
  *   (benchmark_lqr_cloth.py:213-270: per seed and estimator fit, gain, lqr_control) in ONE call after the fits and gains.
  *   Every unit has its own model, gain, lifted initial state and lifted reference; the units of a call share `steps` and

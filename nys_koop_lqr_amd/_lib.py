@@ -53,6 +53,17 @@ class PlantUnit(C.Structure):
                 ("uopt", C.c_int32), ("reserved", C.c_int32)]
 
 
+class PolyTerm(C.Structure):
+    """nk_poly_term (include/nyskoop.h): one monomial of a polynomial plant, 24 bytes."""
+    _fields_ = [("row", C.c_int32), ("ex", C.c_uint8 * 4), ("eu", C.c_uint8 * 4), ("coef", C.c_double)]
+
+
+class PolyPlant(C.Structure):
+    """nk_poly_plant (include/nyskoop.h): the table of a polynomial plant."""
+    _fields_ = [("d", C.c_int32), ("p", C.c_int32), ("n_terms", C.c_int32), ("k4_at_k1", C.c_int32), ("Ts", C.c_double),
+                ("terms", PolyTerm * 32)]
+
+
 class LoopUnit(C.Structure):
     """nk_loop_unit (include/nyskoop.h), one unit of nk_closed_loop_multi: six pointers (model, K, phi0, phi_ref, target,
     u_init): 48 bytes, no padding."""
@@ -145,6 +156,10 @@ SIGNATURES = {
     "nk_plant_step": (C.c_int, [C.c_int, _D, _P, _P, _P]),
     "nk_plant_loop": (C.c_int, [_P, _P, C.c_int, _D, _P, _P, _P, _I32, _I32, _P, _P]),
     "nk_plant_loop_multi": (C.c_int, [_P, C.c_int, _D, _I32, C.POINTER(PlantUnit), _I32, _P, _I32, _P, _P, _P]),
+    "nk_poly_plant_step": (C.c_int, [C.POINTER(PolyPlant), _P, _P, _P]),
+    "nk_poly_plant_loop": (C.c_int, [_P, _P, C.POINTER(PolyPlant), _P, _P, _P, _I32, _I32, _P, _P]),
+    "nk_poly_plant_loop_multi": (C.c_int, [_P, C.POINTER(PolyPlant), _I32, C.POINTER(PlantUnit), _I32, _P, _I32, _P, _P,
+                                           _P]),
     "nk_closed_loop_multi": (C.c_int, [_P, _I32, _D, C.POINTER(LoopUnit), _I32, _P, _P, _P, _P, _P]),
     "nk_dare_batch": (C.c_int, [_P, C.POINTER(DareProblem), _I32, _D, _I32, C.POINTER(_I32), C.POINTER(_I32)]),
     "nk_model_lqr_gain_batch": (C.c_int, [_P, C.POINTER(_P), _I32, _D, _P, _D, _I32, _P, C.POINTER(_I32),
@@ -391,6 +406,40 @@ class Context:
         ptr = lambda a: None if a is None else a.ctypes.data
         rc = self.lib.nk_plant_loop_multi(self.handle, int(plant_id), float(Ts), steps, arr, n, ptr(uo), n_uopt, ptr(ox),
                                           ptr(ou), ptr(sc))
+        check_mapped(rc)
+        return sc, ox, ou
+
+    def poly_plant_loop_multi(self, descriptor, steps, models, gains, x0s, x_refs, u_opt=None, uopt_rows=None, want_x=False,
+                              want_u=False, want_scores=True):
+        """nk_poly_plant_loop_multi: plant_loop_multi around a polynomial plant (descriptor: a PolyPlant) with p inputs.
+        gains: one (p, m) array per unit; u_opt: (n_uopt, steps, p) or None.  Returns (scores (n_units, 4) or None, states
+        (n_units, steps + 1, d) or None, controls (n_units, steps, p) or None)."""
+        n = len(models)
+        steps = int(steps)
+        d, p = int(descriptor.d), int(descriptor.p)
+        x0s = np.ascontiguousarray(np.asarray(x0s, dtype=np.float64).reshape(n, d))
+        x_refs = np.ascontiguousarray(np.asarray(x_refs, dtype=np.float64).reshape(n, d))
+        if len(gains) != n:
+            raise ValueError(f"{len(gains)} gains for {n} models")
+        Ks = [np.ascontiguousarray(K, dtype=np.float64).reshape(-1) for K in gains]
+        uo, n_uopt = None, 0
+        if u_opt is not None:
+            uo = np.ascontiguousarray(np.asarray(u_opt, dtype=np.float64).reshape(-1, max(steps, 1) * p))
+            n_uopt = uo.shape[0]
+        if uopt_rows is None:
+            uopt_rows = [0 if n_uopt else -1] * n
+        arr = (PlantUnit * max(n, 1))()
+        for i in range(n):
+            h = models[i]
+            arr[i].model = h.value if isinstance(h, C.c_void_p) else h
+            arr[i].K, arr[i].x0, arr[i].x_ref = Ks[i].ctypes.data, x0s[i].ctypes.data, x_refs[i].ctypes.data
+            arr[i].uopt = int(uopt_rows[i])
+        sc = np.full((n, 4), np.nan) if want_scores else None
+        ox = np.empty((n, max(steps, 0) + 1, d)) if want_x else None
+        ou = np.empty((n, max(steps, 0), p)) if want_u else None
+        ptr = lambda a: None if a is None else a.ctypes.data
+        rc = self.lib.nk_poly_plant_loop_multi(self.handle, C.byref(descriptor), steps, arr, n, ptr(uo), n_uopt, ptr(ox),
+                                               ptr(ou), ptr(sc))
         check_mapped(rc)
         return sc, ox, ou
 

@@ -1,10 +1,11 @@
-// Closed loops that run as one launch behind the C ABI: the plant loops (nk_plant_step, nk_plant_loop, nk_plant_loop_multi;
-// nk_plant_loop.hip) and the lifted loop of many models (nk_closed_loop_multi; nk_loop_multi.hip).  The unit-table calls
+// Closed loops that run as one launch behind the C ABI: the plant loops (nk_plant_step, nk_plant_loop, nk_plant_loop_multi and
+// their forms for a polynomial plant the caller describes, nk_poly_plant_*; nk_plant_loop.hip) and the lifted loop of many models (nk_closed_loop_multi; nk_loop_multi.hip).  The unit-table calls
 // check every unit, lay its host operands out in one staging block (nk_unit_pack.h), move it with one copy, build the
 // table of device records, launch, and bring the results back behind one synchronisation.
 #include "nk_common.h"
 #include "nk_api_internal.h"
 #include "nk_plant.h"
+#include "nk_poly_plant.h"
 
 #include <cmath>
 #include <string>
@@ -22,6 +23,30 @@ static int check_plant_model(nk_ctx* ctx, const char* who, int unit, const nk_mo
              plant_name(plant), plant_dim(plant), mdl->d);
   NK_REQUIRE(mdl->m >= 1 && mdl->m <= plant_loop_max_m(), "%s: %sm = %d landmarks, at most %d fit one workgroup", who,
              at().c_str(), mdl->m, plant_loop_max_m());
+  NK_REQUIRE(mdl->kind == NK_MODEL_SPLINE
+                 ? mdl->ktype == NK_KERNEL_TPS
+                 : (mdl->ktype == NK_KERNEL_RBF || mdl->ktype == NK_KERNEL_MATERN52 || mdl->ktype == NK_KERNEL_LINEAR),
+             "%s: %skernel type %d is not supported for this model", who, at().c_str(), mdl->ktype);
+  return NK_OK;
+}
+
+// The plant description of the polynomial-plant entries: the one validation of nk_poly_plant.h, its message behind `who`.
+static int check_poly_plant(const char* who, const nk_poly_plant* plant) {
+  char msg[160];
+  NK_REQUIRE(poly_plant_check(plant, msg, sizeof msg), "%s: %s", who, msg);
+  return NK_OK;
+}
+
+// One model against a (validated) polynomial plant, for both polynomial-plant loops; unit as in check_plant_model.
+static int check_poly_model(nk_ctx* ctx, const char* who, int unit, const nk_model* mdl, const nk_poly_plant& pl) {
+  auto at = [unit] { return unit >= 0 ? "unit " + std::to_string(unit) + ": " : std::string(); };  // (a failed check only)
+  NK_REQUIRE(mdl->device == ctx->device, "%s: %sthe model lives on device %d, the context on %d", who, at().c_str(),
+             mdl->device, ctx->device);
+  NK_REQUIRE(mdl->p == pl.p, "%s: %sthe plant has %d inputs, the model has %d", who, at().c_str(), pl.p, mdl->p);
+  NK_REQUIRE(mdl->d == pl.d, "%s: %sthe plant has %d states, the model has %d", who, at().c_str(), pl.d, mdl->d);
+  const int max_m = poly_loop_max_m(pl.d, pl.p);
+  NK_REQUIRE(mdl->m >= 1 && mdl->m <= max_m, "%s: %sm = %d landmarks, at most %d fit one workgroup with %d states and %d inputs",
+             who, at().c_str(), mdl->m, max_m, pl.d, pl.p);
   NK_REQUIRE(mdl->kind == NK_MODEL_SPLINE
                  ? mdl->ktype == NK_KERNEL_TPS
                  : (mdl->ktype == NK_KERNEL_RBF || mdl->ktype == NK_KERNEL_MATERN52 || mdl->ktype == NK_KERNEL_LINEAR),
@@ -133,6 +158,119 @@ int nk_plant_loop_multi(nk_ctx* ctx, int plant, double Ts, int32_t steps, const 
     ktypes[u] = mdl->ktype;
   }
   NK_TRY(launch_plant_loop_multi(ctx, plant, Ts, steps, recs.data(), ktypes.data(), n_units));
+  if (out_x) NK_TRY(finish_out(ctx, ox));
+  if (out_u) NK_TRY(finish_out(ctx, ou));
+  if (scores) NK_HIP(hipMemcpyAsync(scores, d_sc, (size_t)n_units * 32, hipMemcpyDeviceToHost, ctx->stream));
+  NK_HIP(hipStreamSynchronize(ctx->stream));  // (the staging block and recs are read by the copies queued above)
+  return NK_OK;
+}
+
+int nk_poly_plant_step(const nk_poly_plant* plant, const double* x, const double* u, double* x_next) {
+  NK_TRY(check_poly_plant("nk_poly_plant_step", plant));
+  NK_REQUIRE(x && u && x_next, "nk_poly_plant_step: null argument");
+  poly_plant_step_host(*plant, x, u, x_next);
+  return NK_OK;
+}
+
+int nk_poly_plant_loop(nk_ctx* ctx, const nk_model* mdl, const nk_poly_plant* plant, const double* K, const double* x0,
+                       const double* x_ref, int32_t steps, int32_t batch, double* out_x, double* out_u) {
+  NK_TRY(check_ctx(ctx));
+  NK_REQUIRE(!ctx_recording(ctx), "nk_poly_plant_loop: not available to the members of a lock-step group");
+  NK_REQUIRE(mdl && K && x0 && x_ref && out_x && out_u, "nk_poly_plant_loop: null argument");
+  NK_TRY(check_poly_plant("nk_poly_plant_loop", plant));
+  NK_TRY(check_poly_model(ctx, "nk_poly_plant_loop", -1, mdl, *plant));
+  NK_REQUIRE(steps >= 1 && batch >= 1, "nk_poly_plant_loop: steps = %d and batch = %d must be positive", steps, batch);
+  const int m = mdl->m, d = mdl->d, p = mdl->p;
+  MatIn k, xi, xr;
+  MatOut ox, ou;
+  NK_TRY(stage_in(ctx, K, m, p, m, &k));
+  NK_TRY(stage_in(ctx, x0, d, batch, d, &xi));
+  NK_TRY(stage_in(ctx, x_ref, d, batch, d, &xr));
+  NK_TRY(stage_out(ctx, out_x, d, (int64_t)batch * (steps + 1), d, &ox));
+  NK_TRY(stage_out(ctx, out_u, p, (int64_t)batch * steps, p, &ou));
+  // u = K phi = K (k S^-1)^T = (S^-1 K^T)^T k: W = S^-1 K^T (m x p) by ONE product; a spline model lifts with the raw
+  // block, W = K^T is the gain read with its strides exchanged
+  const double* w = k.ptr;
+  int64_t w_ls = 1, w_js = k.ld;
+  if (mdl->kind != NK_MODEL_SPLINE) {
+    double* wf = nullptr;
+    NK_TRY(arena_alloc_t(ctx, (size_t)m * p + 2, &wf));
+    NK_TRY(launch_gemm(ctx, false, true, m, p, m, 1.0, mdl->Sinv, m, k.ptr, k.ld, 0.0, wf, p));
+    w = wf;
+    w_ls = p;
+    w_js = 1;
+  }
+  NK_TRY(launch_poly_loop(ctx, mdl, *plant, w, w_ls, w_js, xi.ptr, xi.ld, xr.ptr, xr.ld, steps, batch, ox.dev, ox.ld, ou.dev,
+                          ou.ld));
+  NK_TRY(finish_out(ctx, ox));
+  NK_TRY(finish_out(ctx, ou));
+  NK_HIP(hipStreamSynchronize(ctx->stream));
+  return NK_OK;
+}
+
+int nk_poly_plant_loop_multi(nk_ctx* ctx, const nk_poly_plant* plant, int32_t steps, const nk_plant_unit* units,
+                             int32_t n_units, const double* u_opt, int32_t n_uopt, double* out_x, double* out_u,
+                             double* scores) {
+  NK_TRY(check_ctx(ctx));
+  NK_REQUIRE(!ctx_recording(ctx), "nk_poly_plant_loop_multi: not available to the members of a lock-step group");
+  NK_TRY(check_poly_plant("nk_poly_plant_loop_multi", plant));
+  NK_REQUIRE(units != nullptr && n_units >= 1, "nk_poly_plant_loop_multi: n_units = %d units at %p: at least one is needed",
+             n_units, (const void*)units);
+  NK_REQUIRE(steps >= 1, "nk_poly_plant_loop_multi: steps = %d must be positive", steps);
+  NK_REQUIRE(out_x || out_u || scores, "nk_poly_plant_loop_multi: out_x, out_u and scores are all null: nothing to return");
+  NK_REQUIRE(n_uopt >= 0 && (n_uopt == 0 || u_opt != nullptr), "nk_poly_plant_loop_multi: n_uopt = %d rows of a null u_opt",
+             n_uopt);
+  NK_REQUIRE(!is_device_ptr(scores), "nk_poly_plant_loop_multi: scores must be host memory");
+  const int d = plant->d, p = plant->p;
+  // every unit is checked before anything is queued; its gain, initial state and reference are laid out on the way
+  UnitPack in, folds;
+  std::vector<PolyUnitOffsets> off((size_t)n_units);
+  for (int u = 0; u < n_units; ++u) {
+    const nk_plant_unit& un = units[u];
+    NK_REQUIRE(un.model && un.K && un.x0 && un.x_ref, "nk_poly_plant_loop_multi: unit %d: null argument", u);
+    NK_TRY(check_poly_model(ctx, "nk_poly_plant_loop_multi", u, un.model, *plant));
+    NK_REQUIRE(un.uopt >= -1 && un.uopt < n_uopt, "nk_poly_plant_loop_multi: unit %d: uopt = %d, u_opt has %d rows", u,
+               un.uopt, n_uopt);
+    NK_REQUIRE(!is_device_ptr(un.K) && !is_device_ptr(un.x0) && !is_device_ptr(un.x_ref),
+               "nk_poly_plant_loop_multi: unit %d: K, x0 and x_ref must be host memory", u);
+    off[u] = pack_poly_unit(in, folds, un.K, un.x0, un.x_ref, (size_t)un.model->m, (size_t)d, (size_t)p,
+                            un.model->kind != NK_MODEL_SPLINE);
+  }
+  double *d_in = nullptr, *d_w = nullptr, *d_sc = nullptr;
+  NK_TRY(stage_pack(ctx, in, &d_in));
+  if (folds.doubles()) NK_TRY(arena_alloc_t(ctx, folds.doubles(), &d_w));
+  if (scores) NK_TRY(arena_alloc_t(ctx, (size_t)n_units * 4, &d_sc));
+  MatIn uo;
+  MatOut ox, ou;
+  const int64_t sp = (int64_t)steps * p;
+  if (n_uopt > 0) NK_TRY(stage_in(ctx, u_opt, sp, n_uopt, sp, &uo));
+  if (out_x) NK_TRY(stage_out(ctx, out_x, d, (int64_t)n_units * (steps + 1), d, &ox));
+  if (out_u) NK_TRY(stage_out(ctx, out_u, p, (int64_t)n_units * steps, p, &ou));
+  std::vector<PolyLoopUnit> recs((size_t)n_units);
+  std::vector<int> ktypes((size_t)n_units);
+  for (int u = 0; u < n_units; ++u) {
+    const nk_plant_unit& un = units[u];
+    const nk_model* mdl = un.model;
+    const int m = mdl->m;
+    // the fold of nk_poly_plant_loop by the same call on the same operands (the gain rows have their leading dimension
+    // there); the folds of all units are queued back to back, nothing waits between them
+    const int64_t ldk = (int64_t)gain_row_reserve((size_t)m);
+    PolyLoopUnit& r = recs[u];
+    r.w = d_in + off[u].K; r.w_ls = 1; r.w_js = ldk;
+    if (mdl->kind != NK_MODEL_SPLINE) {
+      double* wf = d_w + off[u].w;
+      NK_TRY(launch_gemm(ctx, false, true, m, p, m, 1.0, mdl->Sinv, m, d_in + off[u].K, ldk, 0.0, wf, p));
+      r.w = wf; r.w_ls = p; r.w_js = 1;
+    }
+    r.Z = mdl->Z; r.winv = mdl->winv; r.x0 = d_in + off[u].x0; r.xref = d_in + off[u].x_ref;
+    r.out_x = out_x ? ox.dev + (int64_t)u * (steps + 1) * ox.ld : nullptr; r.ldx = out_x ? ox.ld : 0;
+    r.out_u = out_u ? ou.dev + (int64_t)u * steps * ou.ld : nullptr; r.ldu = out_u ? ou.ld : 0;
+    r.u_opt = un.uopt >= 0 ? uo.ptr + (int64_t)un.uopt * uo.ld : nullptr;
+    r.score = scores ? d_sc + 4 * (size_t)u : nullptr;
+    r.sigma0sq = mdl->sigma0 * mdl->sigma0; r.m = m; r.reserved = 0;
+    ktypes[u] = mdl->ktype;
+  }
+  NK_TRY(launch_poly_loop_multi(ctx, *plant, steps, recs.data(), ktypes.data(), n_units));
   if (out_x) NK_TRY(finish_out(ctx, ox));
   if (out_u) NK_TRY(finish_out(ctx, ou));
   if (scores) NK_HIP(hipMemcpyAsync(scores, d_sc, (size_t)n_units * 32, hipMemcpyDeviceToHost, ctx->stream));

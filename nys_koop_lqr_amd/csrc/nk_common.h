@@ -587,6 +587,31 @@ struct PlantLoopUnit {
 };
 int launch_plant_loop_multi(nk_ctx* ctx, int plant, double Ts, int steps, PlantLoopUnit* units, const int* ktypes,
                             int n_units);
+// The same loops around a polynomial plant the caller describes (nk_poly_plant.h; nk_poly_plant_loop and its multi form): d
+// states, p inputs, the plant table by value in the kernel arguments.  One record per loop, every pointer device memory.
+// W: the folded gain, entry (landmark l, input j) at w[l * w_ls + j * w_js]; out_u: steps rows of ldu, p columns; u_opt:
+// steps x p, dense.  Classes of a launch: (kernel family, landmarks per lane, waves per workgroup); the kernels are
+// instantiated for the states and inputs padded with exact zeros to D in {2, 4} and P in {1, 2, 4}.
+struct PolyLoopUnit {
+  const double* Z;      // m x d landmarks
+  const double* winv;   // d
+  const double* w;      // folded gain
+  const double* x0;     // d
+  const double* xref;   // d
+  double* out_x;        // (steps + 1) rows of ldx, or nullptr (multi form)
+  double* out_u;        // steps rows of ldu, or nullptr (multi form)
+  const double* u_opt;  // steps x p controls to score against, or nullptr
+  double* score;        // {sse_u, ss_opt, J, u_absmax}, or nullptr
+  int64_t ldx, ldu, w_ls, w_js;
+  double sigma0sq;
+  int m, reserved;
+};
+int poly_loop_max_m(int d, int p);  // the class limit on m (0: d or p out of range)
+int launch_poly_loop(nk_ctx* ctx, const nk_model* mdl, const nk_poly_plant& plant, const double* w, int64_t w_ls,
+                     int64_t w_js, const double* x0, int64_t x0_stride, const double* xref, int64_t xref_stride, int steps,
+                     int batch, double* out_x, int64_t ldx, double* out_u, int64_t ldu);
+int launch_poly_loop_multi(nk_ctx* ctx, const nk_poly_plant& plant, int steps, PolyLoopUnit* units, const int* ktypes,
+                           int n_units);
 
 // ---- lifted closed loops of many models in ONE launch, scored on the device (nk_loop_multi.hip): one 1024-thread workgroup
 // per unit, blockIdx.x = the record.  Every pointer is device memory.  Per step t < steps: u_t = K (phi_ref - phi_t),

@@ -18,6 +18,7 @@
 // 0 stores x_{t+1} and u_t with ordinary vector stores that nothing in the loop waits for.
 #include "nk_common.h"
 #include "nk_plant.h"
+#include "nk_poly_plant.h"
 
 #include <algorithm>
 #include <type_traits>
@@ -322,6 +323,404 @@ int launch_plant_loop_multi(nk_ctx* ctx, int plant, double Ts, int steps, PlantL
     NK_TRY(plant_loop_dispatch("plant_loop_multi", plant, k.ktype, k.lpt, [&](auto pl, auto kt, auto lp) {
       hipLaunchKernelGGL((plant_loop_multi_kernel<decltype(pl)::value, decltype(kt)::value, decltype(lp)::value>), dim3(e - b),
                          dim3(64 * k.waves), 0, ctx->stream, first, Ts, steps);
+    }));
+    b = e;
+  }
+  return NK_OK;
+}
+
+// =====================================================================================================================
+// The same loop around a polynomial plant the caller describes (nk_poly_plant.h): d <= 4 states, p <= 4 inputs.
+// The gain is folded into W = S^-1 K^T (m x p; spline models: K^T), u_j = sum_l W[l][j] (kref_l - k(z_l, x_t)): a lane
+// keeps its landmarks, their reference values and its rows of W in registers, forms P partial sums and reduces them with P
+// DPP wave reductions (independent chains, interleaved by the scheduler); with several waves P LDS words per wave, still
+// ONE LDS-only barrier per step, and the 16-word DPP reduction once per input.  The plant table arrives by value in the
+// kernel arguments, compiled by the host into a PolyProgram, and is evaluated in the lanes of every wave (PolyLanes): all
+// terms at once, the row sums in table order through v_readlane, all control flow uniform.  The kernels are instantiated for D in {2, 4} and P in {1, 2, 4}; states, landmarks coordinates, inverse
+// length scales, weights and controls beyond the plant's d and p are exact zeros, which changes no bit of the others.
+// Every summation order is fixed by m and P alone.
+// =====================================================================================================================
+struct PolyLoopParams {
+  const double* Z;      // m x d landmarks
+  const double* winv;   // d
+  const double* w;      // folded gain, entry (l, j) at w[l * w_ls + j * w_js]
+  int64_t w_ls, w_js;
+  int m;
+  double sigma0sq;
+  const double* x0; int64_t x0_stride;      // batch x d
+  const double* xref; int64_t xref_stride;  // batch x d (stride 0: shared)
+  double* out_x; int64_t ldx;               // rows b * (steps + 1) + t, d columns
+  double* out_u; int64_t ldu;               // rows b * steps + t, p columns
+  int steps;
+};
+
+constexpr int poly_pad_d(int d) { return d <= 2 ? 2 : 4; }
+constexpr int poly_pad_p(int p) { return p == 3 ? 4 : p; }
+// Landmarks per lane of the workgroups of more than 64 landmarks: the most (of 4, 2, 1) at which both 16-wave kernels of the
+// class (the scored one needs more) keep everything in their 128 registers per lane -- no scratch; DESIGN.md 5d lists what
+// the compiler reports.  The class limit on m is 1024 times this number.
+constexpr int poly_lpt(int D, int P) { return D == 2 ? (P <= 2 ? 4 : 2) : (P <= 2 ? 2 : 1); }
+
+// The plant table as the device loop wants it, compiled on the host from a validated description (poly_compile) and passed
+// by value in the kernel arguments.  The terms are sorted by row -- stable, so the terms of a row keep their table order,
+// which is all the order of the row sums depends on --; max_e[v] is the largest exponent any term gives variable v (states,
+// then inputs).
+struct PolyProgram {
+  int32_t d, p, n, from_k1;
+  double Ts;
+  int32_t row_end[NK_POLY_MAX_D];  // row r owns the sorted terms [row_end[r - 1], row_end[r])
+  int32_t max_e[NK_POLY_MAX_D + NK_POLY_MAX_P];
+  uint32_t word[NK_POLY_MAX_TERMS];  // poly_pack_term of the sorted terms (0 beyond n)
+  double coef[NK_POLY_MAX_TERMS];
+};
+static PolyProgram poly_compile(const nk_poly_plant& pl) {
+  PolyProgram g = {};
+  g.d = pl.d; g.p = pl.p; g.n = pl.n_terms; g.from_k1 = pl.k4_at_k1; g.Ts = pl.Ts;
+  int at = 0;
+  for (int r = 0; r < NK_POLY_MAX_D; ++r) {
+    for (int i = 0; i < pl.n_terms; ++i) {
+      const nk_poly_term& t = pl.terms[i];
+      if (t.row != r) continue;
+      g.word[at] = poly_pack_term(t);
+      g.coef[at] = t.coef;
+      for (int k = 0; k < NK_POLY_MAX_D; ++k) g.max_e[k] = std::max<int32_t>(g.max_e[k], t.ex[k]);
+      for (int j = 0; j < NK_POLY_MAX_P; ++j) g.max_e[NK_POLY_MAX_D + j] = std::max<int32_t>(g.max_e[NK_POLY_MAX_D + j], t.eu[j]);
+      ++at;
+    }
+    g.row_end[r] = at;
+  }
+  return g;
+}
+
+// The right-hand side in the lanes of a wave.  The four right-hand sides of a step are on its latency chain, and a single
+// wave issues one instruction every few cycles: walking the table term by term costs about 35 instructions per term
+// (measured: 2.5 us per step for the five terms of the Duffing table with the terms fetched by v_readlane, 3.5 us with
+// the terms fetched from the kernel arguments).  Here lane l holds sorted term l (its word and coefficient,
+// loaded once before the loop) and ALL terms are evaluated at once: for every variable, max_e rounds of
+// v = v * (e < the lane's exponent ? x_k : 1.0) -- a product with 1.0 changes no bit, so every term sees exactly its own
+// multiplications in the order of the interface.  Then the rows are summed in table order, f[r] = f[r] + v of lane i for
+// the lanes of row r, v fetched with v_readlane at the uniform index i.  All control flow is uniform.
+struct PolyLanes {
+  int n, from_k1;
+  double ts;
+  int row_end[NK_POLY_MAX_D], max_e[NK_POLY_MAX_D + NK_POLY_MAX_P];
+  int w;     // per lane
+  double c;  // per lane
+  __device__ __forceinline__ PolyLanes(const PolyProgram& g, int lane) : n(g.n), from_k1(g.from_k1), ts(g.Ts) {
+#pragma unroll
+    for (int r = 0; r < NK_POLY_MAX_D; ++r) row_end[r] = g.row_end[r];
+#pragma unroll
+    for (int v = 0; v < NK_POLY_MAX_D + NK_POLY_MAX_P; ++v) max_e[v] = g.max_e[v];
+    const int li = lane & (NK_POLY_MAX_TERMS - 1);
+    w = (int)g.word[li];
+    c = g.coef[li];
+  }
+  __device__ __forceinline__ double Ts() const { return ts; }
+  __device__ __forceinline__ bool k4_at_k1() const { return from_k1 != 0; }
+  template <int D, int P>
+  __device__ __forceinline__ void rhs(const double* x, const double* u, double* f) const {
+#pragma clang fp contract(off)
+    double v = c;
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      const int ex = (w >> (2 + 3 * k)) & 7;
+      for (int e = 0; e < max_e[k]; ++e) v = v * (e < ex ? x[k] : 1.0);
+    }
+#pragma unroll
+    for (int j = 0; j < P; ++j) {
+      const int eu = (w >> (14 + 3 * j)) & 7;
+      for (int e = 0; e < max_e[NK_POLY_MAX_D + j]; ++e) v = v * (e < eu ? u[j] : 1.0);
+    }
+    const int vlo = __double2loint(v), vhi = __double2hiint(v);
+    int i = 0;
+#pragma unroll
+    for (int r = 0; r < D; ++r) {
+      double acc = 0.0;
+      for (; i < row_end[r]; ++i)
+        acc = acc + __hiloint2double(__builtin_amdgcn_readlane(vhi, i), __builtin_amdgcn_readlane(vlo, i));
+      f[r] = acc;
+    }
+  }
+};
+
+// u_j = sum_l W[l][j] (kref_l - k(z_l, x)) for j < P, the same bits in every lane
+template <int KTYPE, int D, int P, int LPT>
+__device__ __forceinline__ void poly_feedback(const double* x, const double* wi, const double (&zs)[LPT][D],
+                                              const double (&wj)[LPT][P], const double (&kref)[LPT], double sigma0sq,
+                                              double (&red)[P][PLANT_LOOP_MAX_WAVES], int lane, int wave, bool multi,
+                                              double* u) {
+  double xs[D];
+  {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int k = 0; k < D; ++k) xs[k] = x[k] * wi[k];
+  }
+  double part[P];
+#pragma unroll
+  for (int j = 0; j < P; ++j) part[j] = 0.0;
+#pragma unroll
+  for (int l = 0; l < LPT; ++l) {
+    const double dk = kref[l] - plant_kval<KTYPE, D>(xs, zs[l], sigma0sq);
+#pragma unroll
+    for (int j = 0; j < P; ++j) part[j] = fma(wj[l][j], dk, part[j]);
+  }
+#pragma unroll
+  for (int j = 0; j < P; ++j) u[j] = wave_sum64_dpp(part[j]);
+  if (multi) {  // uniform over the workgroup
+    if (lane == 0) {
+#pragma unroll
+      for (int j = 0; j < P; ++j) red[j][wave] = u[j];
+    }
+    // LDS-only barrier (the global stores of earlier steps need not have retired: nothing reads them back)
+    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+#pragma unroll
+    for (int j = 0; j < P; ++j) u[j] = row_sum16_dpp(red[j][lane & 15]);
+  }
+}
+
+// The loop of one workgroup; SCORED as in plant_loop_body, the sums of the scores running over the inputs in index order.
+template <int KTYPE, int LPT, int D, int P, bool SCORED>
+__device__ __forceinline__ void poly_loop_body(const PolyLoopUnit& U, const PolyProgram& pl, int steps,
+                                               double (&red)[2][P][PLANT_LOOP_MAX_WAVES]) {
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nthreads = blockDim.x;
+  const int d = pl.d, p = pl.p;
+  const bool multi = nthreads > 64;
+  for (int i = tid; i < 2 * P * PLANT_LOOP_MAX_WAVES; i += nthreads) (&red[0][0][0])[i] = 0.0;  // words of absent waves stay zero
+  const PolyLanes tb(pl, lane);
+  double wi[D], zs[LPT][D], wj[LPT][P], kref[LPT], x[D], xr[D], u[P];
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    const bool have = k < d;
+    wi[k] = have ? U.winv[k] : 0.0;
+    x[k] = have ? U.x0[k] : 0.0;
+    xr[k] = have ? U.xref[k] : 0.0;
+  }
+  {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int l = 0; l < LPT; ++l) {
+      const int i = tid + l * nthreads;
+      const bool have = i < U.m;  // a slot without a landmark: weights 0, landmark 0 (finite kernel value, exact 0 products)
+#pragma unroll
+      for (int j = 0; j < P; ++j) wj[l][j] = (have && j < p) ? U.w[(int64_t)i * U.w_ls + (int64_t)j * U.w_js] : 0.0;
+#pragma unroll
+      for (int k = 0; k < D; ++k) zs[l][k] = (have && k < d) ? U.Z[(int64_t)i * d + k] * wi[k] : 0.0;
+    }
+    double xrs[D];
+#pragma unroll
+    for (int k = 0; k < D; ++k) xrs[k] = xr[k] * wi[k];
+#pragma unroll
+    for (int l = 0; l < LPT; ++l) kref[l] = plant_kval<KTYPE, D>(xrs, zs[l], U.sigma0sq);
+  }
+  double* ox = U.out_x;
+  double* ou = U.out_u;
+  const bool st_x = !SCORED || ox != nullptr, st_u = !SCORED || ou != nullptr;
+  if (tid == 0 && st_x) {
+#pragma unroll
+    for (int k = 0; k < D; ++k)
+      if (k < d) ox[k] = x[k];
+  }
+  double sse = 0.0, sso = 0.0, J = 0.0, umax = 0.0, uo[P];
+#pragma unroll
+  for (int j = 0; j < P; ++j) uo[j] = 0.0;
+  const double* uopt = SCORED ? U.u_opt : nullptr;
+  if (SCORED) {
+#pragma clang fp contract(off)
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      const double sq = x[k] * x[k];
+      J = k == 0 ? sq : J + sq;
+    }
+    if (uopt) {
+#pragma unroll
+      for (int j = 0; j < P; ++j)
+        if (j < p) uo[j] = uopt[j];
+    }
+  }
+  __syncthreads();  // red is zeroed
+  for (int t = 0; t < steps; ++t) {
+    // buffer t & 1: a wave still reading it in step t is at most one barrier behind the wave that writes it again in t + 2
+    poly_feedback<KTYPE, D, P, LPT>(x, wi, zs, wj, kref, U.sigma0sq, red[t & 1], lane, wave, multi, u);
+#pragma unroll
+    for (int j = 0; j < P; ++j) u[j] = j < p ? u[j] : 0.0;
+    double xn[D];
+    poly_plant_step<D, P>(tb, x, u, xn);
+#pragma unroll
+    for (int k = 0; k < D; ++k) x[k] = xn[k];
+    if (SCORED) {
+#pragma clang fp contract(off)
+      double sx = 0.0, su = 0.0;
+#pragma unroll
+      for (int k = 0; k < D; ++k) {
+        const double sq = x[k] * x[k];
+        sx = k == 0 ? sq : sx + sq;
+      }
+#pragma unroll
+      for (int j = 0; j < P; ++j) {
+        const double sq = u[j] * u[j];
+        su = j == 0 ? sq : su + sq;
+        const double au = fabs(u[j]);
+        umax = (au > umax || au != au) ? au : umax;  // a NaN enters once and stays: no later comparison is true
+      }
+      J = (J + sx) + su;
+      if (uopt) {
+        const int64_t tn = t + 1 < steps ? t + 1 : t;
+#pragma unroll
+        for (int j = 0; j < P; ++j) {
+          const double df = u[j] - uo[j];
+          const double dsq = df * df, osq = uo[j] * uo[j];
+          sse = sse + dsq;
+          sso = sso + osq;
+          if (j < p) uo[j] = uopt[tn * p + j];  // next step's values, loaded a step ahead (not on the chain)
+        }
+      }
+    }
+    if (tid == 0) {
+      if (st_u) {
+#pragma unroll
+        for (int j = 0; j < P; ++j)
+          if (j < p) ou[(int64_t)t * U.ldu + j] = u[j];
+      }
+      if (st_x) {
+#pragma unroll
+        for (int k = 0; k < D; ++k)
+          if (k < d) ox[(int64_t)(t + 1) * U.ldx + k] = x[k];
+      }
+    }
+  }
+  if (SCORED && tid == 0 && U.score) {
+    U.score[0] = sse;
+    U.score[1] = sso;
+    U.score[2] = J;
+    U.score[3] = umax;
+  }
+}
+
+// WG: the largest workgroup a kernel is launched with (64: one wave with one landmark per lane; else 16 waves)
+template <int KTYPE, int LPT, int D, int P, int WG>
+__global__ void __launch_bounds__(WG) poly_loop_kernel(PolyLoopParams Q, PolyProgram pl) {
+  __shared__ double red[2][P][PLANT_LOOP_MAX_WAVES];  // per input one partial sum per wave, two buffers (parity of the step)
+  const int b = blockIdx.x;
+  PolyLoopUnit U;
+  U.Z = Q.Z; U.winv = Q.winv; U.w = Q.w; U.w_ls = Q.w_ls; U.w_js = Q.w_js; U.m = Q.m; U.reserved = 0; U.sigma0sq = Q.sigma0sq;
+  U.x0 = Q.x0 + (int64_t)b * Q.x0_stride;
+  U.xref = Q.xref + (int64_t)b * Q.xref_stride;
+  U.out_x = Q.out_x + (int64_t)b * (Q.steps + 1) * Q.ldx; U.ldx = Q.ldx;
+  U.out_u = Q.out_u + (int64_t)b * Q.steps * Q.ldu; U.ldu = Q.ldu;
+  U.u_opt = nullptr; U.score = nullptr;
+  poly_loop_body<KTYPE, LPT, D, P, false>(U, pl, Q.steps, red);
+}
+
+// the multi-model form: unit blockIdx.x of `table` (all units of a launch share KTYPE, LPT and the block size)
+template <int KTYPE, int LPT, int D, int P, int WG>
+__global__ void __launch_bounds__(WG)
+    poly_loop_multi_kernel(const PolyLoopUnit* __restrict__ table, PolyProgram pl, int steps) {
+  __shared__ double red[2][P][PLANT_LOOP_MAX_WAVES];
+  const PolyLoopUnit U = table[blockIdx.x];
+  poly_loop_body<KTYPE, LPT, D, P, true>(U, pl, steps, red);
+}
+
+int poly_loop_max_m(int d, int p) {
+  if (d < 1 || d > NK_POLY_MAX_D || p < 1 || p > NK_POLY_MAX_P) return 0;
+  return 64 * poly_lpt(poly_pad_d(d), poly_pad_p(p)) * PLANT_LOOP_MAX_WAVES;
+}
+
+// The workgroup shape of a model of m landmarks in the class (D, P): one wave with one landmark per lane up to 64, the
+// class's landmarks per lane beyond.
+static void poly_loop_class(int m, int lpt_class, int* lpt, int* waves) {
+  if (m <= 64) {
+    *lpt = 1;
+    *waves = 1;
+  } else {
+    *lpt = lpt_class;
+    *waves = (m + 64 * lpt_class - 1) / (64 * lpt_class);
+  }
+}
+
+// launch(kernel family, landmarks per lane, D, P, workgroup bound) for the plant's class; many = false: one wave with one
+// landmark per lane
+template <class F>
+static int poly_loop_dispatch(const char* who, int d, int p, int ktype, bool many, F&& launch) {
+  auto with_lpt = [&](auto kt, auto dd, auto pp) {
+    constexpr int L = poly_lpt(decltype(dd)::value, decltype(pp)::value);
+    if (many) launch(kt, std::integral_constant<int, L>{}, dd, pp, std::integral_constant<int, 64 * PLANT_LOOP_MAX_WAVES>{});
+    else launch(kt, std::integral_constant<int, 1>{}, dd, pp, std::integral_constant<int, 64>{});
+  };
+  auto with_p = [&](auto kt, auto dd) {
+    switch (poly_pad_p(p)) {
+      case 1: with_lpt(kt, dd, std::integral_constant<int, 1>{}); break;
+      case 2: with_lpt(kt, dd, std::integral_constant<int, 2>{}); break;
+      default: with_lpt(kt, dd, std::integral_constant<int, 4>{}); break;
+    }
+  };
+  return with_kernel_family(who, ktype, [&](auto kt) {
+    if (poly_pad_d(d) == 2) with_p(kt, std::integral_constant<int, 2>{});
+    else with_p(kt, std::integral_constant<int, 4>{});
+  });
+}
+
+// all pointers device memory; out_x: batch * (steps + 1) rows of d, out_u: batch * steps rows of p
+int launch_poly_loop(nk_ctx* ctx, const nk_model* mdl, const nk_poly_plant& plant, const double* w, int64_t w_ls,
+                     int64_t w_js, const double* x0, int64_t x0_stride, const double* xref, int64_t xref_stride, int steps,
+                     int batch, double* out_x, int64_t ldx, double* out_u, int64_t ldu) {
+  NK_REQUIRE(plant.d == mdl->d && plant.p == mdl->p && mdl->m >= 1 && mdl->m <= poly_loop_max_m(plant.d, plant.p) &&
+                 steps >= 1 && batch >= 1, "poly_plant_loop: bad sizes");
+  PolyLoopParams Q;
+  Q.Z = mdl->Z; Q.winv = mdl->winv; Q.w = w; Q.w_ls = w_ls; Q.w_js = w_js; Q.m = mdl->m;
+  Q.sigma0sq = mdl->sigma0 * mdl->sigma0;
+  Q.x0 = x0; Q.x0_stride = x0_stride; Q.xref = xref; Q.xref_stride = xref_stride;
+  Q.out_x = out_x; Q.ldx = ldx; Q.out_u = out_u; Q.ldu = ldu; Q.steps = steps;
+  const PolyProgram prog = poly_compile(plant);
+  int lpt = 0, waves = 0;
+  poly_loop_class(mdl->m, poly_lpt(poly_pad_d(plant.d), poly_pad_p(plant.p)), &lpt, &waves);
+  return poly_loop_dispatch("poly_plant_loop", plant.d, plant.p, mdl->ktype, waves > 1 || lpt > 1, [&](auto kt, auto lp, auto dd, auto pp, auto wg) {
+    hipLaunchKernelGGL((poly_loop_kernel<decltype(kt)::value, decltype(lp)::value, decltype(dd)::value, decltype(pp)::value,
+                                         decltype(wg)::value>),
+                       dim3(batch), dim3(64 * waves), 0, ctx->stream, Q, prog);
+  });
+}
+
+// The multi-model form: as launch_plant_loop_multi -- the records are sorted (stable) into classes of (kernel family,
+// landmarks per lane, waves), staged with ONE copy and run with one launch per class.  `units` is reordered in place and
+// must stay alive until the stream has been synchronised.
+int launch_poly_loop_multi(nk_ctx* ctx, const nk_poly_plant& plant, int steps, PolyLoopUnit* units, const int* ktypes,
+                           int n_units) {
+  NK_REQUIRE(steps >= 1 && n_units >= 1, "poly_plant_loop_multi: bad sizes");
+  const int max_m = poly_loop_max_m(plant.d, plant.p);
+  NK_REQUIRE(max_m > 0, "poly_plant_loop_multi: bad plant");
+  const int lpt_class = poly_lpt(poly_pad_d(plant.d), poly_pad_p(plant.p));
+  struct Key { int ktype, lpt, waves, idx; };
+  std::vector<Key> keys((size_t)n_units);
+  for (int u = 0; u < n_units; ++u) {
+    NK_REQUIRE(units[u].m >= 1 && units[u].m <= max_m, "poly_plant_loop_multi: unit %d: bad m", u);
+    keys[u].ktype = ktypes[u];
+    keys[u].idx = u;
+    poly_loop_class(units[u].m, lpt_class, &keys[u].lpt, &keys[u].waves);
+  }
+  auto less = [](const Key& a, const Key& b) {
+    if (a.ktype != b.ktype) return a.ktype < b.ktype;
+    if (a.lpt != b.lpt) return a.lpt < b.lpt;
+    return a.waves < b.waves;
+  };
+  std::stable_sort(keys.begin(), keys.end(), less);
+  {
+    std::vector<PolyLoopUnit> sorted((size_t)n_units);
+    for (int u = 0; u < n_units; ++u) sorted[u] = units[keys[u].idx];
+    std::copy(sorted.begin(), sorted.end(), units);
+  }
+  const PolyProgram prog = poly_compile(plant);
+  PolyLoopUnit* table = nullptr;
+  NK_TRY(arena_alloc_t(ctx, (size_t)n_units, &table));
+  NK_HIP(hipMemcpyAsync(table, units, sizeof(PolyLoopUnit) * (size_t)n_units, hipMemcpyHostToDevice, ctx->stream));
+  for (int b = 0; b < n_units;) {
+    int e = b + 1;
+    while (e < n_units && !less(keys[b], keys[e])) ++e;
+    const Key& k = keys[b];
+    const PolyLoopUnit* first = table + b;
+    NK_TRY(poly_loop_dispatch("poly_plant_loop_multi", plant.d, plant.p, k.ktype, k.waves > 1 || k.lpt > 1, [&](auto kt, auto lp, auto dd, auto pp, auto wg) {
+      hipLaunchKernelGGL((poly_loop_multi_kernel<decltype(kt)::value, decltype(lp)::value, decltype(dd)::value, decltype(pp)::value,
+                                                 decltype(wg)::value>),
+                         dim3(e - b), dim3(64 * k.waves), 0, ctx->stream, first, prog, steps);
     }));
     b = e;
   }

@@ -72,6 +72,24 @@ inline PlantUnitOffsets pack_plant_unit(UnitPack& in, UnitPack& folds, const dou
   return o;
 }
 
+// A unit of the polynomial-plant form (nk_poly_plant_loop_multi), p inputs.  `in`: the p rows of K, each with the leading
+// dimension of a gain row (what stage_in gives the p x m gain of nk_poly_plant_loop) | x0, x_ref together in one piece of
+// 2 d.  `folds` (device only): the folded gain of a unit that has one, m p + 2 doubles.
+struct PolyUnitOffsets { size_t K = 0, x0 = 0, x_ref = 0, w = 0; };
+inline PolyUnitOffsets pack_poly_unit(UnitPack& in, UnitPack& folds, const double* K, const double* x0, const double* x_ref,
+                                      size_t m, size_t d, size_t p, bool fold) {
+  PolyUnitOffsets o;
+  const size_t ldk = gain_row_reserve(m);
+  o.K = in.reserve(p * ldk);
+  for (size_t j = 0; j < p; ++j) in.copy(o.K + j * ldk, K + j * m, m);
+  o.x0 = in.reserve(2 * d);
+  o.x_ref = o.x0 + d;
+  in.copy(o.x0, x0, d);
+  in.copy(o.x_ref, x_ref, d);
+  if (fold) o.w = folds.reserve(m * p + 2);
+  return o;
+}
+
 // A loop unit (nk_closed_loop_multi).  `in`: K (p x m) | phi0 | phi_ref | target (d, may be null) | u_init (p, may be null).
 // `ws` (device only): phi_t of every step | sum u^2 per step | sum (x - target)^2 per step.
 struct LoopUnitOffsets { size_t K = 0, phi0 = 0, phi_ref = 0, target = 0, u_init = 0, Phi = 0, usq = 0, sse = 0; };

@@ -8,6 +8,7 @@ import itertools
 import numpy as np
 
 from . import _lib
+from .dynamical_systems import PolynomialSystem
 from .regressors import KoopmanNystromRegressor, KoopmanSplineRegressor
 
 
@@ -467,6 +468,17 @@ def lqr_control(num_steps, reference, initial_state, regressor, K, control_nodes
     return x_s, y_s, z_s, final_us
 
 
+def plant_snapshots(plant, n, rng, bound=1.0, u_bound=1.0):
+    """n snapshot pairs of a plant object (n_states, update_SOM; n_inputs when it has more than one input): states uniform in
+    [-bound, bound]^d, inputs uniform in [-u_bound, u_bound]^p, drawn from `rng` (a numpy Generator) states first.  Returns
+    X = [state | input] (n, d + p) and Y = the next states (n, d)."""
+    d, p = int(plant.n_states), int(getattr(plant, "n_inputs", 1))
+    S = rng.uniform(-bound, bound, size=(d, n))
+    U = rng.uniform(-u_bound, u_bound, size=(p, n))
+    Y = np.asarray(plant.update_SOM(S, U), dtype=np.float64)
+    return np.ascontiguousarray(np.vstack((S, U)).T), np.ascontiguousarray(Y.T)
+
+
 def lqr_control_plant(num_steps, reference, initial_state, regressor, K, plant_step):
     """The plant-in-the-loop variant of benchmark_lqr_hjb.py:73-97 (and _classic.py:67-89): u = K (phi(ref) - phi(x)),
     x <- plant_step(x, u), phi re-lifted from the true state every step (one cached-square-root lift per step instead of
@@ -487,7 +499,7 @@ def lqr_control_plant(num_steps, reference, initial_state, regressor, K, plant_s
 
 def lqr_control_plant_device(num_steps, reference, initial_state, regressor, K, plant):
     """lqr_control_plant with the whole loop in ONE device launch (regressor.closed_loop_plant -> nk_plant_loop): `plant` is one
-    of dynamical_systems.DuffingOscillator / DoubleIntegrator / HJB instead of a callable.  Returns (x_s (num_steps,),
+    of dynamical_systems.DuffingOscillator / DoubleIntegrator / HJB or a PolynomialSystem instead of a callable.  Returns (x_s (num_steps,),
     u_s (p, num_steps)) like lqr_control_plant: x_s is the first coordinate of the states the controls were computed at."""
     x0 = np.asarray(initial_state, dtype=np.float64).reshape(-1)
     ref = np.asarray(reference, dtype=np.float64).reshape(-1)
@@ -526,20 +538,25 @@ def rmse_control_percent(sse_u, ss_opt):
 
 
 def control_scores(states, controls, u_opt=None):
-    """The four scores of nk_plant_loop_multi on the host, in the device's order of operations, from one loop's visited
-    states (d, steps + 1) (x0 first) and controls (steps,) / (1, steps): sse_u and ss_opt (step order; 0 without u_opt),
-    J = the cost of open_loop_control (benchmark_lqr_hjb.py:99-107: J = sum_k x0_k^2, then (J + sum_k x_{t+1,k}^2) + u_t^2)
-    and u_absmax (NaN from the first NaN control on); plus rmse_control (benchmark_lqr_hjb.py:313).  Returns a dict of
-    floats.  Needs no GPU."""
+    """The four scores of nk_plant_loop_multi / nk_poly_plant_loop_multi on the host, in the device's order of operations, from
+    one loop's visited states (d, steps + 1) (x0 first) and controls (steps,) / (p, steps) / (steps, p): sse_u and ss_opt (sums over the
+    steps and, within a step, over the inputs in index order; 0 without u_opt; u_opt: (steps,) or (steps, p)),
+    J = the cost of open_loop_control (benchmark_lqr_hjb.py:99-107: J = sum_k x0_k^2, then (J + sum_k x_{t+1,k}^2) +
+    sum_j u_{t,j}^2) and u_absmax (over steps and inputs, NaN from the first NaN control on); plus rmse_control
+    (benchmark_lqr_hjb.py:313).  Returns a dict of floats.  Needs no GPU."""
     xs = np.asarray(states, dtype=np.float64)
     xs = xs.reshape(1, -1) if xs.ndim == 1 else xs
-    us = np.asarray(controls, dtype=np.float64).reshape(-1)
-    steps = us.size
+    us = np.asarray(controls, dtype=np.float64)
+    us = us.reshape(1, -1) if us.ndim < 2 else us
+    if us.shape[1] != xs.shape[1] - 1 and us.shape[0] == xs.shape[1] - 1:
+        us = us.T  # (steps, p), as the multi-model call returns a unit's controls
+    p, steps = us.shape
     if xs.shape[1] != steps + 1:
         raise ValueError(f"states have shape {xs.shape}, expected (d, {steps + 1})")
-    uo = None if u_opt is None else np.asarray(u_opt, dtype=np.float64).reshape(-1)
-    if uo is not None and uo.size != steps:
-        raise ValueError(f"u_opt has {uo.size} entries, the loop has {steps} steps")
+    uo = None if u_opt is None else np.asarray(u_opt, dtype=np.float64)
+    if uo is not None and uo.size != steps * p:
+        raise ValueError(f"u_opt has {uo.size} entries, the loop has {steps} steps of {p} inputs")
+    uo = None if uo is None else uo.reshape(steps, p)
 
     def sumsq(col):
         acc = float(col[0]) * float(col[0])
@@ -549,15 +566,16 @@ def control_scores(states, controls, u_opt=None):
 
     J, sse, sso, umax = sumsq(xs[:, 0]), 0.0, 0.0, 0.0
     for t in range(steps):
-        u = float(us[t])
-        J = (J + sumsq(xs[:, t + 1])) + u * u
-        au = abs(u)
-        if au > umax or au != au:
-            umax = au
-        if uo is not None:
-            df = u - float(uo[t])
-            sse = sse + df * df
-            sso = sso + float(uo[t]) * float(uo[t])
+        J = (J + sumsq(xs[:, t + 1])) + sumsq(us[:, t])
+        for j in range(p):
+            u = float(us[j, t])
+            au = abs(u)
+            if au > umax or au != au:
+                umax = au
+            if uo is not None:
+                df = u - float(uo[t, j])
+                sse = sse + df * df
+                sso = sso + float(uo[t, j]) * float(uo[t, j])
     return dict(sse_u=sse, ss_opt=sso, J=J, u_absmax=umax, rmse_control=float(rmse_control_percent(sse, sso)))
 
 
@@ -594,32 +612,42 @@ def plant_loop_multi(regressors, gains, x0s, x_refs, num_steps, plant, u_opt=Non
     k = n_units > 1, else row 0).
     Returns a dict of (n_units,) arrays sse_u, ss_opt, J, u_absmax (see include/nyskoop.h) and rmse_control =
     100 sqrt(sse_u) / sqrt(ss_opt); with return_trajectories also states (n_units, num_steps + 1, d) and controls
-    (n_units, num_steps).  Without them nothing but the scores leaves the device."""
+    (n_units, num_steps).  Without them nothing but the scores leaves the device.
+    A dynamical_systems.PolynomialSystem as `plant` runs nk_poly_plant_loop_multi: gains (p, m), u_opt (num_steps, p) or
+    (k, num_steps, p), controls (n_units, num_steps, p), the scores summed over the inputs (control_scores)."""
     regs = list(regressors)
     n = len(regs)
     plant_id, Ts = getattr(plant, "plant_id", None), getattr(plant, "Ts", None)
-    if plant_id is None or Ts is None:
-        raise ValueError("plant must be one of the package's dynamical systems (plant_id) with its step length Ts set")
+    poly = isinstance(plant, PolynomialSystem)
+    if (plant_id is None and not poly) or Ts is None:
+        raise ValueError("plant must be one of the package's dynamical systems (plant_id) or a PolynomialSystem, with its step "
+                         "length Ts set")
     d = int(plant.n_states)
+    p = int(plant.n_inputs) if poly else 1
     ctx = _lib.get_context()
     handles = [r._ensure_model() for r in regs]
     Ks = []
     for r, K in zip(regs, gains):
         K = np.ascontiguousarray(K, dtype=np.float64)
         m = r._landmark_shape()[1]
-        if K.size != m:
-            raise ValueError(f"gain has shape {K.shape}, expected {(1, m)}")
+        if K.size != p * m or (poly and K.shape != (p, m)):
+            raise ValueError(f"gain has shape {K.shape}, expected {(p, m)}")
         Ks.append(K)
     if len(Ks) != n:
         raise ValueError(f"{len(Ks)} gains for {n} regressors")
     rows = uopt_rows
     if u_opt is not None:
-        uo = np.asarray(u_opt, dtype=np.float64).reshape(-1, int(num_steps))
+        uo = np.asarray(u_opt, dtype=np.float64).reshape(-1, int(num_steps) * p)
         if rows is None:
             rows = list(range(n)) if uo.shape[0] == n and n > 1 else [0] * n
-    sc, ox, ou = ctx.plant_loop_multi(plant_id, Ts, num_steps, handles, Ks, _broadcast_states(x0s, n, d, "x0s"),
-                                      _broadcast_states(x_refs, n, d, "x_refs"), u_opt=None if u_opt is None else uo,
-                                      uopt_rows=rows, want_x=return_trajectories, want_u=return_trajectories)
+    x0b, xrb = _broadcast_states(x0s, n, d, "x0s"), _broadcast_states(x_refs, n, d, "x_refs")
+    if poly:
+        sc, ox, ou = ctx.poly_plant_loop_multi(plant.descriptor(), num_steps, handles, Ks, x0b, xrb,
+                                               u_opt=None if u_opt is None else uo, uopt_rows=rows,
+                                               want_x=return_trajectories, want_u=return_trajectories)
+    else:
+        sc, ox, ou = ctx.plant_loop_multi(plant_id, Ts, num_steps, handles, Ks, x0b, xrb, u_opt=None if u_opt is None else uo,
+                                          uopt_rows=rows, want_x=return_trajectories, want_u=return_trajectories)
     out = {name: sc[:, i].copy() for i, name in enumerate(SCORE_NAMES)}
     out["rmse_control"] = rmse_control_percent(out["sse_u"], out["ss_opt"])
     if return_trajectories:

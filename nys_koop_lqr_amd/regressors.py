@@ -13,6 +13,7 @@ import numpy as np
 from sklearn.base import BaseEstimator
 
 from . import _lib
+from .dynamical_systems import PolynomialSystem
 from .lqr import dlqr
 
 
@@ -436,7 +437,8 @@ class _DeviceModelRegressor(KoopmanRegressor):
         """LQR closed loop around the TRUE plant (lqr_control of benchmark_lqr_hjb.py:73-97 / benchmark_lqr_classic.py:67-89):
         u_t = K (phi(x_ref) - phi(x_t)), x_{t+1} = plant(x_t, u_t), all `num_steps` steps in one device launch
         (nk_plant_loop).  `plant`: one of dynamical_systems.DuffingOscillator / DoubleIntegrator / HJB (its `plant_id` and
-        `Ts` are used), whose state dimension is the model's; one input.
+        `Ts` are used), whose state dimension is the model's; one input.  Or a dynamical_systems.PolynomialSystem
+        (nk_poly_plant_loop): up to four states and four inputs, the model's; K is (p, m) and u below has p rows / columns.
 
         x0: (d,) / (d, 1)  -> (states (d, num_steps + 1) with x0 first, u (1, num_steps)); a (1, 1) array with d = 1 is this case;
         x0: (batch, d)     -> (states (batch, num_steps + 1, d), u (batch, num_steps, 1)): independent loops that share the
@@ -446,8 +448,10 @@ class _DeviceModelRegressor(KoopmanRegressor):
         d, m = self._landmark_shape()
         p = int(self.n_inputs)
         plant_id, Ts = getattr(plant, "plant_id", None), getattr(plant, "Ts", None)
-        if plant_id is None or Ts is None:
-            raise ValueError("plant must be one of the package's dynamical systems (plant_id) with its step length Ts set")
+        poly = isinstance(plant, PolynomialSystem)
+        if (plant_id is None and not poly) or Ts is None:
+            raise ValueError("plant must be one of the package's dynamical systems (plant_id) or a PolynomialSystem, with its "
+                             "step length Ts set")
         K = np.ascontiguousarray(K, dtype=np.float64)
         if K.shape != (p, m):
             raise ValueError(f"gain has shape {K.shape}, expected {(p, m)}")
@@ -462,9 +466,13 @@ class _DeviceModelRegressor(KoopmanRegressor):
         if x_ref.size not in (d, batch * d):
             raise ValueError(f"reference has shape {x_ref.shape}, expected one state of dimension {d} or {(batch, d)}")
         xr = np.ascontiguousarray(np.broadcast_to(x_ref.reshape(-1, d), (batch, d)))
-        ox, ou = np.empty((batch, max(num_steps, 0) + 1, d)), np.empty((batch, max(num_steps, 0), 1))
-        rc = ctx.lib.nk_plant_loop(ctx.handle, h, int(plant_id), float(Ts), K.ctypes.data, xb.ctypes.data, xr.ctypes.data,
-                                   num_steps, batch, ox.ctypes.data, ou.ctypes.data)
+        ox, ou = np.empty((batch, max(num_steps, 0) + 1, d)), np.empty((batch, max(num_steps, 0), p if poly else 1))
+        if poly:
+            rc = ctx.lib.nk_poly_plant_loop(ctx.handle, h, plant.descriptor(), K.ctypes.data, xb.ctypes.data, xr.ctypes.data,
+                                            num_steps, batch, ox.ctypes.data, ou.ctypes.data)
+        else:
+            rc = ctx.lib.nk_plant_loop(ctx.handle, h, int(plant_id), float(Ts), K.ctypes.data, xb.ctypes.data,
+                                       xr.ctypes.data, num_steps, batch, ox.ctypes.data, ou.ctypes.data)
         _lib.check_mapped(rc)
         if single:
             return ox[0].T, ou[0].T
