@@ -611,6 +611,64 @@ int nk_model_lqr_gain(nk_ctx* ctx, const nk_model* model, double c, const double
  * around every phase -- out[1] = the LU launches, out[2] = the products and elementwise kernels of the steps, out[3] = the
  * per-step synchronisation; out[4] = steps taken. */
 int nk_dare_large_times(double out[5]);
+/* ---- Constrained Koopman MPC around a polynomial plant in ONE launch: box and rate limits on the inputs.
+ *   Per step, with e = phi(x_t) - phi(x_ref) and the decision vector U = (u_0, ..., u_{N-1}) of nv = N p entries:
+ *       minimise 1/2 U'HU + (F e)'U   subject to   lo <= U <= hi,   dlo <= u_k - u_{k-1} <= dhi  (k = 0 .. N-1),
+ *   u_{-1} = the control applied at the previous step (u_init, or zeros, at t = 0), and the first p entries are applied.  H
+ *   (nv x nv) and F (nv x m) are the condensed problem of the lifted model (lqr.mpc_condense in Python).  Bounds of +-inf are
+ *   allowed and make a constraint inactive.
+ *   THE ITERATION IS PART OF THE INTERFACE (lqr.mpc_admm_step / lqr.mpc_solve are its NumPy statement).  Constraint rows
+ *   A_c = [I; D], D the block first difference, (D U)_k = u_k - u_{k-1} with (D U)_0 = u_0; the first p rate bounds are shifted
+ *   by u_{-1}.  M = (H + rho (I + D'D))^-1 and H^-1 are formed once per call on the host (Cholesky).  With g = F e:
+ *       U_unc = -H^-1 g;   s = A_c U_unc;   z = clip(s);   lambda = 0;   r = max |s - z|;   k = 0
+ *       while k < iters and not (r <= tol and (k == 0 or tol > 0)):
+ *           w = z - lambda;   U = M (rho (w_1 + D'w_2) - g);   s = A_c U;   z = clip(s + lambda);   lambda += s - z
+ *           r = max |s - z|;   k += 1
+ *       v = the first p entries of z;   u_t = clip(clip(v, lo, hi), u_{-1} + dlo, u_{-1} + dhi)
+ *   The rate clip comes last, so a returned control never violates a rate limit whatever iters is, and never a bound either
+ *   when u_{-1} lies within the bounds and dlo <= 0 <= dhi; at convergence both clips change nothing.  When U_unc is feasible
+ *   r = 0 at k = 0: no iteration runs and u_t is the LQR control to rounding (the first p rows of H^-1 F are the Riccati gain
+ *   when the terminal cost is the Riccati solution).  tol = 0 runs all iterations unless the start is feasible.
+ *   iters = 0 is the SATURATED LQR: v = -K e = K (phi(x_ref) - phi(x_t)) from the gain K and the two clips above; H and F
+ *   are not read.  For one input under a symmetric box alone and the Riccati terminal cost this IS the first move of the QP
+ *   (measured: equal to 1e-15 of the bound at every step), so a bounds-only single-input user should take this mode.
+ *   out_info (may be NULL): batch x steps x 2 = {iterations run, final max |s - z|} (iters = 0: zeros).
+ *   Device side (nk_mpc_loop.hip): one workgroup per trajectory, ceil(m / 64) waves, the whole loop inside it.  F is folded
+ *   into the lift once per call, W = S^-1 F' (m x nv; spline models: F'), and lives in LDS; g = W'(k(Z, x_t) - k(Z, x_ref)),
+ *   the difference taken landmark by landmark before the product.  Lane i of the first wave owns decision variable i: its row
+ *   of M stays in registers, the iterate is broadcast with v_readlane, D and D' are shifts by p lanes; the plant step
+ *   follows in the same wave and the new state reaches the others through LDS.  Every summation order is fixed by (m, nv, p)
+ *   alone: a trajectory has the same bits alone or in any batch.
+ *   Limits: nv <= NK_MPC_MAX_NV, p <= 4, d <= 4, m <= 512 (eight waves: the largest workgroup whose lanes keep a row of M
+ *   in registers without scratch) and 8 (m nv + 64 ceil(m / 64) + 16) <= 160 KB of LDS: m <= 512 up to nv = 38, 314 at
+ *   nv = 64 (nk_mpc_loop_max_m).  Beyond: NK_ERR_BAD_ARG before anything is queued, as for every malformed field (H not
+ *   symmetric positive definite, lo > hi, dlo > dhi, rho not finite and positive, iters < 0, tol negative, sizes) with the
+ *   field named in nk_last_error(); no output is touched.  The arrays of the description are HOST memory; x0 (batch x d),
+ *   x_ref (batch x d), u_init (batch x p, may be NULL), out_x (batch x (steps + 1) x d), out_u (batch x steps x p) and
+ *   out_info are host or device memory.  Ordinary contexts only.
+ *   nk_mpc_qp_host: ONE solve of the same iteration in the host build, no context and no GPU: e (m), u_prev (p, NULL =
+ *   zeros); out_u (p) the control, out_z (nv, may be NULL; not written when iters = 0) the first nv entries of z, out_info
+ *   (2, may be NULL). */
+#define NK_MPC_MAX_NV 64
+typedef struct nk_mpc_desc {
+  int32_t N, p;       /* horizon and inputs; nv = N p */
+  int32_t m;          /* lifted dimension: F is nv x m, K is p x m */
+  int32_t iters;      /* >= 0; 0 = the saturated LQR */
+  const double* H;    /* nv x nv dense, symmetric positive definite (iters > 0) */
+  const double* F;    /* nv x m dense (iters > 0) */
+  const double* lo;   /* nv, or NULL = -inf */
+  const double* hi;   /* nv, or NULL = +inf */
+  const double* dlo;  /* nv, or NULL = -inf */
+  const double* dhi;  /* nv, or NULL = +inf */
+  const double* K;    /* p x m dense (iters = 0) */
+  double rho, tol;    /* rho finite > 0; tol finite >= 0 */
+} nk_mpc_desc;
+int nk_mpc_loop(nk_ctx* ctx, const nk_model* model, const nk_poly_plant* plant, const nk_mpc_desc* desc, const double* x0,
+                const double* x_ref, const double* u_init_or_NULL, int32_t steps, int32_t batch, double* out_x, double* out_u,
+                double* out_info_or_NULL);
+int nk_mpc_qp_host(const nk_mpc_desc* desc, const double* e, const double* u_prev_or_NULL, double* out_u, double* out_z,
+                   double* out_info);
+int nk_mpc_loop_max_m(int32_t nv);  /* the limit on m for nv decision variables (0: nv out of range) */
 /* ---- rollout of explicit operators without a model (any estimator that exposes A, B, C: the exact-kernel comparator of
  *   benchmark_lqr_hjb.py:334-381, un-pickled gains): z0: batch x m lifted initial states; A: m x m, B: m x p, C: d x m
  *   (row-major, host or device); U, out_x, out_z as in nk_rollout. --------------------------------------------------- */

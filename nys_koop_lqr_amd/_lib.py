@@ -64,6 +64,35 @@ class PolyPlant(C.Structure):
                 ("terms", PolyTerm * 32)]
 
 
+class MpcDesc(C.Structure):
+    """nk_mpc_desc (include/nyskoop.h): the condensed QP of the constrained MPC loop.  The arrays are host memory the
+    caller keeps alive for the call."""
+    _fields_ = [("N", C.c_int32), ("p", C.c_int32), ("m", C.c_int32), ("iters", C.c_int32), ("H", C.c_void_p),
+                ("F", C.c_void_p), ("lo", C.c_void_p), ("hi", C.c_void_p), ("dlo", C.c_void_p), ("dhi", C.c_void_p),
+                ("K", C.c_void_p), ("rho", C.c_double), ("tol", C.c_double)]
+
+
+def mpc_desc(controller, iters, tol):
+    """(MpcDesc, keep-alive list) of an lqr.MPCController: infinite bounds travel as NULL only when a whole vector is
+    infinite."""
+    ds, keep = MpcDesc(), []
+
+    def ptr(a, skip=None):
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if skip is not None and np.all(a == skip):
+            return None
+        keep.append(a)
+        return a.ctypes.data
+
+    p, m = controller.K.shape
+    ds.N, ds.p, ds.m, ds.iters = int(controller.horizon), p, m, int(iters)
+    ds.H, ds.F, ds.K = ptr(controller.H), ptr(controller.F), ptr(controller.K)
+    ds.lo, ds.hi = ptr(controller.lo, -np.inf), ptr(controller.hi, np.inf)
+    ds.dlo, ds.dhi = ptr(controller.dlo, -np.inf), ptr(controller.dhi, np.inf)
+    ds.rho, ds.tol = float(controller.rho), float(tol)
+    return ds, keep
+
+
 class LoopUnit(C.Structure):
     """nk_loop_unit (include/nyskoop.h), one unit of nk_closed_loop_multi: six pointers (model, K, phi0, phi_ref, target,
     u_init): 48 bytes, no padding."""
@@ -160,6 +189,9 @@ SIGNATURES = {
     "nk_poly_plant_loop": (C.c_int, [_P, _P, C.POINTER(PolyPlant), _P, _P, _P, _I32, _I32, _P, _P]),
     "nk_poly_plant_loop_multi": (C.c_int, [_P, C.POINTER(PolyPlant), _I32, C.POINTER(PlantUnit), _I32, _P, _I32, _P, _P,
                                            _P]),
+    "nk_mpc_loop": (C.c_int, [_P, _P, C.POINTER(PolyPlant), C.POINTER(MpcDesc), _P, _P, _P, _I32, _I32, _P, _P, _P]),
+    "nk_mpc_qp_host": (C.c_int, [C.POINTER(MpcDesc), _P, _P, _P, _P, _P]),
+    "nk_mpc_loop_max_m": (C.c_int, [_I32]),
     "nk_closed_loop_multi": (C.c_int, [_P, _I32, _D, C.POINTER(LoopUnit), _I32, _P, _P, _P, _P, _P]),
     "nk_dare_batch": (C.c_int, [_P, C.POINTER(DareProblem), _I32, _D, _I32, C.POINTER(_I32), C.POINTER(_I32)]),
     "nk_model_lqr_gain_batch": (C.c_int, [_P, C.POINTER(_P), _I32, _D, _P, _D, _I32, _P, C.POINTER(_I32),

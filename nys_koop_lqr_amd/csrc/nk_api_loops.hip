@@ -1,13 +1,16 @@
 // Closed loops that run as one launch behind the C ABI: the plant loops (nk_plant_step, nk_plant_loop, nk_plant_loop_multi and
-// their forms for a polynomial plant the caller describes, nk_poly_plant_*; nk_plant_loop.hip) and the lifted loop of many models (nk_closed_loop_multi; nk_loop_multi.hip).  The unit-table calls
+// their forms for a polynomial plant the caller describes, nk_poly_plant_*; nk_plant_loop.hip), the constrained MPC loop
+// (nk_mpc_loop, nk_mpc_qp_host; nk_mpc_loop.hip, nk_mpc.h) and the lifted loop of many models (nk_closed_loop_multi; nk_loop_multi.hip).  The unit-table calls
 // check every unit, lay its host operands out in one staging block (nk_unit_pack.h), move it with one copy, build the
 // table of device records, launch, and bring the results back behind one synchronisation.
 #include "nk_common.h"
 #include "nk_api_internal.h"
 #include "nk_plant.h"
 #include "nk_poly_plant.h"
+#include "nk_mpc.h"
 
 #include <cmath>
+#include <limits>
 #include <string>
 #include <vector>
 
@@ -275,6 +278,98 @@ int nk_poly_plant_loop_multi(nk_ctx* ctx, const nk_poly_plant* plant, int32_t st
   if (out_u) NK_TRY(finish_out(ctx, ou));
   if (scores) NK_HIP(hipMemcpyAsync(scores, d_sc, (size_t)n_units * 32, hipMemcpyDeviceToHost, ctx->stream));
   NK_HIP(hipStreamSynchronize(ctx->stream));  // (the staging block and recs are read by the copies queued above)
+  return NK_OK;
+}
+
+int nk_mpc_loop_max_m(int32_t nv) { return mpc_loop_max_m(nv); }
+
+int nk_mpc_qp_host(const nk_mpc_desc* desc, const double* e, const double* u_prev, double* out_u, double* out_z,
+                   double* out_info) {
+  char msg[200];
+  NK_REQUIRE(mpc_qp_host(desc, e, u_prev, out_u, out_z, out_info, msg, sizeof msg) == 0, "nk_mpc_qp_host: %s", msg);
+  return NK_OK;
+}
+
+int nk_mpc_loop(nk_ctx* ctx, const nk_model* mdl, const nk_poly_plant* plant, const nk_mpc_desc* desc, const double* x0,
+                const double* x_ref, const double* u_init, int32_t steps, int32_t batch, double* out_x, double* out_u,
+                double* out_info) {
+  NK_TRY(check_ctx(ctx));
+  NK_REQUIRE(!ctx_recording(ctx), "nk_mpc_loop: not available to the members of a lock-step group");
+  NK_REQUIRE(mdl && x0 && x_ref && out_x && out_u, "nk_mpc_loop: null argument");
+  NK_TRY(check_poly_plant("nk_mpc_loop", plant));
+  char msg[200];
+  NK_REQUIRE(desc != nullptr, "nk_mpc_loop: the description is null");
+  // the validation reads the arrays of the description on the host: a device pointer is rejected before it is followed
+  NK_REQUIRE(!is_device_ptr(desc->H) && !is_device_ptr(desc->F) && !is_device_ptr(desc->K) && !is_device_ptr(desc->lo) &&
+                 !is_device_ptr(desc->hi) && !is_device_ptr(desc->dlo) && !is_device_ptr(desc->dhi),
+             "nk_mpc_loop: the arrays of the description (H, F, K, lo, hi, dlo, dhi) must be host memory");
+  NK_REQUIRE(mpc_desc_check(desc, msg, sizeof msg), "nk_mpc_loop: %s", msg);
+  NK_REQUIRE(desc->p == plant->p, "nk_mpc_loop: the plant has %d inputs, the description has p = %d", plant->p, desc->p);
+  NK_REQUIRE(mdl->device == ctx->device, "nk_mpc_loop: the model lives on device %d, the context on %d", mdl->device,
+             ctx->device);
+  NK_REQUIRE(mdl->p == plant->p, "nk_mpc_loop: the plant has %d inputs, the model has %d", plant->p, mdl->p);
+  NK_REQUIRE(mdl->d == plant->d, "nk_mpc_loop: the plant has %d states, the model has %d", plant->d, mdl->d);
+  NK_REQUIRE(desc->m == mdl->m, "nk_mpc_loop: the description is for m = %d, the model has %d landmarks", desc->m, mdl->m);
+  const int m = mdl->m, d = mdl->d, p = mdl->p;
+  const bool cheap = desc->iters == 0;
+  const int nv = cheap ? p : desc->N * p;  // the saturated LQR runs the loop on the p entries of one move
+  NK_REQUIRE(m <= mpc_loop_max_m(nv), "nk_mpc_loop: m = %d landmarks, at most %d fit one workgroup with nv = %d variables", m,
+             mpc_loop_max_m(nv), nv);
+  NK_REQUIRE(mdl->kind == NK_MODEL_SPLINE
+                 ? mdl->ktype == NK_KERNEL_TPS
+                 : (mdl->ktype == NK_KERNEL_RBF || mdl->ktype == NK_KERNEL_MATERN52 || mdl->ktype == NK_KERNEL_LINEAR),
+             "nk_mpc_loop: kernel type %d is not supported for this model", mdl->ktype);
+  NK_REQUIRE(steps >= 1 && batch >= 1, "nk_mpc_loop: steps = %d and batch = %d must be positive", steps, batch);
+  NK_TRY(mpc_loop_check_lds(ctx, m, nv));  // the device's LDS per workgroup against what this (m, nv) needs
+  // the constants of the call on the host: [M | H^-1 | lo hi dlo dhi]
+  const size_t nn = cheap ? 0 : (size_t)nv * nv;
+  std::vector<double> blk(2 * nn + 4 * (size_t)nv);
+  if (!cheap) NK_REQUIRE(mpc_prepare(*desc, blk.data() + nn, blk.data(), msg, sizeof msg), "nk_mpc_loop: %s", msg);
+  {
+    const double inf = std::numeric_limits<double>::infinity();
+    double* bnd = blk.data() + 2 * nn;
+    for (int i = 0; i < nv; ++i) {
+      bnd[i] = mpc_bound(desc->lo, i, -inf);
+      bnd[nv + i] = mpc_bound(desc->hi, i, inf);
+      bnd[2 * nv + i] = mpc_bound(desc->dlo, i, -inf);
+      bnd[3 * nv + i] = mpc_bound(desc->dhi, i, inf);
+    }
+  }
+  // ---- everything is checked: stage and queue
+  const double* G = cheap ? desc->K : desc->F;  // nv x m, host
+  MatIn cst, gm, xi, xr, ui;
+  MatOut ox, ou, oi;
+  NK_TRY(stage_in(ctx, blk.data(), (int64_t)blk.size(), 1, (int64_t)blk.size(), &cst));
+  NK_TRY(stage_in(ctx, x0, d, batch, d, &xi));
+  NK_TRY(stage_in(ctx, x_ref, d, batch, d, &xr));
+  if (u_init) NK_TRY(stage_in(ctx, u_init, p, batch, p, &ui));
+  NK_TRY(stage_out(ctx, out_x, d, (int64_t)batch * (steps + 1), d, &ox));
+  NK_TRY(stage_out(ctx, out_u, p, (int64_t)batch * steps, p, &ou));
+  if (out_info) NK_TRY(stage_out(ctx, out_info, 2, (int64_t)batch * steps, 2, &oi));
+  // g = F e = F (k S^-1)^T = (S^-1 F^T)^T k: W = S^-1 F^T (m x nv) by ONE product; a spline model lifts with the raw block,
+  // W = F^T
+  const double* w = nullptr;
+  std::vector<double> Gt;
+  if (mdl->kind != NK_MODEL_SPLINE) {
+    double* wf = nullptr;
+    NK_TRY(stage_in(ctx, G, m, nv, m, &gm));
+    NK_TRY(arena_alloc_t(ctx, (size_t)m * nv + 2, &wf));
+    NK_TRY(launch_gemm(ctx, false, true, m, nv, m, 1.0, mdl->Sinv, m, gm.ptr, gm.ld, 0.0, wf, nv));
+    w = wf;
+  } else {
+    Gt.resize((size_t)m * nv);
+    for (int l = 0; l < m; ++l)
+      for (int i = 0; i < nv; ++i) Gt[(size_t)l * nv + i] = G[(size_t)i * m + l];
+    NK_TRY(stage_in(ctx, Gt.data(), (int64_t)Gt.size(), 1, (int64_t)Gt.size(), &gm));
+    w = gm.ptr;
+  }
+  NK_TRY(launch_mpc_loop(ctx, mdl, *plant, nv, desc->iters, desc->rho, desc->tol, w, cst.ptr, cst.ptr + nn, cst.ptr + 2 * nn,
+                         xi.ptr, xi.ld, xr.ptr, xr.ld, u_init ? ui.ptr : nullptr, u_init ? ui.ld : 0, steps, batch, ox.dev,
+                         ox.ld, ou.dev, ou.ld, out_info ? oi.dev : nullptr));
+  NK_TRY(finish_out(ctx, ox));
+  NK_TRY(finish_out(ctx, ou));
+  if (out_info) NK_TRY(finish_out(ctx, oi));
+  NK_HIP(hipStreamSynchronize(ctx->stream));  // (blk and Gt are read by the copies queued above)
   return NK_OK;
 }
 

@@ -612,6 +612,15 @@ int launch_poly_loop(nk_ctx* ctx, const nk_model* mdl, const nk_poly_plant& plan
                      int batch, double* out_x, int64_t ldx, double* out_u, int64_t ldu);
 int launch_poly_loop_multi(nk_ctx* ctx, const nk_poly_plant& plant, int steps, PolyLoopUnit* units, const int* ktypes,
                            int n_units);
+// The constrained MPC loop around a polynomial plant (nk_mpc_loop.hip; nk_mpc_loop): every pointer device memory.  w: the
+// folded gradient map, m x nv dense (iters = 0: nv = p and w the folded gain); M, Hinv: nv x nv dense (iters = 0: unused); bnd:
+// lo, hi, dlo, dhi back to back, nv each, infinite where a bound is absent; uinit / out_info may be null.  The limit on m
+// for nv variables is mpc_loop_max_m (nk_mpc.h).
+int mpc_loop_check_lds(nk_ctx* ctx, int m, int nv, int* lds_max_out = nullptr);  // before anything is queued
+int launch_mpc_loop(nk_ctx* ctx, const nk_model* mdl, const nk_poly_plant& plant, int nv, int iters, double rho, double tol,
+                    const double* w, const double* M, const double* Hinv, const double* bnd, const double* x0, int64_t x0_stride,
+                    const double* xref, int64_t xref_stride, const double* uinit, int64_t uinit_stride, int steps, int batch,
+                    double* out_x, int64_t ldx, double* out_u, int64_t ldu, double* out_info);
 
 // ---- lifted closed loops of many models in ONE launch, scored on the device (nk_loop_multi.hip): one 1024-thread workgroup
 // per unit, blockIdx.x = the record.  Every pointer is device memory.  Per step t < steps: u_t = K (phi_ref - phi_t),

@@ -507,6 +507,27 @@ def lqr_control_plant_device(num_steps, reference, initial_state, regressor, K, 
     return np.array(states[0, :num_steps]), us
 
 
+def mpc_control_plant(num_steps, reference, initial_state, regressor, controller, plant_step, iters=50, tol=0.0,
+                      u_init=None):
+    """The host loop of the constrained MPC (regressor.closed_loop_plant_mpc is the same loop in one device launch): one
+    lift per step, e = phi(x) - phi(ref), the control from lqr.mpc_solve (controller.control) with u_{-1} = the control
+    applied last (u_init, zeros by default, before the first step), x <- plant_step(x (d, 1), u (p, 1)).  iters = 0: the
+    saturated LQR.  Returns (states (d, num_steps + 1) with the initial state first, u_s (p, num_steps), info (num_steps, 2)
+    = {iterations run, final max |s - z|})."""
+    x = np.asarray(initial_state, dtype=np.float64).reshape(-1, 1)
+    phi_ref = regressor.lift(np.asarray(reference, dtype=np.float64).reshape(-1, 1))
+    p = controller.n_inputs
+    u_prev = np.zeros(p) if u_init is None else np.asarray(u_init, dtype=np.float64).reshape(p)
+    xs, us, info = [x], [], []
+    for _ in range(num_steps):
+        u_prev, it = controller.control((regressor.lift(x) - phi_ref).reshape(-1), u_prev, iters, tol)
+        us.append(u_prev.reshape(-1, 1))
+        info.append(it)
+        x = np.asarray(plant_step(x, u_prev.reshape(-1, 1)), dtype=np.float64).reshape(-1, 1)
+        xs.append(x)
+    return np.hstack(xs), np.hstack(us), np.array(info, dtype=np.float64).reshape(num_steps, 2)
+
+
 def open_loop_control(plant_step, initial_state, controls):
     """benchmark_lqr_classic.py:91-97: replay a control sequence (p x T) on the true plant; returns the visited states
     (d x (T + 1)), the initial state first."""

@@ -108,3 +108,193 @@ def dlqr_device(A, B, Q, R, tol=1e-13, max_iter=40):
 def cloth_gain_for_simulator(K):
     """Row permutation expected by the MATLAB cloth simulator (benchmark_lqr_cloth.py:263)."""
     return K[[0, 3, 1, 4, 2, 5], :]
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Constrained Koopman MPC: the condensed QP of the lifted model under box and rate limits on the inputs, and the fixed-step
+# ADMM iteration that the device loop runs (csrc/nk_mpc_loop.hip) and the host build states (csrc/nk_mpc.h, nk_mpc_qp_host).
+# ---------------------------------------------------------------------------------------------------------------------------
+def mpc_condense(A, B, Q, R, P, N):
+    """(H, F) of  sum_{k<N} (e_k'Q e_k + u_k'R u_k) + e_N'P e_N  under  e_{k+1} = A e_k + B u_k  as a function of
+    U = (u_0, ..., u_{N-1}) (nv = N p entries) and e_0: the cost is 1/2 U'HU + (F e_0)'U + const, H (nv x nv) symmetrised,
+    F (nv x m).  With P the Riccati solution the first p rows of H^-1 F are the dlqr gain for every N.
+    Only thin products: G_k = A^k B (m x p) and, per block column j, the Horner recursion
+        W_l = T_l + A' W_{l+1},  l = N .. 0,  T_l = Q_l G_{l-1-j} for l > j (Q_N = P), 0 otherwise,
+    which gives H_ij = 2 B'W_{i+1} (i >= j) and F_j = 2 W_0'; no power of A is formed.  O(N^2 m^2 p) operations."""
+    A = np.asarray(A, dtype=np.float64)
+    m = A.shape[0]
+    B = np.asarray(B, dtype=np.float64).reshape(m, -1)
+    p = B.shape[1]
+    Q, P = np.asarray(Q, dtype=np.float64), np.asarray(P, dtype=np.float64)
+    R = np.asarray(R, dtype=np.float64).reshape(p, p)
+    N = int(N)
+    if N < 1:
+        raise ValueError("the horizon N must be at least 1")
+    G = [B]
+    for _ in range(N - 1):
+        G.append(A @ G[-1])
+    nv = N * p
+    H, F = np.zeros((nv, nv)), np.zeros((nv, m))
+    for j in range(N):
+        W = np.zeros((m, p))
+        for l in range(N, -1, -1):
+            W = A.T @ W
+            if l > j:
+                W = W + (P if l == N else Q) @ G[l - 1 - j]
+            if j + 1 <= l <= N:  # W_l = W_{i+1} with i = l - 1 >= j
+                H[(l - 1) * p:l * p, j * p:(j + 1) * p] = 2.0 * (B.T @ W)
+        F[j * p:(j + 1) * p, :] = 2.0 * W.T
+    low = np.tril(H, -1)
+    H = low + low.T + np.diag(np.diag(H))
+    for j in range(N):  # the diagonal blocks are symmetric up to rounding
+        blk = H[j * p:(j + 1) * p, j * p:(j + 1) * p]
+        H[j * p:(j + 1) * p, j * p:(j + 1) * p] = (blk + blk.T) / 2 + 2.0 * _sym(R)
+    return _sym(H), F
+
+
+def dare_refine(A, B, Q, R, K, steps=2):
+    """Newton (Hewer) steps on a stabilising gain: P = (A - BK)'P(A - BK) + Q + K'RK by a Lyapunov solve, then
+    K = (R + B'PB)^-1 B'PA.  Returns (K, P).  scipy's Riccati solution of the lifted models (spectral radius of A just above 1,
+    of the closed loop just below) leaves a relative Riccati residual of 1e-9 .. 1e-10, and dlqr's gain then differs from the
+    first move of the condensed problem by 2e-9 .. 1e-8; one step brings the residual to 1e-14 and the two to 1e-13."""
+    A, B = np.asarray(A, dtype=np.float64), np.asarray(B, dtype=np.float64).reshape(np.shape(A)[0], -1)
+    R = np.asarray(R, dtype=np.float64).reshape(B.shape[1], B.shape[1])
+    K, P = np.asarray(K, dtype=np.float64), None
+    for _ in range(int(steps)):
+        Ac = A - B @ K
+        P = _sym(scipy.linalg.solve_discrete_lyapunov(Ac.T, Q + K.T @ R @ K))
+        K = np.linalg.solve(B.T @ P @ B + R, B.T @ P @ A)
+    return K, P
+
+
+def mpc_diff(U, p):
+    """D U: the block first difference, (D U)_k = u_k - u_{k-1}, (D U)_0 = u_0."""
+    s = np.array(U, dtype=np.float64)
+    s[p:] -= U[:-p]
+    return s
+
+
+def mpc_diff_t(w, p):
+    """D'w: (D'w)_k = w_k - w_{k+1}, the last block w_{N-1}."""
+    r = np.array(w, dtype=np.float64)
+    r[:-p] -= w[p:]
+    return r
+
+
+def mpc_matrices(H, rho, p):
+    """(M, Hinv) = ((H + rho (I + D'D))^-1, H^-1): what a call forms once.  Raises np.linalg.LinAlgError when H is not
+    positive definite."""
+    H = np.asarray(H, dtype=np.float64)
+    nv = H.shape[0]
+    D = np.eye(nv) - np.eye(nv, k=-p)
+    eye = np.eye(nv)
+    Hinv = scipy.linalg.cho_solve(scipy.linalg.cho_factor(H, lower=True), eye)
+    M = scipy.linalg.cho_solve(scipy.linalg.cho_factor(H + rho * (eye + D.T @ D), lower=True), eye)
+    return _sym(M), _sym(Hinv)
+
+
+def mpc_default_rho(H):
+    """sqrt(lambda_min(H) lambda_max(H)): the fixed step that reached 1e-9 of the bound in at most 26 / 52 / 242 iterations at
+    N = 32 for Q = c C'C, c = 1 / 1e2 / 1e4 on the Duffing models."""
+    ev = np.linalg.eigvalsh(np.asarray(H, dtype=np.float64))
+    if not ev[0] > 0:
+        raise np.linalg.LinAlgError("H is not positive definite")
+    return float(np.sqrt(ev[0] * ev[-1]))
+
+
+def mpc_admm_step(M, rho, g, lo_c, hi_c, z, lam, p):
+    """One iteration on the constraint rows A_c = [I; D] (2 nv rows; lo_c, hi_c their bounds, the first p rate rows already
+    shifted by the control applied last):  w = z - lambda;  U = M (rho (w_1 + D'w_2) - g);  s = A_c U;
+    z = clip(s + lambda);  lambda += s - z.  Returns (U, z, lambda, max |s - z|)."""
+    nv = g.size
+    w = z - lam
+    U = M @ (rho * (w[:nv] + mpc_diff_t(w[nv:], p)) - g)
+    s = np.concatenate([U, mpc_diff(U, p)])
+    z = np.minimum(np.maximum(s + lam, lo_c), hi_c)
+    lam = lam + (s - z)
+    return U, z, lam, float(np.max(np.abs(s - z)))
+
+
+def mpc_saturate(v, lo, hi, dlo, dhi, u_prev):
+    """clip(clip(v, lo, hi), u_prev + dlo, u_prev + dhi) on the p entries of one move: the rate clip last."""
+    p = np.size(v)
+    a = np.minimum(np.maximum(np.asarray(v, dtype=np.float64).reshape(p), lo[:p]), hi[:p])
+    return np.minimum(np.maximum(a, u_prev + dlo[:p]), u_prev + dhi[:p])
+
+
+def mpc_bounds(nv, lo=None, hi=None, dlo=None, dhi=None):
+    """The four bound vectors of nv entries; None is the infinite bound, a scalar or one move (p entries) is repeated."""
+    def full(a, missing):
+        if a is None:
+            return np.full(nv, missing)
+        a = np.asarray(a, dtype=np.float64).reshape(-1)
+        if nv % a.size:
+            raise ValueError(f"a bound of {a.size} entries does not tile {nv} decision variables")
+        return np.ascontiguousarray(np.tile(a, nv // a.size))
+    return full(lo, -np.inf), full(hi, np.inf), full(dlo, -np.inf), full(dhi, np.inf)
+
+
+def mpc_solve(H, g, lo, hi, dlo, dhi, u_prev, rho, iters, tol=0.0, p=1, M=None, Hinv=None, K_e=None):
+    """One solve of  min 1/2 U'HU + g'U,  lo <= U <= hi,  dlo <= u_k - u_{k-1} <= dhi  (u_{-1} = u_prev) by the iteration of
+    include/nyskoop.h -- the NumPy statement the device kernel follows:
+        U_unc = -H^-1 g;  s = A_c U_unc;  z = clip(s);  lambda = 0;  r = max |s - z|;  k = 0
+        while k < iters and not (r <= tol and (k == 0 or tol > 0)):  mpc_admm_step;  k += 1
+        u = clip(clip(z[:p], lo, hi), u_prev + dlo, u_prev + dhi)
+    Returns (u (p,), z_1 (nv,), (k, r)).  iters = 0 is the saturated LQR: u from v = -K_e (the caller's K e), z_1 = None.
+    lo, hi, dlo, dhi: nv entries each (mpc_bounds); M, Hinv: mpc_matrices(H, rho, p) when the caller keeps them."""
+    u_prev = np.zeros(p) if u_prev is None else np.asarray(u_prev, dtype=np.float64).reshape(p)
+    if iters == 0:
+        return mpc_saturate(-np.asarray(K_e, dtype=np.float64).reshape(p), lo, hi, dlo, dhi, u_prev), None, (0, 0.0)
+    g = np.asarray(g, dtype=np.float64).reshape(-1)
+    nv = g.size
+    if M is None or Hinv is None:
+        M, Hinv = mpc_matrices(H, rho, p)
+    shift = np.zeros(nv)
+    shift[:p] = u_prev
+    lo_c, hi_c = np.concatenate([lo, dlo + shift]), np.concatenate([hi, dhi + shift])
+    U = -(Hinv @ g)
+    s = np.concatenate([U, mpc_diff(U, p)])
+    z = np.minimum(np.maximum(s, lo_c), hi_c)
+    lam = np.zeros(2 * nv)
+    r, k = float(np.max(np.abs(s - z))), 0
+    while k < iters and not (r <= tol and (k == 0 or tol > 0)):
+        U, z, lam, r = mpc_admm_step(M, rho, g, lo_c, hi_c, z, lam, p)
+        k += 1
+    return mpc_saturate(z[:p], lo, hi, dlo, dhi, u_prev), z[:nv].copy(), (k, r)
+
+
+class MPCController:
+    """What reg.solve_mpc returns: the condensed QP (H, F), the bounds lo, hi, dlo, dhi (nv entries each, +-inf where
+    absent), the LQR gain K of the same cost (the saturated-LQR mode, iters = 0), rho and the horizon.  Plain arrays: picklable."""
+
+    def __init__(self, H, F, lo, hi, dlo, dhi, K, rho, horizon):
+        self.H, self.F = np.ascontiguousarray(H, dtype=np.float64), np.ascontiguousarray(F, dtype=np.float64)
+        self.K = np.ascontiguousarray(K, dtype=np.float64)
+        self.lo, self.hi, self.dlo, self.dhi = (np.ascontiguousarray(a, dtype=np.float64) for a in (lo, hi, dlo, dhi))
+        self.rho, self.horizon = float(rho), int(horizon)
+        self._mats = None
+
+    n_inputs = property(lambda self: self.K.shape[0])
+    nv = property(lambda self: self.H.shape[0])
+
+    def matrices(self):
+        if self.__dict__.get("_mats") is None:
+            self._mats = mpc_matrices(self.H, self.rho, self.n_inputs)
+        return self._mats
+
+    def __getstate__(self):
+        st = dict(self.__dict__)
+        st["_mats"] = None
+        return st
+
+    def control(self, e, u_prev=None, iters=50, tol=0.0):
+        """The control for the lifted error e = phi(x) - phi(x_ref) (m,): (u (p,), (iterations, residual)) by mpc_solve."""
+        e = np.asarray(e, dtype=np.float64).reshape(-1)
+        if iters == 0:
+            u, _, info = mpc_solve(None, None, self.lo, self.hi, self.dlo, self.dhi, u_prev, self.rho, 0, p=self.n_inputs,
+                                   K_e=self.K @ e)
+            return u, info
+        M, Hinv = self.matrices()
+        u, _, info = mpc_solve(self.H, self.F @ e, self.lo, self.hi, self.dlo, self.dhi, u_prev, self.rho, iters, tol,
+                               self.n_inputs, M, Hinv)
+        return u, info
