@@ -633,6 +633,10 @@ int nk_dare_large_times(double out[5]);
  *   are not read.  For one input under a symmetric box alone and the Riccati terminal cost this IS the first move of the QP
  *   (measured: equal to 1e-15 of the bound at every step), so a bounds-only single-input user should take this mode.
  *   out_info (may be NULL): batch x steps x 2 = {iterations run, final max |s - z|} (iters = 0: zeros).
+ *   NaN: a step whose gradient F e (a NaN state) or whose shifted rate bound u_{-1} + dlo / dhi (a NaN seed, inf - inf) holds a
+ *   NaN ends as the NumPy statement ends it, whose clips hand a NaN on: every entry of u_t is NaN, out_info = {iters, NaN}
+ *   (iters = 0: the entries of u_t whose own v or bounds are NaN, out_info zeros).  The device loop and nk_mpc_qp_host decide such a
+ *   step before the iteration (their clips are fmin / fmax, which would return a bound); no other step is affected.
  *   Device side (nk_mpc_loop.hip): one workgroup per trajectory, ceil(m / 64) waves, the whole loop inside it.  F is folded
  *   into the lift once per call, W = S^-1 F' (m x nv; spline models: F'), and lives in LDS; g = W'(k(Z, x_t) - k(Z, x_ref)),
  *   the difference taken landmark by landmark before the product.  Lane i of the first wave owns decision variable i: its row
@@ -669,6 +673,52 @@ int nk_mpc_loop(nk_ctx* ctx, const nk_model* model, const nk_poly_plant* plant, 
 int nk_mpc_qp_host(const nk_mpc_desc* desc, const double* e, const double* u_prev_or_NULL, double* out_u, double* out_z,
                    double* out_info);
 int nk_mpc_loop_max_m(int32_t nv);  /* the limit on m for nv decision variables (0: nv out of range) */
+/* ---- the multi-model form of the constrained MPC loop, scored on the device: the seeds x m table of the control experiments
+ *   under actuator limits in ONE call after the fits and controllers.  The units of a call share the plant and `steps` and
+ *   may differ in everything else: model kind, kernel family, m, horizon, iters (0, the saturated LQR, included), rho, tol,
+ *   limits, x0, x_ref, u_init.  UNIT u IS BIT FOR BIT nk_mpc_loop(model, plant, desc, x0, x_ref, u_init, steps, batch = 1) in
+ *   out_x, out_u and out_info, whatever else the call holds and in whatever order: M, H^-1 and the bounds come from the same
+ *   host preparation, and the fold W = S^-1 F' (iters = 0: S^-1 K') is the same product on operands laid out as the single
+ *   call lays them out.
+ *   Outputs, host or device memory, EACH MAY BE NULL and is then never written on the device either:
+ *     out_x:    n_units x (steps + 1) x d   (row 0 = x0)
+ *     out_u:    n_units x steps x p
+ *     out_info: n_units x steps x 2         {iterations run, final max |s - z|}
+ *   scores: HOST, n_units x NK_MPC_N_SCORES, may be NULL.  The four outputs must not all be NULL.
+ *   u_opt: n_uopt x steps x p reference controls (host or device), unit u is scored against row units[u].uopt (-1: none, and
+ *   then sse_u = ss_opt = 0), as in nk_poly_plant_loop_multi.
+ *     scores[u] = {sse_u, ss_opt, J, u_absmax, iters_sum, r_max, n_at_limit, n_iterated}
+ *   The first four are those of nk_poly_plant_loop_multi: the same order of operations, rounded squares, no contraction.
+ *     iters_sum  = sum over t of the iterations run (out_info[t][0]), in step order;
+ *     r_max      = max over t of the final max |s - z| (out_info[t][1]), NaN from the first NaN on (the rule of u_absmax);
+ *     n_at_limit = the number of (t, j) at which the applied u_tj equals one of its four bounds of that step: lo_j, hi_j,
+ *                  fl(u_{t-1,j} + dlo_j), fl(u_{t-1,j} + dhi_j) (u_{-1} = u_init or zeros).  A clip returns the bound itself,
+ *                  so this is exact; a (t, j) at two bounds at once counts once;
+ *     n_iterated = the number of steps with at least one iteration.
+ *   A host loop over the returned out_x, out_u, out_info and the bounds gives the same bits for all eight
+ *   (harness.mpc_scores in Python).  A unit started at a NaN x0 has NaN controls (the NaN rule of nk_mpc_loop), so its
+ *   u_absmax, J and r_max are NaN, iters_sum = steps * iters and n_at_limit = 0; the other units are not affected.
+ *   Everything is checked before anything is queued or written; a bad unit is NK_ERR_BAD_ARG with its index and the field in
+ *   nk_last_error().  Per unit every check of nk_mpc_loop applies (the description and its host arrays, d / p / m agreement,
+ *   kernel family, m <= nk_mpc_loop_max_m(nv), LDS), and: uopt in -1 .. n_uopt - 1, reserved == 0, x0 / x_ref / u_init host
+ *   memory; n_units >= 1, steps >= 1.  Ordinary contexts only (not lock-step members); models need not belong to ctx, the
+ *   same device suffices.
+ *   Device side (nk_mpc_loop.hip): the loop body of nk_mpc_loop reading a per-unit record; blockIdx.x selects a record of a
+ *   table staged with one copy, all constants, F / K, states and seeds are staged with one more.  One launch per class of
+ *   (kernel family, padded states, nv padded to 16 / 32 / 64, ceil(m / 64) waves); no kernel waits for another workgroup.
+ *   The scores are accumulated by one lane in step order. */
+typedef struct nk_mpc_unit {
+  const nk_model* model;    /* as for nk_mpc_loop: Nystrom (RBF / Matern-5/2 / linear) or spline model, d and p = the plant's */
+  const nk_mpc_desc* desc;  /* HOST, its arrays HOST; desc->m == model->m, desc->p == plant->p; units may share one */
+  const double* x0;         /* HOST, d */
+  const double* x_ref;      /* HOST, d */
+  const double* u_init;     /* HOST, p, or NULL = zeros */
+  int32_t uopt;             /* row of u_opt this unit is scored against, or -1 */
+  int32_t reserved;         /* must be 0 */
+} nk_mpc_unit;
+#define NK_MPC_N_SCORES 8
+int nk_mpc_loop_multi(nk_ctx* ctx, const nk_poly_plant* plant, int32_t steps, const nk_mpc_unit* units, int32_t n_units,
+                      const double* u_opt, int32_t n_uopt, double* out_x, double* out_u, double* out_info, double* scores);
 /* ---- rollout of explicit operators without a model (any estimator that exposes A, B, C: the exact-kernel comparator of
  *   benchmark_lqr_hjb.py:334-381, un-pickled gains): z0: batch x m lifted initial states; A: m x m, B: m x p, C: d x m
  *   (row-major, host or device); U, out_x, out_z as in nk_rollout. --------------------------------------------------- */

@@ -93,6 +93,16 @@ def mpc_desc(controller, iters, tol):
     return ds, keep
 
 
+class MpcUnit(C.Structure):
+    """nk_mpc_unit (include/nyskoop.h), one unit of nk_mpc_loop_multi: five pointers (model, desc, x0, x_ref, u_init) and
+    two int32 (uopt, reserved): 48 bytes, no padding."""
+    _fields_ = [("model", C.c_void_p), ("desc", C.POINTER(MpcDesc)), ("x0", C.c_void_p), ("x_ref", C.c_void_p),
+                ("u_init", C.c_void_p), ("uopt", C.c_int32), ("reserved", C.c_int32)]
+
+
+MPC_N_SCORES = 8  # NK_MPC_N_SCORES
+
+
 class LoopUnit(C.Structure):
     """nk_loop_unit (include/nyskoop.h), one unit of nk_closed_loop_multi: six pointers (model, K, phi0, phi_ref, target,
     u_init): 48 bytes, no padding."""
@@ -190,6 +200,7 @@ SIGNATURES = {
     "nk_poly_plant_loop_multi": (C.c_int, [_P, C.POINTER(PolyPlant), _I32, C.POINTER(PlantUnit), _I32, _P, _I32, _P, _P,
                                            _P]),
     "nk_mpc_loop": (C.c_int, [_P, _P, C.POINTER(PolyPlant), C.POINTER(MpcDesc), _P, _P, _P, _I32, _I32, _P, _P, _P]),
+    "nk_mpc_loop_multi": (C.c_int, [_P, C.POINTER(PolyPlant), _I32, C.POINTER(MpcUnit), _I32, _P, _I32, _P, _P, _P, _P]),
     "nk_mpc_qp_host": (C.c_int, [C.POINTER(MpcDesc), _P, _P, _P, _P, _P]),
     "nk_mpc_loop_max_m": (C.c_int, [_I32]),
     "nk_closed_loop_multi": (C.c_int, [_P, _I32, _D, C.POINTER(LoopUnit), _I32, _P, _P, _P, _P, _P]),
@@ -474,6 +485,53 @@ class Context:
                                                ptr(ou), ptr(sc))
         check_mapped(rc)
         return sc, ox, ou
+
+    def mpc_loop_multi(self, descriptor, steps, models, descs, x0s, x_refs, u_inits=None, u_opt=None, uopt_rows=None,
+                       want_x=False, want_u=False, want_info=False, want_scores=True):
+        """nk_mpc_loop_multi: one constrained MPC loop around a polynomial plant (descriptor: a PolyPlant) per unit, all units
+        in one call, scored on the device.  models: device-model handles; descs: one MpcDesc per unit (units may share one;
+        the caller keeps their arrays alive); x0s, x_refs: (n_units, d); u_inits: (n_units, p), a list with None entries, or
+        None = zeros; u_opt: (n_uopt, steps, p) or None; uopt_rows as in poly_plant_loop_multi.  Returns (scores
+        (n_units, 8) or None, states (n_units, steps + 1, d) or None, controls (n_units, steps, p) or None, info
+        (n_units, steps, 2) or None)."""
+        n = len(models)
+        steps = int(steps)
+        d, p = int(descriptor.d), int(descriptor.p)
+        x0s = np.ascontiguousarray(np.asarray(x0s, dtype=np.float64).reshape(n, d))
+        x_refs = np.ascontiguousarray(np.asarray(x_refs, dtype=np.float64).reshape(n, d))
+        if len(descs) != n:
+            raise ValueError(f"{len(descs)} descriptions for {n} models")
+        uis = [None] * n
+        if u_inits is not None:
+            if len(u_inits) != n:
+                raise ValueError(f"{len(u_inits)} u_inits for {n} models")
+            for i, ui in enumerate(u_inits):
+                if ui is not None:
+                    uis[i] = np.ascontiguousarray(ui, dtype=np.float64).reshape(p)
+        uo, n_uopt = None, 0
+        if u_opt is not None:
+            uo = np.ascontiguousarray(np.asarray(u_opt, dtype=np.float64).reshape(-1, max(steps, 1) * p))
+            n_uopt = uo.shape[0]
+        if uopt_rows is None:
+            uopt_rows = [0 if n_uopt else -1] * n
+        arr = (MpcUnit * max(n, 1))()
+        for i in range(n):
+            h = models[i]
+            arr[i].model = h.value if isinstance(h, C.c_void_p) else h
+            arr[i].desc = C.pointer(descs[i])
+            arr[i].x0, arr[i].x_ref = x0s[i].ctypes.data, x_refs[i].ctypes.data
+            arr[i].u_init = None if uis[i] is None else uis[i].ctypes.data
+            arr[i].uopt = int(uopt_rows[i])
+        T = max(steps, 0)
+        sc = np.full((n, MPC_N_SCORES), np.nan) if want_scores else None
+        ox = np.empty((n, T + 1, d)) if want_x else None
+        ou = np.empty((n, T, p)) if want_u else None
+        oi = np.empty((n, T, 2)) if want_info else None
+        ptr = lambda a: None if a is None else a.ctypes.data
+        rc = self.lib.nk_mpc_loop_multi(self.handle, C.byref(descriptor), steps, arr, n, ptr(uo), n_uopt, ptr(ox), ptr(ou),
+                                        ptr(oi), ptr(sc))
+        check_mapped(rc)
+        return sc, ox, ou, oi
 
     def closed_loop_multi(self, steps, c, models, dims, gains, phi0s, phi_refs, targets=None, u_inits=None, want_x=False,
                           want_u=False, want_ucum=False, want_err=True, want_scores=True):

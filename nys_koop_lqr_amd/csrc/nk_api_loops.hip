@@ -1,6 +1,7 @@
 // Closed loops that run as one launch behind the C ABI: the plant loops (nk_plant_step, nk_plant_loop, nk_plant_loop_multi and
 // their forms for a polynomial plant the caller describes, nk_poly_plant_*; nk_plant_loop.hip), the constrained MPC loop
-// (nk_mpc_loop, nk_mpc_qp_host; nk_mpc_loop.hip, nk_mpc.h) and the lifted loop of many models (nk_closed_loop_multi; nk_loop_multi.hip).  The unit-table calls
+// (nk_mpc_loop, nk_mpc_loop_multi, nk_mpc_qp_host; nk_mpc_loop.hip, nk_mpc.h) and the lifted loop of many models
+// (nk_closed_loop_multi; nk_loop_multi.hip).  The unit-table calls
 // check every unit, lay its host operands out in one staging block (nk_unit_pack.h), move it with one copy, build the
 // table of device records, launch, and bring the results back behind one synchronisation.
 #include "nk_common.h"
@@ -11,6 +12,7 @@
 
 #include <cmath>
 #include <limits>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -54,6 +56,62 @@ static int check_poly_model(nk_ctx* ctx, const char* who, int unit, const nk_mod
                  ? mdl->ktype == NK_KERNEL_TPS
                  : (mdl->ktype == NK_KERNEL_RBF || mdl->ktype == NK_KERNEL_MATERN52 || mdl->ktype == NK_KERNEL_LINEAR),
              "%s: %skernel type %d is not supported for this model", who, at().c_str(), mdl->ktype);
+  return NK_OK;
+}
+
+// One model and description against a (validated) polynomial plant, for both MPC loops; unit as in check_plant_model.
+// *nv_out: the decision variables the loop runs on (the saturated LQR: the p entries of one move).
+static int check_mpc_model(nk_ctx* ctx, const char* who, int unit, const nk_model* mdl, const nk_poly_plant& pl,
+                           const nk_mpc_desc* desc, int* nv_out) {
+  auto at = [unit] { return unit >= 0 ? "unit " + std::to_string(unit) + ": " : std::string(); };  // (a failed check only)
+  char msg[200];
+  NK_REQUIRE(desc != nullptr, "%s: %sthe description is null", who, at().c_str());
+  // the validation reads the arrays of the description on the host: a device pointer is rejected before it is followed
+  NK_REQUIRE(!is_device_ptr(desc->H) && !is_device_ptr(desc->F) && !is_device_ptr(desc->K) && !is_device_ptr(desc->lo) &&
+                 !is_device_ptr(desc->hi) && !is_device_ptr(desc->dlo) && !is_device_ptr(desc->dhi),
+             "%s: %sthe arrays of the description (H, F, K, lo, hi, dlo, dhi) must be host memory", who, at().c_str());
+  NK_REQUIRE(mpc_desc_check(desc, msg, sizeof msg), "%s: %s%s", who, at().c_str(), msg);
+  NK_REQUIRE(desc->p == pl.p, "%s: %sthe plant has %d inputs, the description has p = %d", who, at().c_str(), pl.p, desc->p);
+  NK_REQUIRE(mdl->device == ctx->device, "%s: %sthe model lives on device %d, the context on %d", who, at().c_str(),
+             mdl->device, ctx->device);
+  NK_REQUIRE(mdl->p == pl.p, "%s: %sthe plant has %d inputs, the model has %d", who, at().c_str(), pl.p, mdl->p);
+  NK_REQUIRE(mdl->d == pl.d, "%s: %sthe plant has %d states, the model has %d", who, at().c_str(), pl.d, mdl->d);
+  NK_REQUIRE(desc->m == mdl->m, "%s: %sthe description is for m = %d, the model has %d landmarks", who, at().c_str(), desc->m,
+             mdl->m);
+  const int m = mdl->m, p = mdl->p;
+  const int nv = desc->iters == 0 ? p : desc->N * p;  // the saturated LQR runs the loop on the p entries of one move
+  NK_REQUIRE(m <= mpc_loop_max_m(nv), "%s: %sm = %d landmarks, at most %d fit one workgroup with nv = %d variables", who,
+             at().c_str(), m, mpc_loop_max_m(nv), nv);
+  NK_REQUIRE(mdl->kind == NK_MODEL_SPLINE
+                 ? mdl->ktype == NK_KERNEL_TPS
+                 : (mdl->ktype == NK_KERNEL_RBF || mdl->ktype == NK_KERNEL_MATERN52 || mdl->ktype == NK_KERNEL_LINEAR),
+             "%s: %skernel type %d is not supported for this model", who, at().c_str(), mdl->ktype);
+  NK_TRY(mpc_loop_check_lds(ctx, m, nv));  // the device's LDS per workgroup against what this (m, nv) needs
+  *nv_out = nv;
+  return NK_OK;
+}
+
+// The constants of one checked description on the host, [M | H^-1 | lo hi dlo dhi] (2 nn + 4 nv doubles, nn = nv^2, or 0
+// for the saturated LQR): mpc_prepare and mpc_bound, the same for the single call and for a unit of the multi form.
+static int mpc_constants(const char* who, int unit, const nk_mpc_desc& desc, int nv, std::vector<double>* out) {
+  const bool cheap = desc.iters == 0;
+  const size_t nn = cheap ? 0 : (size_t)nv * nv;
+  std::vector<double>& blk = *out;
+  blk.assign(2 * nn + 4 * (size_t)nv, 0.0);
+  char msg[200];
+  if (!cheap && !mpc_prepare(desc, blk.data() + nn, blk.data(), msg, sizeof msg)) {
+    if (unit >= 0) set_error("%s: unit %d: %s", who, unit, msg);
+    else set_error("%s: %s", who, msg);
+    return NK_ERR_BAD_ARG;
+  }
+  const double inf = std::numeric_limits<double>::infinity();
+  double* bnd = blk.data() + 2 * nn;
+  for (int i = 0; i < nv; ++i) {
+    bnd[i] = mpc_bound(desc.lo, i, -inf);
+    bnd[nv + i] = mpc_bound(desc.hi, i, inf);
+    bnd[2 * nv + i] = mpc_bound(desc.dlo, i, -inf);
+    bnd[3 * nv + i] = mpc_bound(desc.dhi, i, inf);
+  }
   return NK_OK;
 }
 
@@ -297,44 +355,15 @@ int nk_mpc_loop(nk_ctx* ctx, const nk_model* mdl, const nk_poly_plant* plant, co
   NK_REQUIRE(!ctx_recording(ctx), "nk_mpc_loop: not available to the members of a lock-step group");
   NK_REQUIRE(mdl && x0 && x_ref && out_x && out_u, "nk_mpc_loop: null argument");
   NK_TRY(check_poly_plant("nk_mpc_loop", plant));
-  char msg[200];
-  NK_REQUIRE(desc != nullptr, "nk_mpc_loop: the description is null");
-  // the validation reads the arrays of the description on the host: a device pointer is rejected before it is followed
-  NK_REQUIRE(!is_device_ptr(desc->H) && !is_device_ptr(desc->F) && !is_device_ptr(desc->K) && !is_device_ptr(desc->lo) &&
-                 !is_device_ptr(desc->hi) && !is_device_ptr(desc->dlo) && !is_device_ptr(desc->dhi),
-             "nk_mpc_loop: the arrays of the description (H, F, K, lo, hi, dlo, dhi) must be host memory");
-  NK_REQUIRE(mpc_desc_check(desc, msg, sizeof msg), "nk_mpc_loop: %s", msg);
-  NK_REQUIRE(desc->p == plant->p, "nk_mpc_loop: the plant has %d inputs, the description has p = %d", plant->p, desc->p);
-  NK_REQUIRE(mdl->device == ctx->device, "nk_mpc_loop: the model lives on device %d, the context on %d", mdl->device,
-             ctx->device);
-  NK_REQUIRE(mdl->p == plant->p, "nk_mpc_loop: the plant has %d inputs, the model has %d", plant->p, mdl->p);
-  NK_REQUIRE(mdl->d == plant->d, "nk_mpc_loop: the plant has %d states, the model has %d", plant->d, mdl->d);
-  NK_REQUIRE(desc->m == mdl->m, "nk_mpc_loop: the description is for m = %d, the model has %d landmarks", desc->m, mdl->m);
+  int nv = 0;
+  NK_TRY(check_mpc_model(ctx, "nk_mpc_loop", -1, mdl, *plant, desc, &nv));
   const int m = mdl->m, d = mdl->d, p = mdl->p;
   const bool cheap = desc->iters == 0;
-  const int nv = cheap ? p : desc->N * p;  // the saturated LQR runs the loop on the p entries of one move
-  NK_REQUIRE(m <= mpc_loop_max_m(nv), "nk_mpc_loop: m = %d landmarks, at most %d fit one workgroup with nv = %d variables", m,
-             mpc_loop_max_m(nv), nv);
-  NK_REQUIRE(mdl->kind == NK_MODEL_SPLINE
-                 ? mdl->ktype == NK_KERNEL_TPS
-                 : (mdl->ktype == NK_KERNEL_RBF || mdl->ktype == NK_KERNEL_MATERN52 || mdl->ktype == NK_KERNEL_LINEAR),
-             "nk_mpc_loop: kernel type %d is not supported for this model", mdl->ktype);
   NK_REQUIRE(steps >= 1 && batch >= 1, "nk_mpc_loop: steps = %d and batch = %d must be positive", steps, batch);
-  NK_TRY(mpc_loop_check_lds(ctx, m, nv));  // the device's LDS per workgroup against what this (m, nv) needs
   // the constants of the call on the host: [M | H^-1 | lo hi dlo dhi]
   const size_t nn = cheap ? 0 : (size_t)nv * nv;
-  std::vector<double> blk(2 * nn + 4 * (size_t)nv);
-  if (!cheap) NK_REQUIRE(mpc_prepare(*desc, blk.data() + nn, blk.data(), msg, sizeof msg), "nk_mpc_loop: %s", msg);
-  {
-    const double inf = std::numeric_limits<double>::infinity();
-    double* bnd = blk.data() + 2 * nn;
-    for (int i = 0; i < nv; ++i) {
-      bnd[i] = mpc_bound(desc->lo, i, -inf);
-      bnd[nv + i] = mpc_bound(desc->hi, i, inf);
-      bnd[2 * nv + i] = mpc_bound(desc->dlo, i, -inf);
-      bnd[3 * nv + i] = mpc_bound(desc->dhi, i, inf);
-    }
-  }
+  std::vector<double> blk;
+  NK_TRY(mpc_constants("nk_mpc_loop", -1, *desc, nv, &blk));
   // ---- everything is checked: stage and queue
   const double* G = cheap ? desc->K : desc->F;  // nv x m, host
   MatIn cst, gm, xi, xr, ui;
@@ -370,6 +399,107 @@ int nk_mpc_loop(nk_ctx* ctx, const nk_model* mdl, const nk_poly_plant* plant, co
   NK_TRY(finish_out(ctx, ou));
   if (out_info) NK_TRY(finish_out(ctx, oi));
   NK_HIP(hipStreamSynchronize(ctx->stream));  // (blk and Gt are read by the copies queued above)
+  return NK_OK;
+}
+
+int nk_mpc_loop_multi(nk_ctx* ctx, const nk_poly_plant* plant, int32_t steps, const nk_mpc_unit* units, int32_t n_units,
+                      const double* u_opt, int32_t n_uopt, double* out_x, double* out_u, double* out_info, double* scores) {
+  NK_TRY(check_ctx(ctx));
+  NK_REQUIRE(!ctx_recording(ctx), "nk_mpc_loop_multi: not available to the members of a lock-step group");
+  NK_TRY(check_poly_plant("nk_mpc_loop_multi", plant));
+  NK_REQUIRE(units != nullptr && n_units >= 1, "nk_mpc_loop_multi: n_units = %d units at %p: at least one is needed", n_units,
+             (const void*)units);
+  NK_REQUIRE(steps >= 1, "nk_mpc_loop_multi: steps = %d must be positive", steps);
+  NK_REQUIRE(out_x || out_u || out_info || scores,
+             "nk_mpc_loop_multi: out_x, out_u, out_info and scores are all null: nothing to return");
+  NK_REQUIRE(n_uopt >= 0 && (n_uopt == 0 || u_opt != nullptr), "nk_mpc_loop_multi: n_uopt = %d rows of a null u_opt", n_uopt);
+  NK_REQUIRE(!is_device_ptr(scores), "nk_mpc_loop_multi: scores must be host memory");
+  const int d = plant->d, p = plant->p;
+  // every unit is checked before anything is queued; its constants (mpc_prepare: the Cholesky inverses of the single call),
+  // its F or K, initial state, reference and seed are laid out on the way
+  UnitPack in, folds;
+  std::vector<MpcUnitOffsets> off((size_t)n_units);
+  std::vector<std::vector<double>> consts((size_t)n_units), gts((size_t)n_units);
+  std::vector<int> nvs((size_t)n_units), first((size_t)n_units);
+  std::map<std::pair<const void*, const void*>, int> prepared;  // (model, description) -> the first unit that holds them
+  for (int u = 0; u < n_units; ++u) {
+    const nk_mpc_unit& un = units[u];
+    NK_REQUIRE(un.model && un.desc && un.x0 && un.x_ref, "nk_mpc_loop_multi: unit %d: null argument (model, desc, x0, x_ref)", u);
+    NK_REQUIRE(un.reserved == 0, "nk_mpc_loop_multi: unit %d: reserved = %d must be 0", u, un.reserved);
+    NK_REQUIRE(!is_device_ptr(un.desc), "nk_mpc_loop_multi: unit %d: the description must be host memory", u);
+    NK_TRY(check_mpc_model(ctx, "nk_mpc_loop_multi", u, un.model, *plant, un.desc, &nvs[u]));
+    NK_REQUIRE(un.uopt >= -1 && un.uopt < n_uopt, "nk_mpc_loop_multi: unit %d: uopt = %d, u_opt has %d rows", u, un.uopt,
+               n_uopt);
+    NK_REQUIRE(!is_device_ptr(un.x0) && !is_device_ptr(un.x_ref) && !is_device_ptr(un.u_init),
+               "nk_mpc_loop_multi: unit %d: x0, x_ref and u_init must be host memory", u);
+    // units that share model and description share the prepared pieces of the first of them: the same M, H^-1, bounds and W
+    first[u] = prepared.emplace(std::make_pair((const void*)un.model, (const void*)un.desc), u).first->second;
+    if (first[u] != u) {
+      off[u] = off[first[u]];
+      pack_mpc_unit_state(in, off[u], un.x0, un.x_ref, un.u_init, (size_t)d, (size_t)p);
+      continue;
+    }
+    NK_TRY(mpc_constants("nk_mpc_loop_multi", u, *un.desc, nvs[u], &consts[u]));
+    const nk_model* mdl = un.model;
+    const int m = mdl->m, nv = nvs[u];
+    const bool cheap = un.desc->iters == 0, fold = mdl->kind != NK_MODEL_SPLINE;
+    const double* G = cheap ? un.desc->K : un.desc->F;  // nv x m, host
+    if (!fold) {  // a spline model lifts with the raw block: W = G', formed here as the single call forms it
+      gts[u].resize((size_t)m * nv);
+      for (int l = 0; l < m; ++l)
+        for (int i = 0; i < nv; ++i) gts[u][(size_t)l * nv + i] = G[(size_t)i * m + l];
+      G = gts[u].data();
+    }
+    off[u] = pack_mpc_unit(in, folds, consts[u].data(), G, un.x0, un.x_ref, un.u_init, (size_t)m, (size_t)nv, (size_t)d,
+                           (size_t)p, !cheap, fold);
+  }
+  double *d_in = nullptr, *d_w = nullptr, *d_sc = nullptr;
+  NK_TRY(stage_pack(ctx, in, &d_in));
+  if (folds.doubles()) NK_TRY(arena_alloc_t(ctx, folds.doubles(), &d_w));
+  if (scores) NK_TRY(arena_alloc_t(ctx, (size_t)n_units * NK_MPC_N_SCORES, &d_sc));
+  MatIn uo;
+  MatOut ox, ou, oi;
+  const int64_t sp = (int64_t)steps * p;
+  if (n_uopt > 0) NK_TRY(stage_in(ctx, u_opt, sp, n_uopt, sp, &uo));
+  if (out_x) NK_TRY(stage_out(ctx, out_x, d, (int64_t)n_units * (steps + 1), d, &ox));
+  if (out_u) NK_TRY(stage_out(ctx, out_u, p, (int64_t)n_units * steps, p, &ou));
+  if (out_info) NK_TRY(stage_out(ctx, out_info, 2, (int64_t)n_units * steps, 2, &oi));
+  std::vector<MpcLoopUnit> recs((size_t)n_units);
+  std::vector<int> ktypes((size_t)n_units);
+  for (int u = 0; u < n_units; ++u) {
+    const nk_mpc_unit& un = units[u];
+    const nk_model* mdl = un.model;
+    const int m = mdl->m, nv = nvs[u];
+    MpcLoopUnit& r = recs[u];
+    // the fold of nk_mpc_loop by the same call on the same operands (the rows of F or K have their leading dimension there);
+    // the folds of all units are queued back to back, nothing waits between them
+    r.w = d_in + off[u].G;
+    if (mdl->kind != NK_MODEL_SPLINE) {
+      double* wf = d_w + off[u].w;
+      if (first[u] == u)
+        NK_TRY(launch_gemm(ctx, false, true, m, nv, m, 1.0, mdl->Sinv, m, d_in + off[u].G, (int64_t)gain_row_reserve((size_t)m),
+                           0.0, wf, nv));
+      r.w = wf;
+    }
+    r.Z = mdl->Z; r.winv = mdl->winv;
+    r.M = d_in + off[u].M; r.Hinv = d_in + off[u].Hinv; r.bnd = d_in + off[u].bnd;
+    r.x0 = d_in + off[u].x0; r.xref = d_in + off[u].x_ref; r.uinit = un.u_init ? d_in + off[u].u_init : nullptr;
+    r.out_x = out_x ? ox.dev + (int64_t)u * (steps + 1) * ox.ld : nullptr; r.ldx = out_x ? ox.ld : 0;
+    r.out_u = out_u ? ou.dev + (int64_t)u * steps * ou.ld : nullptr; r.ldu = out_u ? ou.ld : 0;
+    r.out_info = out_info ? oi.dev + (int64_t)u * steps * oi.ld : nullptr;
+    r.u_opt = un.uopt >= 0 ? uo.ptr + (int64_t)un.uopt * uo.ld : nullptr;
+    r.score = scores ? d_sc + (size_t)NK_MPC_N_SCORES * u : nullptr;
+    r.sigma0sq = mdl->sigma0 * mdl->sigma0; r.rho = un.desc->rho; r.tol = un.desc->tol;
+    r.m = m; r.nv = nv; r.iters = un.desc->iters; r.reserved = 0;
+    ktypes[u] = mdl->ktype;
+  }
+  NK_TRY(launch_mpc_loop_multi(ctx, *plant, steps, recs.data(), ktypes.data(), n_units));
+  if (out_x) NK_TRY(finish_out(ctx, ox));
+  if (out_u) NK_TRY(finish_out(ctx, ou));
+  if (out_info) NK_TRY(finish_out(ctx, oi));
+  if (scores)
+    NK_HIP(hipMemcpyAsync(scores, d_sc, sizeof(double) * NK_MPC_N_SCORES * (size_t)n_units, hipMemcpyDeviceToHost, ctx->stream));
+  NK_HIP(hipStreamSynchronize(ctx->stream));  // (the staging block and recs are read by the copies queued above)
   return NK_OK;
 }
 

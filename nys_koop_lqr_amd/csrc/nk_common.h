@@ -621,6 +621,31 @@ int launch_mpc_loop(nk_ctx* ctx, const nk_model* mdl, const nk_poly_plant& plant
                     const double* w, const double* M, const double* Hinv, const double* bnd, const double* x0, int64_t x0_stride,
                     const double* xref, int64_t xref_stride, const double* uinit, int64_t uinit_stride, int steps, int batch,
                     double* out_x, int64_t ldx, double* out_u, int64_t ldu, double* out_info);
+// The multi-model form (nk_mpc_loop_multi): one record per unit, every pointer device memory.  The records are sorted into
+// classes of (kernel family, variables padded to 16 / 32 / 64, waves per workgroup), staged with one copy and run with one
+// launch per class, its dynamic LDS the largest need among its units; a workgroup finds its record by its block index.
+// out_x / out_u / out_info / u_opt / score / uinit may be null per unit.
+struct MpcLoopUnit {
+  const double* Z;      // m x d landmarks
+  const double* winv;   // d
+  const double* w;      // m x nv folded gradient map (iters = 0: m x p folded gain), dense
+  const double* M;      // nv x nv (unused for iters = 0)
+  const double* Hinv;   // nv x nv
+  const double* bnd;    // 4 x nv: lo, hi, dlo, dhi (infinite where the caller gave none)
+  const double* x0;     // d
+  const double* xref;   // d
+  const double* uinit;  // p, or nullptr (zeros)
+  double* out_x;        // (steps + 1) rows of ldx, or nullptr (multi form)
+  double* out_u;        // steps rows of ldu, or nullptr (multi form)
+  double* out_info;     // steps rows of 2, or nullptr
+  const double* u_opt;  // steps x p controls to score against, or nullptr
+  double* score;        // the NK_MPC_N_SCORES scores, or nullptr
+  int64_t ldx, ldu;
+  double sigma0sq, rho, tol;
+  int m, nv, iters, reserved;
+};
+int launch_mpc_loop_multi(nk_ctx* ctx, const nk_poly_plant& plant, int steps, MpcLoopUnit* units, const int* ktypes,
+                          int n_units);
 
 // ---- lifted closed loops of many models in ONE launch, scored on the device (nk_loop_multi.hip): one 1024-thread workgroup
 // per unit, blockIdx.x = the record.  Every pointer is device memory.  Per step t < steps: u_t = K (phi_ref - phi_t),

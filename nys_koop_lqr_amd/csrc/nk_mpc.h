@@ -124,13 +124,17 @@ inline bool mpc_prepare(const nk_mpc_desc& ds, double* Hinv, double* M, char* ms
 
 inline double mpc_clip(double v, double lo, double hi) { return std::fmin(std::fmax(v, lo), hi); }
 
-// The saturated control from v (p entries): clip(clip(v, lo, hi), u_prev + dlo, u_prev + dhi), the rate clip last.
+// The saturated control from v (p entries): clip(clip(v, lo, hi), u_prev + dlo, u_prev + dhi), the rate clip last.  A NaN in v
+// or in a shifted rate bound gives a NaN control, as np.minimum / np.maximum of the NumPy statement do (fmin / fmax would
+// drop it and return a bound).
 inline void mpc_saturate(const nk_mpc_desc& ds, const double* v, const double* u_prev, double* u) {
   const double inf = std::numeric_limits<double>::infinity();
   for (int j = 0; j < ds.p; ++j) {
     const double up = u_prev ? u_prev[j] : 0.0;
+    const double dlo = up + mpc_bound(ds.dlo, j, -inf), dhi = up + mpc_bound(ds.dhi, j, inf);
     const double a = mpc_clip(v[j], mpc_bound(ds.lo, j, -inf), mpc_bound(ds.hi, j, inf));
-    u[j] = mpc_clip(a, up + mpc_bound(ds.dlo, j, -inf), up + mpc_bound(ds.dhi, j, inf));
+    u[j] = (std::isnan(v[j]) || std::isnan(dlo) || std::isnan(dhi)) ? std::numeric_limits<double>::quiet_NaN()
+                                                                  : mpc_clip(a, dlo, dhi);
   }
 }
 
@@ -149,6 +153,21 @@ inline void mpc_qp(const nk_mpc_desc& ds, const double* Hinv, const double* M, c
     hi[i] = mpc_bound(ds.hi, i, inf);
     dlo[i] = mpc_bound(ds.dlo, i, -inf) + shift;
     dhi[i] = mpc_bound(ds.dhi, i, inf) + shift;
+  }
+  // a NaN in the gradient or in a shifted rate bound: in the NumPy statement every variable is NaN after the first product,
+  // all iterations run, the residual and the control are NaN; the step is decided here as the device loop decides it
+  bool nanstep = false;
+  for (int i = 0; i < nv; ++i) nanstep = nanstep || std::isnan(g[i]) || std::isnan(dlo[i]) || std::isnan(dhi[i]);
+  if (nanstep) {
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (int j = 0; j < p; ++j) u[j] = nan;
+    if (z1_out)
+      for (int i = 0; i < nv; ++i) z1_out[i] = nan;
+    if (info) {
+      info[0] = (double)ds.iters;
+      info[1] = nan;
+    }
+    return;
   }
   double r = 0.0;
   for (int i = 0; i < nv; ++i) {

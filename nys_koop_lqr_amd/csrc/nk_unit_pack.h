@@ -1,5 +1,5 @@
-// Staging layout of the unit-table calls (nk_plant_loop_multi, nk_closed_loop_multi; nk_api_loops.hip): host only, no HIP
-// include, so that a plain C++17 compiler builds it (tests/unit_pack_main.cpp).
+// Staging layout of the unit-table calls (nk_plant_loop_multi, nk_mpc_loop_multi, nk_closed_loop_multi; nk_api_loops.hip):
+// host only, no HIP include, so that a plain C++17 compiler builds it (tests/unit_pack_main.cpp, tests/mpc_unit_pack_main.cpp).
 //
 // A call lays the operands of all its units out in ONE block of doubles that a single host-to-device copy moves; the
 // device records then point into the copy.  Every piece starts on a slot boundary (32 doubles = 256 bytes) and what a
@@ -87,6 +87,44 @@ inline PolyUnitOffsets pack_poly_unit(UnitPack& in, UnitPack& folds, const doubl
   in.copy(o.x0, x0, d);
   in.copy(o.x_ref, x_ref, d);
   if (fold) o.w = folds.reserve(m * p + 2);
+  return o;
+}
+
+// A unit of the constrained MPC loop (nk_mpc_loop_multi), nv decision variables (iters = 0: nv = p and G the gain K).
+// `in`: the constants [M | H^-1 | lo hi dlo dhi] in one piece of 2 nn + 4 nv doubles (nn = nv^2; nn = 0 when `qp` is false:
+// the saturated LQR has no M and no H^-1) | G -- fold = true: its nv rows of m entries, each with the leading dimension of
+// a gain row (what stage_in gives the nv x m matrix of nk_mpc_loop); fold = false (a spline model): the m x nv transpose
+// the caller formed, dense | x0, x_ref, u_init together in one piece of 2 d + p (a null u_init leaves zeros).
+// `folds` (device only): the folded W of a unit that has one, m nv + 2 doubles.
+// A unit that shares model and description with an earlier unit of the call may share that unit's prepared pieces (the
+// constants, G and the fold): pack_mpc_unit_state lays out its own x0, x_ref, u_init alone and the other offsets are copied.
+struct MpcUnitOffsets { size_t M = 0, Hinv = 0, bnd = 0, G = 0, x0 = 0, x_ref = 0, u_init = 0, w = 0; };
+inline void pack_mpc_unit_state(UnitPack& in, MpcUnitOffsets& o, const double* x0, const double* x_ref, const double* u_init,
+                                size_t d, size_t p) {
+  o.x0 = in.reserve(2 * d + p);
+  o.x_ref = o.x0 + d;
+  o.u_init = o.x_ref + d;
+  in.copy(o.x0, x0, d);
+  in.copy(o.x_ref, x_ref, d);
+  in.copy(o.u_init, u_init, p);
+}
+inline MpcUnitOffsets pack_mpc_unit(UnitPack& in, UnitPack& folds, const double* consts, const double* G, const double* x0,
+                                    const double* x_ref, const double* u_init, size_t m, size_t nv, size_t d, size_t p, bool qp,
+                                    bool fold) {
+  MpcUnitOffsets o;
+  const size_t nn = qp ? nv * nv : 0;
+  o.M = in.append(consts, 2 * nn + 4 * nv);
+  o.Hinv = o.M + nn;
+  o.bnd = o.M + 2 * nn;
+  if (fold) {
+    const size_t ldg = gain_row_reserve(m);
+    o.G = in.reserve(nv * ldg);
+    for (size_t i = 0; i < nv; ++i) in.copy(o.G + i * ldg, G + i * m, m);
+  } else {
+    o.G = in.append(G, m * nv);
+  }
+  pack_mpc_unit_state(in, o, x0, x_ref, u_init, d, p);
+  if (fold) o.w = folds.reserve(m * nv + 2);
   return o;
 }
 

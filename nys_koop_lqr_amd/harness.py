@@ -676,6 +676,115 @@ def plant_loop_multi(regressors, gains, x0s, x_refs, num_steps, plant, u_opt=Non
     return out
 
 
+MPC_SCORE_NAMES = SCORE_NAMES + ("iters_sum", "r_max", "n_at_limit", "n_iterated")
+
+
+def mpc_scores(states, controls, info, controller, u_opt=None, u_init=None):
+    """The eight scores of nk_mpc_loop_multi on the host, in the device's order of operations, from one loop's visited states
+    (d, steps + 1), controls (p, steps) / (steps, p), info (steps, 2) = {iterations run, final max |s - z|} and the bounds of
+    `controller` (lo, hi, dlo, dhi; the first p entries are the applied move's): control_scores' four, then iters_sum (sum
+    of the iterations in step order), r_max (the largest final residual, NaN from the first NaN on), n_at_limit (the (t, j) at
+    which u_tj equals lo_j, hi_j, fl(u_{t-1,j} + dlo_j) or fl(u_{t-1,j} + dhi_j), u_{-1} = u_init or zeros; counted once
+    each) and n_iterated (steps with at least one iteration); plus rmse_control.  Returns a dict of floats.  Needs no GPU."""
+    out = control_scores(states, controls, u_opt)
+    xs = np.asarray(states, dtype=np.float64)
+    steps = (xs.reshape(1, -1) if xs.ndim == 1 else xs).shape[1] - 1
+    us = np.asarray(controls, dtype=np.float64)
+    us = us.reshape(1, -1) if us.ndim < 2 else us
+    if us.shape[1] != steps and us.shape[0] == steps:
+        us = us.T
+    p = us.shape[0]
+    info = np.asarray(info, dtype=np.float64).reshape(steps, 2)
+    lo, hi, dlo, dhi = (np.asarray(a, dtype=np.float64).reshape(-1)[:p] for a in
+                        (controller.lo, controller.hi, controller.dlo, controller.dhi))
+    prev = np.zeros(p) if u_init is None else np.asarray(u_init, dtype=np.float64).reshape(p).copy()
+    it_sum, r_max, n_lim, n_it = 0.0, 0.0, 0, 0
+    for t in range(steps):
+        it, r = float(info[t, 0]), float(info[t, 1])
+        it_sum = it_sum + it
+        n_it += it > 0
+        if r > r_max or r != r:
+            r_max = r
+        with np.errstate(invalid="ignore"):  # inf - inf of an absent rate limit: NaN, equal to nothing
+            rl, rh = prev + dlo, prev + dhi
+        for j in range(p):
+            u = us[j, t]
+            n_lim += bool(u == lo[j] or u == hi[j] or u == rl[j] or u == rh[j])
+        prev = us[:, t]
+    out.update(iters_sum=it_sum, r_max=r_max, n_at_limit=float(n_lim), n_iterated=float(n_it))
+    return out
+
+
+def mpc_loop_multi(regressors, controllers, x0s, x_refs, num_steps, plant, iters=50, tol=0.0, u_inits=None, u_opt=None,
+                   uopt_rows=None, return_trajectories=False, return_info=False):
+    """One constrained MPC loop around the TRUE plant per (regressor, controller, x0, x_ref) unit, all units in ONE device call
+    (nk_mpc_loop_multi), scored on the device.  Unit u is bit for bit regressors[u].closed_loop_plant_mpc(controllers[u],
+    x0s[u], x_refs[u], num_steps, plant, iters[u], tol[u], u_inits[u]); the units may mix model kinds, kernels, landmark
+    counts, horizons, limits and iteration counts (iters = 0: the saturated LQR).  iters, tol: scalars or one per unit.
+    x0s, x_refs: (n_units, d) or one state for all; u_inits: (n_units, p), one (p,) for all, or None = zeros.  plant: what
+    closed_loop_plant_mpc accepts.  u_opt: (num_steps, p) scored against by every unit, or (k, num_steps, p) with
+    uopt_rows[u] = the row of unit u (-1: none; default: row u when k = n_units > 1, else row 0).
+    Returns a dict of (n_units,) arrays, the eight MPC_SCORE_NAMES (see include/nyskoop.h) and rmse_control; with
+    return_trajectories also states (n_units, num_steps + 1, d) and controls (n_units, num_steps, p), with return_info info
+    (n_units, num_steps, 2).  Without them nothing but the scores leaves the device."""
+    from .regressors import _as_polynomial_plant
+    regs, ctls = list(regressors), list(controllers)
+    n = len(regs)
+    if len(ctls) != n:
+        raise ValueError(f"{len(ctls)} controllers for {n} regressors")
+    plant = _as_polynomial_plant(plant)
+    d, p = int(plant.n_states), int(plant.n_inputs)
+    num_steps = int(num_steps)
+
+    def per_unit(v, what):
+        a = np.asarray(v)
+        if a.ndim == 0:
+            return [a.item()] * n
+        if a.size != n:
+            raise ValueError(f"{what} has {a.size} entries for {n} units")
+        return [x.item() for x in a.reshape(-1)]
+
+    its, tols = per_unit(iters, "iters"), per_unit(tol, "tol")
+    ctx = _lib.get_context()
+    handles = [r._ensure_model() for r in regs]
+    descs, keep, shared = [], [], {}
+    for r, c, it, tl in zip(regs, ctls, its, tols):
+        m = r._landmark_shape()[1]
+        if c.K.shape != (p, m) or c.F.shape[1] != m:
+            raise ValueError(f"the controller is for a model with K of shape {c.K.shape}, expected {(p, m)}")
+        key = (id(c), int(it), float(tl))
+        if key not in shared:  # units with the same controller, iters and tol share one description
+            shared[key] = _lib.mpc_desc(c, it, tl)
+            keep.append(shared[key][1])
+        descs.append(shared[key][0])
+    rows = uopt_rows
+    uo = None
+    if u_opt is not None:
+        uo = np.asarray(u_opt, dtype=np.float64).reshape(-1, num_steps * p)
+        if rows is None:
+            rows = list(range(n)) if uo.shape[0] == n and n > 1 else [0] * n
+    uis = None
+    if u_inits is not None:
+        ua = np.asarray(u_inits, dtype=np.float64)
+        if ua.size == p:
+            ua = np.broadcast_to(ua.reshape(1, p), (n, p))
+        elif ua.size != n * p:
+            raise ValueError(f"u_inits has shape {ua.shape}, expected {p} entries or {(n, p)}")
+        uis = list(np.ascontiguousarray(ua.reshape(n, p)))
+    x0b, xrb = _broadcast_states(x0s, n, d, "x0s"), _broadcast_states(x_refs, n, d, "x_refs")
+    sc, ox, ou, oi = ctx.mpc_loop_multi(plant.descriptor(), num_steps, handles, descs, x0b, xrb, u_inits=uis, u_opt=uo,
+                                        uopt_rows=rows, want_x=return_trajectories, want_u=return_trajectories,
+                                        want_info=return_info)
+    del keep
+    out = {name: sc[:, i].copy() for i, name in enumerate(MPC_SCORE_NAMES)}
+    out["rmse_control"] = rmse_control_percent(out["sse_u"], out["ss_opt"])
+    if return_trajectories:
+        out["states"], out["controls"] = ox, ou
+    if return_info:
+        out["info"] = oi
+    return out
+
+
 def lqr_default_gain(c=1.0):
     """gain_fn of lqr_sweep: K = dlqr(A, B, c C^T C symmetrised, I), the arithmetic of regressor.solve_lqr(c=c)."""
     from .lqr import dlqr
@@ -718,17 +827,21 @@ def lqr_fit_unit(X, Y, n_inputs, params, unit, estimator="nystrom"):
 
 
 def lqr_fit_and_gain(X, Y, n_inputs, params, units, estimator="nystrom", gain_fn=None, c=1.0, batch=32, workers=4,
-                     fit_fn=None, gain="host", gain_batch_fn=None, after_fit=None):
+                     fit_fn=None, gain="host", gain_batch_fn=None, after_fit=None, controller=None):
     """The fits and gains of planned units -- what lqr_run_units and cloth_lqr_sweep share.  Fits: `batch` at a time through
     the lock-step pool (a plain loop with batch <= 1 or a fit_fn); a unit may carry its own "estimator" and "params".
     after_fit(reg, unit): called on the fitting thread right after a successful fit, inside the lock-step round (its result
     is kept per unit).  Gains: gain="host": gain_fn(A, B, C) in `workers` host threads while later rounds fit;
     gain="device": ONE nk_model_lqr_gain_batch call after the fits (gain_batch_fn(regs, c) stands in for it).
+    controller (the checked dict of lqr_sweep): instead of a gain, reg.solve_mpc(horizon, c=c, limits, rho) is built per
+    unit on the same host threads, and gains[i] is that lqr.MPCController (None when it raises).
     Returns (regs, gains, extras, timing): a unit whose fit failed has regs[i] None, one without a gain gains[i] None;
     timing = dict(fit_s, gain_wait_s, gain_cpu_s)."""
     import time
     if gain not in ("host", "device"):
         raise ValueError(f"gain must be 'host' or 'device', got {gain!r}")
+    if controller is not None and gain == "device":
+        raise ValueError("controller needs gain='host': the terminal cost of the MPC is the host Riccati solution")
     if gain == "device" and gain_fn is not None:
         raise ValueError("gain='device' solves K = dlqr(A, B, c C'C, I) on the device: gain_fn cannot be combined with it")
     device_gain = gain == "device"
@@ -741,6 +854,9 @@ def lqr_fit_and_gain(X, Y, n_inputs, params, units, estimator="nystrom", gain_fn
     def gain_of(i, reg):
         t0 = time.perf_counter()
         try:
+            if controller is not None:
+                return reg.solve_mpc(controller["horizon"], c=c, u_min=controller["u_min"], u_max=controller["u_max"],
+                                     du_min=controller["du_min"], du_max=controller["du_max"], rho=controller["rho"])
             return np.asarray(gain_fn(np.asarray(reg.A), np.asarray(reg.B), np.asarray(reg.C)), dtype=np.float64)
         finally:
             gain_s[i] = time.perf_counter() - t0
@@ -780,36 +896,66 @@ def lqr_fit_and_gain(X, Y, n_inputs, params, units, estimator="nystrom", gain_fn
     for i, f in enumerate(futures):
         if f is not None:
             try:
-                gains[i] = f.result()
+                gains[i] = f.result()  # (an lqr.MPCController with `controller`)
             except Exception:  # noqa: BLE001 -- a unit without a gain scores NaN, like GridSearchCV's error_score=nan
                 gains[i] = None
     t2 = time.perf_counter()
     return regs, gains, extras, dict(fit_s=t1 - t0, gain_wait_s=t2 - t1, gain_cpu_s=float(sum(gain_s)))
 
 
+CONTROLLER_KEYS = ("horizon", "u_min", "u_max", "du_min", "du_max", "iters", "tol", "rho")
+
+
+def lqr_controller_spec(controller):
+    """The `controller` dict of lqr_sweep with its defaults filled in (limits None = absent, iters = 50, tol = 0.0, rho None
+    = lqr.mpc_default_rho); `horizon` is required and an unknown key is a ValueError.  None stays None."""
+    if controller is None:
+        return None
+    spec = dict(u_min=None, u_max=None, du_min=None, du_max=None, iters=50, tol=0.0, rho=None)
+    unknown = sorted(set(controller) - set(CONTROLLER_KEYS))
+    if unknown:
+        raise ValueError(f"controller has unknown keys {unknown}; known: {CONTROLLER_KEYS}")
+    if "horizon" not in controller:
+        raise ValueError("controller needs a 'horizon'")
+    spec.update(controller)
+    return spec
+
+
 def lqr_run_units(X, Y, n_inputs, params, units, plant, x0, x_ref, num_steps, estimator="nystrom", gain_fn=None, c=1.0,
                   u_opt=None, batch=32, workers=4, return_trajectories=False, fit_fn=None, loop_fn=None, gain="host",
-                  gain_batch_fn=None):
+                  gain_batch_fn=None, controller=None):
     """Scores of planned units, in their order: an (n_units, 4) array (SCORE_NAMES; NaN for a unit whose fit or gain
     failed), the trajectories (or None, None) and the wall-clock split.  fit_fn / loop_fn stand in for lqr_fit_unit /
     plant_loop_multi (rehearsals without a GPU; with a fit_fn the fits run as a plain loop).
     gain="device": the gains of all fitted units come from ONE nk_model_lqr_gain_batch call after the fits (K =
     dlqr(A, B, c sym(C'C), I) by the batched doubling solver; gain_fn is not used); a unit whose solve reports a non-zero
     status gets NaN scores and is not run.  timing keeps its keys: gain_wait_s is that call, gain_cpu_s is 0.
-    gain_batch_fn(regs, c) -> (Ks, status, iterations) stands in for the device call."""
+    gain_batch_fn(regs, c) -> (Ks, status, iterations) stands in for the device call.
+    controller (lqr_sweep's dict): the units run the constrained MPC instead -- reg.solve_mpc per fitted unit where the
+    gains are built, ONE mpc_loop_multi call (loop_fn stands in for it, with its signature), eight scores per unit
+    (MPC_SCORE_NAMES); a unit whose controller raises scores NaN and is not run.  gain="device" with it is a ValueError."""
     import time
-    loop_fn = loop_fn or plant_loop_multi
+    controller = lqr_controller_spec(controller)
+    if controller is not None and gain == "device":
+        raise ValueError("controller needs gain='host': the terminal cost of the MPC is the host Riccati solution")
+    names = SCORE_NAMES if controller is None else MPC_SCORE_NAMES
+    loop_fn = loop_fn or (plant_loop_multi if controller is None else mpc_loop_multi)
     n = len(units)
     regs, gains, _, tm = lqr_fit_and_gain(X, Y, n_inputs, params, units, estimator, gain_fn, c, batch, workers, fit_fn, gain,
-                                          gain_batch_fn)
+                                          gain_batch_fn, controller=controller)
     t2 = time.perf_counter()
     live = [i for i in range(n) if gains[i] is not None]
-    scores = np.full((n, len(SCORE_NAMES)), np.nan)
+    scores = np.full((n, len(names)), np.nan)
     states = controls = None
     if live:
-        res = loop_fn([regs[i] for i in live], [gains[i] for i in live], x0, x_ref, num_steps, plant, u_opt=u_opt,
-                      return_trajectories=return_trajectories)
-        for k, name in enumerate(SCORE_NAMES):
+        if controller is None:
+            res = loop_fn([regs[i] for i in live], [gains[i] for i in live], x0, x_ref, num_steps, plant, u_opt=u_opt,
+                          return_trajectories=return_trajectories)
+        else:
+            res = loop_fn([regs[i] for i in live], [gains[i] for i in live], x0, x_ref, num_steps, plant,
+                          iters=controller["iters"], tol=controller["tol"], u_opt=u_opt,
+                          return_trajectories=return_trajectories)
+        for k, name in enumerate(names):
             scores[live, k] = res[name]
         if return_trajectories:
             states = np.full((n,) + np.shape(res["states"])[1:], np.nan)
@@ -835,7 +981,7 @@ def lqr_table(units, values, n_seeds, n_ms):
 
 def lqr_sweep(X, Y, n_inputs, params, ms, seeds, plant, x0, x_ref, num_steps, estimator="nystrom", gain_fn=None, c=1.0,
               u_opt=None, batch=32, workers=4, return_trajectories=False, centers=None, fit_fn=None, loop_fn=None,
-              gain="host", gain_batch_fn=None):
+              gain="host", gain_batch_fn=None, controller=None):
     """The control branch of the reference's one-input drivers (benchmark_lqr_classic.py:256-299: seeds x {Nystrom,
     splines}; benchmark_lqr_hjb.py:265-333: seeds x m) as one call: for every seed and every m in `ms`
     fit -> K = dlqr(A, B, c C^T C, I) -> `num_steps` feedback steps around the true plant -> replay cost and control scores.
@@ -850,18 +996,24 @@ def lqr_sweep(X, Y, n_inputs, params, ms, seeds, plant, x0, x_ref, num_steps, es
     x0, x_ref: one state each, shared by the units.  Returns a dict of (len(seeds), len(ms)) tables sse_u, ss_opt, J,
     u_absmax, rmse_control, the planned `units`, the wall-clock split `timing` (fit_s, gain_wait_s, loop_s; gain_cpu_s =
     host seconds summed over the gain solves, which overlap the fits) and, with return_trajectories, states
-    (len(seeds), len(ms), num_steps + 1, d) and controls (len(seeds), len(ms), num_steps)."""
+    (len(seeds), len(ms), num_steps + 1, d) and controls (len(seeds), len(ms), num_steps).
+    controller: None, or a dict (horizon, and optionally u_min, u_max, du_min, du_max, iters = 50, tol = 0, rho) -- the
+    sweep under actuator limits: every fitted unit gets reg.solve_mpc(horizon, c=c, limits) where the gains are built (host
+    threads, while later rounds fit), all surviving units run in ONE mpc_loop_multi call, the tables gain iters_sum, r_max,
+    n_at_limit and n_iterated (MPC_SCORE_NAMES), the plant may have several inputs (controls: (.., num_steps, p)) and must be
+    one closed_loop_plant_mpc accepts.  gain_fn is not used; gain="device" is a ValueError."""
     _check_estimator(estimator)
     units = lqr_plan(X, Y, n_inputs, params, ms, seeds, estimator, centers)
     scores, states, controls, timing = lqr_run_units(X, Y, n_inputs, params, units, plant, x0, x_ref, num_steps, estimator,
                                                      gain_fn, c, u_opt, batch, workers, return_trajectories, fit_fn, loop_fn,
-                                                     gain, gain_batch_fn)
+                                                     gain, gain_batch_fn, controller)
     return lqr_result(units, scores, states, controls, len(seeds), len(ms), timing)
 
 
 def lqr_result(units, scores, states, controls, n_seeds, n_ms, timing=None):
-    """The dict lqr_sweep returns, from per-unit values in plan order."""
-    out = {name: lqr_table(units, scores[:, k], n_seeds, n_ms) for k, name in enumerate(SCORE_NAMES)}
+    """The dict lqr_sweep returns, from per-unit values in plan order (four score columns, or the eight of the MPC sweep)."""
+    names = MPC_SCORE_NAMES if np.shape(scores)[1] == len(MPC_SCORE_NAMES) else SCORE_NAMES
+    out = {name: lqr_table(units, scores[:, k], n_seeds, n_ms) for k, name in enumerate(names)}
     out["rmse_control"] = rmse_control_percent(out["sse_u"], out["ss_opt"])
     out["units"], out["timing"] = units, timing
     if states is not None:
