@@ -391,8 +391,10 @@ int cholesky_flow_pair(nk_ctx* ctx, const CholSys* sys, int nsys) {
   NK_HIP(hipMemsetAsync(a.hdr, 0, words * sizeof(int), ctx->stream));
   // Half the CUs, one workgroup on each: the launch is latency bound (the diagonal chain), a workgroup of it (320 VGPRs)
   // leaves room on its CU for one GEMM workgroup (the square-root iteration beside the pair chain), and the two chains of a
-  // fit (prep and main stream) run side by side instead of one waiting for CUs the other holds.
-  const int grid = std::max(1, std::min(a.total, ctx->num_cu / 2));
+  // fit (prep and main stream) run side by side instead of one waiting for CUs the other holds.  A caller that knows what
+  // runs beside the launch may ask for another width (nk::FlowWidth; same bits at any width).
+  const int width = ctx->chol_flow_wgs > 0 ? ctx->chol_flow_wgs : ctx->num_cu / 2;
+  const int grid = std::max(1, std::min(a.total, width));
   hipLaunchKernelGGL(chol_flow_kernel, dim3((unsigned)grid), dim3(FLOW_THREADS), 0, ctx->stream, a);
   NK_HIP(hipGetLastError());
   count_event(CNT_CHOL_FLOW);

@@ -69,7 +69,8 @@ enum {
   EV_SQRT_END = 7,       // side stream behind the square-root iteration / statistics
   EV_LANDMARKS = 8,      // landmark matrices built (main or preparation stream) / the preparation stream, and the main
                          // stream where it assembles the systems
-  EV_SQRT_PREPARED = 9,  // sqrtm_prepare's chain, preparation stream / the side stream in front of the iteration
+  EV_SQRT_PREPARED = 9,  // sqrtm_prepare's chain, preparation stream / the side stream in front of the iteration, and the
+                         // main stream in front of a fit's first Gram launch when the chain was queued ahead of it
   EV_SQRT_RESID = 10,    // residual copy of the host-checked square-root iteration (nk_sqrtm.hip) / the host, same place
   EV_SQRT_SCALARS = 11,  // sqrtm_prepare's schedule scalars on their way to the host / the host in sqrtm_finish
   EV_FORK = 12,          // scratch fork point, recorded on the main stream and waited for at once by the stream that
@@ -150,6 +151,7 @@ struct nk_ctx {
   bool spline_defer_svd = false;  // first phase of nk_spline_cv_grid: nk_spline_fit stops (NK_ERR_NOT_SPD) where it would
                                  // enter the pseudo-inverse, so that such units can be run together afterwards
   bool chol_flow_off = false;  // set by nk::ChainOnly: the re-run of a factorisation whose dataflow launch gave up
+  int chol_flow_wgs = 0;       // set by nk::FlowWidth: workgroups of a dataflow Cholesky launch (0: half the CUs)
   double* h_stage = nullptr;    // page-locked, device-visible staging block for the small latency-bound calls (rollouts):
   size_t h_stage_bytes = 0;     // kernels read their inputs from it and write their results into it directly (no DMA)
 };
@@ -194,6 +196,15 @@ struct ChainOnly {
   bool b0;
   explicit ChainOnly(nk_ctx* ctx) : c(ctx), b0(ctx->chol_flow_off) { c->chol_flow_off = true; }
   ~ChainOnly() { c->chol_flow_off = b0; }
+};
+
+// For the lifetime of the scope a dataflow Cholesky launch of the context takes `wgs` workgroups (0: the default).  The
+// result does not depend on it: every tile is the same arithmetic whichever workgroup draws it.
+struct FlowWidth {
+  nk_ctx* c;
+  int w0;
+  FlowWidth(nk_ctx* ctx, int wgs) : c(ctx), w0(ctx->chol_flow_wgs) { c->chol_flow_wgs = wgs; }
+  ~FlowWidth() { c->chol_flow_wgs = w0; }
 };
 
 // factorisation failure flags: slots 0-1 belong to the main stream, 2-3 to the side stream (each stream may have a paired

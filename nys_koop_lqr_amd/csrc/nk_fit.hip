@@ -182,7 +182,7 @@ struct NystromFit {
   int host_passes = 1;
   // landmark matrices, Gram accumulators and their counters
   double *Kmm = nullptr, *Kj = nullptr, *Kj_in = nullptr, *Kxo = nullptr;
-  bool landmarks_aside = false;
+  bool landmarks_aside = false, sqrt_early = false;
   double *G1 = nullptr, *G2 = nullptr, *G3 = nullptr, *G4 = nullptr;
   int64_t ldd = 0;
   float ms_gram_kernel = 0.f;
@@ -211,6 +211,8 @@ struct NystromFit {
   int validate(), stage_rows(), stage_landmarks(), landmark_matrices(), alloc_gram(), load_gram(), prepare_features(), run_passes();
   int upload_pass(size_t ip), pass_f32(size_t ip), pass_f64(size_t ip), blocks_overlapped(const Piece& pc, double* Fo);
   int return_gram();
+  bool sqrt_factor_early() const;
+  int fence_sqrt_factor(size_t ip);
   int queue_sqrt_prep(), assemble_and_factor(), queue_sqrt_side(), sqrt_products(), operator_products();
   int settle_factorisations(), refine(), settle_sqrt();
   void read_refinement(), write_stats();
@@ -286,10 +288,11 @@ int NystromFit::landmark_matrices() {
     NK_TRY(arena_alloc_t(ctx, (size_t)m * m, &Kj_in));
     NK_TRY(arena_alloc_t(ctx, (size_t)m * m, &Kxo));
   }
-  // Nothing needs the landmark matrices before the fused Gram launch has ended (the square root's preparation chain, the
-  // regularisers of the two systems), and at the headline shape K_mm is 160 us on 16 workgroups: for large fits they are
-  // built on the preparation stream, beside the row preparation and the kernel blocks instead of in front of them
-  // (EV_LANDMARKS: ready; the main stream waits for it where it assembles the systems).
+  // Nothing on the main stream needs the landmark matrices before the fused Gram launch has ended (the regularisers of
+  // the two systems; the square root's preparation follows them on the preparation stream), and at the headline shape
+  // K_mm is 160 us on 16 workgroups: for large fits they are built on the preparation stream, beside the row preparation
+  // and the kernel blocks instead of in front of them (EV_LANDMARKS: ready; the main stream waits for it where it
+  // assembles the systems).
   {
     const char* la = getenv("NYSKOOP_LANDMARKS_ASIDE");  // 0: on the main stream, in front of the kernel blocks (read per fit: A/B runs)
     landmarks_aside = mode == FIT_FULL && n_eff >= 20000 && m >= 1024 && !ctx_recording(ctx) && !(la && la[0] == '0');
@@ -453,6 +456,7 @@ int NystromFit::pass_f32(size_t ip) {
     NK_HIP(hipEventRecord(ctx->ev[EV_KMAT_DONE], ctx->stream));
     tr.mark("kmat issued");
   }
+  NK_TRY(fence_sqrt_factor(ip));
   TnProblemF pf[4];
   pf[0].A = F32; pf[0].B = F32; pf[0].lda = pf[0].ldb = ldf; pf[0].M = pf[0].N = mp; pf[0].C = G1; pf[0].ldc = mp;
   pf[0].tri = TRI_UPPER_MIRROR;
@@ -507,6 +511,7 @@ int NystromFit::pass_f64(size_t ip) {
     tr.mark("kmat issued");
   }
   // -- contraction of this pass: ONE fused launch when the operands meet the LDS-DMA alignment contract
+  NK_TRY(fence_sqrt_factor(ip));
   TnProblem pr[4];
   pr[0].A = F; pr[0].B = F; pr[0].lda = pr[0].ldb = ldf; pr[0].M = pr[0].N = mp; pr[0].C = G1; pr[0].ldc = mp;
   pr[0].tri = TRI_UPPER_MIRROR;
@@ -570,11 +575,13 @@ int NystromFit::return_gram() {
 
 // ---- the matrix square root S = (K_mm + jitter I)^{1/2}, S^-1 (regressors.py:140,163) runs beside the main stream's work in
 //      two parts, queue_sqrt_prep and queue_sqrt_side: the latency-bound preparation (preparation stream) and the GEMM-bound
-//      iteration with the products that depend on S only (side stream), both behind the fused Gram launch and beside the
-//      factorisation chain of the regularised systems.  (Round 3 also measured the whole square root queued BEFORE the Gram
-//      launch, beside the kernel blocks, with the Gram launch waiting for it: 44.5 against 42.9 ms per fit -- the chain's
-//      ~100 small kernels each wait for a workgroup slot of the long-running kernel blocks, the square root takes 13 ms
-//      there instead of 9, and what the tail gains (the factorisation chain alone: 4.2 ms) the wait gives back.)
+//      iteration with the products that depend on S only (side stream).  The iteration runs behind the fused Gram launch,
+//      beside the factorisation of the regularised systems; where the preparation runs is queue_sqrt_prep's schedule.
+//      (Round 3 also measured the whole square root queued BEFORE the Gram launch, beside the kernel blocks, with the Gram
+//      launch waiting for it: 44.5 against 42.9 ms per fit -- the factorisation was a chain of ~100 small kernels then, each
+//      waiting for a workgroup slot of the long-running kernel blocks; the square root took 13 ms there instead of 9, and
+//      what the tail gained (the factorisation chain alone: 4.2 ms) the wait gave back.  Only the preparation, now one
+//      dataflow launch, goes there.)
 
 // products that depend on the square root only (current stream)
 int NystromFit::sqrt_products() {
@@ -591,30 +598,61 @@ int NystromFit::sqrt_products() {
   return NK_OK;
 }
 
-// Cholesky factor of K_mm + jitter and its inverse, the latency-bound half of the square root: small kernels on the
-// preparation stream (queued behind the kernel-block / Gram launches so that the main stream is never kept waiting for
-// the host)
+// Schedule of the preparation (queue_sqrt_prep) in a large fit whose factorisations are dataflow launches: true = queued as
+// soon as the landmark matrices are, beside the kernel blocks, and fenced from the fused Gram launch (fence_sqrt_factor);
+// false = queued behind the Gram launch, where NYSKOOP_PREP_PAUSE (read per fit: A/B runs) says what it waits for.
+bool NystromFit::sqrt_factor_early() const {
+  if (mode != FIT_FULL || n_eff < 20000 || m < 1024 || ctx_recording(ctx)) return false;
+  if (ctx->chol_flow_off || !chol_flow_enabled()) return false;  // launch-per-step chain: the fractional pause below
+  const char* e = getenv("NYSKOOP_PREP_PAUSE");
+  return !(e && e[0]);
+}
+
+// The first fused Gram launch of a fit waits for the early-queued preparation (EV_SQRT_PREPARED, recorded behind
+// tri_scale_both).  The factorisation is done by then and the wait is free; were it ever slow to become resident, the
+// Gram launch starts late by the rest of that launch instead of sharing its first round of workgroups with it.
+int NystromFit::fence_sqrt_factor(size_t ip) {
+  if (sqrt_early && ip == 0) NK_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev[EV_SQRT_PREPARED], 0));
+  return NK_OK;
+}
+
+// Cholesky factor of K_mm + jitter and its inverse, the latency-bound half of the square root, on the preparation stream
 int NystromFit::queue_sqrt_prep() {
   SideScope prep(ctx, ctx->stream_prep);
   NK_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev[EV_LANDMARKS], 0));
   // kernel matrices are positive semi-definite: the jitter bounds the smallest eigenvalue of K_mm + jitter I from
   // below, which lets the iteration be queued before this factorisation has run (SqrtPlan::lambda_min_hint)
   splan.lambda_min_hint = jitter > 0.0 ? jitter : 0.0;
-  // This chain of ~100 small high-priority kernels must not run beside the fused Gram launch: that launch fills the
-  // chip in exact rounds of 3-ms workgroups, and a Gram workgroup whose slot a chain kernel holds at a round boundary
-  // finds the next free slot a whole round later -- measured: the launch takes 26.5-27.0 ms inside the fit against 25.0
-  // alone.  So the chain waits for the Gram launch and runs after it -- ahead of the square-root iteration, which has
-  // that much slack against the factorisation chain of the regularised systems.  NYSKOOP_PREP_PAUSE = fraction of the
-  // block steps to run BEFORE the pause, beside the kernel blocks (1 = never pause).  Measured on one box, ms per fit:
-  // 1 -> 44.1, 0.75 -> 44.1, 0.5 -> 43.2, 0.25 -> 43.2, 0 (default) -> 42.9 (kernel blocks 6.9 -> 6.3, Gram 26.7 -> 25.5).
-  if (mode == FIT_FULL && n_eff >= 20000 && m >= 1024) {
-    static const double frac = getenv("NYSKOOP_PREP_PAUSE") ? atof(getenv("NYSKOOP_PREP_PAUSE")) : 0.0;
+  // The factorisation must not run beside the fused Gram launch: that launch fills the chip in exact rounds of 3-ms
+  // workgroups, and a Gram workgroup whose slot the factorisation holds at a round boundary finds the next free slot a
+  // whole round later (measured with the launch-per-step chain: the launch takes 26.5-27.0 ms inside the fit against 25.0
+  // alone).  It needs the landmarks only, so as ONE dataflow launch it runs beside the kernel blocks, queued ahead of
+  // their 12 512 workgroups, and the Gram launch is fenced from it.  The square-root iteration then starts when the Gram
+  // launch ends instead of 2 ms later, and the tail is 0.9 ms shorter.  What the kernel blocks pay decides the width: a
+  // workgroup of the launch takes one of the two slots of their engine on its CU, and the engine's lone workgroup there
+  // does not make up for it (its exp epilogue, it seems, no longer hides behind the other's MFMA).  Headline fit, same
+  // process, alternating, 5 x 12 fits, fit less Gram stage (ms): behind the Gram 14.0-14.1; here with 128 workgroups 14.0-14.2
+  // (kernel blocks 5.75 -> 6.65: nothing gained); 96: 13.7-13.9; 64: 13.6-13.75 (kernel blocks 6.2); 48: 13.6-13.7; 32:
+  // the launch (6.3-6.9 ms) outlasts the kernel blocks and the Gram starts 0.5 ms late.  So a quarter of the CUs where
+  // the kernel blocks last as long as such a launch -- 5.7-6.0 ms beside them at m = 2000, growing as m^3, against 5.8 ms
+  // of kernel blocks at n = 1e5, d = 384, growing as n m d: n d >= 9 m^2 --, half of them (2.2 ms) otherwise.  bench.py,
+  // 5 interleaved runs against the build before: 39.98-40.51 against 40.60-40.92 ms per fit (median -0.54 ms).
+  // NYSKOOP_PREP_PAUSE unset: that schedule.  Set, with dataflow factorisations: queued behind the Gram launch; 0 (any
+  // value below 1) waits for the Gram's end -- the schedule before this one --, 1 does not wait.  On the launch-per-step
+  // chain (NYSKOOP_CHOL_FLOW=0) it is queued behind the Gram launch and the value is the fraction of the block steps to
+  // run BEFORE the wait, beside the kernel blocks (1 = never wait; default 0).  Measured on one box with that chain, ms
+  // per fit: 1 -> 44.1, 0.75 -> 44.1, 0.5 -> 43.2, 0.25 -> 43.2, 0 -> 42.9 (kernel blocks 6.9 -> 6.3, Gram 26.7 -> 25.5).
+  if (!sqrt_early && mode == FIT_FULL && n_eff >= 20000 && m >= 1024) {
+    const char* e = getenv("NYSKOOP_PREP_PAUSE");
+    const double frac = e ? atof(e) : 0.0;
     const int nb = (m + CHOL_NB - 1) / CHOL_NB;
     if (frac < 1.0) {
       splan.pause_event = ctx->ev_fork;  // recorded behind the last Gram launch
       splan.pause_step = std::max(0, std::min(nb - 1, (int)(frac * nb)));
     }
   }
+  const bool narrow = sqrt_early && (double)n_eff * d >= 9.0 * (double)m * m;
+  FlowWidth width(ctx, narrow ? std::max(1, ctx->num_cu / 4) : 0);
   NK_TRY(sqrtm_prepare(ctx, Kj, m, m, &splan));
   NK_HIP(hipEventRecord(ctx->ev[EV_SQRT_PREPARED], ctx->stream));
   return NK_OK;
@@ -652,6 +690,10 @@ int NystromFit::assemble_and_factor() {
   sys[0].pivlog = pivlog; sys[1].pivlog = pivlog + mp + (mp & 1);
   // both systems advance in lock step (paired launches); the per-block kernels are latency bound and leave the chip
   // mostly idle ...
+  // (With the square root prepared ahead of the Gram launch, the iteration runs beside this factorisation from its first
+  // step on, and each of its workgroups costs the iteration's GEMMs a slot: same measurement as in queue_sqrt_prep, fit less
+  // Gram stage with 256 / 192 / 128 / 96 / 80 / 64 workgroups here: 14.1 / 13.9 / 13.7 / 13.5 / 13.65 / 14.05 ms.)
+  FlowWidth width(ctx, sqrt_early ? std::max(1, 3 * ctx->num_cu / 8) : 0);
   NK_TRY(cholesky_aug_pair_async(ctx, sys, 2));  // G2 <- cross inner^-1 (m x mp) ; G4 <- left_rec inner_rec^-1 (d x m)
   // (tried: holding the GEMM-bound iteration back until this latency-bound chain is done -- 43.3 against 42.7 ms per fit;
   // with look-ahead in both chains 43.7 / 47.5: the overlap of the two, slow as each becomes, is still the best schedule)
@@ -863,6 +905,8 @@ int NystromFit::run() {
   if (mode != FIT_SOLVE) NK_TRY(stage_rows());
   NK_TRY(stage_landmarks());
   if (mode != FIT_GRAM) NK_TRY(landmark_matrices());
+  sqrt_early = sqrt_factor_early();
+  if (sqrt_early) NK_TRY(queue_sqrt_prep());  // preparation stream, beside the kernel blocks
   NK_TRY(alloc_gram());
   if (mode == FIT_SOLVE) {
     NK_TRY(load_gram());
@@ -875,7 +919,7 @@ int NystromFit::run() {
 
   NK_HIP(hipEventRecord(ctx->ev_fork, ctx->stream));  // the square-root iteration starts when the Gram launch is done
   tr.mark("gram issued");
-  NK_TRY(queue_sqrt_prep());      // preparation stream
+  if (!sqrt_early) NK_TRY(queue_sqrt_prep());  // preparation stream
   NK_TRY(assemble_and_factor());  // main stream
   NK_TRY(queue_sqrt_side());      // side stream
   NK_HIP(hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
