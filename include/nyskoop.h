@@ -726,12 +726,15 @@ int nk_linear_rollout(nk_ctx* ctx, const double* A, const double* B, const doubl
                       const double* z0, const double* U, int32_t T, int32_t batch, double* out_x, double* out_z);
 
 /* ---- building blocks exported for parity tests and reuse (device or host pointers) --------------------- */
-/* C[M x N] = alpha * op(A) op(B) + beta * C;  transA: A is stored K x M;  transB: B is stored N x K. */
 /* C[M x N] (fp64) = A^T B with fp32 operands stored K x M / K x N (the fp32 engine of nk_set_compute_dtype as a building
- * block: fp32 products, fp32 partial sums over at most 32 rows, fp64 beyond).  Operands 16-byte aligned, lda / ldb
- * multiples of 4, M, N >= 4. */
+ * block: fp32 products, fp32 partial sums over at most 32 rows, fp64 beyond).  M, N >= 4, K > 0.  Host operands need only
+ * lda >= M, ldb >= N, ldc >= N: they are packed for the engine, and only the M x N block of a host C is written.  A DEVICE A
+ * or B is read in place and must be 16-byte aligned with a leading dimension that is a multiple of 4 and covers the columns
+ * rounded up to one (the pad columns are read, never used); a device C needs ldc >= N only.  A device operand that breaks
+ * this is NK_ERR_BAD_ARG before anything is copied or written. */
 int nk_gemm_f32(nk_ctx* ctx, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B, int64_t ldb,
                 double* C, int64_t ldc);
+/* C[M x N] = alpha * op(A) op(B) + beta * C;  transA: A is stored K x M;  transB: B is stored N x K. */
 int nk_gemm(nk_ctx* ctx, int transA, int transB, int64_t M, int64_t N, int64_t K, double alpha,
             const double* A, int64_t lda, const double* B, int64_t ldb, double beta, double* C, int64_t ldc);
 /* S = P^{1/2}, Sinv = P^{-1/2} for symmetric positive definite P (m x m); regressors.py:140,163,175. */

@@ -249,35 +249,55 @@ int nk_gemm(nk_ctx* ctx, int transA, int transB, int64_t M, int64_t N, int64_t K
   return NK_OK;
 }
 
+// An fp32 operand of nk_gemm_f32 (rows x cols): a device pointer in place, a host array packed into a 16-byte aligned arena
+// block whose leading dimension is cols rounded up to a multiple of 4 (the engine's contract; stage_in for floats).
+static int stage_in_f32(nk_ctx* ctx, const float* p, int64_t ld, int64_t rows, int64_t cols, const float** out, int64_t* ld_out) {
+  if (is_device_ptr(p)) {
+    *out = p;
+    *ld_out = ld;
+    return NK_OK;
+  }
+  const int64_t ldd = (cols + 3) & ~(int64_t)3;
+  float* d = nullptr;
+  NK_TRY(arena_alloc_t(ctx, (size_t)rows * ldd, &d));
+  NK_HIP(hipMemcpy2DAsync(d, (size_t)ldd * 4, p, (size_t)ld * 4, (size_t)cols * 4, (size_t)rows, hipMemcpyHostToDevice,
+                          ctx->stream));
+  *out = d;
+  *ld_out = ldd;
+  return NK_OK;
+}
+
+static int gemm_f32_staged(nk_ctx* ctx, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B,
+                           int64_t ldb, double* Cm, int64_t ldc) {
+  TnProblemF pf;
+  pf.M = (int)M; pf.N = (int)N;
+  NK_TRY(stage_in_f32(ctx, A, lda, K, M, &pf.A, &pf.lda));
+  NK_TRY(stage_in_f32(ctx, B, ldb, K, N, &pf.B, &pf.ldb));
+  MatOut c;
+  NK_TRY(stage_out(ctx, Cm, ldc, M, N, &c));
+  pf.C = c.dev; pf.ldc = c.ld;
+  NK_TRY(launch_gemm_tn_f32_multi(ctx, &pf, 1, K, 0, nullptr, true));
+  NK_TRY(finish_out(ctx, c));
+  NK_HIP(hipStreamSynchronize(ctx->stream));
+  return NK_OK;
+}
+
 int nk_gemm_f32(nk_ctx* ctx, int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B, int64_t ldb,
                 double* Cm, int64_t ldc) {
   NK_TRY(check_ctx(ctx));
-  NK_REQUIRE(A && B && Cm && M > 0 && N > 0 && K > 0 && M < (1 << 30) && N < (1 << 30) && lda >= M && ldb >= N && ldc >= N,
-             "nk_gemm_f32: bad argument");
+  NK_REQUIRE(A && B && Cm && M >= 4 && N >= 4 && K > 0 && M < (1 << 30) && N < (1 << 30) && lda >= M && ldb >= N && ldc >= N,
+             "nk_gemm_f32: bad argument (M, N >= 4, K > 0, lda >= M, ldb >= N, ldc >= N)");
+  // the engine's operand contract binds the operands it reads in place; host operands are packed to it.  Checked before
+  // anything is allocated or copied.
+  const bool a_dev = is_device_ptr(A), b_dev = is_device_ptr(B);
+  NK_REQUIRE(!a_dev || (aligned16(A) && lda % 4 == 0 && lda >= ((M + 3) & ~(int64_t)3)),
+             "nk_gemm_f32: a device A must be 16-byte aligned with lda a multiple of 4 that covers M rounded up to one");
+  NK_REQUIRE(!b_dev || (aligned16(B) && ldb % 4 == 0 && ldb >= ((N + 3) & ~(int64_t)3)),
+             "nk_gemm_f32: a device B must be 16-byte aligned with ldb a multiple of 4 that covers N rounded up to one");
   const ArenaMark mk = arena_mark(ctx);
-  const float *Ad = A, *Bd = B;
-  double* Cd = Cm;
-  double* tmp = nullptr;
-  if (!is_device_ptr(A)) {
-    NK_TRY(arena_alloc_t(ctx, ((size_t)K * lda + 1) / 2 + 2, &tmp));
-    NK_HIP(hipMemcpyAsync(tmp, A, (size_t)K * lda * 4, hipMemcpyHostToDevice, ctx->stream));
-    Ad = reinterpret_cast<const float*>(tmp);
-  }
-  if (!is_device_ptr(B)) {
-    NK_TRY(arena_alloc_t(ctx, ((size_t)K * ldb + 1) / 2 + 2, &tmp));
-    NK_HIP(hipMemcpyAsync(tmp, B, (size_t)K * ldb * 4, hipMemcpyHostToDevice, ctx->stream));
-    Bd = reinterpret_cast<const float*>(tmp);
-  }
-  const bool c_host = !is_device_ptr(Cm);
-  if (c_host) NK_TRY(arena_alloc_t(ctx, (size_t)M * ldc, &Cd));
-  TnProblemF pf;
-  pf.A = Ad; pf.B = Bd; pf.lda = lda; pf.ldb = ldb; pf.M = (int)M; pf.N = (int)N; pf.C = Cd; pf.ldc = ldc;
-  NK_REQUIRE(tnf_fast_ok(pf), "nk_gemm_f32: operands must be 16-byte aligned with leading dimensions that are multiples of 4 and >= 4 columns");
-  NK_TRY(launch_gemm_tn_f32_multi(ctx, &pf, 1, K, 0, nullptr, true));
-  if (c_host) NK_HIP(hipMemcpyAsync(Cm, Cd, (size_t)M * ldc * 8, hipMemcpyDeviceToHost, ctx->stream));
-  NK_HIP(hipStreamSynchronize(ctx->stream));
+  const int rc = gemm_f32_staged(ctx, M, N, K, A, lda, B, ldb, Cm, ldc);
   arena_release(ctx, mk);
-  return NK_OK;
+  return rc;
 }
 
 int nk_sqrtm_spd(nk_ctx* ctx, const double* P, int64_t ldp, int32_t m, double* S, double* Sinv, int32_t* iters,

@@ -50,7 +50,9 @@ WORKER = textwrap.dedent("""
     rank, world = nkd.init_process_group("gloo")
     res = nkd.sharded_lqr_sweep(*S.ARGS, fit_fn=S.fit_fn, loop_fn=S.loop_fn, controller=S.BOX)
     np.savez(os.path.join({out!r}, f"tables_{{rank}}.npz"), **{{k: res[k] for k in harness.MPC_SCORE_NAMES + ("rmse_control",)}})
-    print(json.dumps(dict(rank=rank, world=world, calls=S.calls)))
+    # one write per rank, newline included: the ranks share the pipe, and print() hands the text and its newline over apart
+    sys.stdout.write(json.dumps(dict(rank=rank, world=world, calls=S.calls)) + "\\n")
+    sys.stdout.flush()
 """)
 
 
