@@ -673,6 +673,61 @@ int nk_mpc_loop(nk_ctx* ctx, const nk_model* model, const nk_poly_plant* plant, 
 int nk_mpc_qp_host(const nk_mpc_desc* desc, const double* e, const double* u_prev_or_NULL, double* out_u, double* out_z,
                    double* out_info);
 int nk_mpc_loop_max_m(int32_t nv);  /* the limit on m for nv decision variables (0: nv out of range) */
+/* ---- Limits on PREDICTED STATES in the constrained MPC loop, hard or soft: ny output rows beside an unchanged nk_mpc_desc.
+ *   Per step, with e = phi(x_t) - phi(x_ref) and U as for nk_mpc_loop:
+ *       minimise 1/2 U'HU + (F e)'U + (w_y / 2) dist^2(G U + T e, [ylo', yhi'])
+ *       subject to lo <= U <= hi,  dlo <= u_k - u_{k-1} <= dhi
+ *   w_y = y_weight = +inf makes the output rows hard constraints; a finite w_y > 0 penalises the squared violation -- that QP
+ *   is always feasible, which a plant pushed outside its limits needs.  A hard problem whose first predicted state is out of
+ *   reach does not converge; w_y far above rho (1e3 rho) converges very slowly.
+ *   G (ny x nv) and T (ny x m) are the condensed prediction of selected state components over the steps k = 1 .. Ny <= N in
+ *   the error coordinates of the cost (lqr.mpc_condense_outputs): row (k, c) of T is C_c A^k, block (k, j) of G is
+ *   C_c A^(k-1-j) B for j < k, else 0.  ycomp[r] names the state component of row r, or -1 for a row without a reference
+ *   shift (NULL: every row -1).  ylo, yhi are ABSOLUTE state bounds: b = ylo_r - x_ref[ycomp_r] is one rounded subtraction
+ *   per trajectory, done once, and the bound of a step is b - t_r with t = T e; likewise for yhi.
+ *   THE ITERATION IS PART OF THE INTERFACE, in the folded form the device runs (lqr.mpc_out_solve is its NumPy statement,
+ *   csrc/nk_mpc_out.h the host build).  A_c = [I; D; G]; nt = nv + ny.  Formed once per call on the host:
+ *       M = (H + rho (I + D'D + G'G))^-1 by Cholesky;   Kb = [[M, M G'], [G M, G M G']] (nt x nt) by plain products from M,
+ *       symmetrised;   S0 = [H^-1; G H^-1] (nt x nv);   theta = rho / (rho + w_y), 0 for w_y = inf.
+ *       prox: box and rate rows clip;  output rows  c = clip(v);  z = c + theta (v - c).
+ *   With g = F e, rows ordered (box, rate, output) and s_K the nt entries (s_1, s_3):
+ *       s_K = -(S0 g);   s = (s_K[:nv], D s_K[:nv], s_K[nv:]);   z = prox(s);   lambda = 0;   r = max |s - z|;   k = 0
+ *       while k < iters and not (r <= tol and (k == 0 or tol > 0)):
+ *           w = z - lambda;   q = [rho (w_1 + D'w_2) - g ; rho w_3];   s_K = Kb q, and s from it as above
+ *           z = prox(s + lambda);   lambda += s - z;   r = max |s - z|;   k += 1
+ *       v = the first p entries of z_1;   u_t = clip(clip(v, lo, hi), u_{-1} + dlo, u_{-1} + dhi)
+ *   Output bounds all inactive at the start give r = 0 at k = 0 (when the input limits are inactive too): no iteration, and
+ *   z_1 = U_unc.  A finite w_y leaves r > 0 at a start outside the output bounds.
+ *   NaN: the rule of nk_mpc_loop, extended to t = T e and to the shifted output bounds: such a step has NaN controls and
+ *   out_info = {iters, NaN}, and affects no other step or trajectory.
+ *   Device side (nk_mpc_out_loop.hip): the loop of nk_mpc_loop on nt lanes of the first wave.  W = S^-1 [F; T]' (m x nt;
+ *   spline models: [F; T]') lives in LDS; lane i < nv receives g_i and lane nv + r receives t_r from the same pass.  Lane i
+ *   keeps row i of Kb in registers (classes 16 / 32 / 64 over nt), one iteration is one pass of FMAs over q broadcast with
+ *   v_readlane; S0 is read once per step, transposed so that lanes read consecutive words; output lanes hold their shifted
+ *   bounds where input lanes hold lo / hi and take no part in the shifts of D.  Every summation order is fixed by
+ *   (m, nv, ny, p) alone: a trajectory has the same bits alone or in any batch.
+ *   Limits: iters >= 1 (iters = 0, the saturated LQR, is nk_mpc_loop's), nv + ny <= 64, m <= nk_mpc_loop_max_m(nv + ny), p <= 4,
+ *   d <= 4.  Everything is validated before anything is queued or written, with the field named in nk_last_error(): every
+ *   rule of nk_mpc_desc, ny outside 1 .. 64 - nv, ylo > yhi, ycomp outside -1 .. d - 1, y_weight not positive or NaN, G or T
+ *   NULL or not finite, M not positive definite.  The arrays of both descriptions are HOST memory; everything else as for
+ *   nk_mpc_loop.  Ordinary contexts only.
+ *   nk_mpc_out_qp_host: ONE solve of the same iteration in the host build, no context and no GPU: e (m), x_ref (the reference
+ *   state, read at ycomp; NULL = no shift; ycomp is checked against -1 .. 3), u_prev (p, NULL = zeros); out_u (p), out_z
+ *   (nt = nv + ny, may be NULL: z_1 then z_3), out_info (2, may be NULL). */
+typedef struct nk_mpc_out {
+  int32_t ny, reserved;  /* output rows, 1 .. 64 - nv */
+  const double* G;       /* ny x nv dense */
+  const double* T;       /* ny x m dense */
+  const double* ylo;     /* ny absolute lower bounds, or NULL = -inf */
+  const double* yhi;     /* ny absolute upper bounds, or NULL = +inf */
+  const int32_t* ycomp;  /* ny state components, -1 = no reference shift; NULL = all -1 */
+  double y_weight;       /* > 0; +inf = hard rows */
+} nk_mpc_out;
+int nk_mpc_out_loop(nk_ctx* ctx, const nk_model* model, const nk_poly_plant* plant, const nk_mpc_desc* desc,
+                    const nk_mpc_out* out, const double* x0, const double* x_ref, const double* u_init_or_NULL, int32_t steps,
+                    int32_t batch, double* out_x, double* out_u, double* out_info_or_NULL);
+int nk_mpc_out_qp_host(const nk_mpc_desc* desc, const nk_mpc_out* out, const double* e, const double* x_ref_or_NULL,
+                       const double* u_prev_or_NULL, double* out_u, double* out_z, double* out_info);
 /* ---- the multi-model form of the constrained MPC loop, scored on the device: the seeds x m table of the control experiments
  *   under actuator limits in ONE call after the fits and controllers.  The units of a call share the plant and `steps` and
  *   may differ in everything else: model kind, kernel family, m, horizon, iters (0, the saturated LQR, included), rho, tol,

@@ -93,6 +93,27 @@ def mpc_desc(controller, iters, tol):
     return ds, keep
 
 
+class MpcOut(C.Structure):
+    """nk_mpc_out (include/nyskoop.h): the output rows of nk_mpc_out_loop beside an MpcDesc.  Host arrays the caller keeps
+    alive for the call."""
+    _fields_ = [("ny", C.c_int32), ("reserved", C.c_int32), ("G", C.c_void_p), ("T", C.c_void_p), ("ylo", C.c_void_p),
+                ("yhi", C.c_void_p), ("ycomp", C.c_void_p), ("y_weight", C.c_double)]
+
+
+def mpc_out(controller):
+    """(MpcOut, keep-alive list) of an lqr.MPCOutputController: infinite bounds travel as NULL only when a whole vector is
+    infinite."""
+    out = MpcOut()
+    G, T = (np.ascontiguousarray(a, dtype=np.float64) for a in (controller.G, controller.T))
+    ylo, yhi = (np.ascontiguousarray(a, dtype=np.float64) for a in (controller.ylo, controller.yhi))
+    yc = np.ascontiguousarray(controller.ycomp, dtype=np.int32)
+    out.ny, out.reserved, out.G, out.T, out.ycomp = int(controller.ny), 0, G.ctypes.data, T.ctypes.data, yc.ctypes.data
+    out.ylo = None if np.all(ylo == -np.inf) else ylo.ctypes.data
+    out.yhi = None if np.all(yhi == np.inf) else yhi.ctypes.data
+    out.y_weight = float(controller.y_weight)
+    return out, [G, T, ylo, yhi, yc]
+
+
 class MpcUnit(C.Structure):
     """nk_mpc_unit (include/nyskoop.h), one unit of nk_mpc_loop_multi: five pointers (model, desc, x0, x_ref, u_init) and
     two int32 (uopt, reserved): 48 bytes, no padding."""
@@ -203,6 +224,9 @@ SIGNATURES = {
     "nk_mpc_loop_multi": (C.c_int, [_P, C.POINTER(PolyPlant), _I32, C.POINTER(MpcUnit), _I32, _P, _I32, _P, _P, _P, _P]),
     "nk_mpc_qp_host": (C.c_int, [C.POINTER(MpcDesc), _P, _P, _P, _P, _P]),
     "nk_mpc_loop_max_m": (C.c_int, [_I32]),
+    "nk_mpc_out_loop": (C.c_int, [_P, _P, C.POINTER(PolyPlant), C.POINTER(MpcDesc), C.POINTER(MpcOut), _P, _P, _P, _I32,
+                                  _I32, _P, _P, _P]),
+    "nk_mpc_out_qp_host": (C.c_int, [C.POINTER(MpcDesc), C.POINTER(MpcOut), _P, _P, _P, _P, _P, _P]),
     "nk_closed_loop_multi": (C.c_int, [_P, _I32, _D, C.POINTER(LoopUnit), _I32, _P, _P, _P, _P, _P]),
     "nk_dare_batch": (C.c_int, [_P, C.POINTER(DareProblem), _I32, _D, _I32, C.POINTER(_I32), C.POINTER(_I32)]),
     "nk_model_lqr_gain_batch": (C.c_int, [_P, C.POINTER(_P), _I32, _D, _P, _D, _I32, _P, C.POINTER(_I32),

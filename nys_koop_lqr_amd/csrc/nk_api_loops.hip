@@ -1,6 +1,7 @@
 // Closed loops that run as one launch behind the C ABI: the plant loops (nk_plant_step, nk_plant_loop, nk_plant_loop_multi and
 // their forms for a polynomial plant the caller describes, nk_poly_plant_*; nk_plant_loop.hip), the constrained MPC loop
-// (nk_mpc_loop, nk_mpc_loop_multi, nk_mpc_qp_host; nk_mpc_loop.hip, nk_mpc.h) and the lifted loop of many models
+// (nk_mpc_loop, nk_mpc_loop_multi, nk_mpc_qp_host; nk_mpc_loop.hip, nk_mpc.h), its form with limits on predicted states
+// (nk_mpc_out_loop, nk_mpc_out_qp_host; nk_mpc_out_loop.hip, nk_mpc_out.h) and the lifted loop of many models
 // (nk_closed_loop_multi; nk_loop_multi.hip).  The unit-table calls
 // check every unit, lay its host operands out in one staging block (nk_unit_pack.h), move it with one copy, build the
 // table of device records, launch, and bring the results back behind one synchronisation.
@@ -9,6 +10,7 @@
 #include "nk_plant.h"
 #include "nk_poly_plant.h"
 #include "nk_mpc.h"
+#include "nk_mpc_out.h"
 
 #include <cmath>
 #include <limits>
@@ -399,6 +401,90 @@ int nk_mpc_loop(nk_ctx* ctx, const nk_model* mdl, const nk_poly_plant* plant, co
   NK_TRY(finish_out(ctx, ou));
   if (out_info) NK_TRY(finish_out(ctx, oi));
   NK_HIP(hipStreamSynchronize(ctx->stream));  // (blk and Gt are read by the copies queued above)
+  return NK_OK;
+}
+
+int nk_mpc_out_qp_host(const nk_mpc_desc* desc, const nk_mpc_out* out, const double* e, const double* x_ref,
+                       const double* u_prev, double* out_u, double* out_z, double* out_info) {
+  char msg[200];
+  NK_REQUIRE(mpc_out_qp_host(desc, out, e, x_ref, u_prev, out_u, out_z, out_info, msg, sizeof msg) == 0,
+             "nk_mpc_out_qp_host: %s", msg);
+  return NK_OK;
+}
+
+int nk_mpc_out_loop(nk_ctx* ctx, const nk_model* mdl, const nk_poly_plant* plant, const nk_mpc_desc* desc,
+                    const nk_mpc_out* out, const double* x0, const double* x_ref, const double* u_init, int32_t steps,
+                    int32_t batch, double* out_x, double* out_u, double* out_info) {
+  const char* who = "nk_mpc_out_loop";
+  NK_TRY(check_ctx(ctx));
+  NK_REQUIRE(!ctx_recording(ctx), "%s: not available to the members of a lock-step group", who);
+  NK_REQUIRE(mdl && x0 && x_ref && out_x && out_u, "%s: null argument", who);
+  NK_TRY(check_poly_plant(who, plant));
+  int nv = 0;
+  NK_TRY(check_mpc_model(ctx, who, -1, mdl, *plant, desc, &nv));
+  NK_REQUIRE(out != nullptr, "%s: the output description is null", who);
+  NK_REQUIRE(!is_device_ptr(out->G) && !is_device_ptr(out->T) && !is_device_ptr(out->ylo) && !is_device_ptr(out->yhi) &&
+                 !is_device_ptr(out->ycomp), "%s: the arrays of the output description (G, T, ylo, yhi, ycomp) must be host memory",
+             who);
+  const int m = mdl->m, d = mdl->d, p = mdl->p;
+  char msg[200];
+  NK_REQUIRE(mpc_out_check(desc, out, d, msg, sizeof msg), "%s: %s", who, msg);
+  const int ny = out->ny, nt = nv + ny;
+  NK_REQUIRE(m <= mpc_loop_max_m(nt), "%s: m = %d landmarks, at most %d fit one workgroup with nv + ny = %d lanes", who, m,
+             mpc_loop_max_m(nt), nt);
+  NK_TRY(mpc_loop_check_lds(ctx, m, nt));
+  NK_REQUIRE(steps >= 1 && batch >= 1, "%s: steps = %d and batch = %d must be positive", who, steps, batch);
+  // the constants of the call on the host: [Kb | S0' | lo hi dlo dhi ycomp]
+  const size_t nkb = (size_t)nt * nt, ns0 = (size_t)nv * nt;
+  std::vector<double> blk(nkb + ns0 + 5 * (size_t)nt);
+  NK_REQUIRE(mpc_out_prepare(*desc, *out, blk.data(), blk.data() + nkb, msg, sizeof msg), "%s: %s", who, msg);
+  const double inf = std::numeric_limits<double>::infinity();
+  double* bnd = blk.data() + nkb + ns0;
+  for (int i = 0; i < nt; ++i) {
+    const bool in = i < nv;
+    bnd[i] = in ? mpc_bound(desc->lo, i, -inf) : mpc_bound(out->ylo, i - nv, -inf);
+    bnd[nt + i] = in ? mpc_bound(desc->hi, i, inf) : mpc_bound(out->yhi, i - nv, inf);
+    bnd[2 * nt + i] = in ? mpc_bound(desc->dlo, i, -inf) : -inf;
+    bnd[3 * nt + i] = in ? mpc_bound(desc->dhi, i, inf) : inf;
+    bnd[4 * nt + i] = in ? -1.0 : (double)mpc_out_ycomp(out, i - nv);
+  }
+  // ---- everything is checked: stage and queue
+  std::vector<double> FT((size_t)nt * m);  // [F; T], nt x m
+  std::copy(desc->F, desc->F + (size_t)nv * m, FT.begin());
+  std::copy(out->T, out->T + (size_t)ny * m, FT.begin() + (size_t)nv * m);
+  MatIn cst, gm, xi, xr, ui;
+  MatOut ox, ou, oi;
+  NK_TRY(stage_in(ctx, blk.data(), (int64_t)blk.size(), 1, (int64_t)blk.size(), &cst));
+  NK_TRY(stage_in(ctx, x0, d, batch, d, &xi));
+  NK_TRY(stage_in(ctx, x_ref, d, batch, d, &xr));
+  if (u_init) NK_TRY(stage_in(ctx, u_init, p, batch, p, &ui));
+  NK_TRY(stage_out(ctx, out_x, d, (int64_t)batch * (steps + 1), d, &ox));
+  NK_TRY(stage_out(ctx, out_u, p, (int64_t)batch * steps, p, &ou));
+  if (out_info) NK_TRY(stage_out(ctx, out_info, 2, (int64_t)batch * steps, 2, &oi));
+  // W = S^-1 [F; T]' (m x nt) by ONE product, as nk_mpc_loop folds F; a spline model lifts with the raw block, W = [F; T]'
+  const double* w = nullptr;
+  std::vector<double> Gt;
+  if (mdl->kind != NK_MODEL_SPLINE) {
+    double* wf = nullptr;
+    NK_TRY(stage_in(ctx, FT.data(), m, nt, m, &gm));
+    NK_TRY(arena_alloc_t(ctx, (size_t)m * nt + 2, &wf));
+    NK_TRY(launch_gemm(ctx, false, true, m, nt, m, 1.0, mdl->Sinv, m, gm.ptr, gm.ld, 0.0, wf, nt));
+    w = wf;
+  } else {
+    Gt.resize((size_t)m * nt);
+    for (int l = 0; l < m; ++l)
+      for (int i = 0; i < nt; ++i) Gt[(size_t)l * nt + i] = FT[(size_t)i * m + l];
+    NK_TRY(stage_in(ctx, Gt.data(), (int64_t)Gt.size(), 1, (int64_t)Gt.size(), &gm));
+    w = gm.ptr;
+  }
+  NK_TRY(launch_mpc_out_loop(ctx, mdl, *plant, nv, ny, desc->iters, desc->rho, desc->tol, mpc_out_theta(desc->rho, out->y_weight),
+                             w, cst.ptr, cst.ptr + nkb, cst.ptr + nkb + ns0, xi.ptr, xi.ld, xr.ptr, xr.ld,
+                             u_init ? ui.ptr : nullptr, u_init ? ui.ld : 0, steps, batch, ox.dev, ox.ld, ou.dev, ou.ld,
+                             out_info ? oi.dev : nullptr));
+  NK_TRY(finish_out(ctx, ox));
+  NK_TRY(finish_out(ctx, ou));
+  if (out_info) NK_TRY(finish_out(ctx, oi));
+  NK_HIP(hipStreamSynchronize(ctx->stream));  // (blk, FT and Gt are read by the copies queued above)
   return NK_OK;
 }
 

@@ -632,6 +632,14 @@ int launch_mpc_loop(nk_ctx* ctx, const nk_model* mdl, const nk_poly_plant& plant
                     const double* w, const double* M, const double* Hinv, const double* bnd, const double* x0, int64_t x0_stride,
                     const double* xref, int64_t xref_stride, const double* uinit, int64_t uinit_stride, int steps, int batch,
                     double* out_x, int64_t ldx, double* out_u, int64_t ldu, double* out_info);
+// The same loop with ny output rows (nk_mpc_out_loop.hip; nk_mpc_out_loop), nt = nv + ny lanes: w the folded map of [F; T]
+// (m x nt), Kb (nt x nt) and S0 transposed (nv x nt) of mpc_out_prepare (nk_mpc_out.h); bnd: five rows of nt -- lo, hi, dlo,
+// dhi (output lanes: ylo, yhi, -inf, +inf) and ycomp as a double (-1 in the input lanes).  m <= mpc_loop_max_m(nt).
+int launch_mpc_out_loop(nk_ctx* ctx, const nk_model* mdl, const nk_poly_plant& plant, int nv, int ny, int iters, double rho,
+                        double tol, double theta, const double* w, const double* Kb, const double* S0t, const double* bnd,
+                        const double* x0, int64_t x0_stride, const double* xref, int64_t xref_stride, const double* uinit,
+                        int64_t uinit_stride, int steps, int batch, double* out_x, int64_t ldx, double* out_u, int64_t ldu,
+                        double* out_info);
 // The multi-model form (nk_mpc_loop_multi): one record per unit, every pointer device memory.  The records are sorted into
 // classes of (kernel family, variables padded to 16 / 32 / 64, waves per workgroup), staged with one copy and run with one
 // launch per class, its dynamic LDS the largest need among its units; a workgroup finds its record by its block index.

@@ -513,14 +513,17 @@ def mpc_control_plant(num_steps, reference, initial_state, regressor, controller
     lift per step, e = phi(x) - phi(ref), the control from lqr.mpc_solve (controller.control) with u_{-1} = the control
     applied last (u_init, zeros by default, before the first step), x <- plant_step(x (d, 1), u (p, 1)).  iters = 0: the
     saturated LQR.  Returns (states (d, num_steps + 1) with the initial state first, u_s (p, num_steps), info (num_steps, 2)
-    = {iterations run, final max |s - z|})."""
+    = {iterations run, final max |s - z|}).  A controller with output rows (lqr.MPCOutputController) is given the reference
+    state as well: its state bounds are absolute."""
     x = np.asarray(initial_state, dtype=np.float64).reshape(-1, 1)
-    phi_ref = regressor.lift(np.asarray(reference, dtype=np.float64).reshape(-1, 1))
+    x_ref = np.asarray(reference, dtype=np.float64).reshape(-1)
+    phi_ref = regressor.lift(x_ref.reshape(-1, 1))
     p = controller.n_inputs
     u_prev = np.zeros(p) if u_init is None else np.asarray(u_init, dtype=np.float64).reshape(p)
+    kw = dict(x_ref=x_ref) if hasattr(controller, "ycomp") else {}
     xs, us, info = [x], [], []
     for _ in range(num_steps):
-        u_prev, it = controller.control((regressor.lift(x) - phi_ref).reshape(-1), u_prev, iters, tol)
+        u_prev, it = controller.control((regressor.lift(x) - phi_ref).reshape(-1), u_prev, iters, tol, **kw)
         us.append(u_prev.reshape(-1, 1))
         info.append(it)
         x = np.asarray(plant_step(x, u_prev.reshape(-1, 1)), dtype=np.float64).reshape(-1, 1)

@@ -298,3 +298,159 @@ class MPCController:
         u, _, info = mpc_solve(self.H, self.F @ e, self.lo, self.hi, self.dlo, self.dhi, u_prev, self.rho, iters, tol,
                                self.n_inputs, M, Hinv)
         return u, info
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Limits on predicted states, hard or soft (nk_mpc_out_loop, nk_mpc_out_qp_host; csrc/nk_mpc_out.h, nk_mpc_out_loop.hip): ny
+# output rows G U + T e with their own bounds join the constraint rows, A_c = [I; D; G].
+# ---------------------------------------------------------------------------------------------------------------------------
+def mpc_condense_outputs(A, B, C_rows, N, Ny=None):
+    """(G, T) of the predicted outputs y_k = C_rows e_k, k = 1 .. Ny (Ny <= N, default N), under e_{k+1} = A e_k + B u_k as a
+    function of U (nv = N p entries) and e_0: the stacked outputs are G U + T e_0, row (k, c) at (k - 1) nc + c.  Row (k, c) of T
+    is C_c A^k, block (k, j) of G is C_c A^(k-1-j) B for j < k and 0 otherwise.  Only thin products: R_k = R_{k-1} A (nc x m)
+    from R_0 = C_rows, and R_i B; no power of A is formed."""
+    A = np.asarray(A, dtype=np.float64)
+    m = A.shape[0]
+    B = np.asarray(B, dtype=np.float64).reshape(m, -1)
+    p = B.shape[1]
+    R = np.asarray(C_rows, dtype=np.float64).reshape(-1, m)
+    nc = R.shape[0]
+    N = int(N)
+    Ny = N if Ny is None else int(Ny)
+    if N < 1 or not 1 <= Ny <= N:
+        raise ValueError("the horizons must satisfy 1 <= Ny <= N")
+    G, T = np.zeros((Ny * nc, N * p)), np.zeros((Ny * nc, m))
+    RB = []
+    for k in range(1, Ny + 1):
+        RB.append(R @ B)  # C A^(k-1) B
+        R = R @ A         # C A^k
+        T[(k - 1) * nc:k * nc] = R
+        for j in range(k):
+            G[(k - 1) * nc:k * nc, j * p:(j + 1) * p] = RB[k - 1 - j]
+    return G, T
+
+
+def mpc_out_matrices(H, rho, p, G):
+    """(Kb, S0, M) of a call with output rows G (ny x nv): M = (H + rho (I + D'D + G'G))^-1 by Cholesky, symmetrised;
+    Kb = [[M, M G'], [G M, G M G']] (nt x nt, nt = nv + ny) by plain products from M, symmetrised; S0 = [H^-1; G H^-1] (nt x nv).
+    Raises np.linalg.LinAlgError when a matrix is not positive definite."""
+    H, G = np.asarray(H, dtype=np.float64), np.asarray(G, dtype=np.float64)
+    nv = H.shape[0]
+    G = G.reshape(-1, nv)
+    D = np.eye(nv) - np.eye(nv, k=-p)
+    eye = np.eye(nv)
+    Hinv = _sym(scipy.linalg.cho_solve(scipy.linalg.cho_factor(H, lower=True), eye))
+    M = _sym(scipy.linalg.cho_solve(scipy.linalg.cho_factor(H + rho * (eye + D.T @ D + G.T @ G), lower=True), eye))
+    MG = M @ G.T
+    Kb = np.block([[M, MG], [G @ M, G @ MG]])
+    return _sym(Kb), np.vstack([Hinv, G @ Hinv]), M
+
+
+def mpc_out_theta(rho, y_weight):
+    """rho / (rho + w_y), and 0 for w_y = inf (hard rows)."""
+    return 0.0 if np.isinf(y_weight) else float(rho / (rho + y_weight))
+
+
+def mpc_out_shift(ylo, yhi, ycomp, x_ref=None):
+    """The bounds of the output rows in error coordinates, b = ylo_r - x_ref[ycomp_r] (one rounded subtraction per row; a row
+    with ycomp = -1, or x_ref = None, keeps its bound)."""
+    ylo, yhi = np.array(ylo, dtype=np.float64).reshape(-1), np.array(yhi, dtype=np.float64).reshape(-1)
+    if x_ref is not None:
+        yc = np.asarray(ycomp, dtype=np.int64).reshape(-1)
+        xr = np.asarray(x_ref, dtype=np.float64).reshape(-1)
+        sel = yc >= 0
+        ylo[sel] = ylo[sel] - xr[yc[sel]]
+        yhi[sel] = yhi[sel] - xr[yc[sel]]
+    return ylo, yhi
+
+
+def mpc_out_prox(v, lo_c, hi_c, nrows_in, theta):
+    """clip on the box and rate rows (the first nrows_in); on the output rows c = clip(v), z = c + theta (v - c)."""
+    c = np.minimum(np.maximum(v, lo_c), hi_c)
+    if theta != 0.0:
+        c[nrows_in:] = c[nrows_in:] + theta * (v[nrows_in:] - c[nrows_in:])
+    return c
+
+
+def mpc_out_solve(g, t, lo, hi, dlo, dhi, ylo_b, yhi_b, u_prev, rho, theta, iters, tol, p, Kb, S0):
+    """One solve of  min 1/2 U'HU + g'U + (w_y / 2) dist^2(G U + t, [ylo_b, yhi_b])  under the box and rate limits of mpc_solve,
+    by the folded iteration of include/nyskoop.h -- the NumPy statement the device kernel follows.  Rows of a stacked vector:
+    (nv box, nv rate, ny output); s_K = (s_1, s_3) has nt = nv + ny entries.
+        bounds of the output rows: ylo_b - t, yhi_b - t  (ylo_b, yhi_b: mpc_out_shift)
+        s_K = -(S0 g);  s = (s_K[:nv], D s_K[:nv], s_K[nv:]);  z = prox(s);  lambda = 0;  r = max |s - z|;  k = 0
+        while k < iters and not (r <= tol and (k == 0 or tol > 0)):
+            w = z - lambda;  q = [rho (w_1 + D'w_2) - g; rho w_3];  s_K = Kb q;  z = prox(s + lambda);  lambda += s - z
+            r = max |s - z|;  k += 1
+        u = clip(clip(z[:p], lo, hi), u_prev + dlo, u_prev + dhi)
+    Returns (u (p,), z_K = (z_1, z_3) (nt,), (k, r)).  iters >= 1."""
+    g, t = np.asarray(g, dtype=np.float64).reshape(-1), np.asarray(t, dtype=np.float64).reshape(-1)
+    nv, ny = g.size, t.size
+    u_prev = np.zeros(p) if u_prev is None else np.asarray(u_prev, dtype=np.float64).reshape(p)
+    shift = np.zeros(nv)
+    shift[:p] = u_prev
+    lo_c = np.concatenate([lo, dlo + shift, np.asarray(ylo_b, dtype=np.float64) - t])
+    hi_c = np.concatenate([hi, dhi + shift, np.asarray(yhi_b, dtype=np.float64) - t])
+
+    def rows(sK):
+        return np.concatenate([sK[:nv], mpc_diff(sK[:nv], p), sK[nv:]])
+
+    s = rows(-(S0 @ g))
+    z = mpc_out_prox(s, lo_c, hi_c, 2 * nv, theta)
+    lam = np.zeros(2 * nv + ny)
+    r, k = float(np.max(np.abs(s - z))), 0
+    while k < iters and not (r <= tol and (k == 0 or tol > 0)):
+        w = z - lam
+        q = np.concatenate([rho * (w[:nv] + mpc_diff_t(w[nv:2 * nv], p)) - g, rho * w[2 * nv:]])
+        s = rows(Kb @ q)
+        z = mpc_out_prox(s + lam, lo_c, hi_c, 2 * nv, theta)
+        lam = lam + (s - z)
+        r = float(np.max(np.abs(s - z)))
+        k += 1
+    return mpc_saturate(z[:p], lo, hi, dlo, dhi, u_prev), np.concatenate([z[:nv], z[2 * nv:]]), (k, r)
+
+
+class MPCOutputController(MPCController):
+    """MPCController with ny output rows: G (ny x nv), T (ny x m) (mpc_condense_outputs), the absolute state bounds ylo, yhi
+    of the rows (+-inf where absent), ycomp (the state component of a row, -1 for a row without a reference shift) and
+    y_weight (np.inf: hard rows; finite > 0: the squared violation is penalised).  Plain arrays: picklable."""
+
+    def __init__(self, H, F, lo, hi, dlo, dhi, K, rho, horizon, G, T, ylo, yhi, ycomp, y_weight=np.inf):
+        super().__init__(H, F, lo, hi, dlo, dhi, K, rho, horizon)
+        self.G, self.T = np.ascontiguousarray(G, dtype=np.float64), np.ascontiguousarray(T, dtype=np.float64)
+        self.ylo, self.yhi = (np.ascontiguousarray(a, dtype=np.float64).reshape(-1) for a in (ylo, yhi))
+        self.ycomp = np.ascontiguousarray(ycomp, dtype=np.int32).reshape(-1)
+        self.y_weight = float(y_weight)
+        ny = self.ylo.size
+        if self.G.shape != (ny, self.nv) or self.T.shape != (ny, self.F.shape[1]) or self.yhi.size != ny or self.ycomp.size != ny:
+            raise ValueError(f"G {self.G.shape}, T {self.T.shape}, ylo, yhi and ycomp must describe the same {ny} output rows")
+        if not self.y_weight > 0:
+            raise ValueError("y_weight must be positive (np.inf: hard rows)")
+        self._omats = None
+
+    ny = property(lambda self: self.G.shape[0])
+
+    def out_matrices(self):
+        if self.__dict__.get("_omats") is None:
+            self._omats = mpc_out_matrices(self.H, self.rho, self.n_inputs, self.G)
+        return self._omats
+
+    def __getstate__(self):
+        st = super().__getstate__()
+        st["_omats"] = None
+        return st
+
+    def input_only(self):
+        """The MPCController of the same problem without the output rows."""
+        return MPCController(self.H, self.F, self.lo, self.hi, self.dlo, self.dhi, self.K, self.rho, self.horizon)
+
+    def control(self, e, u_prev=None, iters=50, tol=0.0, x_ref=None):
+        """The control for the lifted error e = phi(x) - phi(x_ref) (m,) and the reference state x_ref (None: no shift of the
+        output bounds): (u (p,), (iterations, residual)) by mpc_out_solve; iters = 0 is the saturated LQR of MPCController."""
+        if iters == 0:
+            return super().control(e, u_prev, 0, tol)
+        e = np.asarray(e, dtype=np.float64).reshape(-1)
+        Kb, S0, _ = self.out_matrices()
+        yl, yh = mpc_out_shift(self.ylo, self.yhi, self.ycomp, x_ref)
+        u, _, info = mpc_out_solve(self.F @ e, self.T @ e, self.lo, self.hi, self.dlo, self.dhi, yl, yh, u_prev, self.rho,
+                                   mpc_out_theta(self.rho, self.y_weight), iters, tol, self.n_inputs, Kb, S0)
+        return u, info

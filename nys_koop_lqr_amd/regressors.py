@@ -491,14 +491,24 @@ class _DeviceModelRegressor(KoopmanRegressor):
             return ox[0].T, ou[0].T
         return ox, ou
 
-    def solve_mpc(self, horizon, c=1.0, R=None, u_min=None, u_max=None, du_min=None, du_max=None, Q=None, rho=None):
+    def solve_mpc(self, horizon, c=1.0, R=None, u_min=None, u_max=None, du_min=None, du_max=None, Q=None, rho=None,
+                  x_min=None, x_max=None, y_horizon=None, y_weight=np.inf):
         """The constrained Koopman MPC of this model: lqr.MPCController with the condensed QP of
         sum_{k<N} (e_k'Q e_k + u_k'R u_k) + e_N'P e_N over the horizon N (lqr.mpc_condense on the host; Q = c sym(C'C), R = I
         by default; P and the gain K from lqr.dlqr, refined by two Newton steps (lqr.dare_refine) so that the first move of the
         unconstrained QP is K to rounding -- K differs from solve_lqr's by the residual scipy leaves, 1e-6 .. 1e-11 relative),
         the box u_min <= u_k <= u_max and the rate limits
         du_min <= u_k - u_{k-1} <= du_max (scalars, p entries or N p entries; None = no limit), and the ADMM step
-        rho = sqrt(lambda_min(H) lambda_max(H)) unless given.  N p <= 64 for the device loop (closed_loop_plant_mpc)."""
+        rho = sqrt(lambda_min(H) lambda_max(H)) unless given.  N p <= 64 for the device loop (closed_loop_plant_mpc).
+
+        x_min / x_max (scalars or d entries; +-inf or None for a free component) limit the PREDICTED states C e_k + x_ref over
+        the steps k = 1 .. y_horizon (default N): every component with a finite bound gets one output row per step
+        (lqr.mpc_condense_outputs) and the result is an lqr.MPCOutputController.  y_weight = np.inf makes the rows hard
+        constraints; a finite y_weight > 0 penalises the squared violation with that weight (always feasible: a plant pushed
+        outside its limits needs this; weights far above rho, 1e3 rho say, converge very slowly).  The rows of a sampled plant
+        are small beside the identity rows of the inputs, so the output rows want a rho far above the default (300 x the
+        default reached a hard velocity limit within 2 % in 100 iterations on the Duffing models; with the default the
+        controls did not move).  N p + rows <= 64 for the device loop.  Without these arguments the result is what it always was."""
         from . import lqr
         p = int(self.n_inputs)
         if Q is None:
@@ -512,7 +522,28 @@ class _DeviceModelRegressor(KoopmanRegressor):
         lo, hi, dlo, dhi = lqr.mpc_bounds(int(horizon) * p, u_min, u_max, du_min, du_max)
         if np.any(lo > hi) or np.any(dlo > dhi):
             raise ValueError("u_min <= u_max and du_min <= du_max are required")
-        return lqr.MPCController(H, F, lo, hi, dlo, dhi, K, lqr.mpc_default_rho(H) if rho is None else rho, horizon)
+        rho = lqr.mpc_default_rho(H) if rho is None else rho
+        if x_min is None and x_max is None:
+            return lqr.MPCController(H, F, lo, hi, dlo, dhi, K, rho, horizon)
+        d = np.shape(self.C)[0]
+
+        def full(a, missing):
+            if a is None:
+                return np.full(d, missing)
+            a = np.asarray(a, dtype=np.float64).reshape(-1)
+            if a.size not in (1, d):
+                raise ValueError(f"a state bound of {a.size} entries, the model has {d} states")
+            return np.ascontiguousarray(np.broadcast_to(a, (d,)))
+        xlo, xhi = full(x_min, -np.inf), full(x_max, np.inf)
+        if np.any(np.isnan(xlo)) or np.any(np.isnan(xhi)) or np.any(xlo > xhi):
+            raise ValueError("x_min <= x_max is required")
+        comps = np.flatnonzero(np.isfinite(xlo) | np.isfinite(xhi))
+        if comps.size == 0:  # no finite bound: no output row
+            return lqr.MPCController(H, F, lo, hi, dlo, dhi, K, rho, horizon)
+        Ny = int(horizon) if y_horizon is None else int(y_horizon)
+        G, T = lqr.mpc_condense_outputs(A, B, np.asarray(self.C, dtype=np.float64)[comps], horizon, Ny)
+        return lqr.MPCOutputController(H, F, lo, hi, dlo, dhi, K, rho, horizon, G, T, np.tile(xlo[comps], Ny),
+                                       np.tile(xhi[comps], Ny), np.tile(comps, Ny), y_weight)
 
     def closed_loop_plant_mpc(self, controller, x0, x_ref, num_steps, plant, iters=50, tol=0.0, u_init=None,
                               return_info=False):
@@ -562,9 +593,16 @@ class _DeviceModelRegressor(KoopmanRegressor):
         steps = max(num_steps, 0)
         ox, ou = np.empty((batch, steps + 1, d)), np.empty((batch, steps, p))
         oi = np.empty((batch, steps, 2)) if return_info else None
-        rc = ctx.lib.nk_mpc_loop(ctx.handle, h, plant.descriptor(), C.byref(ds), xb.ctypes.data, xr.ctypes.data,
-                                 None if ui is None else ui.ctypes.data, num_steps, batch, ox.ctypes.data, ou.ctypes.data,
-                                 None if oi is None else oi.ctypes.data)
+        if hasattr(controller, "ycomp") and int(iters) != 0:  # an lqr.MPCOutputController (iters = 0: the saturated LQR)
+            out, keep_out = _lib.mpc_out(controller)
+            rc = ctx.lib.nk_mpc_out_loop(ctx.handle, h, plant.descriptor(), C.byref(ds), C.byref(out), xb.ctypes.data,
+                                         xr.ctypes.data, None if ui is None else ui.ctypes.data, num_steps, batch,
+                                         ox.ctypes.data, ou.ctypes.data, None if oi is None else oi.ctypes.data)
+            del keep_out
+        else:
+            rc = ctx.lib.nk_mpc_loop(ctx.handle, h, plant.descriptor(), C.byref(ds), xb.ctypes.data, xr.ctypes.data,
+                                     None if ui is None else ui.ctypes.data, num_steps, batch, ox.ctypes.data, ou.ctypes.data,
+                                     None if oi is None else oi.ctypes.data)
         _lib.check_mapped(rc)
         del keep
         if single:
