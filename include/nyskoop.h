@@ -774,6 +774,41 @@ typedef struct nk_mpc_unit {
 #define NK_MPC_N_SCORES 8
 int nk_mpc_loop_multi(nk_ctx* ctx, const nk_poly_plant* plant, int32_t steps, const nk_mpc_unit* units, int32_t n_units,
                       const double* u_opt, int32_t n_uopt, double* out_x, double* out_u, double* out_info, double* scores);
+/* ---- the multi-model form of the loop with limits on predicted states, scored on the device: the seeds x m table under a
+ *   state limit in ONE call, with and without the limit side by side.  `units` is the unit table of nk_mpc_loop_multi,
+ *   unchanged; outs[u] (HOST, its arrays HOST) is the output description of unit u, outs[u] == NULL marks a unit without rows,
+ *   and outs itself may be NULL (no unit has rows).
+ *   WITH ROWS, UNIT u IS BIT FOR BIT nk_mpc_out_loop(model, plant, desc, outs[u], x0, x_ref, u_init, steps, batch = 1) in out_x,
+ *   out_u and out_info; WITHOUT ROWS IT IS BIT FOR BIT nk_mpc_loop(...), and with it its entry of nk_mpc_loop_multi.  Both hold
+ *   whatever else the call holds and in whatever order, and one call may mix both kinds: Kb, S0, M, H^-1 and the bounds come
+ *   from the host preparation of the single calls, and the fold W = S^-1 [F; T]' (W = S^-1 F', S^-1 K') is the same product on
+ *   operands laid out as the single call lays them out.  Units that share (model, desc, outs[u]) share every prepared piece.
+ *   A unit with outs[u] != NULL and desc->iters == 0 is NK_ERR_BAD_ARG naming the unit, as nk_mpc_out_loop refuses it (the
+ *   saturated LQR has no rows: pass outs[u] = NULL).
+ *   Outputs as for nk_mpc_loop_multi: each may be NULL, not all four; scores: HOST, n_units x NK_MPC_OUT_N_SCORES.
+ *     scores[u] = {sse_u, ss_opt, J, u_absmax, iters_sum, r_max, n_at_limit, n_iterated, y_viol_max, n_y_viol}
+ *   The first eight keep the definitions of nk_mpc_loop_multi (n_at_limit counts input bounds only).
+ *     y_viol_max = max over the steps t = 0 .. steps - 1 and the output rows r with ycomp[r] >= 0 of
+ *                  max(fl(ylo_r - x_{t+1}[c]), fl(x_{t+1}[c] - yhi_r), 0), c = ycomp[r]: each difference is one rounded
+ *                  subtraction on the ABSOLUTE bounds and the REALISED next state -- for the tiled bounds that solve_mpc builds,
+ *                  the largest excursion of the plant past its state limits.  0 when nothing is violated.  The NaN rule of
+ *                  u_absmax: a step with a NaN difference has a NaN maximum, which enters once and stays;
+ *     n_y_viol   = the number of steps at which that per-step maximum is > 0 (a NaN step does not count).
+ *   A unit without rows has 0 and 0 in both.  A host loop over the returned out_x and the bounds gives the same bits
+ *   (harness.mpc_out_scores in Python).  A unit started at a NaN x0 has NaN u_absmax, J, r_max and y_viol_max (the latter when
+ *   a row has a component); the other units are not affected.
+ *   Everything is checked before anything is queued or written, with the unit index and the field in nk_last_error(): every
+ *   check of nk_mpc_loop_multi, and per unit with rows every check of nk_mpc_out_loop (the rules of nk_mpc_out, m <=
+ *   nk_mpc_loop_max_m(nv + ny), LDS, outs[u] and its arrays host memory).  Ordinary contexts only.
+ *   Device side (nk_mpc_out_loop.hip): the loop body of nk_mpc_out_loop on a per-unit record, one launch per class of (kernel
+ *   family, padded states, nv + ny padded to 16 / 32 / 64, ceil(m / 64) waves); the units without rows run the launches of
+ *   nk_mpc_loop_multi.  One staging copy, one table copy per kind, one synchronisation; no kernel waits for another workgroup.
+ *   An output lane keeps its absolute bounds and forms its violation from the new state; one butterfly per step gives the
+ *   maximum, lane 0 of the first wave folds it in step order. */
+#define NK_MPC_OUT_N_SCORES 10
+int nk_mpc_out_loop_multi(nk_ctx* ctx, const nk_poly_plant* plant, int32_t steps, const nk_mpc_unit* units,
+                          const nk_mpc_out* const* outs, int32_t n_units, const double* u_opt, int32_t n_uopt, double* out_x,
+                          double* out_u, double* out_info, double* scores);
 /* ---- rollout of explicit operators without a model (any estimator that exposes A, B, C: the exact-kernel comparator of
  *   benchmark_lqr_hjb.py:334-381, un-pickled gains): z0: batch x m lifted initial states; A: m x m, B: m x p, C: d x m
  *   (row-major, host or device); U, out_x, out_z as in nk_rollout. --------------------------------------------------- */

@@ -122,6 +122,7 @@ class MpcUnit(C.Structure):
 
 
 MPC_N_SCORES = 8  # NK_MPC_N_SCORES
+MPC_OUT_N_SCORES = 10  # NK_MPC_OUT_N_SCORES
 
 
 class LoopUnit(C.Structure):
@@ -222,6 +223,8 @@ SIGNATURES = {
                                            _P]),
     "nk_mpc_loop": (C.c_int, [_P, _P, C.POINTER(PolyPlant), C.POINTER(MpcDesc), _P, _P, _P, _I32, _I32, _P, _P, _P]),
     "nk_mpc_loop_multi": (C.c_int, [_P, C.POINTER(PolyPlant), _I32, C.POINTER(MpcUnit), _I32, _P, _I32, _P, _P, _P, _P]),
+    "nk_mpc_out_loop_multi": (C.c_int, [_P, C.POINTER(PolyPlant), _I32, C.POINTER(MpcUnit), C.POINTER(C.POINTER(MpcOut)), _I32,
+                                        _P, _I32, _P, _P, _P, _P]),
     "nk_mpc_qp_host": (C.c_int, [C.POINTER(MpcDesc), _P, _P, _P, _P, _P]),
     "nk_mpc_loop_max_m": (C.c_int, [_I32]),
     "nk_mpc_out_loop": (C.c_int, [_P, _P, C.POINTER(PolyPlant), C.POINTER(MpcDesc), C.POINTER(MpcOut), _P, _P, _P, _I32,
@@ -511,13 +514,15 @@ class Context:
         return sc, ox, ou
 
     def mpc_loop_multi(self, descriptor, steps, models, descs, x0s, x_refs, u_inits=None, u_opt=None, uopt_rows=None,
-                       want_x=False, want_u=False, want_info=False, want_scores=True):
+                       want_x=False, want_u=False, want_info=False, want_scores=True, outs=None):
         """nk_mpc_loop_multi: one constrained MPC loop around a polynomial plant (descriptor: a PolyPlant) per unit, all units
         in one call, scored on the device.  models: device-model handles; descs: one MpcDesc per unit (units may share one;
         the caller keeps their arrays alive); x0s, x_refs: (n_units, d); u_inits: (n_units, p), a list with None entries, or
         None = zeros; u_opt: (n_uopt, steps, p) or None; uopt_rows as in poly_plant_loop_multi.  Returns (scores
         (n_units, 8) or None, states (n_units, steps + 1, d) or None, controls (n_units, steps, p) or None, info
-        (n_units, steps, 2) or None)."""
+        (n_units, steps, 2) or None).
+        outs: None, or one entry per unit, an MpcOut (units may share one; the caller keeps their arrays alive) or None for a
+        unit without rows -- the call is then nk_mpc_out_loop_multi and the scores are (n_units, 10)."""
         n = len(models)
         steps = int(steps)
         d, p = int(descriptor.d), int(descriptor.p)
@@ -547,13 +552,23 @@ class Context:
             arr[i].u_init = None if uis[i] is None else uis[i].ctypes.data
             arr[i].uopt = int(uopt_rows[i])
         T = max(steps, 0)
-        sc = np.full((n, MPC_N_SCORES), np.nan) if want_scores else None
+        if outs is not None and len(outs) != n:
+            raise ValueError(f"{len(outs)} output descriptions for {n} models")
+        sc = np.full((n, MPC_N_SCORES if outs is None else MPC_OUT_N_SCORES), np.nan) if want_scores else None
         ox = np.empty((n, T + 1, d)) if want_x else None
         ou = np.empty((n, T, p)) if want_u else None
         oi = np.empty((n, T, 2)) if want_info else None
         ptr = lambda a: None if a is None else a.ctypes.data
-        rc = self.lib.nk_mpc_loop_multi(self.handle, C.byref(descriptor), steps, arr, n, ptr(uo), n_uopt, ptr(ox), ptr(ou),
-                                        ptr(oi), ptr(sc))
+        if outs is None:
+            rc = self.lib.nk_mpc_loop_multi(self.handle, C.byref(descriptor), steps, arr, n, ptr(uo), n_uopt, ptr(ox), ptr(ou),
+                                            ptr(oi), ptr(sc))
+        else:
+            oarr = (C.POINTER(MpcOut) * max(n, 1))()  # (null pointers; `outs` keeps the structures alive through the call)
+            for i, o in enumerate(outs):
+                if o is not None:
+                    oarr[i] = C.pointer(o)
+            rc = self.lib.nk_mpc_out_loop_multi(self.handle, C.byref(descriptor), steps, arr, oarr, n, ptr(uo), n_uopt, ptr(ox),
+                                                ptr(ou), ptr(oi), ptr(sc))
         check_mapped(rc)
         return sc, ox, ou, oi
 

@@ -16,6 +16,7 @@
 #include <limits>
 #include <map>
 #include <string>
+#include <tuple>
 #include <vector>
 
 using namespace nk;
@@ -114,6 +115,56 @@ static int mpc_constants(const char* who, int unit, const nk_mpc_desc& desc, int
     bnd[2 * nv + i] = mpc_bound(desc.dlo, i, -inf);
     bnd[3 * nv + i] = mpc_bound(desc.dhi, i, inf);
   }
+  return NK_OK;
+}
+
+// The output description of one (checked) model and description, for nk_mpc_out_loop and a unit with rows of
+// nk_mpc_out_loop_multi; unit as in check_plant_model.  nv: what check_mpc_model gave.
+static int check_mpc_out(nk_ctx* ctx, const char* who, int unit, const nk_model* mdl, const nk_mpc_desc* desc,
+                         const nk_mpc_out* out, int nv) {
+  auto at = [unit] { return unit >= 0 ? "unit " + std::to_string(unit) + ": " : std::string(); };  // (a failed check only)
+  NK_REQUIRE(out != nullptr, "%s: %sthe output description is null", who, at().c_str());
+  NK_REQUIRE(!is_device_ptr(out), "%s: %sthe output description must be host memory", who, at().c_str());
+  NK_REQUIRE(!is_device_ptr(out->G) && !is_device_ptr(out->T) && !is_device_ptr(out->ylo) && !is_device_ptr(out->yhi) &&
+                 !is_device_ptr(out->ycomp),
+             "%s: %sthe arrays of the output description (G, T, ylo, yhi, ycomp) must be host memory", who, at().c_str());
+  char msg[200];
+  NK_REQUIRE(mpc_out_check(desc, out, mdl->d, msg, sizeof msg), "%s: %s%s", who, at().c_str(), msg);
+  const int m = mdl->m, nt = nv + out->ny;
+  NK_REQUIRE(m <= mpc_loop_max_m(nt), "%s: %sm = %d landmarks, at most %d fit one workgroup with nv + ny = %d lanes", who,
+             at().c_str(), m, mpc_loop_max_m(nt), nt);
+  NK_TRY(mpc_loop_check_lds(ctx, m, nt));
+  return NK_OK;
+}
+
+// The constants of one checked pair of descriptions on the host, [Kb | S0' | lo hi dlo dhi ycomp] (nt^2 + nv nt + 5 nt
+// doubles), and [F; T] (nt x m): mpc_out_prepare and the bounds, the same for the single call and for a unit of the multi
+// form.
+static int mpc_out_constants(const char* who, int unit, const nk_mpc_desc& desc, const nk_mpc_out& out, int nv,
+                             std::vector<double>* consts, std::vector<double>* ft) {
+  const int ny = out.ny, nt = nv + ny, m = desc.m;
+  const size_t nkb = (size_t)nt * nt, ns0 = (size_t)nv * nt;
+  std::vector<double>& blk = *consts;
+  blk.assign(nkb + ns0 + 5 * (size_t)nt, 0.0);
+  char msg[200];
+  if (!mpc_out_prepare(desc, out, blk.data(), blk.data() + nkb, msg, sizeof msg)) {
+    if (unit >= 0) set_error("%s: unit %d: %s", who, unit, msg);
+    else set_error("%s: %s", who, msg);
+    return NK_ERR_BAD_ARG;
+  }
+  const double inf = std::numeric_limits<double>::infinity();
+  double* bnd = blk.data() + nkb + ns0;
+  for (int i = 0; i < nt; ++i) {
+    const bool in = i < nv;
+    bnd[i] = in ? mpc_bound(desc.lo, i, -inf) : mpc_bound(out.ylo, i - nv, -inf);
+    bnd[nt + i] = in ? mpc_bound(desc.hi, i, inf) : mpc_bound(out.yhi, i - nv, inf);
+    bnd[2 * nt + i] = in ? mpc_bound(desc.dlo, i, -inf) : -inf;
+    bnd[3 * nt + i] = in ? mpc_bound(desc.dhi, i, inf) : inf;
+    bnd[4 * nt + i] = in ? -1.0 : (double)mpc_out_ycomp(&out, i - nv);
+  }
+  ft->resize((size_t)nt * m);
+  std::copy(desc.F, desc.F + (size_t)nv * m, ft->begin());
+  std::copy(out.T, out.T + (size_t)ny * m, ft->begin() + (size_t)nv * m);
   return NK_OK;
 }
 
@@ -422,36 +473,15 @@ int nk_mpc_out_loop(nk_ctx* ctx, const nk_model* mdl, const nk_poly_plant* plant
   NK_TRY(check_poly_plant(who, plant));
   int nv = 0;
   NK_TRY(check_mpc_model(ctx, who, -1, mdl, *plant, desc, &nv));
-  NK_REQUIRE(out != nullptr, "%s: the output description is null", who);
-  NK_REQUIRE(!is_device_ptr(out->G) && !is_device_ptr(out->T) && !is_device_ptr(out->ylo) && !is_device_ptr(out->yhi) &&
-                 !is_device_ptr(out->ycomp), "%s: the arrays of the output description (G, T, ylo, yhi, ycomp) must be host memory",
-             who);
+  NK_TRY(check_mpc_out(ctx, who, -1, mdl, desc, out, nv));
   const int m = mdl->m, d = mdl->d, p = mdl->p;
-  char msg[200];
-  NK_REQUIRE(mpc_out_check(desc, out, d, msg, sizeof msg), "%s: %s", who, msg);
   const int ny = out->ny, nt = nv + ny;
-  NK_REQUIRE(m <= mpc_loop_max_m(nt), "%s: m = %d landmarks, at most %d fit one workgroup with nv + ny = %d lanes", who, m,
-             mpc_loop_max_m(nt), nt);
-  NK_TRY(mpc_loop_check_lds(ctx, m, nt));
   NK_REQUIRE(steps >= 1 && batch >= 1, "%s: steps = %d and batch = %d must be positive", who, steps, batch);
-  // the constants of the call on the host: [Kb | S0' | lo hi dlo dhi ycomp]
+  // the constants of the call on the host: [Kb | S0' | lo hi dlo dhi ycomp], and [F; T] (nt x m)
   const size_t nkb = (size_t)nt * nt, ns0 = (size_t)nv * nt;
-  std::vector<double> blk(nkb + ns0 + 5 * (size_t)nt);
-  NK_REQUIRE(mpc_out_prepare(*desc, *out, blk.data(), blk.data() + nkb, msg, sizeof msg), "%s: %s", who, msg);
-  const double inf = std::numeric_limits<double>::infinity();
-  double* bnd = blk.data() + nkb + ns0;
-  for (int i = 0; i < nt; ++i) {
-    const bool in = i < nv;
-    bnd[i] = in ? mpc_bound(desc->lo, i, -inf) : mpc_bound(out->ylo, i - nv, -inf);
-    bnd[nt + i] = in ? mpc_bound(desc->hi, i, inf) : mpc_bound(out->yhi, i - nv, inf);
-    bnd[2 * nt + i] = in ? mpc_bound(desc->dlo, i, -inf) : -inf;
-    bnd[3 * nt + i] = in ? mpc_bound(desc->dhi, i, inf) : inf;
-    bnd[4 * nt + i] = in ? -1.0 : (double)mpc_out_ycomp(out, i - nv);
-  }
+  std::vector<double> blk, FT;
+  NK_TRY(mpc_out_constants(who, -1, *desc, *out, nv, &blk, &FT));
   // ---- everything is checked: stage and queue
-  std::vector<double> FT((size_t)nt * m);  // [F; T], nt x m
-  std::copy(desc->F, desc->F + (size_t)nv * m, FT.begin());
-  std::copy(out->T, out->T + (size_t)ny * m, FT.begin() + (size_t)nv * m);
   MatIn cst, gm, xi, xr, ui;
   MatOut ox, ou, oi;
   NK_TRY(stage_in(ctx, blk.data(), (int64_t)blk.size(), 1, (int64_t)blk.size(), &cst));
@@ -488,44 +518,77 @@ int nk_mpc_out_loop(nk_ctx* ctx, const nk_model* mdl, const nk_poly_plant* plant
   return NK_OK;
 }
 
-int nk_mpc_loop_multi(nk_ctx* ctx, const nk_poly_plant* plant, int32_t steps, const nk_mpc_unit* units, int32_t n_units,
-                      const double* u_opt, int32_t n_uopt, double* out_x, double* out_u, double* out_info, double* scores) {
+}  // extern "C"
+
+// The body of nk_mpc_loop_multi (outs = nullptr, n_scores = NK_MPC_N_SCORES) and of nk_mpc_out_loop_multi (n_scores =
+// NK_MPC_OUT_N_SCORES): the units without rows are prepared and launched as nk_mpc_loop_multi always did (their score row is
+// n_scores wide), the units with rows (outs[u] != nullptr) get the preparation of nk_mpc_out_loop and run in
+// launch_mpc_out_loop_multi.  One staging copy and one synchronisation for both kinds.
+static int mpc_multi_run(const char* who, nk_ctx* ctx, const nk_poly_plant* plant, int32_t steps, const nk_mpc_unit* units,
+                         const nk_mpc_out* const* outs, int32_t n_units, const double* u_opt, int32_t n_uopt, double* out_x,
+                         double* out_u, double* out_info, double* scores, int n_scores) {
   NK_TRY(check_ctx(ctx));
-  NK_REQUIRE(!ctx_recording(ctx), "nk_mpc_loop_multi: not available to the members of a lock-step group");
-  NK_TRY(check_poly_plant("nk_mpc_loop_multi", plant));
-  NK_REQUIRE(units != nullptr && n_units >= 1, "nk_mpc_loop_multi: n_units = %d units at %p: at least one is needed", n_units,
+  NK_REQUIRE(!ctx_recording(ctx), "%s: not available to the members of a lock-step group", who);
+  NK_TRY(check_poly_plant(who, plant));
+  NK_REQUIRE(units != nullptr && n_units >= 1, "%s: n_units = %d units at %p: at least one is needed", who, n_units,
              (const void*)units);
-  NK_REQUIRE(steps >= 1, "nk_mpc_loop_multi: steps = %d must be positive", steps);
-  NK_REQUIRE(out_x || out_u || out_info || scores,
-             "nk_mpc_loop_multi: out_x, out_u, out_info and scores are all null: nothing to return");
-  NK_REQUIRE(n_uopt >= 0 && (n_uopt == 0 || u_opt != nullptr), "nk_mpc_loop_multi: n_uopt = %d rows of a null u_opt", n_uopt);
-  NK_REQUIRE(!is_device_ptr(scores), "nk_mpc_loop_multi: scores must be host memory");
+  NK_REQUIRE(steps >= 1, "%s: steps = %d must be positive", who, steps);
+  NK_REQUIRE(out_x || out_u || out_info || scores, "%s: out_x, out_u, out_info and scores are all null: nothing to return", who);
+  NK_REQUIRE(n_uopt >= 0 && (n_uopt == 0 || u_opt != nullptr), "%s: n_uopt = %d rows of a null u_opt", who, n_uopt);
+  NK_REQUIRE(!is_device_ptr(scores), "%s: scores must be host memory", who);
+  NK_REQUIRE(!is_device_ptr(outs), "%s: outs must be host memory", who);
   const int d = plant->d, p = plant->p;
-  // every unit is checked before anything is queued; its constants (mpc_prepare: the Cholesky inverses of the single call),
-  // its F or K, initial state, reference and seed are laid out on the way
+  // every unit is checked before anything is queued; its constants (mpc_prepare / mpc_out_prepare: the Cholesky inverses of
+  // the single calls), its F or K or [F; T], initial state, reference and seed are laid out on the way
   UnitPack in, folds;
   std::vector<MpcUnitOffsets> off((size_t)n_units);
-  std::vector<std::vector<double>> consts((size_t)n_units), gts((size_t)n_units);
+  std::vector<MpcOutUnitOffsets> ooff((size_t)n_units);
+  std::vector<std::vector<double>> consts((size_t)n_units), gts((size_t)n_units), fts((size_t)n_units);
   std::vector<int> nvs((size_t)n_units), first((size_t)n_units);
-  std::map<std::pair<const void*, const void*>, int> prepared;  // (model, description) -> the first unit that holds them
+  // (model, description, output description) -> the first unit that holds them
+  std::map<std::tuple<const void*, const void*, const void*>, int> prepared;
+  int n_rows = 0;
   for (int u = 0; u < n_units; ++u) {
     const nk_mpc_unit& un = units[u];
-    NK_REQUIRE(un.model && un.desc && un.x0 && un.x_ref, "nk_mpc_loop_multi: unit %d: null argument (model, desc, x0, x_ref)", u);
-    NK_REQUIRE(un.reserved == 0, "nk_mpc_loop_multi: unit %d: reserved = %d must be 0", u, un.reserved);
-    NK_REQUIRE(!is_device_ptr(un.desc), "nk_mpc_loop_multi: unit %d: the description must be host memory", u);
-    NK_TRY(check_mpc_model(ctx, "nk_mpc_loop_multi", u, un.model, *plant, un.desc, &nvs[u]));
-    NK_REQUIRE(un.uopt >= -1 && un.uopt < n_uopt, "nk_mpc_loop_multi: unit %d: uopt = %d, u_opt has %d rows", u, un.uopt,
-               n_uopt);
+    const nk_mpc_out* out = outs ? outs[u] : nullptr;
+    NK_REQUIRE(un.model && un.desc && un.x0 && un.x_ref, "%s: unit %d: null argument (model, desc, x0, x_ref)", who, u);
+    NK_REQUIRE(un.reserved == 0, "%s: unit %d: reserved = %d must be 0", who, u, un.reserved);
+    NK_REQUIRE(!is_device_ptr(un.desc), "%s: unit %d: the description must be host memory", who, u);
+    NK_TRY(check_mpc_model(ctx, who, u, un.model, *plant, un.desc, &nvs[u]));
+    if (out) NK_TRY(check_mpc_out(ctx, who, u, un.model, un.desc, out, nvs[u]));
+    NK_REQUIRE(un.uopt >= -1 && un.uopt < n_uopt, "%s: unit %d: uopt = %d, u_opt has %d rows", who, u, un.uopt, n_uopt);
     NK_REQUIRE(!is_device_ptr(un.x0) && !is_device_ptr(un.x_ref) && !is_device_ptr(un.u_init),
-               "nk_mpc_loop_multi: unit %d: x0, x_ref and u_init must be host memory", u);
-    // units that share model and description share the prepared pieces of the first of them: the same M, H^-1, bounds and W
-    first[u] = prepared.emplace(std::make_pair((const void*)un.model, (const void*)un.desc), u).first->second;
+               "%s: unit %d: x0, x_ref and u_init must be host memory", who, u);
+    n_rows += out != nullptr;
+    // units that share model and descriptions share the prepared pieces of the first of them: the same constants, bounds, W
+    first[u] = prepared.emplace(std::make_tuple((const void*)un.model, (const void*)un.desc, (const void*)out), u).first->second;
     if (first[u] != u) {
-      off[u] = off[first[u]];
-      pack_mpc_unit_state(in, off[u], un.x0, un.x_ref, un.u_init, (size_t)d, (size_t)p);
+      if (out) {
+        ooff[u] = ooff[first[u]];
+        pack_mpc_out_unit_state(in, ooff[u], un.x0, un.x_ref, un.u_init, (size_t)d, (size_t)p);
+      } else {
+        off[u] = off[first[u]];
+        pack_mpc_unit_state(in, off[u], un.x0, un.x_ref, un.u_init, (size_t)d, (size_t)p);
+      }
       continue;
     }
-    NK_TRY(mpc_constants("nk_mpc_loop_multi", u, *un.desc, nvs[u], &consts[u]));
+    if (out) {
+      NK_TRY(mpc_out_constants(who, u, *un.desc, *out, nvs[u], &consts[u], &fts[u]));
+      const nk_model* mdl = un.model;
+      const int m = mdl->m, nt = nvs[u] + out->ny;
+      const bool fold = mdl->kind != NK_MODEL_SPLINE;
+      const double* FT = fts[u].data();
+      if (!fold) {  // a spline model lifts with the raw block: W = [F; T]', formed here as the single call forms it
+        gts[u].resize((size_t)m * nt);
+        for (int l = 0; l < m; ++l)
+          for (int i = 0; i < nt; ++i) gts[u][(size_t)l * nt + i] = FT[(size_t)i * m + l];
+        FT = gts[u].data();
+      }
+      ooff[u] = pack_mpc_out_unit(in, folds, consts[u].data(), FT, un.x0, un.x_ref, un.u_init, (size_t)m, (size_t)nvs[u],
+                                  (size_t)out->ny, (size_t)d, (size_t)p, fold);
+      continue;
+    }
+    NK_TRY(mpc_constants(who, u, *un.desc, nvs[u], &consts[u]));
     const nk_model* mdl = un.model;
     const int m = mdl->m, nv = nvs[u];
     const bool cheap = un.desc->iters == 0, fold = mdl->kind != NK_MODEL_SPLINE;
@@ -542,7 +605,12 @@ int nk_mpc_loop_multi(nk_ctx* ctx, const nk_poly_plant* plant, int32_t steps, co
   double *d_in = nullptr, *d_w = nullptr, *d_sc = nullptr;
   NK_TRY(stage_pack(ctx, in, &d_in));
   if (folds.doubles()) NK_TRY(arena_alloc_t(ctx, folds.doubles(), &d_w));
-  if (scores) NK_TRY(arena_alloc_t(ctx, (size_t)n_units * NK_MPC_N_SCORES, &d_sc));
+  if (scores) {
+    NK_TRY(arena_alloc_t(ctx, (size_t)n_units * n_scores, &d_sc));
+    // a unit without rows writes its first NK_MPC_N_SCORES scores: the two behind them read 0
+    if (n_scores > NK_MPC_N_SCORES && n_rows < n_units)
+      NK_HIP(hipMemsetAsync(d_sc, 0, sizeof(double) * (size_t)n_units * n_scores, ctx->stream));
+  }
   MatIn uo;
   MatOut ox, ou, oi;
   const int64_t sp = (int64_t)steps * p;
@@ -550,13 +618,51 @@ int nk_mpc_loop_multi(nk_ctx* ctx, const nk_poly_plant* plant, int32_t steps, co
   if (out_x) NK_TRY(stage_out(ctx, out_x, d, (int64_t)n_units * (steps + 1), d, &ox));
   if (out_u) NK_TRY(stage_out(ctx, out_u, p, (int64_t)n_units * steps, p, &ou));
   if (out_info) NK_TRY(stage_out(ctx, out_info, 2, (int64_t)n_units * steps, 2, &oi));
-  std::vector<MpcLoopUnit> recs((size_t)n_units);
-  std::vector<int> ktypes((size_t)n_units);
+  // the records of the two kinds, each in unit order: a kind is launched only when it has units
+  std::vector<MpcLoopUnit> recs;
+  std::vector<MpcOutLoopUnit> orecs;
+  std::vector<int> ktypes, oktypes;
+  recs.reserve((size_t)(n_units - n_rows)); ktypes.reserve((size_t)(n_units - n_rows));
+  orecs.reserve((size_t)n_rows); oktypes.reserve((size_t)n_rows);
   for (int u = 0; u < n_units; ++u) {
     const nk_mpc_unit& un = units[u];
+    const nk_mpc_out* out = outs ? outs[u] : nullptr;
     const nk_model* mdl = un.model;
     const int m = mdl->m, nv = nvs[u];
-    MpcLoopUnit& r = recs[u];
+    double* const r_out_x = out_x ? ox.dev + (int64_t)u * (steps + 1) * ox.ld : nullptr;
+    double* const r_out_u = out_u ? ou.dev + (int64_t)u * steps * ou.ld : nullptr;
+    double* const r_out_info = out_info ? oi.dev + (int64_t)u * steps * oi.ld : nullptr;
+    const double* const r_uopt = un.uopt >= 0 ? uo.ptr + (int64_t)un.uopt * uo.ld : nullptr;
+    double* const r_score = scores ? d_sc + (size_t)n_scores * u : nullptr;
+    if (out) {
+      // the fold of nk_mpc_out_loop by the same call on the same operands (the rows of [F; T] have their leading dimension
+      // there), queued back to back with the others
+      const int nt = nv + out->ny;
+      const MpcOutUnitOffsets& o = ooff[u];
+      orecs.emplace_back();
+      MpcOutLoopUnit& r = orecs.back();
+      r.w = d_in + o.FT;
+      if (mdl->kind != NK_MODEL_SPLINE) {
+        double* wf = d_w + o.w;
+        if (first[u] == u)
+          NK_TRY(launch_gemm(ctx, false, true, m, nt, m, 1.0, mdl->Sinv, m, d_in + o.FT, (int64_t)gain_row_reserve((size_t)m),
+                             0.0, wf, nt));
+        r.w = wf;
+      }
+      r.Z = mdl->Z; r.winv = mdl->winv;
+      r.Kb = d_in + o.Kb; r.S0t = d_in + o.S0t; r.bnd = d_in + o.bnd;
+      r.x0 = d_in + o.x0; r.xref = d_in + o.x_ref; r.uinit = un.u_init ? d_in + o.u_init : nullptr;
+      r.out_x = r_out_x; r.ldx = out_x ? ox.ld : 0;
+      r.out_u = r_out_u; r.ldu = out_u ? ou.ld : 0;
+      r.out_info = r_out_info; r.u_opt = r_uopt; r.score = r_score;
+      r.sigma0sq = mdl->sigma0 * mdl->sigma0; r.rho = un.desc->rho; r.tol = un.desc->tol;
+      r.theta = mpc_out_theta(un.desc->rho, out->y_weight);
+      r.m = m; r.nv = nv; r.ny = out->ny; r.iters = un.desc->iters;
+      oktypes.push_back(mdl->ktype);
+      continue;
+    }
+    recs.emplace_back();
+    MpcLoopUnit& r = recs.back();
     // the fold of nk_mpc_loop by the same call on the same operands (the rows of F or K have their leading dimension there);
     // the folds of all units are queued back to back, nothing waits between them
     r.w = d_in + off[u].G;
@@ -570,23 +676,37 @@ int nk_mpc_loop_multi(nk_ctx* ctx, const nk_poly_plant* plant, int32_t steps, co
     r.Z = mdl->Z; r.winv = mdl->winv;
     r.M = d_in + off[u].M; r.Hinv = d_in + off[u].Hinv; r.bnd = d_in + off[u].bnd;
     r.x0 = d_in + off[u].x0; r.xref = d_in + off[u].x_ref; r.uinit = un.u_init ? d_in + off[u].u_init : nullptr;
-    r.out_x = out_x ? ox.dev + (int64_t)u * (steps + 1) * ox.ld : nullptr; r.ldx = out_x ? ox.ld : 0;
-    r.out_u = out_u ? ou.dev + (int64_t)u * steps * ou.ld : nullptr; r.ldu = out_u ? ou.ld : 0;
-    r.out_info = out_info ? oi.dev + (int64_t)u * steps * oi.ld : nullptr;
-    r.u_opt = un.uopt >= 0 ? uo.ptr + (int64_t)un.uopt * uo.ld : nullptr;
-    r.score = scores ? d_sc + (size_t)NK_MPC_N_SCORES * u : nullptr;
+    r.out_x = r_out_x; r.ldx = out_x ? ox.ld : 0;
+    r.out_u = r_out_u; r.ldu = out_u ? ou.ld : 0;
+    r.out_info = r_out_info; r.u_opt = r_uopt; r.score = r_score;
     r.sigma0sq = mdl->sigma0 * mdl->sigma0; r.rho = un.desc->rho; r.tol = un.desc->tol;
     r.m = m; r.nv = nv; r.iters = un.desc->iters; r.reserved = 0;
-    ktypes[u] = mdl->ktype;
+    ktypes.push_back(mdl->ktype);
   }
-  NK_TRY(launch_mpc_loop_multi(ctx, *plant, steps, recs.data(), ktypes.data(), n_units));
+  if (!recs.empty()) NK_TRY(launch_mpc_loop_multi(ctx, *plant, steps, recs.data(), ktypes.data(), (int)recs.size()));
+  if (!orecs.empty()) NK_TRY(launch_mpc_out_loop_multi(ctx, *plant, steps, orecs.data(), oktypes.data(), (int)orecs.size()));
   if (out_x) NK_TRY(finish_out(ctx, ox));
   if (out_u) NK_TRY(finish_out(ctx, ou));
   if (out_info) NK_TRY(finish_out(ctx, oi));
   if (scores)
-    NK_HIP(hipMemcpyAsync(scores, d_sc, sizeof(double) * NK_MPC_N_SCORES * (size_t)n_units, hipMemcpyDeviceToHost, ctx->stream));
-  NK_HIP(hipStreamSynchronize(ctx->stream));  // (the staging block and recs are read by the copies queued above)
+    NK_HIP(hipMemcpyAsync(scores, d_sc, sizeof(double) * (size_t)n_scores * (size_t)n_units, hipMemcpyDeviceToHost, ctx->stream));
+  NK_HIP(hipStreamSynchronize(ctx->stream));  // (the staging block and the records are read by the copies queued above)
   return NK_OK;
+}
+
+extern "C" {
+
+int nk_mpc_loop_multi(nk_ctx* ctx, const nk_poly_plant* plant, int32_t steps, const nk_mpc_unit* units, int32_t n_units,
+                      const double* u_opt, int32_t n_uopt, double* out_x, double* out_u, double* out_info, double* scores) {
+  return mpc_multi_run("nk_mpc_loop_multi", ctx, plant, steps, units, nullptr, n_units, u_opt, n_uopt, out_x, out_u, out_info,
+                       scores, NK_MPC_N_SCORES);
+}
+
+int nk_mpc_out_loop_multi(nk_ctx* ctx, const nk_poly_plant* plant, int32_t steps, const nk_mpc_unit* units,
+                          const nk_mpc_out* const* outs, int32_t n_units, const double* u_opt, int32_t n_uopt, double* out_x,
+                          double* out_u, double* out_info, double* scores) {
+  return mpc_multi_run("nk_mpc_out_loop_multi", ctx, plant, steps, units, outs, n_units, u_opt, n_uopt, out_x, out_u, out_info,
+                       scores, NK_MPC_OUT_N_SCORES);
 }
 
 // every unit of nk_closed_loop_multi is checked before anything is queued

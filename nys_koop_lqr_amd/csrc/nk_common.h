@@ -665,6 +665,31 @@ struct MpcLoopUnit {
 };
 int launch_mpc_loop_multi(nk_ctx* ctx, const nk_poly_plant& plant, int steps, MpcLoopUnit* units, const int* ktypes,
                           int n_units);
+// The multi-model form of the loop with output rows (nk_mpc_out_loop_multi): the fields of launch_mpc_out_loop with the batch
+// strides resolved, one record per unit, every pointer device memory.  Classes of a launch: (kernel family, nt = nv + ny
+// padded to 16 / 32 / 64, waves per workgroup); staged and launched as launch_mpc_loop_multi does.  score: the
+// NK_MPC_OUT_N_SCORES scores (the eight of MpcLoopUnit, then y_viol_max and n_y_viol).
+struct MpcOutLoopUnit {
+  const double* Z;      // m x d landmarks
+  const double* winv;   // d
+  const double* w;      // m x nt folded map of [F; T], dense
+  const double* Kb;     // nt x nt
+  const double* S0t;    // nv x nt: S0 transposed
+  const double* bnd;    // 5 x nt: lo, hi, dlo, dhi (output lanes: ylo, yhi, -inf, inf), ycomp as a double
+  const double* x0;     // d
+  const double* xref;   // d
+  const double* uinit;  // p, or nullptr (zeros)
+  double* out_x;        // (steps + 1) rows of ldx, or nullptr (multi form)
+  double* out_u;        // steps rows of ldu, or nullptr (multi form)
+  double* out_info;     // steps rows of 2, or nullptr
+  const double* u_opt;  // steps x p controls to score against, or nullptr
+  double* score;        // the NK_MPC_OUT_N_SCORES scores, or nullptr
+  int64_t ldx, ldu;
+  double sigma0sq, rho, tol, theta;
+  int m, nv, ny, iters;
+};
+int launch_mpc_out_loop_multi(nk_ctx* ctx, const nk_poly_plant& plant, int steps, MpcOutLoopUnit* units, const int* ktypes,
+                              int n_units);
 
 // ---- lifted closed loops of many models in ONE launch, scored on the device (nk_loop_multi.hip): one 1024-thread workgroup
 // per unit, blockIdx.x = the record.  Every pointer is device memory.  Per step t < steps: u_t = K (phi_ref - phi_t),

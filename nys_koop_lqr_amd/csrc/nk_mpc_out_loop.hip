@@ -12,12 +12,16 @@
 //              is needed once per step: it is stored transposed (nv x nt), lane i reads word j nt + i of global memory.
 //   plant:     as in mpc_loop_body; two LDS-only barriers per step.
 // Every summation order is fixed by (m, nv, ny, p) alone, so a trajectory has the same bits alone or in any batch.
+// The multi-model form (nk_mpc_out_loop_multi) runs the SAME loop body on one record per unit (MpcOutLoopUnit, nk_common.h),
+// selected from a device table by the block index, one launch per class of (kernel family, D, NTP, waves), and scores every
+// unit in its first wave; a unit has the bits of the single call whatever else the launch holds.
 #include "nk_common.h"
 #include "nk_mpc.h"
 #include "nk_mpc_lanes.h"
 #include "nk_poly_lanes.h"
 
 #include <algorithm>
+#include <vector>
 
 namespace nk {
 
@@ -38,20 +42,26 @@ struct MpcOutParams {
   int m, nv, ny, iters, steps;
 };
 
-template <int KTYPE, int D, int NTP>
-__global__ void __launch_bounds__(64 * MPC_MAX_WAVES) mpc_out_loop_kernel(MpcOutParams Q, PolyProgram pl) {
-  extern __shared__ double mpc_out_lds[];
+// The loop of one workgroup on the record of one trajectory.  SCORED = false: nk_mpc_out_loop (out_x and out_u are stored,
+// out_info when it is given, nothing is scored).  SCORED = true: the multi-model form -- every output may be null, and lane 0
+// of the first wave accumulates the ten scores of nk_mpc_out_loop_multi in step order.  The first eight are those of
+// mpc_loop_body, computed as there; the floating-point ones live in the spare words of the broadcast state (mpc_lds_doubles
+// reserves 16 words: x_{t+1} takes 4, the scores 6), the counters are wave-uniform integers.  y_viol_max / n_y_viol: an output lane keeps its ABSOLUTE bounds and its component and
+// forms max(ylo - x_{t+1}[c], x_{t+1}[c] - yhi, 0) from the new state, which every lane of the first wave holds (the plant
+// step works on broadcast values only); one butterfly gives the maximum of the step, a ballot its NaN case.
+template <int KTYPE, int D, int NTP, bool SCORED>
+__device__ __forceinline__ void mpc_out_loop_body(const MpcOutLoopUnit& Q, const PolyProgram& pl, int steps, double* mpc_out_lds) {
   constexpr int P = NK_POLY_MAX_P;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nthreads = blockDim.x, waves = nthreads >> 6;
-  const int m = Q.m, nv = Q.nv, nt = Q.nv + Q.ny, d = pl.d, p = pl.p, steps = Q.steps;
-  const int64_t b = blockIdx.x;
+  const int m = Q.m, nv = Q.nv, nt = Q.nv + Q.ny, d = pl.d, p = pl.p;
   double* Wl = mpc_out_lds;                   // m x nt
   double* part = Wl + (size_t)m * nt;         // waves x 64
   double* xb = part + 64 * waves;             // D words of x_{t+1}
+  double* sc = xb + 4;                        // SCORED: sse_u, ss_opt, J, u_absmax, r_max, y_viol_max (lane 0 of the first wave only)
   for (int i = tid; i < m * nt; i += nthreads) Wl[i] = Q.w[i];
   const PolyLanes tb(pl, lane);
-  const double* x0 = Q.x0 + b * Q.x0_stride;
-  const double* xrp = Q.xref + b * Q.xref_stride;
+  const double* x0 = Q.x0;
+  const double* xrp = Q.xref;
   double wi[D], zs[D], x[D], kref;
   const bool have = tid < m;  // a lane without a landmark: landmark 0, and its dk is never read
 #pragma unroll
@@ -74,6 +84,8 @@ __global__ void __launch_bounds__(64 * MPC_MAX_WAVES) mpc_out_loop_kernel(MpcOut
   const double inf = __builtin_huge_val();
   const double theta = outl ? Q.theta : 0.0;
   double Krow[NTP], lo = -inf, hi = inf, dlo0 = -inf, dhi0 = inf, uprev = 0.0;
+  double ylo_a = -inf, yhi_a = inf;  // SCORED: the absolute bounds of an output lane with a component (yc >= 0)
+  int yc = -1;
 #pragma unroll
   for (int j = 0; j < NTP; ++j) Krow[j] = 0.0;
   if (wave == 0 && row) {
@@ -84,19 +96,43 @@ __global__ void __launch_bounds__(64 * MPC_MAX_WAVES) mpc_out_loop_kernel(MpcOut
     if (outl) {  // absolute state bounds: one rounded subtraction per trajectory
       const int c = (int)Q.bnd[4 * nt + lane];
       if (c >= 0) {
+        if (SCORED) {
+          ylo_a = lo; yhi_a = hi; yc = c;
+        }
         const double xr = xrp[c];
         lo = lo - xr;
         hi = hi - xr;
       }
     }
-    if (lane < p && Q.uinit) uprev = Q.uinit[b * Q.uinit_stride + lane];
+    if (lane < p && Q.uinit) uprev = Q.uinit[lane];
   }
-  const gmut_f64 ox = (gmut_f64)(Q.out_x + b * (steps + 1) * Q.ldx), ou = (gmut_f64)(Q.out_u + b * steps * Q.ldu);
-  const gmut_f64 oi = (gmut_f64)(Q.out_info ? Q.out_info + b * steps * 2 : nullptr);
-  if (tid == 0) {
+  const gmut_f64 ox = (gmut_f64)Q.out_x, ou = (gmut_f64)Q.out_u, oi = (gmut_f64)Q.out_info;
+  const bool st_x = !SCORED || ox != nullptr, st_u = !SCORED || ou != nullptr;
+  if (tid == 0 && st_x) {
 #pragma unroll
     for (int k = 0; k < D; ++k)
       if (k < d) ox[k] = x[k];
+  }
+  const gconst_f64 uopt = SCORED ? (gconst_f64)Q.u_opt : nullptr;
+  double uo[P];
+#pragma unroll
+  for (int j = 0; j < P; ++j) uo[j] = 0.0;
+  long long it_sum = 0;
+  int n_lim = 0, n_it = 0, n_yv = 0;
+  if (SCORED && tid == 0) {
+#pragma clang fp contract(off)
+    double J = 0.0;
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      const double sq = x[k] * x[k];
+      J = k == 0 ? sq : J + sq;
+    }
+    sc[0] = 0.0; sc[1] = 0.0; sc[2] = J; sc[3] = 0.0; sc[4] = 0.0; sc[5] = 0.0;
+    if (uopt) {
+#pragma unroll
+      for (int j = 0; j < P; ++j)
+        if (j < p) uo[j] = uopt[j];
+    }
   }
   const int l0 = 64 * wave, cnt = min(64, m - l0);  // this wave's landmarks
   __syncthreads();  // W is in LDS
@@ -169,23 +205,82 @@ __global__ void __launch_bounds__(64 * MPC_MAX_WAVES) mpc_out_loop_kernel(MpcOut
       // the control: both clips, the rate clip last (lanes < p; the others carry values nobody reads)
       const double uc = clipd(clipd(z1, lo, hi), dlo, dhi);
       const double un = nanstep ? __builtin_nan("") : uc;
+      if (SCORED) {  // as in mpc_loop_body; under lane < p, so the output lanes never count
+        const int its = __builtin_amdgcn_readfirstlane(it);
+        it_sum += its;
+        n_it += its > 0;
+        n_lim += __builtin_popcountll(__ballot(lane < p && (un == lo || un == hi || un == dlo || un == dhi)));
+      }
       uprev = un;
       double u[P], xn[D];
 #pragma unroll
       for (int j = 0; j < P; ++j) u[j] = j < p ? lane_bcast(un, j) : 0.0;
       poly_plant_step<D, P>(tb, x, u, xn);
+      double yv = 0.0;  // SCORED: the largest excursion of x_{t+1} past the absolute bounds of the output rows, NaN when one is
+      if (SCORED) {
+#pragma clang fp contract(off)
+        double xc = xn[0];  // xn is the same in every lane: the plant step works on broadcast values
+#pragma unroll
+        for (int k = 1; k < D; ++k) xc = yc == k ? xn[k] : xc;
+        const double below = ylo_a - xc, above = xc - yhi_a;  // one rounded subtraction each
+        const bool nanrow = yc >= 0 && (below != below || above != above);
+        const double mine = (yc >= 0 && !nanrow) ? fmax(fmax(below, above), 0.0) : 0.0;
+        const bool nany = __ballot(nanrow) != 0;  // uniform over the wave
+        yv = wave_max64_dpp(mine);
+        yv = nany ? __builtin_nan("") : yv;
+        n_yv += yv > 0.0;
+      }
       if (lane == 0) {
 #pragma unroll
         for (int k = 0; k < D; ++k) xb[k] = xn[k];
+        if (st_u) {
 #pragma unroll
-        for (int j = 0; j < P; ++j)
-          if (j < p) ou[(int64_t)t * Q.ldu + j] = u[j];
+          for (int j = 0; j < P; ++j)
+            if (j < p) ou[(int64_t)t * Q.ldu + j] = u[j];
+        }
+        if (st_x) {
 #pragma unroll
-        for (int k = 0; k < D; ++k)
-          if (k < d) ox[(int64_t)(t + 1) * Q.ldx + k] = xn[k];
+          for (int k = 0; k < D; ++k)
+            if (k < d) ox[(int64_t)(t + 1) * Q.ldx + k] = xn[k];
+        }
         if (oi) {
           oi[2 * (int64_t)t] = (double)it;
           oi[2 * (int64_t)t + 1] = r;
+        }
+        if (SCORED) {  // the sums of mpc_loop_body, and the two maxima under the NaN rule of u_absmax
+#pragma clang fp contract(off)
+          double sx = 0.0, su = 0.0, umax = sc[3];
+#pragma unroll
+          for (int k = 0; k < D; ++k) {
+            const double sq = xn[k] * xn[k];
+            sx = k == 0 ? sq : sx + sq;
+          }
+#pragma unroll
+          for (int j = 0; j < P; ++j) {
+            const double sq = u[j] * u[j];
+            su = j == 0 ? sq : su + sq;
+            const double au = fabs(u[j]);
+            umax = (au > umax || au != au) ? au : umax;  // a NaN enters once and stays: no later comparison is true
+          }
+          sc[2] = (sc[2] + sx) + su;
+          sc[3] = umax;
+          const double rmax = sc[4];
+          sc[4] = (r > rmax || r != r) ? r : rmax;
+          const double ymax = sc[5];
+          sc[5] = (yv > ymax || yv != yv) ? yv : ymax;
+          if (uopt) {
+            const int64_t tn = t + 1 < steps ? t + 1 : t;
+            double sse = sc[0], sso = sc[1];
+#pragma unroll
+            for (int j = 0; j < P; ++j) {
+              const double df = u[j] - uo[j];
+              const double dsq = df * df, osq = uo[j] * uo[j];
+              sse = sse + dsq;
+              sso = sso + osq;
+              if (j < p) uo[j] = uopt[tn * p + j];  // next step's values, loaded a step ahead (not on the chain)
+            }
+            sc[0] = sse; sc[1] = sso;
+          }
         }
       }
     }
@@ -193,6 +288,39 @@ __global__ void __launch_bounds__(64 * MPC_MAX_WAVES) mpc_out_loop_kernel(MpcOut
 #pragma unroll
     for (int k = 0; k < D; ++k) x[k] = xb[k];
   }
+  if (SCORED && tid == 0 && Q.score) {
+    double* s = Q.score;
+    s[0] = sc[0]; s[1] = sc[1]; s[2] = sc[2]; s[3] = sc[3];
+    s[4] = (double)it_sum; s[5] = sc[4]; s[6] = (double)n_lim; s[7] = (double)n_it;
+    s[8] = sc[5]; s[9] = (double)n_yv;
+  }
+}
+
+template <int KTYPE, int D, int NTP>
+__global__ void __launch_bounds__(64 * MPC_MAX_WAVES) mpc_out_loop_kernel(MpcOutParams Q, PolyProgram pl) {
+  extern __shared__ double mpc_out_lds[];
+  const int64_t b = blockIdx.x;
+  MpcOutLoopUnit U;
+  U.Z = Q.Z; U.winv = Q.winv; U.w = Q.w; U.Kb = Q.Kb; U.S0t = Q.S0t; U.bnd = Q.bnd;
+  U.x0 = Q.x0 + b * Q.x0_stride;
+  U.xref = Q.xref + b * Q.xref_stride;
+  U.uinit = Q.uinit ? Q.uinit + b * Q.uinit_stride : nullptr;
+  U.out_x = Q.out_x + b * (Q.steps + 1) * Q.ldx; U.ldx = Q.ldx;
+  U.out_u = Q.out_u + b * Q.steps * Q.ldu; U.ldu = Q.ldu;
+  U.out_info = Q.out_info ? Q.out_info + b * Q.steps * 2 : nullptr;
+  U.u_opt = nullptr; U.score = nullptr;
+  U.sigma0sq = Q.sigma0sq; U.rho = Q.rho; U.tol = Q.tol; U.theta = Q.theta;
+  U.m = Q.m; U.nv = Q.nv; U.ny = Q.ny; U.iters = Q.iters;
+  mpc_out_loop_body<KTYPE, D, NTP, false>(U, pl, Q.steps, mpc_out_lds);
+}
+
+// the multi-model form: unit blockIdx.x of `table` (all units of a launch share KTYPE, NTP and the block size)
+template <int KTYPE, int D, int NTP>
+__global__ void __launch_bounds__(64 * MPC_MAX_WAVES)
+    mpc_out_loop_multi_kernel(const MpcOutLoopUnit* __restrict__ table, PolyProgram pl, int steps) {
+  extern __shared__ double mpc_out_lds[];
+  const MpcOutLoopUnit U = table[blockIdx.x];
+  mpc_out_loop_body<KTYPE, D, NTP, true>(U, pl, steps, mpc_out_lds);
 }
 
 // all pointers device memory; w: m x nt dense; Kb: nt x nt; S0t: nv x nt; bnd: 5 x nt
@@ -224,6 +352,60 @@ int launch_mpc_out_loop(nk_ctx* ctx, const nk_model* mdl, const nk_poly_plant& p
     hipLaunchKernelGGL(kern, dim3(batch), dim3(64 * waves), lds, ctx->stream, Q, prog);
   }));
   NK_TRY(rc_lds);
+  NK_HIP(hipGetLastError());
+  return NK_OK;
+}
+
+// The multi-model form, as launch_mpc_loop_multi: the records are sorted (stable) into classes of (kernel family, padded
+// lanes, waves), staged with ONE copy and run with one launch per class.  `units` is reordered in place and must stay alive
+// until the stream has been synchronised.
+int launch_mpc_out_loop_multi(nk_ctx* ctx, const nk_poly_plant& plant, int steps, MpcOutLoopUnit* units, const int* ktypes,
+                              int n_units) {
+  NK_REQUIRE(steps >= 1 && n_units >= 1, "mpc_out_loop_multi: bad sizes");
+  int lds_max = 0;
+  NK_HIP(hipDeviceGetAttribute(&lds_max, hipDeviceAttributeMaxSharedMemoryPerBlock, ctx->device));
+  struct Key { int ktype, ntp, waves, idx; };
+  std::vector<Key> keys((size_t)n_units);
+  for (int u = 0; u < n_units; ++u) {
+    const int m = units[u].m, nv = units[u].nv, ny = units[u].ny, nt = nv + ny;
+    NK_REQUIRE(nv >= 1 && ny >= 1 && nt <= NK_MPC_MAX_NV && m >= 1 && m <= mpc_loop_max_m(nt) && units[u].iters >= 1 &&
+                   sizeof(double) * (size_t)mpc_lds_doubles(m, nt) <= (size_t)lds_max, "mpc_out_loop_multi: unit %d: bad sizes", u);
+    keys[u] = Key{ktypes[u], nt <= 16 ? 16 : nt <= 32 ? 32 : 64, (m + 63) / 64, u};
+  }
+  auto less = [](const Key& a, const Key& b) {
+    if (a.ktype != b.ktype) return a.ktype < b.ktype;
+    if (a.ntp != b.ntp) return a.ntp < b.ntp;
+    return a.waves < b.waves;
+  };
+  std::stable_sort(keys.begin(), keys.end(), less);
+  {
+    std::vector<MpcOutLoopUnit> sorted((size_t)n_units);
+    for (int u = 0; u < n_units; ++u) sorted[u] = units[keys[u].idx];
+    std::copy(sorted.begin(), sorted.end(), units);
+  }
+  const PolyProgram prog = poly_compile(plant);
+  MpcOutLoopUnit* table = nullptr;
+  NK_TRY(arena_alloc_t(ctx, (size_t)n_units, &table));
+  NK_HIP(hipMemcpyAsync(table, units, sizeof(MpcOutLoopUnit) * (size_t)n_units, hipMemcpyHostToDevice, ctx->stream));
+  auto lds_of = [](const MpcOutLoopUnit& r) { return mpc_lds_doubles(r.m, r.nv + r.ny); };
+  for (int b = 0; b < n_units;) {
+    int e = b + 1;
+    long lds_doubles = lds_of(units[b]);
+    for (; e < n_units && !less(keys[b], keys[e]); ++e) lds_doubles = std::max(lds_doubles, lds_of(units[e]));
+    const Key& k = keys[b];
+    const MpcOutLoopUnit* first = table + b;
+    int rc_lds = NK_OK;
+    NK_TRY(mpc_loop_dispatch("mpc_out_loop_multi", k.ktype, plant.d, k.ntp, [&](auto kt, auto dd, auto np) {
+      auto* kern = mpc_out_loop_multi_kernel<decltype(kt)::value, decltype(dd)::value, decltype(np)::value>;
+      static const hipError_t er = dynamic_lds_register(std::min(lds_max, MPC_LDS_DOUBLES * 8), kern);  // once per instantiation
+      rc_lds = dynamic_lds_status(er);
+      if (rc_lds != NK_OK) return;
+      hipLaunchKernelGGL(kern, dim3(e - b), dim3(64 * k.waves), sizeof(double) * (size_t)lds_doubles, ctx->stream, first, prog,
+                         steps);
+    }));
+    NK_TRY(rc_lds);
+    b = e;
+  }
   NK_HIP(hipGetLastError());
   return NK_OK;
 }

@@ -1,5 +1,6 @@
-// Staging layout of the unit-table calls (nk_plant_loop_multi, nk_mpc_loop_multi, nk_closed_loop_multi; nk_api_loops.hip):
-// host only, no HIP include, so that a plain C++17 compiler builds it (tests/unit_pack_main.cpp, tests/mpc_unit_pack_main.cpp).
+// Staging layout of the unit-table calls (nk_plant_loop_multi, nk_mpc_loop_multi, nk_mpc_out_loop_multi, nk_closed_loop_multi;
+// nk_api_loops.hip): host only, no HIP include, so that a plain C++17 compiler builds it (tests/unit_pack_main.cpp,
+// tests/mpc_unit_pack_main.cpp, tests/mpc_out_unit_pack_main.cpp).
 //
 // A call lays the operands of all its units out in ONE block of doubles that a single host-to-device copy moves; the
 // device records then point into the copy.  Every piece starts on a slot boundary (32 doubles = 256 bytes) and what a
@@ -125,6 +126,43 @@ inline MpcUnitOffsets pack_mpc_unit(UnitPack& in, UnitPack& folds, const double*
   }
   pack_mpc_unit_state(in, o, x0, x_ref, u_init, d, p);
   if (fold) o.w = folds.reserve(m * nv + 2);
+  return o;
+}
+
+// A unit of nk_mpc_out_loop_multi with output rows, nt = nv + ny lanes.  `in`: the constants [Kb | S0' | lo hi dlo dhi ycomp]
+// in one piece of nt^2 + nv nt + 5 nt doubles (what mpc_out_prepare and the bounds of nk_mpc_out_loop give) | FT = [F; T] --
+// fold = true: its nt rows of m entries, each with the leading dimension of a gain row (what stage_in gives the nt x m
+// matrix of nk_mpc_out_loop); fold = false (a spline model): the m x nt transpose the caller formed, dense | x0, x_ref,
+// u_init together in one piece of 2 d + p (a null u_init leaves zeros).  `folds` (device only): the folded W of a unit that
+// has one, m nt + 2 doubles.  Units that share model, description and output description may share the prepared pieces of
+// the first of them: pack_mpc_out_unit_state lays out x0, x_ref, u_init alone and the other offsets are copied.
+struct MpcOutUnitOffsets { size_t Kb = 0, S0t = 0, bnd = 0, FT = 0, x0 = 0, x_ref = 0, u_init = 0, w = 0; };
+inline void pack_mpc_out_unit_state(UnitPack& in, MpcOutUnitOffsets& o, const double* x0, const double* x_ref,
+                                    const double* u_init, size_t d, size_t p) {
+  o.x0 = in.reserve(2 * d + p);
+  o.x_ref = o.x0 + d;
+  o.u_init = o.x_ref + d;
+  in.copy(o.x0, x0, d);
+  in.copy(o.x_ref, x_ref, d);
+  in.copy(o.u_init, u_init, p);
+}
+inline MpcOutUnitOffsets pack_mpc_out_unit(UnitPack& in, UnitPack& folds, const double* consts, const double* FT,
+                                           const double* x0, const double* x_ref, const double* u_init, size_t m, size_t nv,
+                                           size_t ny, size_t d, size_t p, bool fold) {
+  MpcOutUnitOffsets o;
+  const size_t nt = nv + ny;
+  o.Kb = in.append(consts, nt * nt + nv * nt + 5 * nt);
+  o.S0t = o.Kb + nt * nt;
+  o.bnd = o.S0t + nv * nt;
+  if (fold) {
+    const size_t ldg = gain_row_reserve(m);
+    o.FT = in.reserve(nt * ldg);
+    for (size_t i = 0; i < nt; ++i) in.copy(o.FT + i * ldg, FT + i * m, m);
+  } else {
+    o.FT = in.append(FT, m * nt);
+  }
+  pack_mpc_out_unit_state(in, o, x0, x_ref, u_init, d, p);
+  if (fold) o.w = folds.reserve(m * nt + 2);
   return o;
 }
 

@@ -145,7 +145,8 @@ def sharded_lqr_sweep(X, Y, n_inputs, params, ms, seeds, plant, x0, x_ref, num_s
     dealt round-robin (shard_units), every rank fits, solves and runs its share on its own GPU (one plant_loop_multi call
     per rank) and ONE all-gather assembles the four scores of every unit.  Trajectories stay on their ranks.  Every rank
     returns the same dict of (len(seeds), len(ms)) tables (harness.lqr_sweep without `timing` and trajectories).
-    controller: lqr_sweep's dict -- every rank runs ONE mpc_loop_multi call and the all-gather carries eight scores."""
+    controller: lqr_sweep's dict -- every rank runs ONE mpc_loop_multi call and the all-gather carries eight scores, or ten
+    (harness.MPC_OUT_SCORE_NAMES) when the dict holds state limits (x_min / x_max)."""
     import torch.distributed as dist
     rank, world = (dist.get_rank(), dist.get_world_size()) if dist.is_initialized() else (0, 1)
     units = harness.lqr_plan(X, Y, n_inputs, params, ms, seeds, estimator, centers)

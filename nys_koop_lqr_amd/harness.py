@@ -718,6 +718,42 @@ def mpc_scores(states, controls, info, controller, u_opt=None, u_init=None):
     return out
 
 
+MPC_OUT_SCORE_NAMES = MPC_SCORE_NAMES + ("y_viol_max", "n_y_viol")
+
+
+def mpc_out_scores(states, controls, info, controller, u_opt=None, u_init=None):
+    """The ten scores of nk_mpc_out_loop_multi on the host, in the device's order of operations: mpc_scores' eight, then
+    y_viol_max = the maximum over the steps t and the output rows r of `controller` with ycomp[r] = c >= 0 of
+    max(ylo_r - x_{t+1}[c], x_{t+1}[c] - yhi_r, 0) -- one rounded subtraction each, on the ABSOLUTE bounds and the realised
+    next state; a step with a NaN difference has a NaN maximum, which enters once and stays (the rule of u_absmax) -- and
+    n_y_viol = the number of steps whose maximum is > 0 (a NaN step does not count).  A controller without output rows (an
+    lqr.MPCController) has 0 and 0.  Returns a dict of floats.  Needs no GPU."""
+    out = mpc_scores(states, controls, info, controller, u_opt, u_init)
+    xs = np.asarray(states, dtype=np.float64)
+    xs = xs.reshape(1, -1) if xs.ndim == 1 else xs
+    steps = xs.shape[1] - 1
+    y_max, n_viol = 0.0, 0
+    if hasattr(controller, "ycomp"):
+        yc = np.asarray(controller.ycomp, dtype=np.int64).reshape(-1)
+        rows = np.flatnonzero(yc >= 0)
+        ylo = np.asarray(controller.ylo, dtype=np.float64).reshape(-1)[rows]
+        yhi = np.asarray(controller.yhi, dtype=np.float64).reshape(-1)[rows]
+        comp = yc[rows]
+        for t in range(steps if rows.size else 0):
+            xc = xs[comp, t + 1]
+            with np.errstate(invalid="ignore"):  # inf - inf: NaN, which the rule below hands on
+                below, above = ylo - xc, xc - yhi
+            if np.any(below != below) or np.any(above != above):
+                v = float("nan")
+            else:
+                v = float(max(np.max(below), np.max(above), 0.0))
+            n_viol += v > 0
+            if v > y_max or v != v:
+                y_max = v
+    out.update(y_viol_max=y_max, n_y_viol=float(n_viol))
+    return out
+
+
 def mpc_loop_multi(regressors, controllers, x0s, x_refs, num_steps, plant, iters=50, tol=0.0, u_inits=None, u_opt=None,
                    uopt_rows=None, return_trajectories=False, return_info=False):
     """One constrained MPC loop around the TRUE plant per (regressor, controller, x0, x_ref) unit, all units in ONE device call
@@ -729,7 +765,13 @@ def mpc_loop_multi(regressors, controllers, x0s, x_refs, num_steps, plant, iters
     uopt_rows[u] = the row of unit u (-1: none; default: row u when k = n_units > 1, else row 0).
     Returns a dict of (n_units,) arrays, the eight MPC_SCORE_NAMES (see include/nyskoop.h) and rmse_control; with
     return_trajectories also states (n_units, num_steps + 1, d) and controls (n_units, num_steps, p), with return_info info
-    (n_units, num_steps, 2).  Without them nothing but the scores leaves the device."""
+    (n_units, num_steps, 2).  Without them nothing but the scores leaves the device.
+    A controller with output rows (lqr.MPCOutputController, solve_mpc(x_min=, x_max=)) runs WITH its rows: when at least one
+    unit has one and iters != 0 the call is nk_mpc_out_loop_multi, such a unit is bit for bit its closed_loop_plant_mpc
+    (nk_mpc_out_loop), the others stay what they were, and the dict holds the ten MPC_OUT_SCORE_NAMES (y_viol_max and n_y_viol
+    are 0 for a unit without rows).  An MPCOutputController at iters = 0 runs as the saturated LQR, as in
+    closed_loop_plant_mpc.  (Before, the rows of such a controller were dropped without a word and the unit ran as the
+    input-only MPC; that no longer happens.)  Without any such unit the call and its eight scores are what they were."""
     from .regressors import _as_polynomial_plant
     regs, ctls = list(regressors), list(controllers)
     n = len(regs)
@@ -751,6 +793,7 @@ def mpc_loop_multi(regressors, controllers, x0s, x_refs, num_steps, plant, iters
     ctx = _lib.get_context()
     handles = [r._ensure_model() for r in regs]
     descs, keep, shared = [], [], {}
+    outs, shared_out = [], {}
     for r, c, it, tl in zip(regs, ctls, its, tols):
         m = r._landmark_shape()[1]
         if c.K.shape != (p, m) or c.F.shape[1] != m:
@@ -760,6 +803,14 @@ def mpc_loop_multi(regressors, controllers, x0s, x_refs, num_steps, plant, iters
             shared[key] = _lib.mpc_desc(c, it, tl)
             keep.append(shared[key][1])
         descs.append(shared[key][0])
+        if hasattr(c, "ycomp") and int(it) != 0:  # an lqr.MPCOutputController (iters = 0: the saturated LQR, no rows)
+            if id(c) not in shared_out:
+                shared_out[id(c)] = _lib.mpc_out(c)
+                keep.append(shared_out[id(c)][1])
+            outs.append(shared_out[id(c)][0])
+        else:
+            outs.append(None)
+    with_rows = any(o is not None for o in outs)
     rows = uopt_rows
     uo = None
     if u_opt is not None:
@@ -777,9 +828,9 @@ def mpc_loop_multi(regressors, controllers, x0s, x_refs, num_steps, plant, iters
     x0b, xrb = _broadcast_states(x0s, n, d, "x0s"), _broadcast_states(x_refs, n, d, "x_refs")
     sc, ox, ou, oi = ctx.mpc_loop_multi(plant.descriptor(), num_steps, handles, descs, x0b, xrb, u_inits=uis, u_opt=uo,
                                         uopt_rows=rows, want_x=return_trajectories, want_u=return_trajectories,
-                                        want_info=return_info)
+                                        want_info=return_info, outs=outs if with_rows else None)
     del keep
-    out = {name: sc[:, i].copy() for i, name in enumerate(MPC_SCORE_NAMES)}
+    out = {name: sc[:, i].copy() for i, name in enumerate(MPC_OUT_SCORE_NAMES if with_rows else MPC_SCORE_NAMES)}
     out["rmse_control"] = rmse_control_percent(out["sse_u"], out["ss_opt"])
     if return_trajectories:
         out["states"], out["controls"] = ox, ou
@@ -837,7 +888,8 @@ def lqr_fit_and_gain(X, Y, n_inputs, params, units, estimator="nystrom", gain_fn
     is kept per unit).  Gains: gain="host": gain_fn(A, B, C) in `workers` host threads while later rounds fit;
     gain="device": ONE nk_model_lqr_gain_batch call after the fits (gain_batch_fn(regs, c) stands in for it).
     controller (the checked dict of lqr_sweep): instead of a gain, reg.solve_mpc(horizon, c=c, limits, rho) is built per
-    unit on the same host threads, and gains[i] is that lqr.MPCController (None when it raises).
+    unit on the same host threads, and gains[i] is that lqr.MPCController (None when it raises); with x_min / x_max (and
+    y_horizon, y_weight) in the dict it is an lqr.MPCOutputController.
     Returns (regs, gains, extras, timing): a unit whose fit failed has regs[i] None, one without a gain gains[i] None;
     timing = dict(fit_s, gain_wait_s, gain_cpu_s)."""
     import time
@@ -858,8 +910,12 @@ def lqr_fit_and_gain(X, Y, n_inputs, params, units, estimator="nystrom", gain_fn
         t0 = time.perf_counter()
         try:
             if controller is not None:
+                rows = {}  # the state limits travel only when the dict holds one: without them the call is what it was
+                if controller.get("x_min") is not None or controller.get("x_max") is not None:
+                    rows = dict(x_min=controller["x_min"], x_max=controller["x_max"], y_horizon=controller.get("y_horizon"),
+                                y_weight=controller.get("y_weight", np.inf))
                 return reg.solve_mpc(controller["horizon"], c=c, u_min=controller["u_min"], u_max=controller["u_max"],
-                                     du_min=controller["du_min"], du_max=controller["du_max"], rho=controller["rho"])
+                                     du_min=controller["du_min"], du_max=controller["du_max"], rho=controller["rho"], **rows)
             return np.asarray(gain_fn(np.asarray(reg.A), np.asarray(reg.B), np.asarray(reg.C)), dtype=np.float64)
         finally:
             gain_s[i] = time.perf_counter() - t0
@@ -906,15 +962,18 @@ def lqr_fit_and_gain(X, Y, n_inputs, params, units, estimator="nystrom", gain_fn
     return regs, gains, extras, dict(fit_s=t1 - t0, gain_wait_s=t2 - t1, gain_cpu_s=float(sum(gain_s)))
 
 
-CONTROLLER_KEYS = ("horizon", "u_min", "u_max", "du_min", "du_max", "iters", "tol", "rho")
+CONTROLLER_KEYS = ("horizon", "u_min", "u_max", "du_min", "du_max", "iters", "tol", "rho", "x_min", "x_max", "y_horizon",
+                   "y_weight")
 
 
 def lqr_controller_spec(controller):
     """The `controller` dict of lqr_sweep with its defaults filled in (limits None = absent, iters = 50, tol = 0.0, rho None
-    = lqr.mpc_default_rho); `horizon` is required and an unknown key is a ValueError.  None stays None."""
+    = lqr.mpc_default_rho; the state limits x_min, x_max None = absent, y_horizon None = the horizon, y_weight = inf = hard
+    rows); `horizon` is required and an unknown key is a ValueError.  None stays None."""
     if controller is None:
         return None
-    spec = dict(u_min=None, u_max=None, du_min=None, du_max=None, iters=50, tol=0.0, rho=None)
+    spec = dict(u_min=None, u_max=None, du_min=None, du_max=None, iters=50, tol=0.0, rho=None, x_min=None, x_max=None,
+                y_horizon=None, y_weight=np.inf)
     unknown = sorted(set(controller) - set(CONTROLLER_KEYS))
     if unknown:
         raise ValueError(f"controller has unknown keys {unknown}; known: {CONTROLLER_KEYS}")
@@ -922,6 +981,16 @@ def lqr_controller_spec(controller):
         raise ValueError("controller needs a 'horizon'")
     spec.update(controller)
     return spec
+
+
+def lqr_controller_has_rows(spec):
+    """Whether the units of a checked controller dict run with output rows and carry the ten MPC_OUT_SCORE_NAMES: x_min or
+    x_max has a finite entry (what makes solve_mpc return an lqr.MPCOutputController) and iters != 0 (the saturated LQR has
+    no rows)."""
+    if spec is None or int(spec["iters"]) == 0:
+        return False
+    given = [np.asarray(spec[k], dtype=np.float64) for k in ("x_min", "x_max") if spec[k] is not None]
+    return any(np.any(np.isfinite(a)) for a in given)
 
 
 def lqr_run_units(X, Y, n_inputs, params, units, plant, x0, x_ref, num_steps, estimator="nystrom", gain_fn=None, c=1.0,
@@ -936,12 +1005,14 @@ def lqr_run_units(X, Y, n_inputs, params, units, plant, x0, x_ref, num_steps, es
     gain_batch_fn(regs, c) -> (Ks, status, iterations) stands in for the device call.
     controller (lqr_sweep's dict): the units run the constrained MPC instead -- reg.solve_mpc per fitted unit where the
     gains are built, ONE mpc_loop_multi call (loop_fn stands in for it, with its signature), eight scores per unit
-    (MPC_SCORE_NAMES); a unit whose controller raises scores NaN and is not run.  gain="device" with it is a ValueError."""
+    (MPC_SCORE_NAMES); a unit whose controller raises scores NaN and is not run.  gain="device" with it is a ValueError.
+    With a state limit in the dict (lqr_controller_has_rows) the units run with their output rows and carry the ten
+    MPC_OUT_SCORE_NAMES."""
     import time
     controller = lqr_controller_spec(controller)
     if controller is not None and gain == "device":
         raise ValueError("controller needs gain='host': the terminal cost of the MPC is the host Riccati solution")
-    names = SCORE_NAMES if controller is None else MPC_SCORE_NAMES
+    names = SCORE_NAMES if controller is None else MPC_OUT_SCORE_NAMES if lqr_controller_has_rows(controller) else MPC_SCORE_NAMES
     loop_fn = loop_fn or (plant_loop_multi if controller is None else mpc_loop_multi)
     n = len(units)
     regs, gains, _, tm = lqr_fit_and_gain(X, Y, n_inputs, params, units, estimator, gain_fn, c, batch, workers, fit_fn, gain,
@@ -1004,7 +1075,14 @@ def lqr_sweep(X, Y, n_inputs, params, ms, seeds, plant, x0, x_ref, num_steps, es
     sweep under actuator limits: every fitted unit gets reg.solve_mpc(horizon, c=c, limits) where the gains are built (host
     threads, while later rounds fit), all surviving units run in ONE mpc_loop_multi call, the tables gain iters_sum, r_max,
     n_at_limit and n_iterated (MPC_SCORE_NAMES), the plant may have several inputs (controls: (.., num_steps, p)) and must be
-    one closed_loop_plant_mpc accepts.  gain_fn is not used; gain="device" is a ValueError."""
+    one closed_loop_plant_mpc accepts.  gain_fn is not used; gain="device" is a ValueError.
+    The dict may also hold x_min, x_max (scalars or d entries), y_horizon and y_weight, passed to reg.solve_mpc: limits on the
+    PREDICTED states, hard (y_weight = inf, the default) or soft.  The units then run with their output rows in ONE
+    nk_mpc_out_loop_multi call and the tables gain y_viol_max (the largest excursion of the plant past its state limits) and
+    n_y_viol (the steps with one): the ten MPC_OUT_SCORE_NAMES.  rho stays the user's to set: the rows of a sampled plant are
+    small beside the identity rows of the inputs, so the output rows want a rho far above the default (300 x the default
+    reached a hard velocity limit within 2 % in 100 iterations on the Duffing models; with the default the controls did not
+    move)."""
     _check_estimator(estimator)
     units = lqr_plan(X, Y, n_inputs, params, ms, seeds, estimator, centers)
     scores, states, controls, timing = lqr_run_units(X, Y, n_inputs, params, units, plant, x0, x_ref, num_steps, estimator,
@@ -1014,8 +1092,10 @@ def lqr_sweep(X, Y, n_inputs, params, ms, seeds, plant, x0, x_ref, num_steps, es
 
 
 def lqr_result(units, scores, states, controls, n_seeds, n_ms, timing=None):
-    """The dict lqr_sweep returns, from per-unit values in plan order (four score columns, or the eight of the MPC sweep)."""
-    names = MPC_SCORE_NAMES if np.shape(scores)[1] == len(MPC_SCORE_NAMES) else SCORE_NAMES
+    """The dict lqr_sweep returns, from per-unit values in plan order (four score columns, the eight of the MPC sweep, or the
+    ten of the MPC sweep under state limits)."""
+    names = {len(MPC_SCORE_NAMES): MPC_SCORE_NAMES, len(MPC_OUT_SCORE_NAMES): MPC_OUT_SCORE_NAMES}.get(np.shape(scores)[1],
+                                                                                                      SCORE_NAMES)
     out = {name: lqr_table(units, scores[:, k], n_seeds, n_ms) for k, name in enumerate(names)}
     out["rmse_control"] = rmse_control_percent(out["sse_u"], out["ss_opt"])
     out["units"], out["timing"] = units, timing
