@@ -229,7 +229,11 @@ int nk_group_stats(nk_ctx* member, uint64_t* out4);
  *   out[2] fits whose regularised system(s) took the rank-truncating branch (regressors.py:155,165: lstsq / gelsd);
  *   out[3] fits that repeated the matrix square root with the factorisation-free iteration;
  *   out[4] fits whose regularised solves were refined with doubled-precision residuals (nk_set_refine).
- * n = number of entries the caller provides (<= 5 are written). */
+ * Three more slots say which implementation of the augmented blocked Cholesky ran (diagnostics, not slow paths as such):
+ *   out[5] tile-dataflow Cholesky launches that gave up waiting (the caller re-ran the launch-per-step chain);
+ *   out[6] tile-dataflow Cholesky launches issued (every call whose systems all have m >= 256, on an ordinary context);
+ *   out[7] launch-per-step chains that ran with look-ahead (NYSKOOP_CHOL_LOOKAHEAD=1, >= 4 blocks, main stream, no group).
+ * n = number of entries the caller provides (<= 8 are written). */
 int nk_runtime_counters(uint64_t* out, int32_t n);
 /* Releases everything the library still holds on every device -- live contexts (their streams, events and workspaces),
  * live models, the model-buffer pool and page-locked host blocks -- after waiting for pending work.  Handles that were

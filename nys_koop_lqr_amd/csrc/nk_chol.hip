@@ -249,6 +249,7 @@ int cholesky_aug_pair_async(nk_ctx* ctx, const CholSys* sys, int nsys, hipEvent_
   bool rest_pending = false;
   hipEvent_t last_rest = nullptr;
   if (lookahead) {  // the look-ahead stream starts behind whatever the chain's stream has queued so far
+    count_event(CNT_CHOL_LOOKAHEAD);
     NK_HIP(hipEventRecord(la_evt[1], s_chain));
     NK_HIP(hipStreamWaitEvent(s_rest, la_evt[1], 0));
   }
@@ -261,7 +262,6 @@ int cholesky_aug_pair_async(nk_ctx* ctx, const CholSys* sys, int nsys, hipEvent_
     CholStep st;
     chol_step_operands(sys, nsys, jb, extra, &st);
     NK_TRY(chol_step_launches(ctx, sys, nsys, jb, st, !lookahead, fuse && jb + 1 < nblk, &diag_done));
-    // test_cholesky_lookahead_gives_the_same_bits (m = 700) no longer reaches this branch: the dataflow launch takes every m >= 256
     if (lookahead) {
       // the trailing update split: the next block column (all rows) | everything to the right of it
       GemmCall next[2], rest[2];

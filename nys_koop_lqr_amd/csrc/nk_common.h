@@ -310,9 +310,9 @@ int group_leave(nk_ctx* c);
 void group_stats(nk_ctx* c, uint64_t out[4]);
 // slow-path counters (nk_runtime_counters)
 // CNT_CHOL_FLOW_GIVEUP: dataflow Cholesky launches that gave up waiting (re-run on the launch-per-step chain);
-// CNT_CHOL_FLOW: dataflow Cholesky launches issued
+// CNT_CHOL_FLOW: dataflow Cholesky launches issued; CNT_CHOL_LOOKAHEAD: launch-per-step chains that ran with look-ahead
 enum { CNT_CHAIN_GIVEUP = 0, CNT_JACOBI_GIVEUP = 1, CNT_RANK_TRUNCATED = 2, CNT_SQRT_RETRY = 3, CNT_REFINED = 4,
-       CNT_CHOL_FLOW_GIVEUP = 5, CNT_CHOL_FLOW = 6, CNT_N = 7 };
+       CNT_CHOL_FLOW_GIVEUP = 5, CNT_CHOL_FLOW = 6, CNT_CHOL_LOOKAHEAD = 7, CNT_N = 8 };
 void count_event(int which);
 uint64_t read_counter(int which);
 hipError_t real_stream_sync(hipStream_t s);

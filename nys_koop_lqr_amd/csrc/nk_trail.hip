@@ -48,6 +48,9 @@ __device__ __forceinline__ void chol_trail_kernel_body(const TrailBatch& tb) {
   const int wm = wave >> 1, wn = wave & 1;
   const int l15 = lane & 15, l4 = lane >> 4;
   const int m0 = tm * 128 + wm * 64, n0 = tn * 128 + wn * 64;
+  // In a 128-tile on the diagonal the 64 x 64 quarter of wave (0, 1) lies strictly above the block diagonal of the factor:
+  // nothing reads it, and nk_chol_aug promises that such tiles return the input (the dataflow launch never touches them)
+  if (tm == tn && wm == 0 && wn == 1) return;
 
   d4 acc[4][4];
 #pragma unroll

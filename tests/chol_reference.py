@@ -38,8 +38,8 @@ def graded_spd(m, seed):
     return (P + P.T) / 2
 
 
-def rbf_spd(m, seed):
-    """RBF kernel matrix of clustered points plus 1e-6 I: what the fits factor (K_mm + jitter)."""
+def rbf_kernel(m, seed):
+    """RBF kernel matrix of clustered points, without jitter."""
     rng = np.random.default_rng(seed)
     nc, d = 8, 6
     centres = rng.standard_normal((nc, d)) * 2.0
@@ -47,8 +47,12 @@ def rbf_spd(m, seed):
     sq = (pts * pts).sum(1)
     r2 = np.maximum(sq[:, None] + sq[None, :] - 2.0 * pts @ pts.T, 0.0)
     K = np.exp(-r2 / (2.0 * 1.5 ** 2))
-    P = (K + K.T) / 2 + 1e-6 * np.eye(m)
-    return P
+    return (K + K.T) / 2
+
+
+def rbf_spd(m, seed):
+    """RBF kernel matrix of clustered points plus 1e-6 I: what the fits factor (K_mm + jitter)."""
+    return rbf_kernel(m, seed) + 1e-6 * np.eye(m)
 
 
 FAMILIES = {"random": random_spd, "graded": graded_spd, "rbf": rbf_spd}
@@ -75,6 +79,15 @@ def indefinite(m, j, seed):
     P = np.array(matrix("random", m, seed))
     L = np.linalg.cholesky(P)
     P[j, j] -= 2.0 * L[j, j] ** 2
+    return P
+
+
+def singular_psd(m=130, seed=130, src=7, dst=100):
+    """An exactly singular PSD matrix: the RBF kernel matrix without its jitter, row and column `src` copied onto row and column
+    `dst` (a duplicated landmark): e_src - e_dst spans its null space."""
+    P = np.array(rbf_kernel(m, seed))
+    P[dst, :] = P[src, :]
+    P[:, dst] = P[:, src]
     return P
 
 
@@ -154,6 +167,16 @@ def cap(m):
     return m * EPS
 
 
+def caps(m):
+    """(cap of the factor residual, cap of the solve backward error).  From m = 5 both are cap(m).  Below that m eps drops the
+    lower-order terms of the theorems it cites (at m = 1 LAPACK itself sits at 0.90 of it), so the constants themselves stand:
+    ||L L^T - P|| <= gamma_(m+1) || |L| |L^T| || (Higham, 2nd ed., Thm 10.3) and (P + dP) x = b with |dP| <= gamma_(3m+1) |L| |L^T|
+    (Thm 10.4), normwise and to first order: (m + 1) eps and (3 m + 1) eps."""
+    if m >= 5:
+        return cap(m), cap(m)
+    return (m + 1) * EPS, (3 * m + 1) * EPS
+
+
 def lapack_bar(values):
     """2 x the worst of LAPACK's own values over the permutations, floored at one rounding (LAPACK's solve backward error is
     about 0.1 eps, below one rounding of X: a ratio to that means nothing).  The factor 2 is the project's existing bar
@@ -162,12 +185,63 @@ def lapack_bar(values):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# the cases below m = 256 (tests/test_gpu_chol_small.py; test_chol_reference_host.py holds LAPACK to the same bars first)
+# ---------------------------------------------------------------------------------------------------------------------
+CHOL_FIX_KAPPA = 8 * NB
+
+# (m, extra, family, ld), seed = m: the smallest shapes at which each piece of the launch-per-step chain changes behaviour
+SMALL_SINGLE = [
+    (1, 1, "rbf", 1),            # order-1 block
+    (2, 3, "graded", 2),
+    (5, 1, "random", 8),         # ld > m
+    (17, 63, "rbf", 17),
+    (40, 7, "graded", 40),       # one partial block, kappa 2e5
+    (63, 64, "random", 63),
+    (64, 1, "rbf", 64),          # exactly one block
+    (64, 65, "graded", 72),
+    (65, 64, "random", 65),      # second block of order 1: fused trailing + next diagonal with nb = 1
+    (66, 2, "rbf", 66),
+    (127, 130, "graded", 127),
+    (128, 63, "rbf", 128),       # trailing matrix exactly one 128-tile wide after step 0
+    (129, 1, "random", 136),
+    (191, 65, "rbf", 191),
+    (192, 192, "graded", 192),
+    (193, 3, "random", 193),     # four blocks, the last a single row
+    (200, 203, "rbf", 200),      # extra = m + 3
+    (255, 64, "graded", 264),    # last size under the threshold of the dataflow launch
+]
+# (m, p, d, fam0, fam1): system 0 is (m + p) with m extra rows (seed 1000 + m + p), system 1 is m with d extra rows (seed 2000 + m)
+SMALL_PAIRS = [
+    (64, 1, 2, "rbf", "random"),       # 65 beside 64: system 1 has no step 1 (order 0, empty calls)
+    (62, 3, 1, "graded", "rbf"),       # 65 beside 62
+    (128, 6, 40, "random", "graded"),  # three blocks beside two
+    (200, 1, 2, "rbf", "rbf"),         # the Duffing sweeps' shape
+    (250, 6, 7, "random", "rbf"),      # 256 beside 250: the rule is "every m_q >= 256", so this pair takes the chain
+]
+# (m, nrhs, family), seed = m: nk_solve_spd (plain factor + forward and backward substitution)
+SOLVE_SPD = [
+    (1, 1, "rbf"),
+    (5, 3, "random"),
+    (64, 5, "graded"),
+    (65, 64, "rbf"),
+    (129, 1, "graded"),
+    (200, 130, "random"),
+    (321, 65, "rbf"),
+]
+
+
+def small_pair_systems(m, p, d, fam0, fam1):
+    """[(family, order, seed, extra), ...] of a pair of SMALL_PAIRS."""
+    return [(fam0, m + p, 1000 + m + p, m), (fam1, m, 2000 + m, d)]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # the device call
 # ---------------------------------------------------------------------------------------------------------------------
 def counters():
     from nys_koop_lqr_amd import _lib
-    v = (C.c_uint64 * 7)()
-    _lib.check(_lib.load_library().nk_runtime_counters(v, 7))
+    v = (C.c_uint64 * 8)()
+    _lib.check(_lib.load_library().nk_runtime_counters(v, 8))
     return [int(x) for x in v]
 
 

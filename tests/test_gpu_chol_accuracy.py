@@ -15,7 +15,11 @@ permutations is at most 0.08 eps):
                                                                       sits at 0.55 .. 0.76, is the one above 1: GPU 0.83 .. 0.94,
                                                                       under the bar's 1 eps floor x 2)
   solve backward error   GPU 0.07 .. 0.14     LAPACK 0.06 .. 0.14    (all far below the 1 eps floor of the bar)
-No case lies between the bar and the cap."""
+No case lies between the bar and the cap.
+
+This file starts where the dataflow launch starts (m >= 256) and runs the chain there only under NYSKOOP_CHOL_FLOW=0.  Where
+the chain runs in production -- every system below 256, every call of a lock-step member at any size -- and the plain factor
+with its two-sided substitution (nk_solve_spd) are held to the same two bars in tests/test_gpu_chol_small.py."""
 import os
 
 import numpy as np
@@ -25,7 +29,7 @@ import chol_reference as cr
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not cr.HAVE_LONGDOUBLE, reason=cr.LONGDOUBLE_SKIP)]
 
-CHOL_FIX_KAPPA = 8 * 64
+CHOL_FIX_KAPPA = cr.CHOL_FIX_KAPPA
 
 # (m, extra, family, ld).  Every m of {256, 257, 319, 320, 321, 384, 705, 1025} (the first size that takes the launch, one row
 # into a new tile, an exact tile multiple, ...) and every extra of {1, 63, 64, 65, m, m + 3} appears; ld > m three times.
@@ -88,23 +92,30 @@ def _both_paths(ctx, monkeypatch, systems):
         assert f1 == f0 and r1 == r0
         # (the strict upper triangle inside a diagonal tile is scratch, see include/nyskoop.h: the factor is the lower triangle)
         assert np.array_equal(np.tril(L1), np.tril(L0)) and np.array_equal(X1, X0)
+    for (P, _, _), (L0, _, _, _) in zip(systems, chain):  # (_check holds the dataflow launch's L to the same)
+        assert cr.upper_tiles_untouched(L0, P)
     return flow
 
 
 def _check(tag, m, extra, family, seed, P, R, L, X, failed):
+    """Both bars on one factored and solved system.  cr.caps(m) is (cap(m), cap(m)) from m = 5 up, and the bar relative to
+    LAPACK applies from there (tests/test_gpu_chol_small.py goes below)."""
     assert failed == 0, failed
     assert np.isfinite(np.tril(L)).all() and np.isfinite(X).all()
     # the contract of the returned L: tiles above the block diagonal are never written
     assert cr.upper_tiles_untouched(L, P)
     fr, be = cr.factor_residual(L, P), cr.solve_backward_error(X, P, R)
     lfr, lbe = cr.lapack_reference(family, m, seed, extra)
+    cap_f, cap_s = cr.caps(m)
     e = cr.EPS
     _log(f"{tag} m={m} extra={extra} family={family} factor: gpu {fr / e:.3f} lapack {lfr[0] / e:.3f} "
          f"(perms {min(lfr) / e:.3f}..{max(lfr) / e:.3f}) bar {cr.lapack_bar(lfr) / e:.3f} | solve: gpu {be / e:.3f} "
-         f"lapack {lbe[0] / e:.3f} (perms {min(lbe) / e:.3f}..{max(lbe) / e:.3f}) bar {cr.lapack_bar(lbe) / e:.3f} | cap {m}")
-    assert fr <= cr.cap(m) and be <= cr.cap(m), (fr / e, be / e, m)
-    assert fr <= cr.lapack_bar(lfr), (fr / e, [v / e for v in lfr])
-    assert be <= cr.lapack_bar(lbe), (be / e, [v / e for v in lbe])
+         f"lapack {lbe[0] / e:.3f} (perms {min(lbe) / e:.3f}..{max(lbe) / e:.3f}) bar {cr.lapack_bar(lbe) / e:.3f} | cap "
+         + (f"{m}" if m >= 5 else f"{cap_f / e:.0f} factor, {cap_s / e:.0f} solve (m < 5: no bar relative to LAPACK)"))
+    assert fr <= cap_f and be <= cap_s, (fr / e, be / e, m)
+    if m >= 5:
+        assert fr <= cr.lapack_bar(lfr), (fr / e, [v / e for v in lfr])
+        assert be <= cr.lapack_bar(lbe), (be / e, [v / e for v in lbe])
 
 
 @pytest.mark.parametrize("m,extra,family,ld", SINGLE)

@@ -231,11 +231,21 @@ def test_fp32_engine_fit_with_assembly_k_loops_gives_the_bits_of_the_compiled_lo
 def test_cholesky_lookahead_gives_the_same_bits(nk, monkeypatch):
     """The blocked Cholesky with look-ahead (next block column on the chain's stream, the rest of the trailing update on a
     second stream) performs exactly the arithmetic of the sequential order: a fit with it computes the same bits as a fit
-    without (NYSKOOP_CHOL_LOOKAHEAD=0 is read once per process, so the two fits run in child processes)."""
+    without (NYSKOOP_CHOL_LOOKAHEAD=0 is read once per process, so the two fits run in child processes).  The look-ahead is a
+    schedule of the launch-per-step chain, so both children keep the dataflow launch off (NYSKOOP_CHOL_FLOW=0: the m = 700
+    fit's factorisations take the chain, 11 blocks), and each also factors and solves one four-block system -- the smallest
+    chain the branch engages on -- through nk_chol_aug.  Slot 7 of nk_runtime_counters proves which schedule ran."""
     code = r'''
-import numpy as np, sys, hashlib
+import numpy as np, sys, hashlib, ctypes as C
+sys.path.insert(0, %r)
 sys.path.insert(0, %r)
 import nys_koop_lqr_amd as nk
+from nys_koop_lqr_amd import _lib
+import chol_reference as cr
+def slots():
+    v = (C.c_uint64 * 8)()
+    _lib.check(_lib.load_library().nk_runtime_counters(v, 8))
+    return [int(x) for x in v]
 rng = np.random.default_rng(8)
 n, d, p, m = 3000, 40, 3, 700
 S = rng.standard_normal((n, d)); U = rng.standard_normal((n, p))
@@ -244,16 +254,28 @@ X = np.hstack([S, U])
 reg = nk.KoopmanNystromRegressor(p, kernel=nk.ThreeDimensionalKernel(6., 6., 6., d), gamma=1e-5, m=m)
 reg.nystrom_centers_output = np.ascontiguousarray(Y[:m].T)
 reg.fit(X, Y)
-h = hashlib.sha256(np.ascontiguousarray(reg.A).tobytes() + np.ascontiguousarray(reg.B).tobytes() + np.ascontiguousarray(reg.C).tobytes()).hexdigest()
-print("HASH", h)
-''' % ROOT
-    hashes = []
+h = hashlib.sha256(np.ascontiguousarray(reg.A).tobytes() + np.ascontiguousarray(reg.B).tobytes() + np.ascontiguousarray(reg.C).tobytes())
+after_fit = slots()
+(L, Xs, failed, ratio), = cr.chol_aug(nk.get_context(), [(cr.matrix("rbf", 200, 200), cr.rhs(203, 200, 200), 200)])
+assert failed == 0, failed
+h.update(np.ascontiguousarray(np.tril(L)).tobytes() + np.ascontiguousarray(Xs).tobytes())
+c = slots()
+print("HASH", h.hexdigest())
+print("COUNTERS lookahead_after_fit", after_fit[7], "lookahead", c[7], "flow", c[6], "flow_giveup", c[5])
+''' % (ROOT, os.path.join(ROOT, "tests"))
+    hashes, counts = [], []
     for la in ("1", "0"):  # (off by default: nk_chol.hip)
-        env = dict(os.environ, NYSKOOP_CHOL_LOOKAHEAD=la)
+        env = dict(os.environ, NYSKOOP_CHOL_LOOKAHEAD=la, NYSKOOP_CHOL_FLOW="0")
         out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, env=env)
         assert out.returncode == 0, (out.stdout[-300:], out.stderr[-1500:])
         hashes.append([l for l in out.stdout.splitlines() if l.startswith("HASH")][0])
-    assert hashes[0] == hashes[1]
+        line = [l for l in out.stdout.splitlines() if l.startswith("COUNTERS")][0]
+        print(f"NYSKOOP_CHOL_LOOKAHEAD={la}: {line}")
+        words = line.split()
+        counts.append({k: int(v) for k, v in zip(words[1::2], words[2::2])})
+    assert counts[0]["lookahead"] > 0 and counts[1]["lookahead"] == 0, counts  # two different schedules ...
+    assert all(c["flow"] == 0 and c["flow_giveup"] == 0 for c in counts), counts  # ... of the chain, in both children
+    assert hashes[0] == hashes[1]                                              # ... and the same bits
 
 
 def test_sample_sharded_fit_through_rccl_with_one_rank():
