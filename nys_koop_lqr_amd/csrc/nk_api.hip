@@ -421,6 +421,14 @@ int nk_create(int device, nk_ctx** out) {
     return NK_ERR_NO_DEVICE;
   }
   NK_REQUIRE(device >= 0 && device < n, "nk_create: device %d out of range (0..%d)", device, n - 1);
+  // NYSKOOP_STRICT_SPD = 0 / 1 / 2, the modes of nk_set_strict_spd (unset or empty: 0); anything else is refused, as there
+  int strict_env = 0;
+  if (const char* st = getenv("NYSKOOP_STRICT_SPD"); st && st[0]) {
+    char* end = nullptr;
+    const long v = strtol(st, &end, 10);
+    NK_REQUIRE(end != st && *end == '\0' && v >= 0 && v <= 2, "nk_create: NYSKOOP_STRICT_SPD=%s is not 0, 1 or 2", st);
+    strict_env = (int)v;
+  }
   NK_HIP(hipSetDevice(device));
   hipDeviceProp_t prop;
   NK_HIP(hipGetDeviceProperties(&prop, device));
@@ -465,8 +473,7 @@ int nk_create(int device, nk_ctx** out) {
   for (int i = 0; i < 8; ++i) NK_HIP(hipEventCreateWithFlags(&ctx->ev_up[i], hipEventDisableTiming));
   const char* km = getenv("NYSKOOP_KMAT");
   ctx->kmat_mode = (km && strcmp(km, "direct") == 0) ? 1 : 0;
-  const char* st = getenv("NYSKOOP_STRICT_SPD");
-  ctx->strict_spd = (st && atoi(st) != 0) ? 1 : 0;
+  ctx->strict_spd = strict_env;
   if (const char* rp = getenv("NYSKOOP_REFINE_PIVOT")) ctx->refine_pivot = atof(rp);
   if (const char* rs = getenv("NYSKOOP_REFINE_STEPS")) ctx->refine_steps = std::max(0, atoi(rs));
   {
