@@ -344,7 +344,8 @@ int nk_model_destroy(nk_model* model);
  *   B = M_ls[:m, m:], C = M_ls[m:, :m], W = C [A B].  pinv follows scipy.linalg.pinv (singular values <= (m+p) eps
  *   sigma_max dropped); systems whose Cholesky pivots show they cannot come near that cut-off are solved by the blocked
  *   Cholesky instead.  stats->rank_inner = singular values kept (m+p on the Cholesky path), rank_inner_rec = 0,
- *   pivot_ratio_inner = smallest / largest Cholesky pivot (0 when it was not used).  fp64 only: the compute dtype of
+ *   pivot_ratio_inner = smallest / largest Cholesky pivot whenever the factorisation succeeded, also when the ratio then
+ *   sent the system to the pseudo-inverse (0 when it failed or, with strict_spd = 2, was not run).  fp64 only: the compute dtype of
  *   nk_set_compute_dtype is ignored (the fit runs in fp64).  strict_spd (nk_set_strict_spd): 1 = a non-positive pivot
  *   is NK_ERR_NOT_SPD, 2 = always the pseudo-inverse.  Members of a lock-step group may call it (same bits as on an
  *   ordinary context; stats may be NULL, the ms_* fields are 0 there; nk_spline_cv_grid is the sweep).  The model is a spline

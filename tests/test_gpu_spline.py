@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import relf
+from spline_fit_reference import tps_bar_direct, tps_bar_gram
 
 pytestmark = pytest.mark.gpu
 EPS = np.finfo(float).eps
@@ -67,8 +68,10 @@ def test_tps_kernel_matrix_direct_exact_zeros(nk, golden, case):
     assert zero.sum() >= 10
     assert np.all(out[zero] == 0.0)  # coincident points: exactly 0, like the reference's nan_to_num
     # log within 1 ulp (nk_common.h), r^2 summed in another order than NumPy: a few ulp of r^2 |log r|
+    # (spline_fit_reference.tps_bar_direct with u = EPS; K is NumPy's own float64 value, so the term for the kernel function's
+    # arithmetic is left out, as it always was here)
     r2 = np.sum((P[:, None, :] - Z[None, :, :]) ** 2, axis=2)
-    bar = (P.shape[1] + 8) * EPS * r2 * (np.abs(np.log(np.maximum(r2, 1e-300))) / 2 + 1)
+    bar = tps_bar_direct(P.shape[1], r2, np.zeros_like(K), u=EPS)
     assert np.all(np.abs(out - K) <= bar), float(np.max(np.abs(out - K) - bar))
 
 
@@ -80,11 +83,8 @@ def test_tps_kernel_matrix_gram_form(nk, golden):
     P, Z = g["d192_points"], g["d192_centers"]
     direct = tps_matrix(P, Z, 1)
     gram = tps_matrix(P, Z, 0)
-    mu = Z.mean(axis=0)
-    na, nb = np.sum((P - mu) ** 2, 1), np.sum((Z - mu) ** 2, 1)
-    delta = (P.shape[1] + 8) * EPS * (na[:, None] + nb[None, :])
     r2 = np.sum((P[:, None, :] - Z[None, :, :]) ** 2, axis=2)
-    bar = delta * (np.abs(np.log(np.maximum(r2, delta))) / 2 + 1) + 8 * EPS * np.abs(direct)
+    bar = tps_bar_gram(P, Z, Z.mean(axis=0), r2, direct, u=EPS)
     assert np.all(np.abs(gram - direct) <= bar), float(np.max(np.abs(gram - direct) / bar))
 
 
