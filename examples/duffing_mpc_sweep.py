@@ -7,8 +7,12 @@ call (nk_mpc_loop_multi) that returns eight numbers per unit.  The same table wi
 stands beside it: the unconstrained loops ask for inputs far outside that range.  Needs an MI355X (the library has no CPU
 path):
 
-    python3 examples/duffing_mpc_sweep.py
+    python3 examples/duffing_mpc_sweep.py [--build device]
+
+--build device builds the controllers of all fits in ONE device call after the fits (nk_model_mpc_build_batch) instead of on
+the host threads.
 """
+import argparse
 import os
 import sys
 
@@ -24,7 +28,9 @@ X, Y = np.ascontiguousarray(g["X"]), np.ascontiguousarray(g["Y"])    # [x | u] -
 plant = nk.DuffingOscillator(Ts=0.01)
 x0, ref, steps, seeds, ms = np.array([-0.5, 0.0]), np.zeros(2), 600, list(range(24)), [20, 65]
 params = dict(kernel=nk.KernelWrapper([1, 1]), gamma=float(g["gamma"]))
-limits = dict(horizon=8, u_min=-10.0, u_max=10.0, du_min=-1.0, du_max=1.0)
+ap = argparse.ArgumentParser()
+ap.add_argument("--build", choices=("host", "device"), default="host")
+limits = dict(horizon=8, u_min=-10.0, u_max=10.0, du_min=-1.0, du_max=1.0, build=ap.parse_args().build)
 
 free = harness.lqr_sweep(X, Y, 1, params, ms, seeds, plant, x0, ref, steps, c=1e2, batch=8)
 for label, ctl in (("saturated LQR", dict(limits, iters=0)), ("MPC, 50 iterations", dict(limits, iters=50))):

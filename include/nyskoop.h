@@ -814,6 +814,85 @@ int nk_mpc_loop_multi(nk_ctx* ctx, const nk_poly_plant* plant, int32_t steps, co
 int nk_mpc_out_loop_multi(nk_ctx* ctx, const nk_poly_plant* plant, int32_t steps, const nk_mpc_unit* units,
                           const nk_mpc_out* const* outs, int32_t n_units, const double* u_opt, int32_t n_uopt, double* out_x,
                           double* out_u, double* out_info, double* scores);
+/* ---- the controllers of the MPC sweeps, built on the device for MANY independent units in one call: the Riccati solution,
+ *   a Newton polish, the condensed problem (H, F) of the loops above and the output rows (G, T) of nk_mpc_out.
+ *   Per unit, with nv = N p:
+ *   Riccati stage (skipped when P is given): (K, P) by the doubling iteration of nk_dare_batch (m <= 256: ONE launch of that
+ *     solver over all such units of a group) or of nk_dare_large (256 < m <= 512: one unit after the other), with tol and
+ *     max_iter; the same code, so with newton_steps = 0 K and P are bit for bit what those calls return.
+ *   Newton stage (newton_steps Hewer steps; skipped when P is given), each step a correction of the current P
+ *   (lqr.dare_newton_smith in Python is the NumPy statement):
+ *       Ac = A - B K,  Y = sym((Ac'P Ac - P) + (Q + (K'R) K));
+ *       repeat  D = sym(Ac' Y Ac),  Y += D,  stop when |D|_1 <= newton_tol |Y|_1,  else Ac = Ac Ac   (at most newton_max_iter times)
+ *       P += Y,  K = (R + sym(B'PB))^-1 B'PA  (Cholesky).
+ *     P + Y solves the step's Lyapunov equation X = Ac'X Ac + Q + K'RK; the Smith iteration carries the correction alone, so
+ *     its rounding is relative to the correction and not to P.
+ *     With P given (symmetric: B'PA is formed as (P B)'A), K = (R + sym(B'PB))^-1 B'PA from that P.
+ *   Condensing (lqr.mpc_condense_blocked in Python is the NumPy statement; the result is that of lqr.mpc_condense):
+ *       G_0 = B, G_k = A G_{k-1};  QG = Q [G_0 .. G_{N-1}],  PG = P [G_0 .. G_{N-1}];  W = 0 (m x nv)
+ *       for l = N .. 0:  W = A' W;  block column j of W += (PG if l == N else QG) block l-1-j, for every j < min(l, N);
+ *                        for l >= 1: block row l-1 of H, columns 0 .. l-1, = 2 B' W
+ *       F = 2 W';  H is mirrored from its lower triangle (entry by entry) and its diagonal blocks get + 2 sym(R):
+ *     H is returned bitwise symmetric.
+ *   Output rows (nc > 0; lqr.mpc_condense_outputs): R_0 = C_rows, R_k = R_{k-1} A; row block k of T = R_k, block (k, j) of G =
+ *     R_{k-1-j} B for j < k and exactly 0 otherwise, k = 1 .. Ny.
+ *   One workgroup owns one unit from start to finish; the products run on the fp64 matrix pipe in orders fixed by (m, p, N,
+ *   nc, Ny) alone, so a unit's results do not depend on what else the call holds or in which order.
+ *   out_status[u]: 0 = success; 1 = the doubling iteration reached max_iter; 2 = non-finite values, a singular pivot, or R /
+ *   R + B'PB not positive definite; 3 = the Smith iteration reached newton_max_iter.  A unit with a status other than 0 has
+ *   NaN in all its outputs; the other units of the call are not affected.  out_iters (may be NULL): n x 2, {doubling steps,
+ *   Smith squarings over all Newton steps}.
+ *   Limits: 1 <= m <= 512, 1 <= p <= 4, N >= 1, N p <= NK_MPC_MAX_NV, 0 <= nc <= 4, 1 <= Ny <= N when nc > 0,
+ *   0 <= newton_steps <= 4, 1 <= max_iter, newton_max_iter <= 1000.  Device workspace per unit: about 6 M^2 + 5 M NVP doubles
+ *   (M, NVP = m, nv rounded up to 16), plus 7 M^2 in the Riccati stage for m <= 256; the library works in groups whose
+ *   workspace stays under NK_DARE_WS_CAP_BYTES.
+ *   nk_mpc_build_batch: every operand and result is HOST memory (staged with one copy in and one copy out per group); the
+ *   operands have leading dimensions, the results are dense.  Everything is checked before anything is queued or allocated: a
+ *   bad field is NK_ERR_BAD_ARG with the problem index and the field's name in nk_last_error(), and no output is touched.
+ *   Ordinary contexts only (not lock-step members). */
+typedef struct nk_mpc_build_problem {
+  int32_t m, p, N;
+  int32_t nc, Ny;                     /* output rows: nc rows of C_rows over the steps 1 .. Ny; nc = 0: none (Ny is ignored) */
+  int32_t reserved;
+  const double* A; int64_t lda;       /* m x m */
+  const double* B; int64_t ldb;       /* m x p */
+  const double* Q; int64_t ldq;       /* m x m, symmetric positive semi-definite */
+  const double* R; int64_t ldr;       /* p x p, symmetric positive definite */
+  const double* P; int64_t ldp;       /* m x m SYMMETRIC terminal cost, or NULL: the Riccati solution of (A, B, Q, R) */
+  const double* C_rows; int64_t ldc;  /* nc x m; may be NULL when nc = 0 */
+  double* out_H;                      /* nv x nv */
+  double* out_F;                      /* nv x m */
+  double* out_K;                      /* p x m */
+  double* out_P;                      /* m x m: the terminal cost used; NULL skips the copy */
+  double* out_G;                      /* Ny nc x nv; may be NULL when nc = 0 */
+  double* out_T;                      /* Ny nc x m; may be NULL when nc = 0 */
+} nk_mpc_build_problem;
+int nk_mpc_build_batch(nk_ctx* ctx, const nk_mpc_build_problem* problems, int32_t n, double tol, int32_t max_iter,
+                       int32_t newton_steps, double newton_tol, int32_t newton_max_iter, int32_t* out_status,
+                       int32_t* out_iters);
+/* The sweep's entry: the controllers of n fitted models.  [A B] and C are read from the models' device allocations,
+ * Q = c sym(C'C) is formed on the device exactly as nk_model_lqr_cost forms it, R: HOST, p x p dense (then every model has p
+ * inputs), or NULL for the identity.  specs[u] (HOST): the horizon N and the output rows, row r = row comps[r] of C (a state
+ * component, 0 <= comps[r] < d), r < nc, over the steps 1 .. Ny.  outs[u] (HOST, its arrays HOST and dense): H, F, K, and G, T
+ * when nc > 0; only these travel back.  Stages, status, limits and checks as in nk_mpc_build_batch (the Riccati stage always
+ * runs).  Models need not belong to ctx: only the device must match (models fitted by lock-step members are accepted); the
+ * call itself is for ordinary contexts. */
+typedef struct nk_mpc_build_spec {
+  int32_t N, nc;
+  int32_t comps[4];
+  int32_t Ny, reserved;
+} nk_mpc_build_spec;
+typedef struct nk_mpc_build_out {
+  double *H, *F, *K, *G, *T;
+} nk_mpc_build_out;
+int nk_model_mpc_build_batch(nk_ctx* ctx, const nk_model* const* models, int32_t n, double c, const double* R_or_NULL,
+                             const nk_mpc_build_spec* specs, double tol, int32_t max_iter, int32_t newton_steps,
+                             double newton_tol, int32_t newton_max_iter, const nk_mpc_build_out* outs, int32_t* out_status,
+                             int32_t* out_iters);
+/* Diagnostics: device time of the calling thread's last nk_mpc_build_batch / nk_model_mpc_build_batch in milliseconds, by
+ * events on the context's stream, summed over the call's groups: out[0] = the Riccati stage (the staging of its table
+ * included; 0 when every P was given), out[1] = the build launch, out[2] = the number of groups. */
+int nk_mpc_build_times(double out[3]);
 /* ---- rollout of explicit operators without a model (any estimator that exposes A, B, C: the exact-kernel comparator of
  *   benchmark_lqr_hjb.py:334-381, un-pickled gains): z0: batch x m lifted initial states; A: m x m, B: m x p, C: d x m
  *   (row-major, host or device); U, out_x, out_z as in nk_rollout. --------------------------------------------------- */

@@ -139,6 +139,26 @@ class DareProblem(C.Structure):
                 ("out_K", C.c_void_p), ("out_P", C.c_void_p), ("out_delta", C.c_void_p)]
 
 
+class MpcBuildProblem(C.Structure):
+    """nk_mpc_build_problem (include/nyskoop.h), one problem of nk_mpc_build_batch."""
+    _fields_ = [("m", C.c_int32), ("p", C.c_int32), ("N", C.c_int32), ("nc", C.c_int32), ("Ny", C.c_int32),
+                ("reserved", C.c_int32), ("A", C.c_void_p), ("lda", C.c_int64), ("B", C.c_void_p), ("ldb", C.c_int64),
+                ("Q", C.c_void_p), ("ldq", C.c_int64), ("R", C.c_void_p), ("ldr", C.c_int64), ("P", C.c_void_p),
+                ("ldp", C.c_int64), ("C_rows", C.c_void_p), ("ldc", C.c_int64), ("out_H", C.c_void_p),
+                ("out_F", C.c_void_p), ("out_K", C.c_void_p), ("out_P", C.c_void_p), ("out_G", C.c_void_p),
+                ("out_T", C.c_void_p)]
+
+
+class MpcBuildSpec(C.Structure):
+    """nk_mpc_build_spec (include/nyskoop.h): the horizon and the output rows of one unit of nk_model_mpc_build_batch."""
+    _fields_ = [("N", C.c_int32), ("nc", C.c_int32), ("comps", C.c_int32 * 4), ("Ny", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MpcBuildOut(C.Structure):
+    """nk_mpc_build_out (include/nyskoop.h): where the results of one unit of nk_model_mpc_build_batch go."""
+    _fields_ = [("H", C.c_void_p), ("F", C.c_void_p), ("K", C.c_void_p), ("G", C.c_void_p), ("T", C.c_void_p)]
+
+
 class FitStats(C.Structure):
     _fields_ = [("ms_total", C.c_double), ("ms_upload", C.c_double), ("ms_kmat", C.c_double),
                 ("ms_gram", C.c_double), ("ms_sqrt", C.c_double), ("ms_solve", C.c_double),
@@ -239,6 +259,11 @@ SIGNATURES = {
                                 C.POINTER(_I32), C.POINTER(_I32)]),
     "nk_model_lqr_gain": (C.c_int, [_P, _P, _D, _P, _D, _I32, _P, C.POINTER(_I32), C.POINTER(_I32)]),
     "nk_dare_large_times": (C.c_int, [C.POINTER(_D)]),
+    "nk_mpc_build_batch": (C.c_int, [_P, C.POINTER(MpcBuildProblem), _I32, _D, _I32, _I32, _D, _I32, C.POINTER(_I32),
+                                     C.POINTER(_I32)]),
+    "nk_model_mpc_build_batch": (C.c_int, [_P, C.POINTER(_P), _I32, _D, _P, C.POINTER(MpcBuildSpec), _D, _I32, _I32, _D,
+                                           _I32, C.POINTER(MpcBuildOut), C.POINTER(_I32), C.POINTER(_I32)]),
+    "nk_mpc_build_times": (C.c_int, [C.POINTER(_D)]),
     "nk_linear_rollout": (C.c_int, [_P, _P, _P, _P, _I32, _I32, _I32, _P, _P, _I32, _I32, _P, _P]),
     "nk_gemm_f32": (C.c_int, [_P, _I64, _I64, _I64, _P, _I64, _P, _I64, _P, _I64]),
     "nk_gemm": (C.c_int, [_P, C.c_int, C.c_int, _I64, _I64, _I64, _D, _P, _I64, _P, _I64, _D, _P, _I64]),
@@ -698,6 +723,109 @@ class Context:
             Ks.append(out[off:off + sz].reshape(int(p), int(m)).copy())
             off += sz
         return Ks, status[:n], iters[:n]
+
+    def mpc_build_batch(self, As, Bs, Qs, Rs, Ns, Ps=None, C_rows=None, Nys=None, tol=1e-13, max_iter=40, newton_steps=1,
+                        newton_tol=1e-15, newton_max_iter=60, want_P=True):
+        """nk_mpc_build_batch: the controllers of a list of problems in one call, one workgroup per problem.  Ps: terminal
+        costs (a None entry, or Ps = None: the Riccati solution with newton_steps Newton steps); C_rows: (nc, m) output rows
+        per problem or None, with the horizons Nys (default N).  Returns a dict of lists H, F, K, P, G, T (G, T None for a
+        problem without rows; P None unless want_P) and the arrays status (n,), iters (n, 2) = {doubling steps, Smith
+        squarings}; status 0 = success, 1 = doubling cap, 2 = non-finite / not positive definite, 3 = Smith cap (NaN outputs)."""
+        n = len(As)
+        if not (len(Bs) == len(Qs) == len(Rs) == len(Ns) == n):
+            raise ValueError("As, Bs, Qs, Rs, Ns must have the same length")
+        arr = (MpcBuildProblem * max(n, 1))()
+        keep = []
+        res = dict(H=[], F=[], K=[], P=[], G=[], T=[])
+        for i in range(n):
+            A = np.ascontiguousarray(As[i], dtype=np.float64)
+            if A.ndim != 2 or A.shape[0] != A.shape[1]:
+                raise ValueError(f"problem {i}: A must be square, got {A.shape}")
+            m = A.shape[0]
+            B = np.ascontiguousarray(np.asarray(Bs[i], dtype=np.float64).reshape(m, -1))
+            p = B.shape[1]
+            Q = np.ascontiguousarray(np.asarray(Qs[i], dtype=np.float64).reshape(m, m))
+            R = np.ascontiguousarray(np.asarray(Rs[i], dtype=np.float64).reshape(p, p))
+            N = int(Ns[i])
+            nv = max(N, 0) * p
+            P = None if Ps is None or Ps[i] is None else np.ascontiguousarray(np.asarray(Ps[i], dtype=np.float64).reshape(m, m))
+            Cr = None if C_rows is None or C_rows[i] is None else \
+                np.ascontiguousarray(np.asarray(C_rows[i], dtype=np.float64).reshape(-1, m))
+            nc = 0 if Cr is None else Cr.shape[0]
+            Ny = 0 if nc == 0 else (N if Nys is None or Nys[i] is None else int(Nys[i]))
+            ny = nc * max(Ny, 0)
+            o = dict(H=np.full((nv, nv), np.nan), F=np.full((nv, m), np.nan), K=np.full((p, m), np.nan),
+                     P=np.full((m, m), np.nan) if want_P else None,
+                     G=np.full((ny, nv), np.nan) if nc else None, T=np.full((ny, m), np.nan) if nc else None)
+            keep.append((A, B, Q, R, P, Cr))
+            for k, v in o.items():
+                res[k].append(v)
+            a = arr[i]
+            a.m, a.p, a.N, a.nc, a.Ny = m, p, N, nc, Ny
+            a.A, a.lda, a.B, a.ldb = A.ctypes.data, max(m, 1), B.ctypes.data, max(p, 1)
+            a.Q, a.ldq, a.R, a.ldr = Q.ctypes.data, max(m, 1), R.ctypes.data, max(p, 1)
+            a.P, a.ldp = (None if P is None else P.ctypes.data), max(m, 1)
+            a.C_rows, a.ldc = (None if Cr is None else Cr.ctypes.data), max(m, 1)
+            a.out_H, a.out_F, a.out_K = o["H"].ctypes.data, o["F"].ctypes.data, o["K"].ctypes.data
+            a.out_P = o["P"].ctypes.data if want_P else None
+            a.out_G = o["G"].ctypes.data if nc else None
+            a.out_T = o["T"].ctypes.data if nc else None
+        status = np.full(max(n, 1), -1, dtype=np.int32)
+        iters = np.zeros((max(n, 1), 2), dtype=np.int32)
+        rc = self.lib.nk_mpc_build_batch(self.handle, arr, n, float(tol), int(max_iter), int(newton_steps), float(newton_tol),
+                                         int(newton_max_iter), status.ctypes.data_as(C.POINTER(_I32)),
+                                         iters.ctypes.data_as(C.POINTER(_I32)))
+        check_mapped(rc)
+        del keep
+        res["status"], res["iters"] = status[:n], iters[:n]
+        return res
+
+    def model_mpc_build_batch(self, models, dims, c, R, specs, tol=1e-13, max_iter=40, newton_steps=1, newton_tol=1e-15,
+                              newton_max_iter=60):
+        """nk_model_mpc_build_batch: the controllers of n device models in one call.  models: device-model handles; dims:
+        their (m, p) pairs; R: (p, p) or None for the identity; specs: per unit (N, comps, Ny) with comps the state components
+        of the output rows (empty: none).  Returns (units, status (n,), iters (n, 2)); units[u] = dict(H, F, K, G, T) (G, T
+        None without rows); a unit with status != 0 has NaN arrays."""
+        n = len(models)
+        hs = (_P * max(n, 1))()
+        for i, h in enumerate(models):
+            hs[i] = h.value if isinstance(h, C.c_void_p) else h
+        sp = (MpcBuildSpec * max(n, 1))()
+        ou = (MpcBuildOut * max(n, 1))()
+        units = []
+        for i in range(n):
+            m, p = int(dims[i][0]), int(dims[i][1])
+            N, comps, Ny = specs[i]
+            N, comps = int(N), [int(v) for v in comps]
+            if len(comps) > 4:
+                raise ValueError(f"unit {i}: {len(comps)} output rows per step, at most 4")
+            nc = len(comps)
+            Ny = 0 if nc == 0 else (N if Ny is None else int(Ny))
+            nv, ny = max(N, 0) * p, nc * max(Ny, 0)
+            u = dict(H=np.full((nv, nv), np.nan), F=np.full((nv, m), np.nan), K=np.full((p, m), np.nan),
+                     G=np.full((ny, nv), np.nan) if nc else None, T=np.full((ny, m), np.nan) if nc else None)
+            units.append(u)
+            sp[i].N, sp[i].nc, sp[i].Ny = N, nc, Ny
+            for k, v in enumerate(comps):
+                sp[i].comps[k] = v
+            ou[i].H, ou[i].F, ou[i].K = u["H"].ctypes.data, u["F"].ctypes.data, u["K"].ctypes.data
+            ou[i].G = u["G"].ctypes.data if nc else None
+            ou[i].T = u["T"].ctypes.data if nc else None
+        Rm = None if R is None else np.ascontiguousarray(R, dtype=np.float64)
+        status = np.full(max(n, 1), -1, dtype=np.int32)
+        iters = np.zeros((max(n, 1), 2), dtype=np.int32)
+        rc = self.lib.nk_model_mpc_build_batch(self.handle, hs, n, float(c), None if Rm is None else Rm.ctypes.data, sp,
+                                               float(tol), int(max_iter), int(newton_steps), float(newton_tol),
+                                               int(newton_max_iter), ou, status.ctypes.data_as(C.POINTER(_I32)),
+                                               iters.ctypes.data_as(C.POINTER(_I32)))
+        check_mapped(rc)
+        return units, status[:n], iters[:n]
+
+    def mpc_build_times(self):
+        """nk_mpc_build_times: dict(ms_riccati, ms_build, groups) of this thread's last build call: device time by events."""
+        v = (_D * 3)()
+        check(self.lib.nk_mpc_build_times(v))
+        return dict(ms_riccati=v[0], ms_build=v[1], groups=int(v[2]))
 
     def dare_large(self, A, B, Q, R, tol=1e-13, max_iter=40, want_P=True):
         """nk_dare_large: K = dlqr(A, B, Q, R) for ONE problem of any size (m <= 10240, p <= 32) by the launch-chain solver.

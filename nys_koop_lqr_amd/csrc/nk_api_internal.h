@@ -1,5 +1,5 @@
 // Helpers shared by the translation units behind the C ABI (nk_api.hip, nk_api_compute.hip, nk_fit.hip, nk_sweep.hip,
-// nk_control.hip, nk_api_loops.hip, nk_api_dare.hip); defined in nk_api.hip unless noted.
+// nk_control.hip, nk_api_loops.hip, nk_api_dare.hip, nk_api_mpc_build.hip); defined in nk_api.hip unless noted.
 #pragma once
 #include "nk_common.h"
 #include "nk_unit_pack.h"

@@ -777,6 +777,37 @@ struct DareLargeTimes {
 };
 void dare_large_last_times(DareLargeTimes* out);
 
+// ---- controller build (nk_mpc_build.hip): Newton polish of the Riccati stage's gain, the condensed problem (H, F) and the
+// output rows (G, T) of one unit per workgroup, blockIdx.x = the record.  Every pointer is device memory and every matrix
+// but A, B, Q, C is dense.  Either Q (m x m) or C (d x m: the cost is c sym(C'C), formed as the Riccati kernel forms it) is
+// set.  Pin: the terminal cost, symmetric (given by the caller, or the Riccati stage's P); Kin: the Riccati stage's gain, or nullptr
+// (then K = (R + B'PB)^-1 B'PA is formed from Pin and no Newton step is taken).  pre_status: the Riccati stage's status
+// word, or nullptr (then pre_status_imm counts).  Crows: the matrix whose rows comps[0 .. nc-1] are the output rows.
+// sq, wide: the workspace of nk_mpc_build_pack.h.
+constexpr int MPC_BUILD_MAX_M = 512;
+constexpr int MPC_BUILD_MAX_P = 4;
+constexpr int MPC_BUILD_MAX_NC = 4;
+struct MpcBuildRec {
+  const double* A; int64_t lda;
+  const double* B; int64_t ldb;
+  const double* Q; int64_t ldq;
+  const double* C; int64_t ldc;
+  const double* R;       // p x p, or nullptr = identity
+  const double* Pin;     // m x m
+  const double* Kin;     // p x m, or nullptr
+  const double* Crows; int64_t ldcr;
+  const int* pre_status;
+  double c;
+  double *sq, *wide;
+  double *outH, *outF, *outK, *outP, *outG, *outT;  // outP, outG, outT may be nullptr
+  int* status;           // 0, or 1 / 2 of the Riccati stage, 2 (non-finite, not positive definite), 3 (Smith cap)
+  int* iters;            // Smith squarings over all Newton steps
+  int m, p, N, nc, Ny, d, M, NVP;
+  int comps[MPC_BUILD_MAX_NC];
+  int newton_steps, pre_status_imm;
+};
+int launch_mpc_build(nk_ctx* ctx, const MpcBuildRec* table_dev, int count, double newton_tol, int newton_max_iter);
+
 // ---- landmark selection (nk_landmarks.hip): partial pivoted Cholesky of K(Y, Y) over the candidate rows rng ([begin, end)
 // pairs of rows of the device matrix Y, nc rows in all), m steps queued without a host round trip.  positions: the
 // m_selected candidate positions in pick order; resid: m entries, trace: m + 1 entries (zero past the stop).  The factor

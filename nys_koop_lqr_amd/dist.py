@@ -140,20 +140,21 @@ def sharded_sysid_sweep(X, Y, n_inputs, params, ms, seeds, trajs, controls, test
 
 def sharded_lqr_sweep(X, Y, n_inputs, params, ms, seeds, plant, x0, x_ref, num_steps, estimator="nystrom", gain_fn=None,
                       c=1.0, u_opt=None, batch=32, workers=4, centers=None, fit_fn=None, loop_fn=None, gain="host",
-                      gain_batch_fn=None, controller=None):
+                      gain_batch_fn=None, controller=None, controller_batch_fn=None):
     """Distributed counterpart of harness.lqr_sweep: every rank plans the same units with the same draws, the units are
     dealt round-robin (shard_units), every rank fits, solves and runs its share on its own GPU (one plant_loop_multi call
     per rank) and ONE all-gather assembles the four scores of every unit.  Trajectories stay on their ranks.  Every rank
     returns the same dict of (len(seeds), len(ms)) tables (harness.lqr_sweep without `timing` and trajectories).
     controller: lqr_sweep's dict -- every rank runs ONE mpc_loop_multi call and the all-gather carries eight scores, or ten
-    (harness.MPC_OUT_SCORE_NAMES) when the dict holds state limits (x_min / x_max)."""
+    (harness.MPC_OUT_SCORE_NAMES) when the dict holds state limits (x_min / x_max); with build="device" in it every rank builds
+    the controllers of its share in ONE device call (controller_batch_fn stands in for it, as in harness.lqr_sweep)."""
     import torch.distributed as dist
     rank, world = (dist.get_rank(), dist.get_world_size()) if dist.is_initialized() else (0, 1)
     units = harness.lqr_plan(X, Y, n_inputs, params, ms, seeds, estimator, centers)
     mine = shard_units(len(units), rank, world)
     local, _, _, _ = harness.lqr_run_units(X, Y, n_inputs, params, [units[u] for u in mine], plant, x0, x_ref, num_steps,
                                            estimator, gain_fn, c, u_opt, batch, workers, False, fit_fn, loop_fn, gain,
-                                           gain_batch_fn, controller)
+                                           gain_batch_fn, controller, controller_batch_fn)
     flat = all_gather_scores(local, len(units), rank, world) if world > 1 else local
     return harness.lqr_result(units, flat, None, None, len(seeds), len(ms))
 

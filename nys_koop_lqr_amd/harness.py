@@ -881,7 +881,7 @@ def lqr_fit_unit(X, Y, n_inputs, params, unit, estimator="nystrom"):
 
 
 def lqr_fit_and_gain(X, Y, n_inputs, params, units, estimator="nystrom", gain_fn=None, c=1.0, batch=32, workers=4,
-                     fit_fn=None, gain="host", gain_batch_fn=None, after_fit=None, controller=None):
+                     fit_fn=None, gain="host", gain_batch_fn=None, after_fit=None, controller=None, controller_batch_fn=None):
     """The fits and gains of planned units -- what lqr_run_units and cloth_lqr_sweep share.  Fits: `batch` at a time through
     the lock-step pool (a plain loop with batch <= 1 or a fit_fn); a unit may carry its own "estimator" and "params".
     after_fit(reg, unit): called on the fitting thread right after a successful fit, inside the lock-step round (its result
@@ -889,7 +889,10 @@ def lqr_fit_and_gain(X, Y, n_inputs, params, units, estimator="nystrom", gain_fn
     gain="device": ONE nk_model_lqr_gain_batch call after the fits (gain_batch_fn(regs, c) stands in for it).
     controller (the checked dict of lqr_sweep): instead of a gain, reg.solve_mpc(horizon, c=c, limits, rho) is built per
     unit on the same host threads, and gains[i] is that lqr.MPCController (None when it raises); with x_min / x_max (and
-    y_horizon, y_weight) in the dict it is an lqr.MPCOutputController.
+    y_horizon, y_weight) in the dict it is an lqr.MPCOutputController.  With controller["build"] == "device" the controllers of
+    all fitted units come from ONE nk_model_mpc_build_batch call after the fits instead (regressors._mpc_controller_batch;
+    controller_batch_fn(regs, c, controller) -> (controllers, status) stands in for it): a unit with a non-zero status, or
+    whose limits solve_mpc refuses, has gains[i] None; gain_wait_s is that call and gain_cpu_s is 0.
     Returns (regs, gains, extras, timing): a unit whose fit failed has regs[i] None, one without a gain gains[i] None;
     timing = dict(fit_s, gain_wait_s, gain_cpu_s)."""
     import time
@@ -900,6 +903,7 @@ def lqr_fit_and_gain(X, Y, n_inputs, params, units, estimator="nystrom", gain_fn
     if gain == "device" and gain_fn is not None:
         raise ValueError("gain='device' solves K = dlqr(A, B, c C'C, I) on the device: gain_fn cannot be combined with it")
     device_gain = gain == "device"
+    device_build = controller is not None and controller.get("build", "host") == "device"
     X = np.ascontiguousarray(X, dtype=np.float64)
     Y = np.ascontiguousarray(Y, dtype=np.float64)
     gain_fn = gain_fn or lqr_default_gain(c)
@@ -940,7 +944,7 @@ def lqr_fit_and_gain(X, Y, n_inputs, params, units, estimator="nystrom", gain_fn
             if after_fit is not None:
                 reg, extras[i] = reg
             regs[i] = reg
-            if reg is not None and not device_gain:
+            if reg is not None and not device_gain and not device_build:
                 futures[i] = pool.submit(gain_of, i, reg)
     t1 = time.perf_counter()
     gains = [None] * n
@@ -952,6 +956,14 @@ def lqr_fit_and_gain(X, Y, n_inputs, params, units, estimator="nystrom", gain_fn
             for i, K, st in zip(fitted_idx, Ks, status):
                 if int(st) == 0:
                     gains[i] = np.asarray(K, dtype=np.float64)
+    if device_build:
+        fitted_idx = [i for i in range(n) if regs[i] is not None]
+        if fitted_idx:
+            from .regressors import _mpc_controller_batch
+            ctrls, status = (controller_batch_fn or _mpc_controller_batch)([regs[i] for i in fitted_idx], c, controller)
+            for i, ctrl, st in zip(fitted_idx, ctrls, status):
+                if int(st) == 0:
+                    gains[i] = ctrl
     for i, f in enumerate(futures):
         if f is not None:
             try:
@@ -962,24 +974,27 @@ def lqr_fit_and_gain(X, Y, n_inputs, params, units, estimator="nystrom", gain_fn
     return regs, gains, extras, dict(fit_s=t1 - t0, gain_wait_s=t2 - t1, gain_cpu_s=float(sum(gain_s)))
 
 
-CONTROLLER_KEYS = ("horizon", "u_min", "u_max", "du_min", "du_max", "iters", "tol", "rho", "x_min", "x_max", "y_horizon",
-                   "y_weight")
+CONTROLLER_KEYS = ("horizon", "u_min", "u_max", "du_min", "du_max", "iters", "tol", "rho", "build", "x_min", "x_max",
+                   "y_horizon", "y_weight")
 
 
 def lqr_controller_spec(controller):
     """The `controller` dict of lqr_sweep with its defaults filled in (limits None = absent, iters = 50, tol = 0.0, rho None
     = lqr.mpc_default_rho; the state limits x_min, x_max None = absent, y_horizon None = the horizon, y_weight = inf = hard
-    rows); `horizon` is required and an unknown key is a ValueError.  None stays None."""
+    rows; build = "host", or "device": the controllers of all units in one device call); `horizon` is required and an unknown
+    key or build value is a ValueError.  None stays None."""
     if controller is None:
         return None
-    spec = dict(u_min=None, u_max=None, du_min=None, du_max=None, iters=50, tol=0.0, rho=None, x_min=None, x_max=None,
-                y_horizon=None, y_weight=np.inf)
+    spec = dict(u_min=None, u_max=None, du_min=None, du_max=None, iters=50, tol=0.0, rho=None, build="host", x_min=None,
+                x_max=None, y_horizon=None, y_weight=np.inf)
     unknown = sorted(set(controller) - set(CONTROLLER_KEYS))
     if unknown:
         raise ValueError(f"controller has unknown keys {unknown}; known: {CONTROLLER_KEYS}")
     if "horizon" not in controller:
         raise ValueError("controller needs a 'horizon'")
     spec.update(controller)
+    if spec["build"] not in ("host", "device"):
+        raise ValueError(f"controller['build'] must be 'host' or 'device', got {spec['build']!r}")
     return spec
 
 
@@ -995,7 +1010,7 @@ def lqr_controller_has_rows(spec):
 
 def lqr_run_units(X, Y, n_inputs, params, units, plant, x0, x_ref, num_steps, estimator="nystrom", gain_fn=None, c=1.0,
                   u_opt=None, batch=32, workers=4, return_trajectories=False, fit_fn=None, loop_fn=None, gain="host",
-                  gain_batch_fn=None, controller=None):
+                  gain_batch_fn=None, controller=None, controller_batch_fn=None):
     """Scores of planned units, in their order: an (n_units, 4) array (SCORE_NAMES; NaN for a unit whose fit or gain
     failed), the trajectories (or None, None) and the wall-clock split.  fit_fn / loop_fn stand in for lqr_fit_unit /
     plant_loop_multi (rehearsals without a GPU; with a fit_fn the fits run as a plain loop).
@@ -1007,7 +1022,8 @@ def lqr_run_units(X, Y, n_inputs, params, units, plant, x0, x_ref, num_steps, es
     gains are built, ONE mpc_loop_multi call (loop_fn stands in for it, with its signature), eight scores per unit
     (MPC_SCORE_NAMES); a unit whose controller raises scores NaN and is not run.  gain="device" with it is a ValueError.
     With a state limit in the dict (lqr_controller_has_rows) the units run with their output rows and carry the ten
-    MPC_OUT_SCORE_NAMES."""
+    MPC_OUT_SCORE_NAMES.  build="device" in the dict: the controllers of all fitted units from ONE nk_model_mpc_build_batch call
+    after the fits (lqr_fit_and_gain; controller_batch_fn stands in for it); a unit with a non-zero status scores NaN."""
     import time
     controller = lqr_controller_spec(controller)
     if controller is not None and gain == "device":
@@ -1016,7 +1032,7 @@ def lqr_run_units(X, Y, n_inputs, params, units, plant, x0, x_ref, num_steps, es
     loop_fn = loop_fn or (plant_loop_multi if controller is None else mpc_loop_multi)
     n = len(units)
     regs, gains, _, tm = lqr_fit_and_gain(X, Y, n_inputs, params, units, estimator, gain_fn, c, batch, workers, fit_fn, gain,
-                                          gain_batch_fn, controller=controller)
+                                          gain_batch_fn, controller=controller, controller_batch_fn=controller_batch_fn)
     t2 = time.perf_counter()
     live = [i for i in range(n) if gains[i] is not None]
     scores = np.full((n, len(names)), np.nan)
@@ -1055,7 +1071,7 @@ def lqr_table(units, values, n_seeds, n_ms):
 
 def lqr_sweep(X, Y, n_inputs, params, ms, seeds, plant, x0, x_ref, num_steps, estimator="nystrom", gain_fn=None, c=1.0,
               u_opt=None, batch=32, workers=4, return_trajectories=False, centers=None, fit_fn=None, loop_fn=None,
-              gain="host", gain_batch_fn=None, controller=None):
+              gain="host", gain_batch_fn=None, controller=None, controller_batch_fn=None):
     """The control branch of the reference's one-input drivers (benchmark_lqr_classic.py:256-299: seeds x {Nystrom,
     splines}; benchmark_lqr_hjb.py:265-333: seeds x m) as one call: for every seed and every m in `ms`
     fit -> K = dlqr(A, B, c C^T C, I) -> `num_steps` feedback steps around the true plant -> replay cost and control scores.
@@ -1082,12 +1098,14 @@ def lqr_sweep(X, Y, n_inputs, params, ms, seeds, plant, x0, x_ref, num_steps, es
     n_y_viol (the steps with one): the ten MPC_OUT_SCORE_NAMES.  rho stays the user's to set: the rows of a sampled plant are
     small beside the identity rows of the inputs, so the output rows want a rho far above the default (300 x the default
     reached a hard velocity limit within 2 % in 100 iterations on the Duffing models; with the default the controls did not
-    move)."""
+    move).  build="device" in the dict builds the controllers of all fitted units in ONE device call after the fits
+    (nk_model_mpc_build_batch: Riccati, one Newton step and the condensing on the device; controller_batch_fn(regs, c,
+    controller) stands in for it) instead of reg.solve_mpc per unit on host threads; the default "host" is what it was."""
     _check_estimator(estimator)
     units = lqr_plan(X, Y, n_inputs, params, ms, seeds, estimator, centers)
     scores, states, controls, timing = lqr_run_units(X, Y, n_inputs, params, units, plant, x0, x_ref, num_steps, estimator,
                                                      gain_fn, c, u_opt, batch, workers, return_trajectories, fit_fn, loop_fn,
-                                                     gain, gain_batch_fn, controller)
+                                                     gain, gain_batch_fn, controller, controller_batch_fn)
     return lqr_result(units, scores, states, controls, len(seeds), len(ms), timing)
 
 

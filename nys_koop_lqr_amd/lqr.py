@@ -167,6 +167,116 @@ def dare_refine(A, B, Q, R, K, steps=2):
     return K, P
 
 
+def mpc_condense_blocked(A, B, Q, R, P, N):
+    """The (H, F) of mpc_condense with the Horner recursion run for all block columns at once on one m x nv matrix W -- the
+    NumPy statement of what the device build computes (csrc/nk_mpc_build.hip).  G_k = A^k B; for l = N .. 0:
+        W = A' W;  block column j of W += (P if l == N else Q) G_{l-1-j} for every j < min(l, N);
+        for l >= 1: block row l-1 of H, columns 0 .. l-1, = 2 B' W[:, :l p];
+    at the end F = 2 W'.  The symmetrisation and + 2 sym(R) are those of mpc_condense.  N + 1 products of m x m by m x nv
+    instead of O(N^2) thin ones."""
+    A = np.asarray(A, dtype=np.float64)
+    m = A.shape[0]
+    B = np.asarray(B, dtype=np.float64).reshape(m, -1)
+    p = B.shape[1]
+    Q, P = np.asarray(Q, dtype=np.float64), np.asarray(P, dtype=np.float64)
+    R = np.asarray(R, dtype=np.float64).reshape(p, p)
+    N = int(N)
+    if N < 1:
+        raise ValueError("the horizon N must be at least 1")
+    nv = N * p
+    Gs = np.zeros((m, nv))  # [G_0 | G_1 | ... | G_{N-1}]
+    Gs[:, :p] = B
+    for k in range(1, N):
+        Gs[:, k * p:(k + 1) * p] = A @ Gs[:, (k - 1) * p:k * p]
+    QG, PG = Q @ Gs, P @ Gs
+    W, H = np.zeros((m, nv)), np.zeros((nv, nv))
+    for l in range(N, -1, -1):
+        W = A.T @ W
+        src = PG if l == N else QG
+        for j in range(min(l, N)):
+            W[:, j * p:(j + 1) * p] += src[:, (l - 1 - j) * p:(l - j) * p]
+        if l >= 1:
+            H[(l - 1) * p:l * p, :l * p] = 2.0 * (B.T @ W[:, :l * p])
+    F = 2.0 * W.T
+    low = np.tril(H, -1)
+    H = low + low.T + np.diag(np.diag(H))
+    for j in range(N):
+        blk = H[j * p:(j + 1) * p, j * p:(j + 1) * p]
+        H[j * p:(j + 1) * p, j * p:(j + 1) * p] = (blk + blk.T) / 2 + 2.0 * _sym(R)
+    return _sym(H), F
+
+
+def lyap_smith(Ac, X0, tol=1e-15, max_iter=60):
+    """The squared Smith iteration for X = Ac' X Ac + X0:  X = sym(X0); repeat  D = sym(Ac' X Ac), X += D, stop when
+    |D|_1 <= tol |X|_1, otherwise Ac = Ac Ac.  Returns (X, iterations, status): status 0 = converged, 3 = max_iter reached,
+    2 = non-finite values.  The device build runs the same steps."""
+    Ac = np.array(Ac, dtype=np.float64)
+    X = _sym(np.array(X0, dtype=np.float64))
+    it = 0
+    with np.errstate(all="ignore"):
+        while it < max_iter:
+            D = _sym(Ac.T @ X @ Ac)
+            X = X + D
+            it += 1
+            nd, nx = np.abs(D).sum(axis=0).max(), np.abs(X).sum(axis=0).max()
+            if not (np.isfinite(nd) and np.isfinite(nx)):
+                return X, it, 2
+            if nd <= tol * nx:
+                return X, it, 0
+            Ac = Ac @ Ac
+    return X, it, 3
+
+
+def dare_newton_smith(A, B, Q, R, K, steps=1, tol=1e-15, max_iter=60, P=None):
+    """Newton (Hewer) steps on a stabilising gain, each as a correction of the current P (zeros when P is None) by lyap_smith:
+        Ac = A - BK,  Res = sym((Ac'P Ac - P) + (Q + K'RK)),  P += lyap_smith(Ac, Res),  K = (R + sym(B'PB))^-1 B'PA.
+    P + the correction solves X = Ac'X Ac + Q + K'RK, the Lyapunov equation of the step; from P = 0 the first step is that
+    solve itself.  From the doubling iteration's P the Smith iteration carries only the correction, so its rounding (which
+    grows with the squarings when the closed-loop radius is near one) is relative to the correction and not to P: on the
+    Duffing fixtures with radius 0.99999 the full solve left a Riccati residual of 3e-13, the correction leaves 4e-16.
+    Returns (K, P, iterations, status): the squarings summed over the steps; status 0, or the first non-zero one of lyap_smith
+    (2 also when R + B'PB is not positive definite), with K and P then NaN.  steps = 0 returns K and P as given."""
+    A = np.asarray(A, dtype=np.float64)
+    m = A.shape[0]
+    B = np.asarray(B, dtype=np.float64).reshape(m, -1)
+    p = B.shape[1]
+    Q = np.asarray(Q, dtype=np.float64)
+    R = np.asarray(R, dtype=np.float64).reshape(p, p)
+    K, total = np.array(K, dtype=np.float64).reshape(p, m), 0
+    nan = (np.full((p, m), np.nan), np.full((m, m), np.nan))
+    if int(steps) > 0:
+        P = np.zeros((m, m)) if P is None else np.array(P, dtype=np.float64)
+    for _ in range(int(steps)):
+        Ac = A - B @ K
+        with np.errstate(all="ignore"):
+            res = (Ac.T @ P @ Ac - P) + (Q + K.T @ R @ K)
+        dP, it, status = lyap_smith(Ac, res, tol=tol, max_iter=max_iter)
+        total += it
+        if status != 0:
+            return nan[0], nan[1], total, status
+        P = P + dP
+        try:
+            K = scipy.linalg.cho_solve(scipy.linalg.cho_factor(R + _sym(B.T @ P @ B), lower=True), B.T @ P @ A)
+        except (np.linalg.LinAlgError, ValueError):
+            return nan[0], nan[1], total, 2
+    return K, P, total, 0
+
+
+def mpc_build_batch(As, Bs, Qs, Rs, Ns, Ps=None, C_rows=None, Nys=None, tol=1e-13, max_iter=40, newton_steps=1,
+                    newton_tol=1e-15, newton_max_iter=60):
+    """The controllers of a list of problems in ONE device call (nk_mpc_build_batch; m <= 512, p <= 4, N p <= 64): per problem
+    the Riccati solution by the doubling iteration (tol, max_iter), newton_steps steps of dare_newton_smith (newton_tol,
+    newton_max_iter), (H, F) of mpc_condense_blocked for the horizon Ns[i] and, with C_rows[i] (nc <= 4 rows) and Nys[i]
+    (default N), (G, T) of mpc_condense_outputs.  A terminal cost Ps[i] skips the Riccati and Newton stages: pure condensing,
+    K = (R + B'PB)^-1 B'PA.  Returns a dict of lists H, F, K, P, G, T (G, T None without rows) and the arrays status (0 =
+    success, 1 = doubling cap, 2 = non-finite / not positive definite, 3 = Smith cap: NaN outputs, the other problems
+    untouched) and iters (n, 2) = {doubling steps, Smith squarings}."""
+    from . import _lib
+    return _lib.get_context().mpc_build_batch(As, Bs, Qs, Rs, Ns, Ps=Ps, C_rows=C_rows, Nys=Nys, tol=tol, max_iter=max_iter,
+                                              newton_steps=newton_steps, newton_tol=newton_tol,
+                                              newton_max_iter=newton_max_iter)
+
+
 def mpc_diff(U, p):
     """D U: the block first difference, (D U)_k = u_k - u_{k-1}, (D U)_0 = u_0."""
     s = np.array(U, dtype=np.float64)

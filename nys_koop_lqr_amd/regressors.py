@@ -43,6 +43,92 @@ def _lqr_gain_batch(regs, c, R=None, tol=1e-13, max_iter=40):
 
 
 DARE_BATCH_MAX_M, DARE_BATCH_MAX_P = 256, 8  # limits of nk_dare_batch (include/nyskoop.h)
+MPC_BUILD_MAX_ROWS = 4  # output rows per step of nk_model_mpc_build_batch (include/nyskoop.h)
+
+
+def _mpc_build_batch(regs, c, R, specs, **solver):
+    """(units, status, iterations) of nk_model_mpc_build_batch for fitted regressors in ONE device call: specs[u] = (N, comps,
+    Ny); units[u] = dict(H, F, K, G, T).  A module-level seam: tests without a GPU replace it."""
+    ctx = _lib.get_context()
+    handles = [r._ensure_model() for r in regs]
+    dims = [(int(r._landmark_shape()[1]), int(r.n_inputs)) for r in regs]
+    return ctx.model_mpc_build_batch(handles, dims, c, R, specs, **solver)
+
+
+def _mpc_controller_batch(regs, c, controller):
+    """The controllers of fitted regressors for the checked `controller` dict of harness.lqr_sweep, built by ONE device call
+    (reg.solve_mpc(..., device=True) for all of them at once).  Returns (controllers, status): a unit whose limits solve_mpc
+    refuses has None and status -1 and is not part of the call; a unit with a non-zero build status has None."""
+    n = len(regs)
+    limits = [None] * n
+    for i, reg in enumerate(regs):
+        try:
+            limits[i] = _mpc_limits(reg, controller["horizon"], controller["u_min"], controller["u_max"], controller["du_min"],
+                                        controller["du_max"], controller.get("x_min"), controller.get("x_max"),
+                                        controller.get("y_horizon"), device=True)
+        except ValueError:
+            pass
+    live = [i for i in range(n) if limits[i] is not None]
+    ctrls, status = [None] * n, np.full(n, -1, dtype=np.int32)
+    if live:
+        units, st, _ = _mpc_build_batch([regs[i] for i in live], c, None,
+                                        [(controller["horizon"], limits[i]["comps"], limits[i]["Ny"]) for i in live])
+        for k, i in enumerate(live):
+            status[i] = int(st[k])
+            if status[i] == 0:
+                try:
+                    ctrls[i] = _mpc_controller(units[k], limits[i], controller["horizon"], controller["rho"],
+                                               controller.get("y_weight", np.inf))
+                except (ValueError, np.linalg.LinAlgError):
+                    pass
+    return ctrls, status
+
+
+def _mpc_limits(reg, horizon, u_min, u_max, du_min, du_max, x_min, x_max, y_horizon, device=False):
+    """The checked limits of reg.solve_mpc: dict(lo, hi, dlo, dhi (nv entries each), xlo, xhi (d entries), comps (the state
+    components with a finite bound), Ny).  Raises ValueError as solve_mpc does."""
+    from . import lqr
+    p = int(reg.n_inputs)
+    lo, hi, dlo, dhi = lqr.mpc_bounds(int(horizon) * p, u_min, u_max, du_min, du_max)
+    if np.any(lo > hi) or np.any(dlo > dhi):
+        raise ValueError("u_min <= u_max and du_min <= du_max are required")
+    lim = dict(lo=lo, hi=hi, dlo=dlo, dhi=dhi, xlo=None, xhi=None, comps=np.zeros(0, dtype=np.int64), Ny=None)
+    if x_min is None and x_max is None:
+        return lim
+    d = int(reg._landmark_shape()[0]) if device else np.shape(reg.C)[0]
+
+    def full(a, missing):
+        if a is None:
+            return np.full(d, missing)
+        a = np.asarray(a, dtype=np.float64).reshape(-1)
+        if a.size not in (1, d):
+            raise ValueError(f"a state bound of {a.size} entries, the model has {d} states")
+        return np.ascontiguousarray(np.broadcast_to(a, (d,)))
+    xlo, xhi = full(x_min, -np.inf), full(x_max, np.inf)
+    if np.any(np.isnan(xlo)) or np.any(np.isnan(xhi)) or np.any(xlo > xhi):
+        raise ValueError("x_min <= x_max is required")
+    comps = np.flatnonzero(np.isfinite(xlo) | np.isfinite(xhi))
+    if comps.size:
+        Ny = int(horizon) if y_horizon is None else int(y_horizon)
+        if device and comps.size > MPC_BUILD_MAX_ROWS:
+            raise ValueError(f"{comps.size} state components have a finite bound: the device build takes at most "
+                             f"{MPC_BUILD_MAX_ROWS} output rows per step")
+        if device and not 1 <= Ny <= int(horizon):
+            raise ValueError("the horizons must satisfy 1 <= Ny <= N")
+        lim.update(xlo=xlo, xhi=xhi, comps=comps, Ny=Ny)
+    return lim
+
+
+def _mpc_controller(built, lim, horizon, rho, y_weight):
+    """The lqr.MPCController / MPCOutputController of built matrices (H, F, K and G, T with rows) and checked limits."""
+    from . import lqr
+    H, F, K = built["H"], built["F"], built["K"]
+    rho = lqr.mpc_default_rho(H) if rho is None else rho
+    if lim["comps"].size == 0:
+        return lqr.MPCController(H, F, lim["lo"], lim["hi"], lim["dlo"], lim["dhi"], K, rho, horizon)
+    comps, Ny = lim["comps"], lim["Ny"]
+    return lqr.MPCOutputController(H, F, lim["lo"], lim["hi"], lim["dlo"], lim["dhi"], K, rho, horizon, built["G"], built["T"],
+                                   np.tile(lim["xlo"][comps], Ny), np.tile(lim["xhi"][comps], Ny), np.tile(comps, Ny), y_weight)
 
 
 def _is_device_tensor(x):
@@ -492,7 +578,7 @@ class _DeviceModelRegressor(KoopmanRegressor):
         return ox, ou
 
     def solve_mpc(self, horizon, c=1.0, R=None, u_min=None, u_max=None, du_min=None, du_max=None, Q=None, rho=None,
-                  x_min=None, x_max=None, y_horizon=None, y_weight=np.inf):
+                  x_min=None, x_max=None, y_horizon=None, y_weight=np.inf, device=False):
         """The constrained Koopman MPC of this model: lqr.MPCController with the condensed QP of
         sum_{k<N} (e_k'Q e_k + u_k'R u_k) + e_N'P e_N over the horizon N (lqr.mpc_condense on the host; Q = c sym(C'C), R = I
         by default; P and the gain K from lqr.dlqr, refined by two Newton steps (lqr.dare_refine) so that the first move of the
@@ -508,9 +594,25 @@ class _DeviceModelRegressor(KoopmanRegressor):
         outside its limits needs this; weights far above rho, 1e3 rho say, converge very slowly).  The rows of a sampled plant
         are small beside the identity rows of the inputs, so the output rows want a rho far above the default (300 x the
         default reached a hard velocity limit within 2 % in 100 iterations on the Duffing models; with the default the
-        controls did not move).  N p + rows <= 64 for the device loop.  Without these arguments the result is what it always was."""
+        controls did not move).  N p + rows <= 64 for the device loop.  Without these arguments the result is what it always was.
+
+        device=True: the same controller built by ONE nk_model_mpc_build_batch call (csrc/nk_mpc_build.hip): Q = c sym(C'C)
+        formed on the device from the model's own operators (so Q must be None), P and K by the doubling Riccati solver and one
+        Newton step (lqr.dare_newton_smith), H, F (lqr.mpc_condense_blocked) and G, T on the device; rho, the bounds and the row
+        bookkeeping stay on the host.  m <= 512, p <= 4, at most 4 bounded state components.  Raises np.linalg.LinAlgError
+        when the build reports a non-zero status, as lqr.dlqr_device does."""
         from . import lqr
         p = int(self.n_inputs)
+        if device:
+            if Q is not None:
+                raise ValueError("solve_mpc(device=True) forms Q = c sym(C'C) on the device: pass c, not Q")
+            lim = _mpc_limits(self, horizon, u_min, u_max, du_min, du_max, x_min, x_max, y_horizon, device=True)
+            units, status, _ = _mpc_build_batch([self], c, R, [(int(horizon), lim["comps"], lim["Ny"])])
+            if int(status[0]) != 0:
+                raise np.linalg.LinAlgError(f"device controller build failed with status {int(status[0])} (1: the doubling "
+                                            "iteration reached max_iter, 2: non-finite values or a matrix that is not positive "
+                                            "definite, 3: the Smith iteration reached its cap)")
+            return _mpc_controller(units[0], lim, horizon, rho, y_weight)
         if Q is None:
             Q = c * self.C.T @ self.C
             Q = (Q + Q.T) / 2
@@ -519,31 +621,12 @@ class _DeviceModelRegressor(KoopmanRegressor):
         A, B = np.asarray(self.A, dtype=np.float64), np.asarray(self.B, dtype=np.float64)
         K, P = lqr.dare_refine(A, B, Q, R, dlqr(A, B, Q, R)[0])
         H, F = lqr.mpc_condense(A, B, Q, R, P, horizon)
-        lo, hi, dlo, dhi = lqr.mpc_bounds(int(horizon) * p, u_min, u_max, du_min, du_max)
-        if np.any(lo > hi) or np.any(dlo > dhi):
-            raise ValueError("u_min <= u_max and du_min <= du_max are required")
-        rho = lqr.mpc_default_rho(H) if rho is None else rho
-        if x_min is None and x_max is None:
-            return lqr.MPCController(H, F, lo, hi, dlo, dhi, K, rho, horizon)
-        d = np.shape(self.C)[0]
-
-        def full(a, missing):
-            if a is None:
-                return np.full(d, missing)
-            a = np.asarray(a, dtype=np.float64).reshape(-1)
-            if a.size not in (1, d):
-                raise ValueError(f"a state bound of {a.size} entries, the model has {d} states")
-            return np.ascontiguousarray(np.broadcast_to(a, (d,)))
-        xlo, xhi = full(x_min, -np.inf), full(x_max, np.inf)
-        if np.any(np.isnan(xlo)) or np.any(np.isnan(xhi)) or np.any(xlo > xhi):
-            raise ValueError("x_min <= x_max is required")
-        comps = np.flatnonzero(np.isfinite(xlo) | np.isfinite(xhi))
-        if comps.size == 0:  # no finite bound: no output row
-            return lqr.MPCController(H, F, lo, hi, dlo, dhi, K, rho, horizon)
-        Ny = int(horizon) if y_horizon is None else int(y_horizon)
-        G, T = lqr.mpc_condense_outputs(A, B, np.asarray(self.C, dtype=np.float64)[comps], horizon, Ny)
-        return lqr.MPCOutputController(H, F, lo, hi, dlo, dhi, K, rho, horizon, G, T, np.tile(xlo[comps], Ny),
-                                       np.tile(xhi[comps], Ny), np.tile(comps, Ny), y_weight)
+        lim = _mpc_limits(self, horizon, u_min, u_max, du_min, du_max, x_min, x_max, y_horizon)
+        built = dict(H=H, F=F, K=K)
+        if lim["comps"].size:
+            built["G"], built["T"] = lqr.mpc_condense_outputs(A, B, np.asarray(self.C, dtype=np.float64)[lim["comps"]], horizon,
+                                                              lim["Ny"])
+        return _mpc_controller(built, lim, horizon, rho, y_weight)
 
     def closed_loop_plant_mpc(self, controller, x0, x_ref, num_steps, plant, iters=50, tol=0.0, u_init=None,
                               return_info=False):
