@@ -1,7 +1,7 @@
 // Closed loops that run as one launch behind the C ABI: the plant loops (nk_plant_step, nk_plant_loop, nk_plant_loop_multi and
 // their forms for a polynomial plant the caller describes, nk_poly_plant_*; nk_plant_loop.hip), the constrained MPC loop
 // (nk_mpc_loop, nk_mpc_loop_multi, nk_mpc_qp_host; nk_mpc_loop.hip, nk_mpc.h), its form with limits on predicted states
-// (nk_mpc_out_loop, nk_mpc_out_qp_host; nk_mpc_out_loop.hip, nk_mpc_out.h) and the lifted loop of many models
+// (nk_mpc_out_loop, nk_mpc_out_qp_host; nk_mpc_loop.hip, nk_mpc_out.h) and the lifted loop of many models
 // (nk_closed_loop_multi; nk_loop_multi.hip).  The unit-table calls
 // check every unit, lay its host operands out in one staging block (nk_unit_pack.h), move it with one copy, build the
 // table of device records, launch, and bring the results back behind one synchronisation.
@@ -619,8 +619,7 @@ static int mpc_multi_run(const char* who, nk_ctx* ctx, const nk_poly_plant* plan
   if (out_u) NK_TRY(stage_out(ctx, out_u, p, (int64_t)n_units * steps, p, &ou));
   if (out_info) NK_TRY(stage_out(ctx, out_info, 2, (int64_t)n_units * steps, 2, &oi));
   // the records of the two kinds, each in unit order: a kind is launched only when it has units
-  std::vector<MpcLoopUnit> recs;
-  std::vector<MpcOutLoopUnit> orecs;
+  std::vector<MpcLoopUnit> recs, orecs;
   std::vector<int> ktypes, oktypes;
   recs.reserve((size_t)(n_units - n_rows)); ktypes.reserve((size_t)(n_units - n_rows));
   orecs.reserve((size_t)n_rows); oktypes.reserve((size_t)n_rows);
@@ -628,60 +627,38 @@ static int mpc_multi_run(const char* who, nk_ctx* ctx, const nk_poly_plant* plan
     const nk_mpc_unit& un = units[u];
     const nk_mpc_out* out = outs ? outs[u] : nullptr;
     const nk_model* mdl = un.model;
-    const int m = mdl->m, nv = nvs[u];
-    double* const r_out_x = out_x ? ox.dev + (int64_t)u * (steps + 1) * ox.ld : nullptr;
-    double* const r_out_u = out_u ? ou.dev + (int64_t)u * steps * ou.ld : nullptr;
-    double* const r_out_info = out_info ? oi.dev + (int64_t)u * steps * oi.ld : nullptr;
-    const double* const r_uopt = un.uopt >= 0 ? uo.ptr + (int64_t)un.uopt * uo.ld : nullptr;
-    double* const r_score = scores ? d_sc + (size_t)n_scores * u : nullptr;
-    if (out) {
-      // the fold of nk_mpc_out_loop by the same call on the same operands (the rows of [F; T] have their leading dimension
-      // there), queued back to back with the others
-      const int nt = nv + out->ny;
-      const MpcOutUnitOffsets& o = ooff[u];
-      orecs.emplace_back();
-      MpcOutLoopUnit& r = orecs.back();
-      r.w = d_in + o.FT;
-      if (mdl->kind != NK_MODEL_SPLINE) {
-        double* wf = d_w + o.w;
-        if (first[u] == u)
-          NK_TRY(launch_gemm(ctx, false, true, m, nt, m, 1.0, mdl->Sinv, m, d_in + o.FT, (int64_t)gain_row_reserve((size_t)m),
-                             0.0, wf, nt));
-        r.w = wf;
-      }
-      r.Z = mdl->Z; r.winv = mdl->winv;
-      r.Kb = d_in + o.Kb; r.S0t = d_in + o.S0t; r.bnd = d_in + o.bnd;
-      r.x0 = d_in + o.x0; r.xref = d_in + o.x_ref; r.uinit = un.u_init ? d_in + o.u_init : nullptr;
-      r.out_x = r_out_x; r.ldx = out_x ? ox.ld : 0;
-      r.out_u = r_out_u; r.ldu = out_u ? ou.ld : 0;
-      r.out_info = r_out_info; r.u_opt = r_uopt; r.score = r_score;
-      r.sigma0sq = mdl->sigma0 * mdl->sigma0; r.rho = un.desc->rho; r.tol = un.desc->tol;
-      r.theta = mpc_out_theta(un.desc->rho, out->y_weight);
-      r.m = m; r.nv = nv; r.ny = out->ny; r.iters = un.desc->iters;
-      oktypes.push_back(mdl->ktype);
-      continue;
-    }
-    recs.emplace_back();
-    MpcLoopUnit& r = recs.back();
-    // the fold of nk_mpc_loop by the same call on the same operands (the rows of F or K have their leading dimension there);
-    // the folds of all units are queued back to back, nothing waits between them
-    r.w = d_in + off[u].G;
+    const int m = mdl->m, nv = nvs[u], ny = out ? out->ny : 0, nt = nv + ny;
+    // where the unit's pieces lie: with rows [F; T], Kb, S0'; without them F or K, M, H^-1.  (Only the offsets of the unit's
+    // own kind were filled above; the other record is all zeros and is named in the untaken branches alone.)
+    const MpcUnitOffsets& o = off[u];
+    const MpcOutUnitOffsets& oo = ooff[u];
+    const size_t at_G = out ? oo.FT : o.G, at_w = out ? oo.w : o.w, at_Kb = out ? oo.Kb : o.M, at_S0t = out ? oo.S0t : o.Hinv,
+                 at_bnd = out ? oo.bnd : o.bnd, at_x0 = out ? oo.x0 : o.x0, at_xref = out ? oo.x_ref : o.x_ref,
+                 at_uinit = out ? oo.u_init : o.u_init;
+    MpcLoopUnit r;
+    // the fold of the single call by the same call on the same operands (the rows of F, K or [F; T] have their leading
+    // dimension there); the folds of all units are queued back to back, nothing waits between them
+    r.w = d_in + at_G;
     if (mdl->kind != NK_MODEL_SPLINE) {
-      double* wf = d_w + off[u].w;
+      double* wf = d_w + at_w;
       if (first[u] == u)
-        NK_TRY(launch_gemm(ctx, false, true, m, nv, m, 1.0, mdl->Sinv, m, d_in + off[u].G, (int64_t)gain_row_reserve((size_t)m),
-                           0.0, wf, nv));
+        NK_TRY(launch_gemm(ctx, false, true, m, nt, m, 1.0, mdl->Sinv, m, d_in + at_G, (int64_t)gain_row_reserve((size_t)m), 0.0,
+                           wf, nt));
       r.w = wf;
     }
     r.Z = mdl->Z; r.winv = mdl->winv;
-    r.M = d_in + off[u].M; r.Hinv = d_in + off[u].Hinv; r.bnd = d_in + off[u].bnd;
-    r.x0 = d_in + off[u].x0; r.xref = d_in + off[u].x_ref; r.uinit = un.u_init ? d_in + off[u].u_init : nullptr;
-    r.out_x = r_out_x; r.ldx = out_x ? ox.ld : 0;
-    r.out_u = r_out_u; r.ldu = out_u ? ou.ld : 0;
-    r.out_info = r_out_info; r.u_opt = r_uopt; r.score = r_score;
+    r.Kb = d_in + at_Kb; r.S0t = d_in + at_S0t; r.bnd = d_in + at_bnd;
+    r.x0 = d_in + at_x0; r.xref = d_in + at_xref; r.uinit = un.u_init ? d_in + at_uinit : nullptr;
+    r.out_x = out_x ? ox.dev + (int64_t)u * (steps + 1) * ox.ld : nullptr; r.ldx = out_x ? ox.ld : 0;
+    r.out_u = out_u ? ou.dev + (int64_t)u * steps * ou.ld : nullptr; r.ldu = out_u ? ou.ld : 0;
+    r.out_info = out_info ? oi.dev + (int64_t)u * steps * oi.ld : nullptr;
+    r.u_opt = un.uopt >= 0 ? uo.ptr + (int64_t)un.uopt * uo.ld : nullptr;
+    r.score = scores ? d_sc + (size_t)n_scores * u : nullptr;
     r.sigma0sq = mdl->sigma0 * mdl->sigma0; r.rho = un.desc->rho; r.tol = un.desc->tol;
-    r.m = m; r.nv = nv; r.iters = un.desc->iters; r.reserved = 0;
-    ktypes.push_back(mdl->ktype);
+    r.theta = out ? mpc_out_theta(un.desc->rho, out->y_weight) : 0.0;
+    r.m = m; r.nv = nv; r.ny = ny; r.iters = un.desc->iters;
+    (out ? orecs : recs).push_back(r);
+    (out ? oktypes : ktypes).push_back(mdl->ktype);
   }
   if (!recs.empty()) NK_TRY(launch_mpc_loop_multi(ctx, *plant, steps, recs.data(), ktypes.data(), (int)recs.size()));
   if (!orecs.empty()) NK_TRY(launch_mpc_out_loop_multi(ctx, *plant, steps, orecs.data(), oktypes.data(), (int)orecs.size()));

@@ -579,9 +579,11 @@ void plant_step_host(int plant, double Ts, const double* x, double u, double* x_
 int launch_plant_loop(nk_ctx* ctx, const nk_model* mdl, int plant, double Ts, const double* w, const double* x0,
                       int64_t x0_stride, const double* xref, int64_t xref_stride, int steps, int batch, double* out_x,
                       int64_t ldx, double* out_u, int64_t ldu);
-// The multi-model form (nk_plant_loop_multi): one record per unit, every pointer device memory.  The records are sorted
-// into classes of (kernel family, landmarks per lane, waves per workgroup), staged with one copy and run with one launch
-// per class; a workgroup finds its record by its block index.  out_x / out_u / u_opt / score may be null per unit.
+// The record of one loop, every pointer device memory.  The single call passes the record of batch member 0 and the strides
+// to the others (LoopStrides, nk_loop_lanes.h; u_opt and score null).  The multi-model form (nk_plant_loop_multi) stages one
+// record per unit: sorted into classes of (kernel family, landmarks per lane, waves per workgroup; nk_loop_classes.h), moved
+// with one copy and run with one launch per class; a workgroup finds its record by its block index.  out_x / out_u / u_opt /
+// score may be null per unit there.
 struct PlantLoopUnit {
   const double* Z;      // m x d landmarks
   const double* winv;   // d
@@ -599,7 +601,8 @@ struct PlantLoopUnit {
 int launch_plant_loop_multi(nk_ctx* ctx, int plant, double Ts, int steps, PlantLoopUnit* units, const int* ktypes,
                             int n_units);
 // The same loops around a polynomial plant the caller describes (nk_poly_plant.h; nk_poly_plant_loop and its multi form): d
-// states, p inputs, the plant table by value in the kernel arguments.  One record per loop, every pointer device memory.
+// states, p inputs, the plant table by value in the kernel arguments.  One record per loop, every pointer device memory, used
+// by the single call and the multi form as PlantLoopUnit is.
 // W: the folded gain, entry (landmark l, input j) at w[l * w_ls + j * w_js]; out_u: steps rows of ldu, p columns; u_opt:
 // steps x p, dense.  Classes of a launch: (kernel family, landmarks per lane, waves per workgroup); the kernels are
 // instantiated for the states and inputs padded with exact zeros to D in {2, 4} and P in {1, 2, 4}.
@@ -632,7 +635,7 @@ int launch_mpc_loop(nk_ctx* ctx, const nk_model* mdl, const nk_poly_plant& plant
                     const double* w, const double* M, const double* Hinv, const double* bnd, const double* x0, int64_t x0_stride,
                     const double* xref, int64_t xref_stride, const double* uinit, int64_t uinit_stride, int steps, int batch,
                     double* out_x, int64_t ldx, double* out_u, int64_t ldu, double* out_info);
-// The same loop with ny output rows (nk_mpc_out_loop.hip; nk_mpc_out_loop), nt = nv + ny lanes: w the folded map of [F; T]
+// The same loop with ny output rows (nk_mpc_loop.hip; nk_mpc_out_loop), nt = nv + ny lanes: w the folded map of [F; T]
 // (m x nt), Kb (nt x nt) and S0 transposed (nv x nt) of mpc_out_prepare (nk_mpc_out.h); bnd: five rows of nt -- lo, hi, dlo,
 // dhi (output lanes: ylo, yhi, -inf, +inf) and ycomp as a double (-1 in the input lanes).  m <= mpc_loop_max_m(nt).
 int launch_mpc_out_loop(nk_ctx* ctx, const nk_model* mdl, const nk_poly_plant& plant, int nv, int ny, int iters, double rho,
@@ -640,55 +643,39 @@ int launch_mpc_out_loop(nk_ctx* ctx, const nk_model* mdl, const nk_poly_plant& p
                         const double* x0, int64_t x0_stride, const double* xref, int64_t xref_stride, const double* uinit,
                         int64_t uinit_stride, int steps, int batch, double* out_x, int64_t ldx, double* out_u, int64_t ldu,
                         double* out_info);
-// The multi-model form (nk_mpc_loop_multi): one record per unit, every pointer device memory.  The records are sorted into
-// classes of (kernel family, variables padded to 16 / 32 / 64, waves per workgroup), staged with one copy and run with one
-// launch per class, its dynamic LDS the largest need among its units; a workgroup finds its record by its block index.
-// out_x / out_u / out_info / u_opt / score / uinit may be null per unit.
+// The record of one MPC loop, every pointer device memory: what a workgroup of either form works on.  The single calls pass
+// the record of batch member 0 and the strides to the others (LoopStrides, nk_loop_lanes.h); the multi-model forms
+// (nk_mpc_loop_multi, nk_mpc_out_loop_multi) stage one record per unit, sorted into classes of (kernel family, nt = nv + ny
+// padded to 16 / 32 / 64, waves per workgroup), with one copy and run one launch per class, its dynamic LDS the largest need
+// among its units; a workgroup finds its record by its block index.  out_x / out_u / out_info / u_opt / score / uinit may be
+// null per unit there.  Without output rows ny = 0 and theta = 0 (neither is read), bnd has four rows and Kb, S0t are M and
+// H^-1 (symmetric, so its transpose); with them nt = nv + ny, the fields are those of mpc_out_prepare (nk_mpc_out.h), and
+// score has the NK_MPC_OUT_N_SCORES scores (the eight of nk_mpc_loop_multi, then y_viol_max and n_y_viol).
 struct MpcLoopUnit {
   const double* Z;      // m x d landmarks
   const double* winv;   // d
-  const double* w;      // m x nv folded gradient map (iters = 0: m x p folded gain), dense
-  const double* M;      // nv x nv (unused for iters = 0)
-  const double* Hinv;   // nv x nv
-  const double* bnd;    // 4 x nv: lo, hi, dlo, dhi (infinite where the caller gave none)
+  const double* w;      // m x nt folded map of F or [F; T] (iters = 0: m x p folded gain), dense
+  const double* Kb;     // nt x nt: M, or Kb of the folded iteration (unused for iters = 0)
+  const double* S0t;    // nv x nt: H^-1, or S0 = [H^-1; G H^-1] transposed
+  const double* bnd;    // rows of nt: lo, hi, dlo, dhi (infinite where the caller gave none; output lanes: ylo, yhi, -inf, inf),
+                        // with output rows a fifth: ycomp as a double (-1 in the input lanes)
   const double* x0;     // d
   const double* xref;   // d
   const double* uinit;  // p, or nullptr (zeros)
-  double* out_x;        // (steps + 1) rows of ldx, or nullptr (multi form)
-  double* out_u;        // steps rows of ldu, or nullptr (multi form)
+  double* out_x;        // (steps + 1) rows of ldx, or nullptr (multi forms)
+  double* out_u;        // steps rows of ldu, or nullptr (multi forms)
   double* out_info;     // steps rows of 2, or nullptr
   const double* u_opt;  // steps x p controls to score against, or nullptr
-  double* score;        // the NK_MPC_N_SCORES scores, or nullptr
+  double* score;        // the NK_MPC_N_SCORES / NK_MPC_OUT_N_SCORES scores, or nullptr
   int64_t ldx, ldu;
   double sigma0sq, rho, tol;
-  int m, nv, iters, reserved;
+  int m, nv, iters, ny;
+  double theta;  // (ny and theta behind the fields the loop without rows reads: those keep the offsets they had, and with them
+                 // the scored kernels of that loop their register counts)
 };
 int launch_mpc_loop_multi(nk_ctx* ctx, const nk_poly_plant& plant, int steps, MpcLoopUnit* units, const int* ktypes,
                           int n_units);
-// The multi-model form of the loop with output rows (nk_mpc_out_loop_multi): the fields of launch_mpc_out_loop with the batch
-// strides resolved, one record per unit, every pointer device memory.  Classes of a launch: (kernel family, nt = nv + ny
-// padded to 16 / 32 / 64, waves per workgroup); staged and launched as launch_mpc_loop_multi does.  score: the
-// NK_MPC_OUT_N_SCORES scores (the eight of MpcLoopUnit, then y_viol_max and n_y_viol).
-struct MpcOutLoopUnit {
-  const double* Z;      // m x d landmarks
-  const double* winv;   // d
-  const double* w;      // m x nt folded map of [F; T], dense
-  const double* Kb;     // nt x nt
-  const double* S0t;    // nv x nt: S0 transposed
-  const double* bnd;    // 5 x nt: lo, hi, dlo, dhi (output lanes: ylo, yhi, -inf, inf), ycomp as a double
-  const double* x0;     // d
-  const double* xref;   // d
-  const double* uinit;  // p, or nullptr (zeros)
-  double* out_x;        // (steps + 1) rows of ldx, or nullptr (multi form)
-  double* out_u;        // steps rows of ldu, or nullptr (multi form)
-  double* out_info;     // steps rows of 2, or nullptr
-  const double* u_opt;  // steps x p controls to score against, or nullptr
-  double* score;        // the NK_MPC_OUT_N_SCORES scores, or nullptr
-  int64_t ldx, ldu;
-  double sigma0sq, rho, tol, theta;
-  int m, nv, ny, iters;
-};
-int launch_mpc_out_loop_multi(nk_ctx* ctx, const nk_poly_plant& plant, int steps, MpcOutLoopUnit* units, const int* ktypes,
+int launch_mpc_out_loop_multi(nk_ctx* ctx, const nk_poly_plant& plant, int steps, MpcLoopUnit* units, const int* ktypes,
                               int n_units);
 
 // ---- lifted closed loops of many models in ONE launch, scored on the device (nk_loop_multi.hip): one 1024-thread workgroup

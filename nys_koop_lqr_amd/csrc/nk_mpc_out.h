@@ -1,7 +1,7 @@
 // Limits on predicted states in the constrained Koopman MPC (nk_mpc_out beside nk_mpc_desc, include/nyskoop.h) on the host:
 // the validation of the output rows, the matrices a call forms once (M = (H + rho (I + D'D + G'G))^-1 by Cholesky, the folded
 // Kb = [[M, M G'], [G M, G M G']] and S0 = [H^-1; G H^-1]) and the folded fixed-step ADMM iteration whose order of operations
-// the interface states.  nk_mpc_out_qp_host is this file behind the C ABI; the device loop (nk_mpc_out_loop.hip) runs the same
+// the interface states.  nk_mpc_out_qp_host is this file behind the C ABI; the device loop (nk_mpc_loop.hip, OUT = true) runs the same
 // steps with one lane per entry of s_K = (s_1, s_3).  No HIP include: a plain C++17 compiler builds this header
 // (tests/mpc_out_main.cpp).
 #pragma once

@@ -17,40 +17,17 @@
 // a trajectory has the same bits alone or in any batch.  All lanes advance the plant (same operands, same bits); thread
 // 0 stores x_{t+1} and u_t with ordinary vector stores that nothing in the loop waits for.
 #include "nk_common.h"
+#include "nk_loop_lanes.h"
 #include "nk_plant.h"
 #include "nk_poly_plant.h"
 #include "nk_poly_lanes.h"
 
-#include <algorithm>
 #include <type_traits>
-#include <vector>
 
 namespace nk {
 
-struct PlantLoopParams {
-  const double* Z;      // m x d landmarks
-  const double* winv;   // d
-  const double* w;      // m folded gain
-  int m;
-  double sigma0sq, Ts;
-  const double* x0; int64_t x0_stride;      // batch x d
-  const double* xref; int64_t xref_stride;  // batch x d (stride 0: shared)
-  double* out_x; int64_t ldx;               // rows b * (steps + 1) + t, d columns
-  double* out_u; int64_t ldu;               // rows b * steps + t, one column
-  int steps;
-};
-
 constexpr int PLANT_LOOP_LPT = 4;
 constexpr int PLANT_LOOP_MAX_M = 64 * PLANT_LOOP_LPT * PLANT_LOOP_MAX_WAVES;
-
-// sum of one value over the 16 lanes of a DPP row, in every lane of the row
-__device__ __forceinline__ double row_sum16_dpp(double c) {
-  c += dpp_f64<0xB1>(c);   // quad_perm [1,0,3,2]
-  c += dpp_f64<0x4E>(c);   // quad_perm [2,3,0,1]
-  c += dpp_f64<0x141>(c);  // row_half_mirror
-  c += dpp_f64<0x140>(c);  // row_mirror
-  return c;
-}
 
 // sum_j w_j (kref_j - k(z_j, x)) over the landmarks of the workgroup, the same bits in every lane
 template <int KTYPE, int D, int LPT>
@@ -76,11 +53,13 @@ __device__ __forceinline__ double plant_feedback(const double* x, const double* 
   return s;
 }
 
-// One loop, as a workgroup sees it, is a PlantLoopUnit (nk_common.h).  nk_plant_loop builds the record from its kernel arguments
-// (PlantLoopParams and the block index); nk_plant_loop_multi reads it from a table in device memory, blockIdx.x = the record.
+// One loop, as a workgroup sees it, is a PlantLoopUnit (nk_common.h).  nk_plant_loop builds the record from the record of batch
+// member 0 and the block index (unit_of_block, nk_loop_lanes.h); nk_plant_loop_multi reads it from a table in device memory,
+// blockIdx.x = the record.
 // The loop of one workgroup.  SCORED = false: the body of nk_plant_loop (out_x, out_u always stored, no scores).
 // SCORED = true: out_x / out_u may be null (uniform over the workgroup), and the four scores of include/nyskoop.h are
-// accumulated in registers -- every lane holds u_t and x_{t+1} -- and stored once by thread 0 after the last step.
+// accumulated in registers (the helpers of nk_loop_lanes.h with one input) -- every lane holds u_t and x_{t+1} -- and stored
+// once by thread 0 after the last step.
 template <int PLANT, int KTYPE, int LPT, bool SCORED>
 __device__ __forceinline__ void plant_loop_body(const PlantLoopUnit& P, double Ts, int steps, double (&red)[2][PLANT_LOOP_MAX_WAVES]) {
   constexpr int D = PlantDim<PLANT>::value;
@@ -117,54 +96,25 @@ __device__ __forceinline__ void plant_loop_body(const PlantLoopUnit& P, double T
 #pragma unroll
     for (int k = 0; k < D; ++k) ox[k] = x[k];
   }
-  // scores (SCORED only): sse = sum (u_t - u_opt[t])^2, sso = sum u_opt[t]^2, J = the running cost of the reference's
-  // open_loop_control in its order, umax = max |u_t|, NaN from the first NaN control on
-  double sse = 0.0, sso = 0.0, J = 0.0, umax = 0.0, uo = 0.0;
+  double sse = 0.0, sso = 0.0, J = 0.0, umax = 0.0, uo[1] = {0.0};  // the scores (SCORED only)
   const double* uopt = SCORED ? P.u_opt : nullptr;
   if (SCORED) {
-#pragma clang fp contract(off)
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-      const double sq = x[k] * x[k];
-      J = k == 0 ? sq : J + sq;
-    }
-    if (uopt) uo = uopt[0];
+    J = sum_sq_ordered(x);
+    if (uopt) uo[0] = uopt[0];
   }
   __syncthreads();  // red is zeroed
   for (int t = 0; t < steps; ++t) {
     // buffer t & 1: a wave still reading it in step t is at most one barrier behind the wave that writes it again in t + 2
-    const double u = plant_feedback<KTYPE, D, LPT>(x, wi, zs, wj, kref, P.sigma0sq, red[t & 1], lane, wave, multi);
+    const double u[1] = {plant_feedback<KTYPE, D, LPT>(x, wi, zs, wj, kref, P.sigma0sq, red[t & 1], lane, wave, multi)};
     double xn[D];
-    plant_step<PLANT>(Ts, x, u, xn);
+    plant_step<PLANT>(Ts, x, u[0], xn);
 #pragma unroll
     for (int k = 0; k < D; ++k) x[k] = xn[k];
     if (SCORED) {
-#pragma clang fp contract(off)
-      double sx = 0.0;
-#pragma unroll
-      for (int k = 0; k < D; ++k) {
-        const double sq = x[k] * x[k];
-        sx = k == 0 ? sq : sx + sq;
-      }
-      const double usq = u * u;
-      J = (J + sx) + usq;
-      const double au = fabs(u);
-      umax = (au > umax || au != au) ? au : umax;  // a NaN enters once and stays: no later comparison is true
-      if (uopt) {
-        const double df = u - uo;
-        const double dsq = df * df, osq = uo * uo;
-        sse = sse + dsq;
-        sso = sso + osq;
-        uo = uopt[t + 1 < steps ? t + 1 : t];  // next step's value, loaded a step ahead (not on the chain)
-      }
+      score_cost_step(x, u, J, umax);
+      if (uopt) score_uopt_step(u, uo, uopt, (int64_t)(t + 1 < steps ? t + 1 : t), 1, sse, sso);
     }
-    if (tid == 0) {
-      if (st_u) ou[(int64_t)t * P.ldu] = u;
-      if (st_x) {
-#pragma unroll
-        for (int k = 0; k < D; ++k) ox[(int64_t)(t + 1) * P.ldx + k] = x[k];
-      }
-    }
+    if (tid == 0) store_step(ou, st_u, P.ldu, ox, st_x, P.ldx, (int64_t)t, u, 1, x, D);
   }
   if (SCORED && tid == 0 && P.score) {
     P.score[0] = sse;
@@ -175,19 +125,10 @@ __device__ __forceinline__ void plant_loop_body(const PlantLoopUnit& P, double T
 }
 
 template <int PLANT, int KTYPE, int LPT>
-__global__ void __launch_bounds__(LPT == 1 ? 64 : 64 * PLANT_LOOP_MAX_WAVES) plant_loop_kernel(PlantLoopParams P) {
-  constexpr int D = PlantDim<PLANT>::value;
-  (void)D;
+__global__ void __launch_bounds__(LPT == 1 ? 64 : 64 * PLANT_LOOP_MAX_WAVES)
+    plant_loop_kernel(PlantLoopUnit base, LoopStrides strides, double Ts) {
   __shared__ double red[2][PLANT_LOOP_MAX_WAVES];  // one partial sum per wave, two buffers (parity of the step)
-  const int b = blockIdx.x;
-  PlantLoopUnit U;
-  U.Z = P.Z; U.winv = P.winv; U.w = P.w; U.m = P.m; U.reserved = 0; U.sigma0sq = P.sigma0sq;
-  U.x0 = P.x0 + (int64_t)b * P.x0_stride;
-  U.xref = P.xref + (int64_t)b * P.xref_stride;
-  U.out_x = P.out_x + (int64_t)b * (P.steps + 1) * P.ldx; U.ldx = P.ldx;
-  U.out_u = P.out_u + (int64_t)b * P.steps * P.ldu; U.ldu = P.ldu;
-  U.u_opt = nullptr; U.score = nullptr;
-  plant_loop_body<PLANT, KTYPE, LPT, false>(U, P.Ts, P.steps, red);
+  plant_loop_body<PLANT, KTYPE, LPT, false>(unit_of_block(base, strides, blockIdx.x), Ts, strides.steps, red);
 }
 
 // the multi-model form: unit blockIdx.x of `table` (all units of a launch share KTYPE, LPT and the block size)
@@ -219,27 +160,17 @@ static auto with_plant(int plant, F&& f) {  // (the id has been checked: plant_d
   if (plant == NK_PLANT_DOUBLE_INTEGRATOR) return f(std::integral_constant<int, NK_PLANT_DOUBLE_INTEGRATOR>{});
   return f(std::integral_constant<int, NK_PLANT_HJB>{});
 }
-template <class F>
-static int with_kernel_family(const char* who, int ktype, F&& f) {
-  switch (ktype) {
-    case NK_KERNEL_RBF: f(std::integral_constant<int, NK_KERNEL_RBF>{}); break;
-    case NK_KERNEL_MATERN52: f(std::integral_constant<int, NK_KERNEL_MATERN52>{}); break;
-    case NK_KERNEL_LINEAR: f(std::integral_constant<int, NK_KERNEL_LINEAR>{}); break;
-    case NK_KERNEL_TPS: f(std::integral_constant<int, NK_KERNEL_TPS>{}); break;
-    default: set_error("%s: unknown kernel type %d", who, ktype); return NK_ERR_BAD_ARG;
-  }
-  NK_HIP(hipGetLastError());
-  return NK_OK;
-}
 // launch(plant, kernel family, landmarks per lane) for a launch whose workgroups have `lpt` landmarks per lane
 template <class F>
 static int plant_loop_dispatch(const char* who, int plant, int ktype, int lpt, F&& launch) {
-  return with_plant(plant, [&](auto pl) {
+  NK_TRY(with_plant(plant, [&](auto pl) {
     return with_kernel_family(who, ktype, [&](auto kt) {
       if (lpt == 1) launch(pl, kt, std::integral_constant<int, 1>{});
       else launch(pl, kt, std::integral_constant<int, PLANT_LOOP_LPT>{});
     });
-  });
+  }));
+  NK_HIP(hipGetLastError());
+  return NK_OK;
 }
 
 // nk_plant_step: one step of the plant in the host build of nk_plant.h (x_next may be x)
@@ -255,61 +186,39 @@ int launch_plant_loop(nk_ctx* ctx, const nk_model* mdl, int plant, double Ts, co
                       int64_t x0_stride, const double* xref, int64_t xref_stride, int steps, int batch, double* out_x,
                       int64_t ldx, double* out_u, int64_t ldu) {
   NK_REQUIRE(plant_dim(plant) == mdl->d && plant_loop_ok(mdl->m) && steps >= 1 && batch >= 1, "plant_loop: bad sizes");
-  PlantLoopParams P;
-  P.Z = mdl->Z; P.winv = mdl->winv; P.w = w; P.m = mdl->m; P.sigma0sq = mdl->sigma0 * mdl->sigma0; P.Ts = Ts;
-  P.x0 = x0; P.x0_stride = x0_stride; P.xref = xref; P.xref_stride = xref_stride;
-  P.out_x = out_x; P.ldx = ldx; P.out_u = out_u; P.ldu = ldu; P.steps = steps;
+  PlantLoopUnit U;  // batch member 0
+  U.Z = mdl->Z; U.winv = mdl->winv; U.w = w; U.m = mdl->m; U.reserved = 0; U.sigma0sq = mdl->sigma0 * mdl->sigma0;
+  U.x0 = x0; U.xref = xref; U.out_x = out_x; U.ldx = ldx; U.out_u = out_u; U.ldu = ldu;
+  U.u_opt = nullptr; U.score = nullptr;
+  const LoopStrides strides{x0_stride, xref_stride, 0, steps};
   int lpt = 0, waves = 0;
   plant_loop_class(mdl->m, &lpt, &waves);
   return plant_loop_dispatch("plant_loop", plant, mdl->ktype, lpt, [&](auto pl, auto kt, auto lp) {
     hipLaunchKernelGGL((plant_loop_kernel<decltype(pl)::value, decltype(kt)::value, decltype(lp)::value>), dim3(batch),
-                       dim3(64 * waves), 0, ctx->stream, P);
+                       dim3(64 * waves), 0, ctx->stream, U, strides, Ts);
   });
 }
 int plant_loop_max_m() { return PLANT_LOOP_MAX_M; }
 
 // ---- multi-model form ------------------------------------------------------------------------------------------------
-// units: host records holding device pointers, ktypes: the kernel family of each.  The records are sorted into classes of
-// (kernel family, landmarks per lane, waves) -- stable, so the order inside a class is the caller's --, staged with ONE
-// copy and run with one launch per class.  `units` is reordered in place and must stay alive until the stream has been
-// synchronised (the copy reads it).
+// units: host records holding device pointers, ktypes: the kernel family of each.  The records run through
+// launch_loop_classes (nk_loop_lanes.h) in classes of (kernel family, landmarks per lane, waves): `units` is reordered in place
+// and must stay alive until the stream has been synchronised.
 int launch_plant_loop_multi(nk_ctx* ctx, int plant, double Ts, int steps, PlantLoopUnit* units, const int* ktypes,
                             int n_units) {
   NK_REQUIRE(plant_dim(plant) > 0 && steps >= 1 && n_units >= 1, "plant_loop_multi: bad sizes");
-  struct Key { int ktype, lpt, waves, idx; };
-  std::vector<Key> keys((size_t)n_units);
-  for (int u = 0; u < n_units; ++u) {
-    NK_REQUIRE(plant_loop_ok(units[u].m), "plant_loop_multi: unit %d: bad m", u);
-    keys[u].ktype = ktypes[u];
-    keys[u].idx = u;
-    plant_loop_class(units[u].m, &keys[u].lpt, &keys[u].waves);
-  }
-  auto less = [](const Key& a, const Key& b) {
-    if (a.ktype != b.ktype) return a.ktype < b.ktype;
-    if (a.lpt != b.lpt) return a.lpt < b.lpt;
-    return a.waves < b.waves;
+  for (int u = 0; u < n_units; ++u) NK_REQUIRE(plant_loop_ok(units[u].m), "plant_loop_multi: unit %d: bad m", u);
+  auto key_of = [&](int u) {
+    LoopClass k{ktypes[u], 0, 0};
+    plant_loop_class(units[u].m, &k.shape, &k.waves);
+    return k;
   };
-  std::stable_sort(keys.begin(), keys.end(), less);
-  {
-    std::vector<PlantLoopUnit> sorted((size_t)n_units);
-    for (int u = 0; u < n_units; ++u) sorted[u] = units[keys[u].idx];
-    std::copy(sorted.begin(), sorted.end(), units);
-  }
-  PlantLoopUnit* table = nullptr;
-  NK_TRY(arena_alloc_t(ctx, (size_t)n_units, &table));
-  NK_HIP(hipMemcpyAsync(table, units, sizeof(PlantLoopUnit) * (size_t)n_units, hipMemcpyHostToDevice, ctx->stream));
-  for (int b = 0; b < n_units;) {
-    int e = b + 1;
-    while (e < n_units && !less(keys[b], keys[e])) ++e;
-    const Key& k = keys[b];
-    const PlantLoopUnit* first = table + b;
-    NK_TRY(plant_loop_dispatch("plant_loop_multi", plant, k.ktype, k.lpt, [&](auto pl, auto kt, auto lp) {
-      hipLaunchKernelGGL((plant_loop_multi_kernel<decltype(pl)::value, decltype(kt)::value, decltype(lp)::value>), dim3(e - b),
+  return launch_loop_classes(ctx, units, n_units, key_of, nullptr, [&](const PlantLoopUnit* first, int count, const LoopClass& k, long) {
+    return plant_loop_dispatch("plant_loop_multi", plant, k.ktype, k.shape, [&](auto pl, auto kt, auto lp) {
+      hipLaunchKernelGGL((plant_loop_multi_kernel<decltype(pl)::value, decltype(kt)::value, decltype(lp)::value>), dim3(count),
                          dim3(64 * k.waves), 0, ctx->stream, first, Ts, steps);
-    }));
-    b = e;
-  }
-  return NK_OK;
+    });
+  });
 }
 
 // =====================================================================================================================
@@ -323,20 +232,6 @@ int launch_plant_loop_multi(nk_ctx* ctx, int plant, double Ts, int steps, PlantL
 // length scales, weights and controls beyond the plant's d and p are exact zeros, which changes no bit of the others.
 // Every summation order is fixed by m and P alone.
 // =====================================================================================================================
-struct PolyLoopParams {
-  const double* Z;      // m x d landmarks
-  const double* winv;   // d
-  const double* w;      // folded gain, entry (l, j) at w[l * w_ls + j * w_js]
-  int64_t w_ls, w_js;
-  int m;
-  double sigma0sq;
-  const double* x0; int64_t x0_stride;      // batch x d
-  const double* xref; int64_t xref_stride;  // batch x d (stride 0: shared)
-  double* out_x; int64_t ldx;               // rows b * (steps + 1) + t, d columns
-  double* out_u; int64_t ldu;               // rows b * steps + t, p columns
-  int steps;
-};
-
 constexpr int poly_pad_p(int p) { return p == 3 ? 4 : p; }
 // Landmarks per lane of the workgroups of more than 64 landmarks: the most (of 4, 2, 1) at which both 16-wave kernels of the
 // class (the scored one needs more) keep everything in their 128 registers per lane -- no scratch; DESIGN.md 5d lists what
@@ -425,12 +320,7 @@ __device__ __forceinline__ void poly_loop_body(const PolyLoopUnit& U, const Poly
   for (int j = 0; j < P; ++j) uo[j] = 0.0;
   const double* uopt = SCORED ? U.u_opt : nullptr;
   if (SCORED) {
-#pragma clang fp contract(off)
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-      const double sq = x[k] * x[k];
-      J = k == 0 ? sq : J + sq;
-    }
+    J = sum_sq_ordered(x);
     if (uopt) {
 #pragma unroll
       for (int j = 0; j < P; ++j)
@@ -448,45 +338,10 @@ __device__ __forceinline__ void poly_loop_body(const PolyLoopUnit& U, const Poly
 #pragma unroll
     for (int k = 0; k < D; ++k) x[k] = xn[k];
     if (SCORED) {
-#pragma clang fp contract(off)
-      double sx = 0.0, su = 0.0;
-#pragma unroll
-      for (int k = 0; k < D; ++k) {
-        const double sq = x[k] * x[k];
-        sx = k == 0 ? sq : sx + sq;
-      }
-#pragma unroll
-      for (int j = 0; j < P; ++j) {
-        const double sq = u[j] * u[j];
-        su = j == 0 ? sq : su + sq;
-        const double au = fabs(u[j]);
-        umax = (au > umax || au != au) ? au : umax;  // a NaN enters once and stays: no later comparison is true
-      }
-      J = (J + sx) + su;
-      if (uopt) {
-        const int64_t tn = t + 1 < steps ? t + 1 : t;
-#pragma unroll
-        for (int j = 0; j < P; ++j) {
-          const double df = u[j] - uo[j];
-          const double dsq = df * df, osq = uo[j] * uo[j];
-          sse = sse + dsq;
-          sso = sso + osq;
-          if (j < p) uo[j] = uopt[tn * p + j];  // next step's values, loaded a step ahead (not on the chain)
-        }
-      }
+      score_cost_step(x, u, J, umax);
+      if (uopt) score_uopt_step(u, uo, uopt, (int64_t)(t + 1 < steps ? t + 1 : t), p, sse, sso);
     }
-    if (tid == 0) {
-      if (st_u) {
-#pragma unroll
-        for (int j = 0; j < P; ++j)
-          if (j < p) ou[(int64_t)t * U.ldu + j] = u[j];
-      }
-      if (st_x) {
-#pragma unroll
-        for (int k = 0; k < D; ++k)
-          if (k < d) ox[(int64_t)(t + 1) * U.ldx + k] = x[k];
-      }
-    }
+    if (tid == 0) store_step(ou, st_u, U.ldu, ox, st_x, U.ldx, (int64_t)t, u, p, x, d);
   }
   if (SCORED && tid == 0 && U.score) {
     U.score[0] = sse;
@@ -498,17 +353,9 @@ __device__ __forceinline__ void poly_loop_body(const PolyLoopUnit& U, const Poly
 
 // WG: the largest workgroup a kernel is launched with (64: one wave with one landmark per lane; else 16 waves)
 template <int KTYPE, int LPT, int D, int P, int WG>
-__global__ void __launch_bounds__(WG) poly_loop_kernel(PolyLoopParams Q, PolyProgram pl) {
+__global__ void __launch_bounds__(WG) poly_loop_kernel(PolyLoopUnit base, LoopStrides strides, PolyProgram pl) {
   __shared__ double red[2][P][PLANT_LOOP_MAX_WAVES];  // per input one partial sum per wave, two buffers (parity of the step)
-  const int b = blockIdx.x;
-  PolyLoopUnit U;
-  U.Z = Q.Z; U.winv = Q.winv; U.w = Q.w; U.w_ls = Q.w_ls; U.w_js = Q.w_js; U.m = Q.m; U.reserved = 0; U.sigma0sq = Q.sigma0sq;
-  U.x0 = Q.x0 + (int64_t)b * Q.x0_stride;
-  U.xref = Q.xref + (int64_t)b * Q.xref_stride;
-  U.out_x = Q.out_x + (int64_t)b * (Q.steps + 1) * Q.ldx; U.ldx = Q.ldx;
-  U.out_u = Q.out_u + (int64_t)b * Q.steps * Q.ldu; U.ldu = Q.ldu;
-  U.u_opt = nullptr; U.score = nullptr;
-  poly_loop_body<KTYPE, LPT, D, P, false>(U, pl, Q.steps, red);
+  poly_loop_body<KTYPE, LPT, D, P, false>(unit_of_block(base, strides, blockIdx.x), pl, strides.steps, red);
 }
 
 // the multi-model form: unit blockIdx.x of `table` (all units of a launch share KTYPE, LPT and the block size)
@@ -553,10 +400,12 @@ static int poly_loop_dispatch(const char* who, int d, int p, int ktype, bool man
       default: with_lpt(kt, dd, std::integral_constant<int, 4>{}); break;
     }
   };
-  return with_kernel_family(who, ktype, [&](auto kt) {
+  NK_TRY(with_kernel_family(who, ktype, [&](auto kt) {
     if (poly_pad_d(d) == 2) with_p(kt, std::integral_constant<int, 2>{});
     else with_p(kt, std::integral_constant<int, 4>{});
-  });
+  }));
+  NK_HIP(hipGetLastError());
+  return NK_OK;
 }
 
 // all pointers device memory; out_x: batch * (steps + 1) rows of d, out_u: batch * steps rows of p
@@ -565,66 +414,45 @@ int launch_poly_loop(nk_ctx* ctx, const nk_model* mdl, const nk_poly_plant& plan
                      int batch, double* out_x, int64_t ldx, double* out_u, int64_t ldu) {
   NK_REQUIRE(plant.d == mdl->d && plant.p == mdl->p && mdl->m >= 1 && mdl->m <= poly_loop_max_m(plant.d, plant.p) &&
                  steps >= 1 && batch >= 1, "poly_plant_loop: bad sizes");
-  PolyLoopParams Q;
-  Q.Z = mdl->Z; Q.winv = mdl->winv; Q.w = w; Q.w_ls = w_ls; Q.w_js = w_js; Q.m = mdl->m;
-  Q.sigma0sq = mdl->sigma0 * mdl->sigma0;
-  Q.x0 = x0; Q.x0_stride = x0_stride; Q.xref = xref; Q.xref_stride = xref_stride;
-  Q.out_x = out_x; Q.ldx = ldx; Q.out_u = out_u; Q.ldu = ldu; Q.steps = steps;
+  PolyLoopUnit U;  // batch member 0
+  U.Z = mdl->Z; U.winv = mdl->winv; U.w = w; U.w_ls = w_ls; U.w_js = w_js; U.m = mdl->m; U.reserved = 0;
+  U.sigma0sq = mdl->sigma0 * mdl->sigma0;
+  U.x0 = x0; U.xref = xref; U.out_x = out_x; U.ldx = ldx; U.out_u = out_u; U.ldu = ldu;
+  U.u_opt = nullptr; U.score = nullptr;
+  const LoopStrides strides{x0_stride, xref_stride, 0, steps};
   const PolyProgram prog = poly_compile(plant);
   int lpt = 0, waves = 0;
   poly_loop_class(mdl->m, poly_lpt(poly_pad_d(plant.d), poly_pad_p(plant.p)), &lpt, &waves);
   return poly_loop_dispatch("poly_plant_loop", plant.d, plant.p, mdl->ktype, waves > 1 || lpt > 1, [&](auto kt, auto lp, auto dd, auto pp, auto wg) {
     hipLaunchKernelGGL((poly_loop_kernel<decltype(kt)::value, decltype(lp)::value, decltype(dd)::value, decltype(pp)::value,
                                          decltype(wg)::value>),
-                       dim3(batch), dim3(64 * waves), 0, ctx->stream, Q, prog);
+                       dim3(batch), dim3(64 * waves), 0, ctx->stream, U, strides, prog);
   });
 }
 
-// The multi-model form: as launch_plant_loop_multi -- the records are sorted (stable) into classes of (kernel family,
-// landmarks per lane, waves), staged with ONE copy and run with one launch per class.  `units` is reordered in place and
-// must stay alive until the stream has been synchronised.
+// The multi-model form, as launch_plant_loop_multi: classes of (kernel family, landmarks per lane, waves).  `units` is
+// reordered in place and must stay alive until the stream has been synchronised.
 int launch_poly_loop_multi(nk_ctx* ctx, const nk_poly_plant& plant, int steps, PolyLoopUnit* units, const int* ktypes,
                            int n_units) {
   NK_REQUIRE(steps >= 1 && n_units >= 1, "poly_plant_loop_multi: bad sizes");
   const int max_m = poly_loop_max_m(plant.d, plant.p);
   NK_REQUIRE(max_m > 0, "poly_plant_loop_multi: bad plant");
   const int lpt_class = poly_lpt(poly_pad_d(plant.d), poly_pad_p(plant.p));
-  struct Key { int ktype, lpt, waves, idx; };
-  std::vector<Key> keys((size_t)n_units);
-  for (int u = 0; u < n_units; ++u) {
+  for (int u = 0; u < n_units; ++u)
     NK_REQUIRE(units[u].m >= 1 && units[u].m <= max_m, "poly_plant_loop_multi: unit %d: bad m", u);
-    keys[u].ktype = ktypes[u];
-    keys[u].idx = u;
-    poly_loop_class(units[u].m, lpt_class, &keys[u].lpt, &keys[u].waves);
-  }
-  auto less = [](const Key& a, const Key& b) {
-    if (a.ktype != b.ktype) return a.ktype < b.ktype;
-    if (a.lpt != b.lpt) return a.lpt < b.lpt;
-    return a.waves < b.waves;
+  auto key_of = [&](int u) {
+    LoopClass k{ktypes[u], 0, 0};
+    poly_loop_class(units[u].m, lpt_class, &k.shape, &k.waves);
+    return k;
   };
-  std::stable_sort(keys.begin(), keys.end(), less);
-  {
-    std::vector<PolyLoopUnit> sorted((size_t)n_units);
-    for (int u = 0; u < n_units; ++u) sorted[u] = units[keys[u].idx];
-    std::copy(sorted.begin(), sorted.end(), units);
-  }
   const PolyProgram prog = poly_compile(plant);
-  PolyLoopUnit* table = nullptr;
-  NK_TRY(arena_alloc_t(ctx, (size_t)n_units, &table));
-  NK_HIP(hipMemcpyAsync(table, units, sizeof(PolyLoopUnit) * (size_t)n_units, hipMemcpyHostToDevice, ctx->stream));
-  for (int b = 0; b < n_units;) {
-    int e = b + 1;
-    while (e < n_units && !less(keys[b], keys[e])) ++e;
-    const Key& k = keys[b];
-    const PolyLoopUnit* first = table + b;
-    NK_TRY(poly_loop_dispatch("poly_plant_loop_multi", plant.d, plant.p, k.ktype, k.waves > 1 || k.lpt > 1, [&](auto kt, auto lp, auto dd, auto pp, auto wg) {
+  return launch_loop_classes(ctx, units, n_units, key_of, nullptr, [&](const PolyLoopUnit* first, int count, const LoopClass& k, long) {
+    return poly_loop_dispatch("poly_plant_loop_multi", plant.d, plant.p, k.ktype, k.waves > 1 || k.shape > 1, [&](auto kt, auto lp, auto dd, auto pp, auto wg) {
       hipLaunchKernelGGL((poly_loop_multi_kernel<decltype(kt)::value, decltype(lp)::value, decltype(dd)::value, decltype(pp)::value,
                                                  decltype(wg)::value>),
-                         dim3(e - b), dim3(64 * k.waves), 0, ctx->stream, first, prog, steps);
-    }));
-    b = e;
-  }
-  return NK_OK;
+                         dim3(count), dim3(64 * k.waves), 0, ctx->stream, first, prog, steps);
+    });
+  });
 }
 
 }  // namespace nk

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """SHA-256 of the operators of a few fits, of square roots and SPD solves through the C-ABI, and of one lock-step round of
 small fits, and of the unit-table calls (plant loops, lifted loops, Riccati gains) on models rebuilt from host copies
-(library given by NYSKOOP_LIB): two builds that compute the same bits print the same lines."""
+(library given by NYSKOOP_LIB), then every single-launch closed loop and its multi form (the cases of ops_hash_loops.py, beside
+this file): two builds that compute the same bits print the same lines."""
 import ctypes as C, hashlib, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -167,3 +168,7 @@ print("fp32 fit 4096 64 3 256", h(reg.A, reg.B, reg.C), "finite", bool(np.all(np
 r = np.random.default_rng(77)
 Kt = nk.kernels.DeviceKernel(_lib.NK_KERNEL_TPS)(r.standard_normal((300, 40)), r.standard_normal((260, 40)))
 print("nk_kernel_matrix tps 300 260 40", h(Kt), "finite", bool(np.all(np.isfinite(Kt))), flush=True)
+
+# ---- the single-launch closed loops (plant, polynomial plant, MPC, MPC with output rows) and their multi forms
+import ops_hash_loops  # noqa: E402  (beside this file)
+ops_hash_loops.main()
