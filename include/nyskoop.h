@@ -705,7 +705,7 @@ int nk_mpc_loop_max_m(int32_t nv);  /* the limit on m for nv decision variables 
  *   z_1 = U_unc.  A finite w_y leaves r > 0 at a start outside the output bounds.
  *   NaN: the rule of nk_mpc_loop, extended to t = T e and to the shifted output bounds: such a step has NaN controls and
  *   out_info = {iters, NaN}, and affects no other step or trajectory.
- *   Device side (nk_mpc_out_loop.hip): the loop of nk_mpc_loop on nt lanes of the first wave.  W = S^-1 [F; T]' (m x nt;
+ *   Device side (nk_mpc_loop.hip): the loop of nk_mpc_loop on nt lanes of the first wave.  W = S^-1 [F; T]' (m x nt;
  *   spline models: [F; T]') lives in LDS; lane i < nv receives g_i and lane nv + r receives t_r from the same pass.  Lane i
  *   keeps row i of Kb in registers (classes 16 / 32 / 64 over nt), one iteration is one pass of FMAs over q broadcast with
  *   v_readlane; S0 is read once per step, transposed so that lanes read consecutive words; output lanes hold their shifted
@@ -805,7 +805,7 @@ int nk_mpc_loop_multi(nk_ctx* ctx, const nk_poly_plant* plant, int32_t steps, co
  *   Everything is checked before anything is queued or written, with the unit index and the field in nk_last_error(): every
  *   check of nk_mpc_loop_multi, and per unit with rows every check of nk_mpc_out_loop (the rules of nk_mpc_out, m <=
  *   nk_mpc_loop_max_m(nv + ny), LDS, outs[u] and its arrays host memory).  Ordinary contexts only.
- *   Device side (nk_mpc_out_loop.hip): the loop body of nk_mpc_out_loop on a per-unit record, one launch per class of (kernel
+ *   Device side (nk_mpc_loop.hip): the loop body of nk_mpc_out_loop on a per-unit record, one launch per class of (kernel
  *   family, padded states, nv + ny padded to 16 / 32 / 64, ceil(m / 64) waves); the units without rows run the launches of
  *   nk_mpc_loop_multi.  One staging copy, one table copy per kind, one synchronisation; no kernel waits for another workgroup.
  *   An output lane keeps its absolute bounds and forms its violation from the new state; one butterfly per step gives the

@@ -400,6 +400,87 @@ class Mat:
             raise ValueError(f"expected a {rows} x {cols} matrix, got {self.shape}")
 
 
+# Packing helpers of the unit-table and batch calls.  A helper that hands out an address appends the array behind it to
+# the `keep` list of the calling method, which lives until the native call has returned.
+def _handle(h):
+    """A model handle as an address: an int as it is, a c_void_p unwrapped."""
+    return h.value if isinstance(h, C.c_void_p) else h
+
+
+def _handle_array(models):
+    hs = (_P * max(len(models), 1))()
+    for i, h in enumerate(models):
+        hs[i] = _handle(h)
+    return hs
+
+
+def _ptr(a):
+    return None if a is None else a.ctypes.data
+
+
+def _i32p(a):
+    return a.ctypes.data_as(C.POINTER(_I32))
+
+
+def _f64(a, shape, keep, unit=None, what=None):
+    """`a` as a C-contiguous float64 array of `shape` in `keep`; with `what`, a vector of `shape` entries or a ValueError."""
+    if what is None:
+        a = np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(shape))
+    else:
+        a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+        if a.size != shape:
+            raise ValueError(f"unit {unit}: {what} has {a.size} entries, expected {shape}")
+    keep.append(a)
+    return a
+
+
+def _uopt_table(u_opt, steps, p, n, uopt_rows, keep):
+    """(table (n_uopt, max(steps, 1) * p) or None, n_uopt, the row of each unit: 0 with a table, else -1, unless given)."""
+    uo, n_uopt = None, 0
+    if u_opt is not None:
+        uo = _f64(u_opt, (-1, max(steps, 1) * p), keep)
+        n_uopt = uo.shape[0]
+    if uopt_rows is None:
+        uopt_rows = [0 if n_uopt else -1] * n
+    return uo, n_uopt, uopt_rows
+
+
+def _status_iters(n, per=None):
+    """The int32 status (-1) and iteration (0) arrays of a batch call: n entries, `per` iteration counts each."""
+    n1 = max(n, 1)
+    return np.full(n1, -1, dtype=np.int32), np.zeros(n1 if per is None else (n1, per), dtype=np.int32)
+
+
+def _pack_abqr(a, i, A, B, Q, R, keep):
+    """The A, B, Q, R block of a DareProblem / MpcBuildProblem; returns (m, p)."""
+    A = np.ascontiguousarray(A, dtype=np.float64)
+    if A.ndim != 2 or A.shape[0] != A.shape[1]:
+        raise ValueError(f"problem {i}: A must be square, got {A.shape}")
+    keep.append(A)
+    m = A.shape[0]
+    B = _f64(B, (m, -1), keep)
+    p = B.shape[1]
+    Q, R = _f64(Q, (m, m), keep), _f64(R, (p, p), keep)
+    a.m, a.p = m, p
+    a.A, a.lda, a.B, a.ldb = A.ctypes.data, max(m, 1), B.ctypes.data, max(p, 1)
+    a.Q, a.ldq, a.R, a.ldr = Q.ctypes.data, max(m, 1), R.ctypes.data, max(p, 1)
+    return m, p
+
+
+def _build_outputs(s, prefix, m, p, N, nc, Ny, want_P=None):
+    """NaN-filled H, F, K, (P,) G, T of one controller build, their addresses in the fields prefix + name of `s`.  G and T
+    are None without output rows, P is None unless wanted (want_P = None: the structure has no such field)."""
+    nv, ny = max(N, 0) * p, nc * max(Ny, 0)
+    o = dict(H=np.full((nv, nv), np.nan), F=np.full((nv, m), np.nan), K=np.full((p, m), np.nan))
+    if want_P is not None:
+        o["P"] = np.full((m, m), np.nan) if want_P else None
+    o["G"] = np.full((ny, nv), np.nan) if nc else None
+    o["T"] = np.full((ny, m), np.nan) if nc else None
+    for k, v in o.items():
+        setattr(s, prefix + k, _ptr(v))
+    return o
+
+
 class Context:
     """One nk_ctx (HIP stream + HBM workspace) on one device.  Not thread-safe; one per process and device."""
 
@@ -468,6 +549,42 @@ class Context:
             raise ValueError("dtype must be 'f64' or 'f32'")
         check(self.lib.nk_set_compute_dtype(self.handle, code))
 
+    def _loop_multi(self, fn, head, d, p, steps, models, x0s, x_refs, u_opt, uopt_rows, want_x, want_u, want_scores, gains=None,
+                    fill=None, keep=None, n_scores=4, want_info=None, mid=(), ou_flat=False):
+        """plant_loop_multi, poly_plant_loop_multi and mpc_loop_multi: fn(ctx, *head, steps, unit table, *mid, n, u_opt table,
+        n_uopt, states, controls, (info,) scores).  Normalises the states ((n, d); d = None: the width of x0s), fills model /
+        x0 / x_ref / uopt of every unit and K from `gains` (PlantUnit) or what fill(unit, i) sets (MpcUnit), allocates the
+        outputs that are wanted (want_info = None: no info argument).  Returns (scores, states, controls, info)."""
+        n, steps, keep = len(models), int(steps), [] if keep is None else keep
+        if gains is not None:
+            if len(gains) != n:
+                raise ValueError(f"{len(gains)} gains for {n} models")
+            Ks = [_f64(K, -1, keep).ctypes.data for K in gains]
+
+            def fill(u, i):
+                u.K = Ks[i]
+        if d is None:
+            x0s = _f64(x0s, (n, -1), keep) if n else np.zeros((0, 1))
+            d = x0s.shape[1]
+            x_refs = _f64(x_refs, (n, d), keep) if n else np.zeros((0, d))
+        else:
+            x0s, x_refs = _f64(x0s, (n, d), keep), _f64(x_refs, (n, d), keep)
+        uo, n_uopt, uopt_rows = _uopt_table(u_opt, steps, p, n, uopt_rows, keep)
+        arr = ((MpcUnit if gains is None else PlantUnit) * max(n, 1))()
+        x0, xr, row = x0s.ctypes.data, x_refs.ctypes.data, 8 * d
+        for i in range(n):
+            u = arr[i]
+            u.model, u.x0, u.x_ref, u.uopt = _handle(models[i]), x0 + i * row, xr + i * row, int(uopt_rows[i])
+            fill(u, i)
+        T = max(steps, 0)
+        sc = np.full((n, n_scores), np.nan) if want_scores else None
+        ox = np.empty((n, T + 1, d)) if want_x else None
+        ou = np.empty((n, T) if ou_flat else (n, T, p)) if want_u else None
+        oi = np.empty((n, T, 2)) if want_info else None
+        info = () if want_info is None else (_ptr(oi),)
+        check_mapped(fn(self.handle, *head, steps, arr, *mid, n, _ptr(uo), n_uopt, _ptr(ox), _ptr(ou), *info, _ptr(sc)))
+        return sc, ox, ou, oi
+
     def plant_loop_multi(self, plant_id, Ts, steps, models, gains, x0s, x_refs, u_opt=None, uopt_rows=None,
                          want_x=False, want_u=False, want_scores=True):
         """nk_plant_loop_multi: one closed loop around the true plant per unit, all units in one call, scored on the device.
@@ -475,68 +592,16 @@ class Context:
         u_opt: (n_uopt, steps) reference controls or None; uopt_rows: the row each unit is scored against (-1: none;
         default: row 0 for every unit when u_opt is given).  Returns (scores (n_units, 4) or None, states
         (n_units, steps + 1, d) or None, controls (n_units, steps) or None); scores[u] = sse_u, ss_opt, J, u_absmax."""
-        n = len(models)
-        steps = int(steps)
-        x0s = np.ascontiguousarray(x0s, dtype=np.float64).reshape(n, -1) if n else np.zeros((0, 1))
-        d = x0s.shape[1]
-        x_refs = np.ascontiguousarray(np.asarray(x_refs, dtype=np.float64).reshape(n, d)) if n else np.zeros((0, d))
-        if len(gains) != n:
-            raise ValueError(f"{len(gains)} gains for {n} models")
-        Ks = [np.ascontiguousarray(K, dtype=np.float64).reshape(-1) for K in gains]
-        uo, n_uopt = None, 0
-        if u_opt is not None:
-            uo = np.ascontiguousarray(np.asarray(u_opt, dtype=np.float64).reshape(-1, max(steps, 1)))
-            n_uopt = uo.shape[0]
-        if uopt_rows is None:
-            uopt_rows = [0 if n_uopt else -1] * n
-        arr = (PlantUnit * max(n, 1))()
-        for i in range(n):
-            h = models[i]
-            arr[i].model = h.value if isinstance(h, C.c_void_p) else h
-            arr[i].K, arr[i].x0, arr[i].x_ref = Ks[i].ctypes.data, x0s[i].ctypes.data, x_refs[i].ctypes.data
-            arr[i].uopt = int(uopt_rows[i])
-        sc = np.full((n, 4), np.nan) if want_scores else None
-        ox = np.empty((n, max(steps, 0) + 1, d)) if want_x else None
-        ou = np.empty((n, max(steps, 0))) if want_u else None
-        ptr = lambda a: None if a is None else a.ctypes.data
-        rc = self.lib.nk_plant_loop_multi(self.handle, int(plant_id), float(Ts), steps, arr, n, ptr(uo), n_uopt, ptr(ox),
-                                          ptr(ou), ptr(sc))
-        check_mapped(rc)
-        return sc, ox, ou
+        return self._loop_multi(self.lib.nk_plant_loop_multi, (int(plant_id), float(Ts)), None, 1, steps, models, x0s, x_refs,
+                                u_opt, uopt_rows, want_x, want_u, want_scores, gains, ou_flat=True)[:3]
 
     def poly_plant_loop_multi(self, descriptor, steps, models, gains, x0s, x_refs, u_opt=None, uopt_rows=None, want_x=False,
                               want_u=False, want_scores=True):
         """nk_poly_plant_loop_multi: plant_loop_multi around a polynomial plant (descriptor: a PolyPlant) with p inputs.
         gains: one (p, m) array per unit; u_opt: (n_uopt, steps, p) or None.  Returns (scores (n_units, 4) or None, states
         (n_units, steps + 1, d) or None, controls (n_units, steps, p) or None)."""
-        n = len(models)
-        steps = int(steps)
-        d, p = int(descriptor.d), int(descriptor.p)
-        x0s = np.ascontiguousarray(np.asarray(x0s, dtype=np.float64).reshape(n, d))
-        x_refs = np.ascontiguousarray(np.asarray(x_refs, dtype=np.float64).reshape(n, d))
-        if len(gains) != n:
-            raise ValueError(f"{len(gains)} gains for {n} models")
-        Ks = [np.ascontiguousarray(K, dtype=np.float64).reshape(-1) for K in gains]
-        uo, n_uopt = None, 0
-        if u_opt is not None:
-            uo = np.ascontiguousarray(np.asarray(u_opt, dtype=np.float64).reshape(-1, max(steps, 1) * p))
-            n_uopt = uo.shape[0]
-        if uopt_rows is None:
-            uopt_rows = [0 if n_uopt else -1] * n
-        arr = (PlantUnit * max(n, 1))()
-        for i in range(n):
-            h = models[i]
-            arr[i].model = h.value if isinstance(h, C.c_void_p) else h
-            arr[i].K, arr[i].x0, arr[i].x_ref = Ks[i].ctypes.data, x0s[i].ctypes.data, x_refs[i].ctypes.data
-            arr[i].uopt = int(uopt_rows[i])
-        sc = np.full((n, 4), np.nan) if want_scores else None
-        ox = np.empty((n, max(steps, 0) + 1, d)) if want_x else None
-        ou = np.empty((n, max(steps, 0), p)) if want_u else None
-        ptr = lambda a: None if a is None else a.ctypes.data
-        rc = self.lib.nk_poly_plant_loop_multi(self.handle, C.byref(descriptor), steps, arr, n, ptr(uo), n_uopt, ptr(ox),
-                                               ptr(ou), ptr(sc))
-        check_mapped(rc)
-        return sc, ox, ou
+        return self._loop_multi(self.lib.nk_poly_plant_loop_multi, (C.byref(descriptor),), int(descriptor.d), int(descriptor.p),
+                                steps, models, x0s, x_refs, u_opt, uopt_rows, want_x, want_u, want_scores, gains)[:3]
 
     def mpc_loop_multi(self, descriptor, steps, models, descs, x0s, x_refs, u_inits=None, u_opt=None, uopt_rows=None,
                        want_x=False, want_u=False, want_info=False, want_scores=True, outs=None):
@@ -548,54 +613,73 @@ class Context:
         (n_units, steps, 2) or None).
         outs: None, or one entry per unit, an MpcOut (units may share one; the caller keeps their arrays alive) or None for a
         unit without rows -- the call is then nk_mpc_out_loop_multi and the scores are (n_units, 10)."""
-        n = len(models)
-        steps = int(steps)
+        n, keep = len(models), []
         d, p = int(descriptor.d), int(descriptor.p)
-        x0s = np.ascontiguousarray(np.asarray(x0s, dtype=np.float64).reshape(n, d))
-        x_refs = np.ascontiguousarray(np.asarray(x_refs, dtype=np.float64).reshape(n, d))
         if len(descs) != n:
             raise ValueError(f"{len(descs)} descriptions for {n} models")
         uis = [None] * n
         if u_inits is not None:
             if len(u_inits) != n:
                 raise ValueError(f"{len(u_inits)} u_inits for {n} models")
-            for i, ui in enumerate(u_inits):
-                if ui is not None:
-                    uis[i] = np.ascontiguousarray(ui, dtype=np.float64).reshape(p)
-        uo, n_uopt = None, 0
-        if u_opt is not None:
-            uo = np.ascontiguousarray(np.asarray(u_opt, dtype=np.float64).reshape(-1, max(steps, 1) * p))
-            n_uopt = uo.shape[0]
-        if uopt_rows is None:
-            uopt_rows = [0 if n_uopt else -1] * n
-        arr = (MpcUnit * max(n, 1))()
-        for i in range(n):
-            h = models[i]
-            arr[i].model = h.value if isinstance(h, C.c_void_p) else h
-            arr[i].desc = C.pointer(descs[i])
-            arr[i].x0, arr[i].x_ref = x0s[i].ctypes.data, x_refs[i].ctypes.data
-            arr[i].u_init = None if uis[i] is None else uis[i].ctypes.data
-            arr[i].uopt = int(uopt_rows[i])
-        T = max(steps, 0)
+            uis = [None if ui is None else _f64(ui, p, keep).ctypes.data for ui in u_inits]
         if outs is not None and len(outs) != n:
             raise ValueError(f"{len(outs)} output descriptions for {n} models")
-        sc = np.full((n, MPC_N_SCORES if outs is None else MPC_OUT_N_SCORES), np.nan) if want_scores else None
-        ox = np.empty((n, T + 1, d)) if want_x else None
-        ou = np.empty((n, T, p)) if want_u else None
-        oi = np.empty((n, T, 2)) if want_info else None
-        ptr = lambda a: None if a is None else a.ctypes.data
+
+        def fill(u, i):
+            u.desc, u.u_init = C.pointer(descs[i]), uis[i]
+
         if outs is None:
-            rc = self.lib.nk_mpc_loop_multi(self.handle, C.byref(descriptor), steps, arr, n, ptr(uo), n_uopt, ptr(ox), ptr(ou),
-                                            ptr(oi), ptr(sc))
+            fn, mid, n_scores = self.lib.nk_mpc_loop_multi, (), MPC_N_SCORES
         else:
             oarr = (C.POINTER(MpcOut) * max(n, 1))()  # (null pointers; `outs` keeps the structures alive through the call)
             for i, o in enumerate(outs):
                 if o is not None:
                     oarr[i] = C.pointer(o)
-            rc = self.lib.nk_mpc_out_loop_multi(self.handle, C.byref(descriptor), steps, arr, oarr, n, ptr(uo), n_uopt, ptr(ox),
-                                                ptr(ou), ptr(oi), ptr(sc))
-        check_mapped(rc)
-        return sc, ox, ou, oi
+            fn, mid, n_scores = self.lib.nk_mpc_out_loop_multi, (oarr,), MPC_OUT_N_SCORES
+        return self._loop_multi(fn, (C.byref(descriptor),), d, p, steps, models, x0s, x_refs, u_opt, uopt_rows, want_x, want_u,
+                                want_scores, None, fill, keep, n_scores, bool(want_info), mid)
+
+    def _single_loop(self, fn, head, K, xb, xr, u_init, steps, p, want_info=None):
+        """fn(ctx, *head, (K,) x0, x_ref, (u_init,) steps, batch, states, controls, (info)): the single-model plant loops on
+        C-contiguous (batch, d) states.  want_info = None: the call has neither u_init nor info."""
+        batch, d = xb.shape
+        T = max(steps, 0)
+        ox, ou = np.empty((batch, T + 1, d)), np.empty((batch, T, p))
+        oi = np.empty((batch, T, 2)) if want_info else None
+        gain = () if K is None else (K.ctypes.data,)
+        seed, info = ((), ()) if want_info is None else ((_ptr(u_init),), (_ptr(oi),))
+        check_mapped(fn(self.handle, *head, *gain, xb.ctypes.data, xr.ctypes.data, *seed, steps, batch, ox.ctypes.data,
+                        ou.ctypes.data, *info))
+        return ox, ou, oi
+
+    def plant_loop(self, model, plant_id, Ts, K, xb, xr, steps):
+        """nk_plant_loop: LQR loops around a built-in plant that share the gain K (1, m).  xb, xr: C-contiguous (batch, d).
+        Returns (states (batch, steps + 1, d), controls (batch, steps, 1))."""
+        return self._single_loop(self.lib.nk_plant_loop, (model, int(plant_id), float(Ts)), K, xb, xr, None, steps, 1)[:2]
+
+    def poly_plant_loop(self, model, descriptor, K, xb, xr, steps):
+        """nk_poly_plant_loop: plant_loop around a polynomial plant (descriptor: a PolyPlant), K (p, m).  Returns (states
+        (batch, steps + 1, d), controls (batch, steps, p))."""
+        return self._single_loop(self.lib.nk_poly_plant_loop, (model, descriptor), K, xb, xr, None, steps, K.shape[0])[:2]
+
+    def mpc_loop(self, model, descriptor, desc, xb, xr, steps, u_init=None, want_info=False, out=None):
+        """nk_mpc_loop, or nk_mpc_out_loop with an MpcOut as `out`: constrained MPC loops around a polynomial plant that share
+        the controller (desc: an MpcDesc; the caller keeps its arrays, and those of `out`, alive).  u_init: C-contiguous
+        (batch, p) or None = zeros.  Returns (states, controls (batch, steps, p), info (batch, steps, 2) or None)."""
+        if out is None:
+            fn, head = self.lib.nk_mpc_loop, (model, descriptor, C.byref(desc))
+        else:
+            fn, head = self.lib.nk_mpc_out_loop, (model, descriptor, C.byref(desc), C.byref(out))
+        return self._single_loop(fn, head, None, xb, xr, u_init, steps, int(desc.p), bool(want_info))
+
+    def closed_loop_batch(self, model, K, f0, fr, steps, d):
+        """nk_closed_loop_batch: lifted closed loops that share the gain K (p, m).  f0, fr: C-contiguous (batch, m); d: the
+        model's state dimension.  Returns (states (batch, steps, d), controls (batch, steps, p))."""
+        batch = f0.shape[0]
+        ox, ou = np.empty((batch, steps, d)), np.empty((batch, steps, K.shape[0]))
+        check(self.lib.nk_closed_loop_batch(self.handle, model, K.ctypes.data, f0.ctypes.data, fr.ctypes.data, int(steps), batch,
+                                            ox.ctypes.data, ou.ctypes.data))
+        return ox, ou
 
     def closed_loop_multi(self, steps, c, models, dims, gains, phi0s, phi_refs, targets=None, u_inits=None, want_x=False,
                           want_u=False, want_ucum=False, want_err=True, want_scores=True):
@@ -613,37 +697,26 @@ class Context:
             raise ValueError("scores and errors need a target per unit")
         arr = (LoopUnit * max(n, 1))()
         keep = []
-
-        def vec(a, size, what, i):
-            a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
-            if a.size != size:
-                raise ValueError(f"unit {i}: {what} has {a.size} entries, expected {size}")
-            keep.append(a)
-            return a.ctypes.data
-
         for i in range(n):
             m, p, d = (int(v) for v in dims[i])
-            h = models[i]
-            arr[i].model = h.value if isinstance(h, C.c_void_p) else h
-            arr[i].K = vec(gains[i], p * m, "the gain", i)
-            arr[i].phi0 = vec(phi0s[i], m, "phi0", i)
-            arr[i].phi_ref = vec(phi_refs[i], m, "phi_ref", i)
+            u = arr[i]
+            u.model = _handle(models[i])
+            u.K = _f64(gains[i], p * m, keep, i, "the gain").ctypes.data
+            u.phi0 = _f64(phi0s[i], m, keep, i, "phi0").ctypes.data
+            u.phi_ref = _f64(phi_refs[i], m, keep, i, "phi_ref").ctypes.data
             if targets is not None:
-                arr[i].target = vec(targets[i], d, "the target", i)
+                u.target = _f64(targets[i], d, keep, i, "the target").ctypes.data
             if u_inits is not None and u_inits[i] is not None:
-                arr[i].u_init = vec(u_inits[i], p, "u_init", i)
+                u.u_init = _f64(u_inits[i], p, keep, i, "u_init").ctypes.data
         T = max(steps, 0)
-        nx = sum(T * int(dm[2]) for dm in dims)
-        nu = sum(T * int(dm[1]) for dm in dims)
-        nc = sum((T + 1) * int(dm[1]) for dm in dims)
+        nx, nu, nc = (sum(rows * int(dm[col]) for dm in dims) for rows, col in ((T, 2), (T, 1), (T + 1, 1)))
         ox = np.empty(max(nx, 1)) if want_x else None
         ou = np.empty(max(nu, 1)) if want_u else None
         oc = np.empty(max(nc, 1)) if want_ucum else None
         oe = np.full((n, T), np.nan) if want_err else None
         sc = np.full((n, 4), np.nan) if want_scores else None
-        ptr = lambda a: None if a is None else a.ctypes.data
-        rc = self.lib.nk_closed_loop_multi(self.handle, steps, float(c), arr, n, ptr(ox), ptr(ou), ptr(oc), ptr(oe), ptr(sc))
-        check_mapped(rc)
+        check_mapped(self.lib.nk_closed_loop_multi(self.handle, steps, float(c), arr, n, _ptr(ox), _ptr(ou), _ptr(oc), _ptr(oe),
+                                                   _ptr(sc)))
 
         def split(flat, rows, col):
             if flat is None:
@@ -668,31 +741,13 @@ class Context:
         keep, Ks, Ps = [], [], []
         delta = np.full(max(n, 1), np.nan)
         for i in range(n):
-            A = np.ascontiguousarray(As[i], dtype=np.float64)
-            if A.ndim != 2 or A.shape[0] != A.shape[1]:
-                raise ValueError(f"problem {i}: A must be square, got {A.shape}")
-            m = A.shape[0]
-            B = np.ascontiguousarray(np.asarray(Bs[i], dtype=np.float64).reshape(m, -1))
-            p = B.shape[1]
-            Q = np.ascontiguousarray(np.asarray(Qs[i], dtype=np.float64).reshape(m, m))
-            R = np.ascontiguousarray(np.asarray(Rs[i], dtype=np.float64).reshape(p, p))
-            K = np.full((p, m), np.nan)
-            P = np.full((m, m), np.nan) if want_P else None
-            keep.append((A, B, Q, R))
-            Ks.append(K)
-            Ps.append(P)
             a = arr[i]
-            a.m, a.p = m, p
-            a.A, a.lda, a.B, a.ldb = A.ctypes.data, max(m, 1), B.ctypes.data, max(p, 1)
-            a.Q, a.ldq, a.R, a.ldr = Q.ctypes.data, max(m, 1), R.ctypes.data, max(p, 1)
-            a.out_K = K.ctypes.data
-            a.out_P = P.ctypes.data if want_P else None
-            a.out_delta = delta.ctypes.data + 8 * i
-        status = np.full(max(n, 1), -1, dtype=np.int32)
-        iters = np.zeros(max(n, 1), dtype=np.int32)
-        rc = self.lib.nk_dare_batch(self.handle, arr, n, float(tol), int(max_iter),
-                                    status.ctypes.data_as(C.POINTER(_I32)), iters.ctypes.data_as(C.POINTER(_I32)))
-        check_mapped(rc)
+            m, p = _pack_abqr(a, i, As[i], Bs[i], Qs[i], Rs[i], keep)
+            Ks.append(np.full((p, m), np.nan))
+            Ps.append(np.full((m, m), np.nan) if want_P else None)
+            a.out_K, a.out_P, a.out_delta = Ks[i].ctypes.data, _ptr(Ps[i]), delta.ctypes.data + 8 * i
+        status, iters = _status_iters(n)
+        check_mapped(self.lib.nk_dare_batch(self.handle, arr, n, float(tol), int(max_iter), _i32p(status), _i32p(iters)))
         return Ks, (Ps if want_P else None), status[:n], iters[:n], delta[:n]
 
     def model_lqr_gain_batch(self, models, c, R=None, tol=1e-13, max_iter=40, dims=None):
@@ -700,9 +755,7 @@ class Context:
         identity).  models: device-model handles; dims: their (m, p) pairs (queried with nk_model_dims when None).
         Returns (Ks, status, iterations); a unit with status != 0 has a NaN gain."""
         n = len(models)
-        hs = (_P * max(n, 1))()
-        for i, h in enumerate(models):
-            hs[i] = h.value if isinstance(h, C.c_void_p) else h
+        hs = _handle_array(models)
         if dims is None:
             dims = []
             for i in range(n):
@@ -712,12 +765,9 @@ class Context:
         sizes = [int(m) * int(p) for m, p in dims]
         out = np.full(max(sum(sizes), 1), np.nan)
         Rm = None if R is None else np.ascontiguousarray(R, dtype=np.float64)
-        status = np.full(max(n, 1), -1, dtype=np.int32)
-        iters = np.zeros(max(n, 1), dtype=np.int32)
-        rc = self.lib.nk_model_lqr_gain_batch(self.handle, hs, n, float(c), None if Rm is None else Rm.ctypes.data,
-                                              float(tol), int(max_iter), out.ctypes.data,
-                                              status.ctypes.data_as(C.POINTER(_I32)), iters.ctypes.data_as(C.POINTER(_I32)))
-        check_mapped(rc)
+        status, iters = _status_iters(n)
+        check_mapped(self.lib.nk_model_lqr_gain_batch(self.handle, hs, n, float(c), _ptr(Rm), float(tol), int(max_iter),
+                                                      out.ctypes.data, _i32p(status), _i32p(iters)))
         Ks, off = [], 0
         for (m, p), sz in zip(dims, sizes):
             Ks.append(out[off:off + sz].reshape(int(p), int(m)).copy())
@@ -738,45 +788,20 @@ class Context:
         keep = []
         res = dict(H=[], F=[], K=[], P=[], G=[], T=[])
         for i in range(n):
-            A = np.ascontiguousarray(As[i], dtype=np.float64)
-            if A.ndim != 2 or A.shape[0] != A.shape[1]:
-                raise ValueError(f"problem {i}: A must be square, got {A.shape}")
-            m = A.shape[0]
-            B = np.ascontiguousarray(np.asarray(Bs[i], dtype=np.float64).reshape(m, -1))
-            p = B.shape[1]
-            Q = np.ascontiguousarray(np.asarray(Qs[i], dtype=np.float64).reshape(m, m))
-            R = np.ascontiguousarray(np.asarray(Rs[i], dtype=np.float64).reshape(p, p))
+            a = arr[i]
+            m, p = _pack_abqr(a, i, As[i], Bs[i], Qs[i], Rs[i], keep)
             N = int(Ns[i])
-            nv = max(N, 0) * p
-            P = None if Ps is None or Ps[i] is None else np.ascontiguousarray(np.asarray(Ps[i], dtype=np.float64).reshape(m, m))
-            Cr = None if C_rows is None or C_rows[i] is None else \
-                np.ascontiguousarray(np.asarray(C_rows[i], dtype=np.float64).reshape(-1, m))
+            P = None if Ps is None or Ps[i] is None else _f64(Ps[i], (m, m), keep)
+            Cr = None if C_rows is None or C_rows[i] is None else _f64(C_rows[i], (-1, m), keep)
             nc = 0 if Cr is None else Cr.shape[0]
             Ny = 0 if nc == 0 else (N if Nys is None or Nys[i] is None else int(Nys[i]))
-            ny = nc * max(Ny, 0)
-            o = dict(H=np.full((nv, nv), np.nan), F=np.full((nv, m), np.nan), K=np.full((p, m), np.nan),
-                     P=np.full((m, m), np.nan) if want_P else None,
-                     G=np.full((ny, nv), np.nan) if nc else None, T=np.full((ny, m), np.nan) if nc else None)
-            keep.append((A, B, Q, R, P, Cr))
-            for k, v in o.items():
+            a.N, a.nc, a.Ny = N, nc, Ny
+            a.P, a.ldp, a.C_rows, a.ldc = _ptr(P), max(m, 1), _ptr(Cr), max(m, 1)
+            for k, v in _build_outputs(a, "out_", m, p, N, nc, Ny, bool(want_P)).items():
                 res[k].append(v)
-            a = arr[i]
-            a.m, a.p, a.N, a.nc, a.Ny = m, p, N, nc, Ny
-            a.A, a.lda, a.B, a.ldb = A.ctypes.data, max(m, 1), B.ctypes.data, max(p, 1)
-            a.Q, a.ldq, a.R, a.ldr = Q.ctypes.data, max(m, 1), R.ctypes.data, max(p, 1)
-            a.P, a.ldp = (None if P is None else P.ctypes.data), max(m, 1)
-            a.C_rows, a.ldc = (None if Cr is None else Cr.ctypes.data), max(m, 1)
-            a.out_H, a.out_F, a.out_K = o["H"].ctypes.data, o["F"].ctypes.data, o["K"].ctypes.data
-            a.out_P = o["P"].ctypes.data if want_P else None
-            a.out_G = o["G"].ctypes.data if nc else None
-            a.out_T = o["T"].ctypes.data if nc else None
-        status = np.full(max(n, 1), -1, dtype=np.int32)
-        iters = np.zeros((max(n, 1), 2), dtype=np.int32)
-        rc = self.lib.nk_mpc_build_batch(self.handle, arr, n, float(tol), int(max_iter), int(newton_steps), float(newton_tol),
-                                         int(newton_max_iter), status.ctypes.data_as(C.POINTER(_I32)),
-                                         iters.ctypes.data_as(C.POINTER(_I32)))
-        check_mapped(rc)
-        del keep
+        status, iters = _status_iters(n, 2)
+        check_mapped(self.lib.nk_mpc_build_batch(self.handle, arr, n, float(tol), int(max_iter), int(newton_steps),
+                                                 float(newton_tol), int(newton_max_iter), _i32p(status), _i32p(iters)))
         res["status"], res["iters"] = status[:n], iters[:n]
         return res
 
@@ -787,9 +812,7 @@ class Context:
         of the output rows (empty: none).  Returns (units, status (n,), iters (n, 2)); units[u] = dict(H, F, K, G, T) (G, T
         None without rows); a unit with status != 0 has NaN arrays."""
         n = len(models)
-        hs = (_P * max(n, 1))()
-        for i, h in enumerate(models):
-            hs[i] = h.value if isinstance(h, C.c_void_p) else h
+        hs = _handle_array(models)
         sp = (MpcBuildSpec * max(n, 1))()
         ou = (MpcBuildOut * max(n, 1))()
         units = []
@@ -801,24 +824,15 @@ class Context:
                 raise ValueError(f"unit {i}: {len(comps)} output rows per step, at most 4")
             nc = len(comps)
             Ny = 0 if nc == 0 else (N if Ny is None else int(Ny))
-            nv, ny = max(N, 0) * p, nc * max(Ny, 0)
-            u = dict(H=np.full((nv, nv), np.nan), F=np.full((nv, m), np.nan), K=np.full((p, m), np.nan),
-                     G=np.full((ny, nv), np.nan) if nc else None, T=np.full((ny, m), np.nan) if nc else None)
-            units.append(u)
             sp[i].N, sp[i].nc, sp[i].Ny = N, nc, Ny
             for k, v in enumerate(comps):
                 sp[i].comps[k] = v
-            ou[i].H, ou[i].F, ou[i].K = u["H"].ctypes.data, u["F"].ctypes.data, u["K"].ctypes.data
-            ou[i].G = u["G"].ctypes.data if nc else None
-            ou[i].T = u["T"].ctypes.data if nc else None
+            units.append(_build_outputs(ou[i], "", m, p, N, nc, Ny))
         Rm = None if R is None else np.ascontiguousarray(R, dtype=np.float64)
-        status = np.full(max(n, 1), -1, dtype=np.int32)
-        iters = np.zeros((max(n, 1), 2), dtype=np.int32)
-        rc = self.lib.nk_model_mpc_build_batch(self.handle, hs, n, float(c), None if Rm is None else Rm.ctypes.data, sp,
-                                               float(tol), int(max_iter), int(newton_steps), float(newton_tol),
-                                               int(newton_max_iter), ou, status.ctypes.data_as(C.POINTER(_I32)),
-                                               iters.ctypes.data_as(C.POINTER(_I32)))
-        check_mapped(rc)
+        status, iters = _status_iters(n, 2)
+        check_mapped(self.lib.nk_model_mpc_build_batch(self.handle, hs, n, float(c), _ptr(Rm), sp, float(tol), int(max_iter),
+                                                       int(newton_steps), float(newton_tol), int(newton_max_iter), ou,
+                                                       _i32p(status), _i32p(iters)))
         return units, status[:n], iters[:n]
 
     def mpc_build_times(self):
@@ -856,13 +870,12 @@ class Context:
     def model_lqr_gain(self, model, m, p, c, R=None, tol=1e-13, max_iter=40):
         """nk_model_lqr_gain: K = dlqr(A, B, c sym(C'C), R) of one device model by the launch-chain solver, whatever m is
         (R = None: the identity).  Returns (K (p, m), status, iterations); a status other than 0 has a NaN gain."""
-        h = model.value if isinstance(model, C.c_void_p) else model
+        keep = []
         K = np.full((int(p), int(m)), np.nan)
-        Rm = None if R is None else np.ascontiguousarray(np.asarray(R, dtype=np.float64).reshape(int(p), int(p)))
+        Rm = None if R is None else _f64(R, (int(p), int(p)), keep)
         status, iters = _I32(-1), _I32(0)
-        rc = self.lib.nk_model_lqr_gain(self.handle, h, float(c), None if Rm is None else Rm.ctypes.data, float(tol),
-                                        int(max_iter), K.ctypes.data, C.byref(status), C.byref(iters))
-        check_mapped(rc)
+        check_mapped(self.lib.nk_model_lqr_gain(self.handle, _handle(model), float(c), _ptr(Rm), float(tol), int(max_iter),
+                                                K.ctypes.data, C.byref(status), C.byref(iters)))
         return K, int(status.value), int(iters.value)
 
     def dare_large_times(self):
@@ -875,8 +888,7 @@ class Context:
     def model_lqr_cost(self, model, m, c):
         """nk_model_lqr_cost: the cost matrix c sym(C'C) (m x m) exactly as nk_model_lqr_gain_batch forms it."""
         Q = np.empty((int(m), int(m)))
-        h = model.value if isinstance(model, C.c_void_p) else model
-        rc = self.lib.nk_model_lqr_cost(self.handle, h, float(c), Q.ctypes.data, int(m))
+        rc = self.lib.nk_model_lqr_cost(self.handle, _handle(model), float(c), Q.ctypes.data, int(m))
         check_mapped(rc)
         return Q
 

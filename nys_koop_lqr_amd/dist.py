@@ -119,6 +119,15 @@ def sharded_grid_search(X, Y, n_inputs, candidates, n_splits=5, centers=None, un
                 best_params=candidates[best] if best >= 0 else None)
 
 
+def _sharded_sweep(units, run, table):
+    """The sharded sweeps: the planned `units` (the same on every rank) are dealt round-robin, run(this rank's units) gives
+    their per-unit values, ONE all-gather assembles all of them in plan order, and every rank returns table(values)."""
+    import torch.distributed as dist
+    rank, world = (dist.get_rank(), dist.get_world_size()) if dist.is_initialized() else (0, 1)
+    local = run([units[u] for u in shard_units(len(units), rank, world)])
+    return table(all_gather_scores(local, len(units), rank, world) if world > 1 else local)
+
+
 def sharded_sysid_sweep(X, Y, n_inputs, params, ms, seeds, trajs, controls, test_index, train_ranges=None,
                         estimator="nystrom", relative=False, extra_draws=0, centers=None, batch=0, batch_groups=1,
                         streams=None, unit_fn=None):
@@ -127,15 +136,11 @@ def sharded_sysid_sweep(X, Y, n_inputs, params, ms, seeds, trajs, controls, test
     on its own GPU -- through the lock-step sweep when batch > 1 -- and ONE all-gather assembles the table.  unit_fn: a
     stand-in for harness.sysid_unit_error (rehearsals without a GPU).  Every rank returns the same
     (len(seeds), n_test_per_seed, len(ms)) array."""
-    import torch.distributed as dist
-    rank, world = (dist.get_rank(), dist.get_world_size()) if dist.is_initialized() else (0, 1)
     units = harness.sysid_plan(X, Y, n_inputs, params, ms, seeds, test_index, train_ranges, estimator, extra_draws, centers,
                                streams)
-    mine = shard_units(len(units), rank, world)
-    local = harness.sysid_run_units(X, Y, n_inputs, params, [units[u] for u in mine], trajs, controls, estimator, relative,
-                                    batch, batch_groups, unit_fn)
-    flat = all_gather_scores(local, len(units), rank, world) if world > 1 else local
-    return harness.sysid_table(units, flat, len(seeds), len(ms))
+    return _sharded_sweep(units, lambda mine: harness.sysid_run_units(X, Y, n_inputs, params, mine, trajs, controls, estimator,
+                                                                      relative, batch, batch_groups, unit_fn),
+                          lambda flat: harness.sysid_table(units, flat, len(seeds), len(ms)))
 
 
 def sharded_lqr_sweep(X, Y, n_inputs, params, ms, seeds, plant, x0, x_ref, num_steps, estimator="nystrom", gain_fn=None,
@@ -148,15 +153,12 @@ def sharded_lqr_sweep(X, Y, n_inputs, params, ms, seeds, plant, x0, x_ref, num_s
     controller: lqr_sweep's dict -- every rank runs ONE mpc_loop_multi call and the all-gather carries eight scores, or ten
     (harness.MPC_OUT_SCORE_NAMES) when the dict holds state limits (x_min / x_max); with build="device" in it every rank builds
     the controllers of its share in ONE device call (controller_batch_fn stands in for it, as in harness.lqr_sweep)."""
-    import torch.distributed as dist
-    rank, world = (dist.get_rank(), dist.get_world_size()) if dist.is_initialized() else (0, 1)
     units = harness.lqr_plan(X, Y, n_inputs, params, ms, seeds, estimator, centers)
-    mine = shard_units(len(units), rank, world)
-    local, _, _, _ = harness.lqr_run_units(X, Y, n_inputs, params, [units[u] for u in mine], plant, x0, x_ref, num_steps,
-                                           estimator, gain_fn, c, u_opt, batch, workers, False, fit_fn, loop_fn, gain,
-                                           gain_batch_fn, controller, controller_batch_fn)
-    flat = all_gather_scores(local, len(units), rank, world) if world > 1 else local
-    return harness.lqr_result(units, flat, None, None, len(seeds), len(ms))
+    return _sharded_sweep(units, lambda mine: harness.lqr_run_units(X, Y, n_inputs, params, mine, plant, x0, x_ref, num_steps,
+                                                                    estimator, gain_fn, c, u_opt, batch, workers, False, fit_fn,
+                                                                    loop_fn, gain, gain_batch_fn, controller,
+                                                                    controller_batch_fn)[0],
+                          lambda flat: harness.lqr_result(units, flat, None, None, len(seeds), len(ms)))
 
 
 def sharded_cloth_lqr_sweep(X, Y, n_inputs, params, m, seeds, x0, x_ref, num_steps=60, estimator="nystrom", c=0.0075,
@@ -167,17 +169,13 @@ def sharded_cloth_lqr_sweep(X, Y, n_inputs, params, m, seeds, x0, x_ref, num_ste
     call per rank) and ONE all-gather assembles the four scores of every unit.  Per-step errors and trajectories stay on
     their ranks.  Every rank returns the same dict of tables J, err_final, u_sumsq, u_absmax (harness.cloth_lqr_sweep
     without `err`, `timing` and trajectories)."""
-    import torch.distributed as dist
-    rank, world = (dist.get_rank(), dist.get_world_size()) if dist.is_initialized() else (0, 1)
     names, units = harness.cloth_lqr_plan(X, Y, n_inputs, params, m, seeds, estimator, centers)
-    mine = shard_units(len(units), rank, world)
-    local = harness.cloth_lqr_run_units(X, Y, n_inputs, [units[u] for u in mine], x0, x_ref, num_steps, c, gain, batch,
-                                        workers, control_nodes, False, fit_fn, loop_fn, gain_batch_fn)[0]
-    flat = all_gather_scores(local, len(units), rank, world) if world > 1 else local
-    out = harness.cloth_lqr_result(names, units, flat, np.full((len(units), 0), np.nan), len(seeds),
-                                   isinstance(estimator, str))
-    del out["err"]
-    return out
+    no_err, single = np.full((len(units), 0), np.nan), isinstance(estimator, str)
+    return _sharded_sweep(units, lambda mine: harness.cloth_lqr_run_units(X, Y, n_inputs, mine, x0, x_ref, num_steps, c, gain,
+                                                                          batch, workers, control_nodes, False, fit_fn, loop_fn,
+                                                                          gain_batch_fn)[0],
+                          lambda flat: {k: v for k, v in harness.cloth_lqr_result(names, units, flat, no_err, len(seeds),
+                                                                                  single).items() if k != "err"})
 
 
 def sample_sharded_fit(reg, X_local, Y_local, landmark_rows=None):

@@ -8,7 +8,6 @@ import itertools
 import numpy as np
 
 from . import _lib
-from .dynamical_systems import PolynomialSystem
 from .regressors import KoopmanNystromRegressor, KoopmanSplineRegressor
 
 
@@ -617,13 +616,36 @@ def hjb_optimal_control(x0, num_steps, plant):
     return u_opt, float(np.squeeze(J))
 
 
-def _broadcast_states(x, n, d, what):
+def _broadcast_states(x, n, d, what, one=None):
+    """(n, d) states of the plant loops, whose units share d: x holds d numbers (one state for all units) or n d (one per unit,
+    row after row).  The count decides, where _per_unit, whose units may differ in d, goes by the shape."""
     x = np.asarray(x, dtype=np.float64)
     if x.size == d:
         return np.ascontiguousarray(np.broadcast_to(x.reshape(1, d), (n, d)))
     if x.size != n * d:
-        raise ValueError(f"{what} has shape {x.shape}, expected one state of dimension {d} or {(n, d)}")
+        raise ValueError(f"{what} has shape {x.shape}, expected {one or f'one state of dimension {d}'} or {(n, d)}")
     return np.ascontiguousarray(x.reshape(n, d))
+
+
+def _uopt_rows(u_opt, width, n, rows):
+    """(u_opt as a (k, width) table or None, the row of each of n units: `rows` if given, else u when k = n > 1, else 0)."""
+    if u_opt is None:
+        return None, rows
+    uo = np.asarray(u_opt, dtype=np.float64).reshape(-1, width)
+    if rows is None:
+        rows = list(range(n)) if uo.shape[0] == n and n > 1 else [0] * n
+    return uo, rows
+
+
+def _score_dict(names, sc, trajectories=False, states=None, controls=None, with_info=False, info=None):
+    """What the multi loops return: the score columns by name, rmse_control, and the trajectories / info that were asked for."""
+    out = {name: sc[:, i].copy() for i, name in enumerate(names)}
+    out["rmse_control"] = rmse_control_percent(out["sse_u"], out["ss_opt"])
+    if trajectories:
+        out["states"], out["controls"] = states, controls
+    if with_info:
+        out["info"] = info
+    return out
 
 
 def plant_loop_multi(regressors, gains, x0s, x_refs, num_steps, plant, u_opt=None, return_trajectories=False,
@@ -641,11 +663,8 @@ def plant_loop_multi(regressors, gains, x0s, x_refs, num_steps, plant, u_opt=Non
     (k, num_steps, p), controls (n_units, num_steps, p), the scores summed over the inputs (control_scores)."""
     regs = list(regressors)
     n = len(regs)
-    plant_id, Ts = getattr(plant, "plant_id", None), getattr(plant, "Ts", None)
-    poly = isinstance(plant, PolynomialSystem)
-    if (plant_id is None and not poly) or Ts is None:
-        raise ValueError("plant must be one of the package's dynamical systems (plant_id) or a PolynomialSystem, with its step "
-                         "length Ts set")
+    from .regressors import _check_plant
+    plant_id, Ts, poly = _check_plant(plant)
     d = int(plant.n_states)
     p = int(plant.n_inputs) if poly else 1
     ctx = _lib.get_context()
@@ -659,24 +678,15 @@ def plant_loop_multi(regressors, gains, x0s, x_refs, num_steps, plant, u_opt=Non
         Ks.append(K)
     if len(Ks) != n:
         raise ValueError(f"{len(Ks)} gains for {n} regressors")
-    rows = uopt_rows
-    if u_opt is not None:
-        uo = np.asarray(u_opt, dtype=np.float64).reshape(-1, int(num_steps) * p)
-        if rows is None:
-            rows = list(range(n)) if uo.shape[0] == n and n > 1 else [0] * n
+    uo, rows = _uopt_rows(u_opt, int(num_steps) * p, n, uopt_rows)
     x0b, xrb = _broadcast_states(x0s, n, d, "x0s"), _broadcast_states(x_refs, n, d, "x_refs")
     if poly:
-        sc, ox, ou = ctx.poly_plant_loop_multi(plant.descriptor(), num_steps, handles, Ks, x0b, xrb,
-                                               u_opt=None if u_opt is None else uo, uopt_rows=rows,
+        sc, ox, ou = ctx.poly_plant_loop_multi(plant.descriptor(), num_steps, handles, Ks, x0b, xrb, u_opt=uo, uopt_rows=rows,
                                                want_x=return_trajectories, want_u=return_trajectories)
     else:
-        sc, ox, ou = ctx.plant_loop_multi(plant_id, Ts, num_steps, handles, Ks, x0b, xrb, u_opt=None if u_opt is None else uo,
-                                          uopt_rows=rows, want_x=return_trajectories, want_u=return_trajectories)
-    out = {name: sc[:, i].copy() for i, name in enumerate(SCORE_NAMES)}
-    out["rmse_control"] = rmse_control_percent(out["sse_u"], out["ss_opt"])
-    if return_trajectories:
-        out["states"], out["controls"] = ox, ou
-    return out
+        sc, ox, ou = ctx.plant_loop_multi(plant_id, Ts, num_steps, handles, Ks, x0b, xrb, u_opt=uo, uopt_rows=rows,
+                                          want_x=return_trajectories, want_u=return_trajectories)
+    return _score_dict(SCORE_NAMES, sc, return_trajectories, ox, ou)
 
 
 MPC_SCORE_NAMES = SCORE_NAMES + ("iters_sum", "r_max", "n_at_limit", "n_iterated")
@@ -811,32 +821,14 @@ def mpc_loop_multi(regressors, controllers, x0s, x_refs, num_steps, plant, iters
         else:
             outs.append(None)
     with_rows = any(o is not None for o in outs)
-    rows = uopt_rows
-    uo = None
-    if u_opt is not None:
-        uo = np.asarray(u_opt, dtype=np.float64).reshape(-1, num_steps * p)
-        if rows is None:
-            rows = list(range(n)) if uo.shape[0] == n and n > 1 else [0] * n
-    uis = None
-    if u_inits is not None:
-        ua = np.asarray(u_inits, dtype=np.float64)
-        if ua.size == p:
-            ua = np.broadcast_to(ua.reshape(1, p), (n, p))
-        elif ua.size != n * p:
-            raise ValueError(f"u_inits has shape {ua.shape}, expected {p} entries or {(n, p)}")
-        uis = list(np.ascontiguousarray(ua.reshape(n, p)))
+    uo, rows = _uopt_rows(u_opt, num_steps * p, n, uopt_rows)
+    uis = None if u_inits is None else list(_broadcast_states(u_inits, n, p, "u_inits", f"{p} entries"))
     x0b, xrb = _broadcast_states(x0s, n, d, "x0s"), _broadcast_states(x_refs, n, d, "x_refs")
     sc, ox, ou, oi = ctx.mpc_loop_multi(plant.descriptor(), num_steps, handles, descs, x0b, xrb, u_inits=uis, u_opt=uo,
                                         uopt_rows=rows, want_x=return_trajectories, want_u=return_trajectories,
                                         want_info=return_info, outs=outs if with_rows else None)
     del keep
-    out = {name: sc[:, i].copy() for i, name in enumerate(MPC_OUT_SCORE_NAMES if with_rows else MPC_SCORE_NAMES)}
-    out["rmse_control"] = rmse_control_percent(out["sse_u"], out["ss_opt"])
-    if return_trajectories:
-        out["states"], out["controls"] = ox, ou
-    if return_info:
-        out["info"] = oi
-    return out
+    return _score_dict(MPC_OUT_SCORE_NAMES if with_rows else MPC_SCORE_NAMES, sc, return_trajectories, ox, ou, return_info, oi)
 
 
 def lqr_default_gain(c=1.0):
@@ -1008,6 +1000,31 @@ def lqr_controller_has_rows(spec):
     return any(np.any(np.isfinite(a)) for a in given)
 
 
+def _run_live_units(gains, names, tm, loop, extras):
+    """The tail of lqr_run_units and cloth_lqr_run_units after lqr_fit_and_gain (timing `tm`): res = loop(live) over the units
+    with a gain; its columns `names` and the arrays res[key] of `extras` go into NaN-filled arrays over all units (extras:
+    key -> trailing shape, or None: res decides, None when no unit is live).  Returns (scores, extras, res, live, timing)."""
+    import time
+    t2 = time.perf_counter()
+    n = len(gains)
+    live = [i for i in range(n) if gains[i] is not None]
+    scores = np.full((n, len(names)), np.nan)
+    more = {key: None if tail is None else np.full((n,) + tail, np.nan) for key, tail in extras.items()}
+    res = None
+    if live:
+        res = loop(live)
+        for k, name in enumerate(names):
+            scores[live, k] = res[name]
+        for key in extras:
+            if more[key] is None:
+                more[key] = np.full((n,) + np.shape(res[key])[1:], np.nan)
+            more[key][live] = res[key]
+    loop_s = time.perf_counter() - t2
+    timing = dict(fit_s=tm["fit_s"], gain_wait_s=tm["gain_wait_s"], loop_s=loop_s, gain_cpu_s=tm["gain_cpu_s"],
+                  total_s=tm["fit_s"] + tm["gain_wait_s"] + loop_s)
+    return scores, more, res, live, timing
+
+
 def lqr_run_units(X, Y, n_inputs, params, units, plant, x0, x_ref, num_steps, estimator="nystrom", gain_fn=None, c=1.0,
                   u_opt=None, batch=32, workers=4, return_trajectories=False, fit_fn=None, loop_fn=None, gain="host",
                   gain_batch_fn=None, controller=None, controller_batch_fn=None):
@@ -1024,37 +1041,22 @@ def lqr_run_units(X, Y, n_inputs, params, units, plant, x0, x_ref, num_steps, es
     With a state limit in the dict (lqr_controller_has_rows) the units run with their output rows and carry the ten
     MPC_OUT_SCORE_NAMES.  build="device" in the dict: the controllers of all fitted units from ONE nk_model_mpc_build_batch call
     after the fits (lqr_fit_and_gain; controller_batch_fn stands in for it); a unit with a non-zero status scores NaN."""
-    import time
     controller = lqr_controller_spec(controller)
     if controller is not None and gain == "device":
         raise ValueError("controller needs gain='host': the terminal cost of the MPC is the host Riccati solution")
     names = SCORE_NAMES if controller is None else MPC_OUT_SCORE_NAMES if lqr_controller_has_rows(controller) else MPC_SCORE_NAMES
     loop_fn = loop_fn or (plant_loop_multi if controller is None else mpc_loop_multi)
-    n = len(units)
     regs, gains, _, tm = lqr_fit_and_gain(X, Y, n_inputs, params, units, estimator, gain_fn, c, batch, workers, fit_fn, gain,
                                           gain_batch_fn, controller=controller, controller_batch_fn=controller_batch_fn)
-    t2 = time.perf_counter()
-    live = [i for i in range(n) if gains[i] is not None]
-    scores = np.full((n, len(names)), np.nan)
-    states = controls = None
-    if live:
-        if controller is None:
-            res = loop_fn([regs[i] for i in live], [gains[i] for i in live], x0, x_ref, num_steps, plant, u_opt=u_opt,
-                          return_trajectories=return_trajectories)
-        else:
-            res = loop_fn([regs[i] for i in live], [gains[i] for i in live], x0, x_ref, num_steps, plant,
-                          iters=controller["iters"], tol=controller["tol"], u_opt=u_opt,
-                          return_trajectories=return_trajectories)
-        for k, name in enumerate(names):
-            scores[live, k] = res[name]
-        if return_trajectories:
-            states = np.full((n,) + np.shape(res["states"])[1:], np.nan)
-            controls = np.full((n,) + np.shape(res["controls"])[1:], np.nan)
-            states[live], controls[live] = res["states"], res["controls"]
-    loop_s = time.perf_counter() - t2
-    timing = dict(fit_s=tm["fit_s"], gain_wait_s=tm["gain_wait_s"], loop_s=loop_s, gain_cpu_s=tm["gain_cpu_s"],
-                  total_s=tm["fit_s"] + tm["gain_wait_s"] + loop_s)
-    return scores, states, controls, timing
+    kw = {} if controller is None else dict(iters=controller["iters"], tol=controller["tol"])
+
+    def loop(live):
+        return loop_fn([regs[i] for i in live], [gains[i] for i in live], x0, x_ref, num_steps, plant, u_opt=u_opt,
+                       return_trajectories=return_trajectories, **kw)
+
+    scores, more, _, _, timing = _run_live_units(gains, names, tm, loop,
+                                                 dict(states=None, controls=None) if return_trajectories else {})
+    return scores, more.get("states"), more.get("controls"), timing
 
 
 def lqr_table(units, values, n_seeds, n_ms):
@@ -1203,7 +1205,9 @@ def closed_loop_multi_lifted(regressors, gains, lifts, targets, num_steps, c=0.0
 
 
 def _per_unit(x, n, what):
-    """One state for all n units (a vector / column) or one per unit (a sequence of n, or an (n, d) array)."""
+    """One state for all n units (a vector / column) or one per unit (a sequence of n, or an (n, d) array), as n vectors: the
+    rule of closed_loop_multi, whose units may differ in d.  The shape decides: a flat array of any length is ONE state and a
+    sequence of n numbers is n states -- _broadcast_states reads n d numbers as rows and d = n numbers as one state."""
     if isinstance(x, np.ndarray) and (x.ndim == 1 or (x.ndim == 2 and x.shape[1] == 1)):
         return [x.reshape(-1)] * n
     x = list(x)
@@ -1270,7 +1274,6 @@ def cloth_lqr_run_units(X, Y, n_inputs, units, x0, x_ref, num_steps=60, c=0.0075
     member's fit), gains (lqr_fit_and_gain) and ONE closed_loop_multi call over the units that have a gain.  Returns
     (scores (n_units, 4) in LOOP_SCORE_NAMES order, err (n_units, num_steps), gains, result of the loop call or None,
     indices of the units it held, timing); a unit whose fit or gain failed is NaN and is not submitted."""
-    import time
     x0 = np.asarray(x0, dtype=np.float64).reshape(-1)
     x_ref = np.asarray(x_ref, dtype=np.float64).reshape(-1)
     both = np.stack((x0, x_ref), axis=1)
@@ -1281,24 +1284,15 @@ def cloth_lqr_run_units(X, Y, n_inputs, units, x0, x_ref, num_steps=60, c=0.0075
         phi = reg.lift(both)
         return np.ascontiguousarray(phi[:, 0]), np.ascontiguousarray(phi[:, 1])
 
-    n = len(units)
     regs, gains, lifts, tm = lqr_fit_and_gain(X, Y, n_inputs, None, units, "nystrom", None, c, batch, workers, fit_fn, gain,
                                               gain_batch_fn, after_fit=lifted)
-    t2 = time.perf_counter()
-    live = [i for i in range(n) if gains[i] is not None]
-    scores = np.full((n, len(LOOP_SCORE_NAMES)), np.nan)
-    err = np.full((n, int(num_steps)), np.nan)
-    res = None
-    if live:
-        res = loop_fn([regs[i] for i in live], [gains[i] for i in live], [lifts[i] for i in live], [x_ref] * len(live),
-                      num_steps, c, [u_init] * len(live), return_trajectories)
-        for k, name in enumerate(LOOP_SCORE_NAMES):
-            scores[live, k] = res[name]
-        err[live] = res["err"]
-    loop_s = time.perf_counter() - t2
-    timing = dict(fit_s=tm["fit_s"], gain_wait_s=tm["gain_wait_s"], loop_s=loop_s, gain_cpu_s=tm["gain_cpu_s"],
-                  total_s=tm["fit_s"] + tm["gain_wait_s"] + loop_s)
-    return scores, err, gains, res, live, timing
+
+    def loop(live):
+        return loop_fn([regs[i] for i in live], [gains[i] for i in live], [lifts[i] for i in live], [x_ref] * len(live),
+                       num_steps, c, [u_init] * len(live), return_trajectories)
+
+    scores, more, res, live, timing = _run_live_units(gains, LOOP_SCORE_NAMES, tm, loop, dict(err=(int(num_steps),)))
+    return scores, more["err"], gains, res, live, timing
 
 
 def cloth_lqr_result(names, units, scores, err, n_seeds, single, timing=None):

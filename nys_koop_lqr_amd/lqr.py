@@ -411,7 +411,7 @@ class MPCController:
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# Limits on predicted states, hard or soft (nk_mpc_out_loop, nk_mpc_out_qp_host; csrc/nk_mpc_out.h, nk_mpc_out_loop.hip): ny
+# Limits on predicted states, hard or soft (nk_mpc_out_loop, nk_mpc_out_qp_host; csrc/nk_mpc_out.h, nk_mpc_loop.hip): ny
 # output rows G U + T e with their own bounds join the constraint rows, A_c = [I; D; G].
 # ---------------------------------------------------------------------------------------------------------------------------
 def mpc_condense_outputs(A, B, C_rows, N, Ny=None):

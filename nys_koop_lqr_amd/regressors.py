@@ -251,17 +251,52 @@ def _fetched(name):
     return property(get, set_)
 
 
+_PLANT_MESSAGE = ("plant must be one of the package's dynamical systems (plant_id) or a PolynomialSystem, with its step length "
+                  "Ts set")
+
+
+def _check_plant(plant):
+    """(plant_id, Ts, whether it is a PolynomialSystem) of a plant the single-launch loops take; ValueError otherwise."""
+    plant_id, Ts = getattr(plant, "plant_id", None), getattr(plant, "Ts", None)
+    poly = isinstance(plant, PolynomialSystem)
+    if (plant_id is None and not poly) or Ts is None:
+        raise ValueError(_PLANT_MESSAGE)
+    return plant_id, Ts, poly
+
+
 def _as_polynomial_plant(plant):
     """A PolynomialSystem as it is; a built-in plant as its table (the reference's RK4 variant)."""
     if isinstance(plant, PolynomialSystem):
         return plant
-    plant_id, Ts = getattr(plant, "plant_id", None), getattr(plant, "Ts", None)
+    plant_id, Ts, _ = _check_plant(plant)
     make = {_lib.NK_PLANT_DUFFING: PolynomialSystem.duffing, _lib.NK_PLANT_DOUBLE_INTEGRATOR: PolynomialSystem.double_integrator,
             _lib.NK_PLANT_HJB: PolynomialSystem.hjb}.get(plant_id)
-    if make is None or Ts is None:
-        raise ValueError("plant must be one of the package's dynamical systems (plant_id) or a PolynomialSystem, with its "
-                         "step length Ts set")
+    if make is None:
+        raise ValueError(_PLANT_MESSAGE)
     return make(float(Ts))
+
+
+def _single_or_batch(x0, x_ref, d, u_init=None, p=None):
+    """(single, xb (batch, d), xr (batch, d), ui (batch, p) or None) of the states a plant loop is called with.  single: x0 is
+    a vector or a (d, 1) column, as the reference's drivers pass states (with d = 1 a (1, 1) array is that column); else x0
+    is (batch, d).  x_ref: one state for all loops or (batch, d); u_init: p entries for all loops or (batch, p)."""
+    x0 = np.asarray(x0, dtype=np.float64)
+    x_ref = np.asarray(x_ref, dtype=np.float64)
+    single = x0.ndim < 2 or x0.shape == (d, 1)
+    if x0.size % d:
+        raise ValueError(f"initial states have shape {x0.shape}, the model has {d} states")
+    xb = np.ascontiguousarray(x0.reshape(1, d) if single else x0.reshape(-1, d))
+    batch = xb.shape[0]
+    if x_ref.size not in (d, batch * d):
+        raise ValueError(f"reference has shape {x_ref.shape}, expected one state of dimension {d} or {(batch, d)}")
+    xr = np.ascontiguousarray(np.broadcast_to(x_ref.reshape(-1, d), (batch, d)))
+    ui = None
+    if u_init is not None:
+        u_init = np.asarray(u_init, dtype=np.float64)
+        if u_init.size not in (p, batch * p):
+            raise ValueError(f"u_init has shape {u_init.shape}, expected {p} entries or {(batch, p)}")
+        ui = np.ascontiguousarray(np.broadcast_to(u_init.reshape(-1, p), (batch, p)))
+    return single, xb, xr, ui
 
 
 class _DeviceModelRegressor(KoopmanRegressor):
@@ -524,13 +559,8 @@ class _DeviceModelRegressor(KoopmanRegressor):
         else:
             f0 = np.ascontiguousarray(phi0.reshape(-1, m))
             fr = np.ascontiguousarray(np.broadcast_to(phi_ref.reshape(-1, m), f0.shape))
-        batch = f0.shape[0]
-        ox, ou = np.empty((batch, num_steps, d)), np.empty((batch, num_steps, p))
-        _lib.check(ctx.lib.nk_closed_loop_batch(ctx.handle, h, K.ctypes.data, f0.ctypes.data, fr.ctypes.data,
-                                                int(num_steps), batch, ox.ctypes.data, ou.ctypes.data))
-        if single:
-            return ox[0].T, ou[0].T
-        return ox, ou
+        ox, ou = ctx.closed_loop_batch(h, K, f0, fr, num_steps, d)
+        return (ox[0].T, ou[0].T) if single else (ox, ou)
 
     def closed_loop_plant(self, K, x0, x_ref, num_steps, plant):
         """LQR closed loop around the TRUE plant (lqr_control of benchmark_lqr_hjb.py:73-97 / benchmark_lqr_classic.py:67-89):
@@ -546,36 +576,16 @@ class _DeviceModelRegressor(KoopmanRegressor):
         h = self._ensure_model()
         d, m = self._landmark_shape()
         p = int(self.n_inputs)
-        plant_id, Ts = getattr(plant, "plant_id", None), getattr(plant, "Ts", None)
-        poly = isinstance(plant, PolynomialSystem)
-        if (plant_id is None and not poly) or Ts is None:
-            raise ValueError("plant must be one of the package's dynamical systems (plant_id) or a PolynomialSystem, with its "
-                             "step length Ts set")
+        plant_id, Ts, poly = _check_plant(plant)
         K = np.ascontiguousarray(K, dtype=np.float64)
         if K.shape != (p, m):
             raise ValueError(f"gain has shape {K.shape}, expected {(p, m)}")
-        num_steps = int(num_steps)
-        x0 = np.asarray(x0, dtype=np.float64)
-        x_ref = np.asarray(x_ref, dtype=np.float64)
-        single = x0.ndim < 2 or x0.shape == (d, 1)  # a vector or a column, as the reference's drivers pass states
-        if x0.size % d:
-            raise ValueError(f"initial states have shape {x0.shape}, the model has {d} states")
-        xb = np.ascontiguousarray(x0.reshape(1, d) if single else x0.reshape(-1, d))
-        batch = xb.shape[0]
-        if x_ref.size not in (d, batch * d):
-            raise ValueError(f"reference has shape {x_ref.shape}, expected one state of dimension {d} or {(batch, d)}")
-        xr = np.ascontiguousarray(np.broadcast_to(x_ref.reshape(-1, d), (batch, d)))
-        ox, ou = np.empty((batch, max(num_steps, 0) + 1, d)), np.empty((batch, max(num_steps, 0), p if poly else 1))
+        single, xb, xr, _ = _single_or_batch(x0, x_ref, d)
         if poly:
-            rc = ctx.lib.nk_poly_plant_loop(ctx.handle, h, plant.descriptor(), K.ctypes.data, xb.ctypes.data, xr.ctypes.data,
-                                            num_steps, batch, ox.ctypes.data, ou.ctypes.data)
+            ox, ou = ctx.poly_plant_loop(h, plant.descriptor(), K, xb, xr, int(num_steps))
         else:
-            rc = ctx.lib.nk_plant_loop(ctx.handle, h, int(plant_id), float(Ts), K.ctypes.data, xb.ctypes.data,
-                                       xr.ctypes.data, num_steps, batch, ox.ctypes.data, ou.ctypes.data)
-        _lib.check_mapped(rc)
-        if single:
-            return ox[0].T, ou[0].T
-        return ox, ou
+            ox, ou = ctx.plant_loop(h, plant_id, Ts, K, xb, xr, int(num_steps))
+        return (ox[0].T, ou[0].T) if single else (ox, ou)
 
     def solve_mpc(self, horizon, c=1.0, R=None, u_min=None, u_max=None, du_min=None, du_max=None, Q=None, rho=None,
                   x_min=None, x_max=None, y_horizon=None, y_weight=np.inf, device=False):
@@ -655,38 +665,13 @@ class _DeviceModelRegressor(KoopmanRegressor):
         plant = _as_polynomial_plant(plant)
         if controller.K.shape != (p, m) or controller.F.shape[1] != m:
             raise ValueError(f"the controller is for a model with K of shape {controller.K.shape}, expected {(p, m)}")
-        num_steps = int(num_steps)
-        x0 = np.asarray(x0, dtype=np.float64)
-        x_ref = np.asarray(x_ref, dtype=np.float64)
-        single = x0.ndim < 2 or x0.shape == (d, 1)
-        if x0.size % d:
-            raise ValueError(f"initial states have shape {x0.shape}, the model has {d} states")
-        xb = np.ascontiguousarray(x0.reshape(1, d) if single else x0.reshape(-1, d))
-        batch = xb.shape[0]
-        if x_ref.size not in (d, batch * d):
-            raise ValueError(f"reference has shape {x_ref.shape}, expected one state of dimension {d} or {(batch, d)}")
-        xr = np.ascontiguousarray(np.broadcast_to(x_ref.reshape(-1, d), (batch, d)))
-        ui = None
-        if u_init is not None:
-            u_init = np.asarray(u_init, dtype=np.float64)
-            if u_init.size not in (p, batch * p):
-                raise ValueError(f"u_init has shape {u_init.shape}, expected {p} entries or {(batch, p)}")
-            ui = np.ascontiguousarray(np.broadcast_to(u_init.reshape(-1, p), (batch, p)))
+        single, xb, xr, ui = _single_or_batch(x0, x_ref, d, u_init, p)
         ds, keep = _lib.mpc_desc(controller, iters, tol)
-        steps = max(num_steps, 0)
-        ox, ou = np.empty((batch, steps + 1, d)), np.empty((batch, steps, p))
-        oi = np.empty((batch, steps, 2)) if return_info else None
+        out = None
         if hasattr(controller, "ycomp") and int(iters) != 0:  # an lqr.MPCOutputController (iters = 0: the saturated LQR)
             out, keep_out = _lib.mpc_out(controller)
-            rc = ctx.lib.nk_mpc_out_loop(ctx.handle, h, plant.descriptor(), C.byref(ds), C.byref(out), xb.ctypes.data,
-                                         xr.ctypes.data, None if ui is None else ui.ctypes.data, num_steps, batch,
-                                         ox.ctypes.data, ou.ctypes.data, None if oi is None else oi.ctypes.data)
-            del keep_out
-        else:
-            rc = ctx.lib.nk_mpc_loop(ctx.handle, h, plant.descriptor(), C.byref(ds), xb.ctypes.data, xr.ctypes.data,
-                                     None if ui is None else ui.ctypes.data, num_steps, batch, ox.ctypes.data, ou.ctypes.data,
-                                     None if oi is None else oi.ctypes.data)
-        _lib.check_mapped(rc)
+            keep.append(keep_out)
+        ox, ou, oi = ctx.mpc_loop(h, plant.descriptor(), ds, xb, xr, int(num_steps), ui, return_info, out)
         del keep
         if single:
             return (ox[0].T, ou[0].T, oi[0]) if return_info else (ox[0].T, ou[0].T)
