@@ -1,6 +1,7 @@
 // Compute entry points of the C ABI that need nothing of the runtime's registry (nk_api.hip): kernel matrix, landmark
 // selection, lift / predict / score and the small linear-algebra calls.
 #include "nk_common.h"
+#include "nk_chol.h"
 #include "nk_tn.h"
 #include "nk_api_internal.h"
 

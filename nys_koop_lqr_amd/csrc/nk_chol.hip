@@ -4,6 +4,7 @@
 // scipy.linalg.lstsq on the (numerically full-rank) regularised normal matrices (regressors.py:155,165).  A non-positive
 // pivot is reported as NK_ERR_NOT_SPD; there is no silent rank truncation.
 #include "nk_common.h"
+#include "nk_chol.h"
 
 #include <algorithm>
 #include <cmath>
@@ -15,10 +16,6 @@ namespace nk {
 // ---------------------------------------------------------------------------------------------------------------
 // blocked Cholesky (lower) with inverted diagonal blocks
 // ---------------------------------------------------------------------------------------------------------------
-// potrf_diag_kernel lives in nk_potrf.hip (fully unrolled, slow to compile)
-int launch_potrf_diag_pair(nk_ctx* ctx, double* const* Ajj, const int64_t* lda, const int* nb, double* const* Linv,
-                           int nsys, int blk, double* const* plog);
-
 // failure flags and [min, max] pivot slots of the current stream's two systems: flags <- 0, min <- +inf, max <- 0
 __device__ __forceinline__ void reset_pivots_kernel_body(int* info, unsigned long long* piv) {
   if (threadIdx.x < 4) piv[threadIdx.x] = (threadIdx.x & 1) ? 0ull : 0x7FF0000000000000ull;
@@ -33,108 +30,108 @@ static int reset_pivots(nk_ctx* ctx) {
   return NK_OK;
 }
 
-// order, workspace and pivot log of diagonal block jb + 1 of every system (order 0: the system has no such block)
-static void next_block(const CholSys* sys, int nsys, int jb, int* nbn, double** Lin, double** Pln) {
-  constexpr int NB = CHOL_NB;
-  const int j1 = (jb + 1) * NB;
-  for (int q = 0; q < nsys; ++q) {
-    const CholSys& y = sys[q];
-    if (j1 >= y.m) continue;
-    nbn[q] = y.m - j1 < NB ? y.m - j1 : NB;
-    Lin[q] = y.Linv + (size_t)(jb + 1) * CHOL_WS;
-    Pln[q] = y.pivlog ? y.pivlog + j1 : nullptr;
-  }
+// the most block steps of any system of a pair
+static int pair_blocks(const CholSys* sys, int nsys) {
+  int nblk = 0;
+  for (int q = 0; q < nsys; ++q) nblk = std::max(nblk, chol_blocks(sys[q].m));
+  return nblk;
 }
 
-// Operands of block step jb of up to two systems (a system that has no such block keeps order 0 and empty calls)
+// diagonal-block record of the current stream with both slots empty (the failure flag and pivot slots are set for both)
+static PotrfBatch potrf_batch(nk_ctx* ctx) {
+  PotrfBatch pb = {};
+  for (int q = 0; q < 2; ++q) {
+    pb.info[q] = ctx->d_info + info_base(ctx) + q;
+    pb.piv[q] = ctx->d_piv + 2 * (info_base(ctx) + q);
+  }
+  return pb;
+}
+// slot q <- diagonal block jb (order nb, top left corner A) of system y
+static void potrf_slot(PotrfBatch& pb, int q, const CholSys& y, int jb, double* A, int nb) {
+  pb.A[q] = A; pb.lda[q] = y.ldp; pb.nb[q] = nb;
+  pb.Linv[q] = y.Linv + (size_t)jb * CHOL_WS;
+  pb.plog[q] = y.pivlog ? y.pivlog + jb * CHOL_NB : nullptr;
+}
+// trailing update of the rows x rem matrix C by the panel P (rows x CHOL_NB)
+static TrailSys trail_sys(const double* P, int64_t ldp, double* C, int64_t ldc, int rows, int rem) {
+  const CholTrailTiles t = chol_trail_tiles(rows, rem);
+  TrailSys s = {};
+  s.P = P; s.ldp = ldp; s.C = C; s.ldc = ldc; s.rows = rows; s.rem = rem;
+  s.tiles_n = t.tiles_n; s.nblocks = t.workgroups;
+  return s;
+}
+// one part of a split trailing update t (look-ahead)
+static TrailSys trail_part(const TrailSys& t, const CholTrailPart& p) {
+  return trail_sys(t.P + (int64_t)p.row0 * t.ldp, t.ldp, t.C + (int64_t)p.row0 * t.ldc + p.col0, t.ldc, p.rows, p.cols);
+}
+
+// Records of block step jb of up to two systems (a system that has no such block, or no such launch, keeps an empty slot)
 struct CholStep {
-  double* Ajj[2] = {nullptr, nullptr};  // diagonal block
-  double* Li[2] = {nullptr, nullptr};   // its workspace (CHOL_WS doubles)
-  double* Pl[2] = {nullptr, nullptr};   // its slice of the pivot log
-  int64_t lda[2] = {0, 0};
-  int nbj[2] = {0, 0};                  // its order
-  GemmCall panel[2], trail[2];
+  PotrfBatch diag;   // the diagonal blocks
+  PanelBatch panel;  // panel <- panel * Linv_jj^T   (in place: every workgroup reads exactly the rows it writes)
+  TrailBatch trail;  // trailing <- trailing - panel * panel^T  (lower tiles of the square part, full tiles for the extra rows)
+  PotrfBatch next;   // the diagonal blocks of step jb + 1: the top left corners of the trailing matrices
+  bool has_next;     // ... of which there is at least one
 };
 // extra[q]: rows below the m x m matrix of system q that ride along (the right-hand sides of the augmented form); zeros for
-// the plain factorisation
-static void chol_step_operands(const CholSys* sys, int nsys, int jb, const int* extra, CholStep* st) {
-  constexpr int NB = CHOL_NB;
-  const int j0 = jb * NB;
+// the plain factorisation.  The shapes are the plan's (nk_chol_plan.h); what the kernels take for granted of them is checked
+// here, where the records are filled.
+static int chol_step_operands(nk_ctx* ctx, const CholSys* sys, int nsys, int jb, const int* extra, CholStep* st) {
+  *st = CholStep{};
+  st->diag = potrf_batch(ctx);
+  st->next = potrf_batch(ctx);
+  const int fix = chol_fix_enabled();
   for (int q = 0; q < nsys; ++q) {
     const CholSys& y = sys[q];
-    if (j0 >= y.m) continue;
-    const int nbj = st->nbj[q] = y.m - j0 < NB ? y.m - j0 : NB;
-    st->Ajj[q] = y.P + (int64_t)j0 * y.ldp + j0;
-    st->lda[q] = y.ldp;
-    st->Li[q] = y.Linv + (size_t)jb * CHOL_WS;
-    st->Pl[q] = y.pivlog ? y.pivlog + j0 : nullptr;
-    const int rem = y.m - j0 - nbj;   // rows of the square part below the diagonal block
-    const int rows = rem + extra[q];  // ... plus the extra rows
-    if (rows <= 0) continue;
-    double* pnl = y.P + (int64_t)(j0 + nbj) * y.ldp + j0;
-    // panel <- panel * Linv_jj^T   (in place: one n-tile, every workgroup reads exactly the rows it writes)
-    GemmCall& panel = st->panel[q];
-    panel.M = rows; panel.N = nbj; panel.K = nbj;
-    panel.A = pnl; panel.lda = y.ldp; panel.B = st->Li[q]; panel.ldb = NB;
-    panel.C = pnl; panel.ldc = y.ldp;
-    if (rem <= 0) continue;
-    // trailing <- trailing - panel * panel^T  (lower tiles of the square part, full tiles for the extra rows)
-    GemmCall& trail = st->trail[q];
-    trail.M = rows; trail.N = rem; trail.K = nbj; trail.alpha = -1.0; trail.beta = 1.0;
-    trail.A = pnl; trail.lda = y.ldp; trail.B = pnl; trail.ldb = y.ldp;
-    trail.C = y.P + (int64_t)(j0 + nbj) * y.ldp + (j0 + nbj); trail.ldc = y.ldp;
-    trail.opts.tri = TRI_LOWER;
+    const CholStepShape sh = chol_step_shape(y.m, extra[q], jb);
+    if (sh.nbj == 0) continue;
+    NK_REQUIRE(sh.nbj <= CHOL_NB && (!sh.trail || (sh.panel && sh.nbj == CHOL_NB && sh.rows >= sh.rem)) &&
+                   (sh.nb_next == 0 || sh.trail),
+               "blocked Cholesky: block step %d of a system of order %d (+%d rows) has no shape the kernels take", jb, y.m,
+               extra[q]);
+    potrf_slot(st->diag, q, y, jb, y.P + (int64_t)sh.j0 * y.ldp + sh.j0, sh.nbj);
+    if (!sh.panel) continue;
+    double* pnl = y.P + (int64_t)(sh.j0 + sh.nbj) * y.ldp + sh.j0;
+    PanelSys& p = st->panel.s[q];  // (the workspace holds the inverse with leading dimension CHOL_NB, as the kernel reads it)
+    p.P = pnl; p.ldp = y.ldp; p.Linv = st->diag.Linv[q]; p.rows = sh.rows; p.nb = sh.nbj; p.fix = fix;
+    p.nblocks = chol_panel_workgroups(sh.rows);
+    if (!sh.trail) continue;
+    // (the kernel contracts over a whole panel of CHOL_NB columns and walks the lower tiles of rows >= rem: required above)
+    st->trail.s[q] = trail_sys(pnl, y.ldp, pnl + sh.nbj, y.ldp, sh.rows, sh.rem);  // (C starts right of the panel's top)
+    if (sh.nb_next == 0) continue;
+    potrf_slot(st->next, q, y, jb + 1, st->trail.s[q].C, sh.nb_next);
+    st->has_next = true;
   }
-}
-
-// K = 64 rank update: specialised kernel (nk_trail.hip), generic engine otherwise
-static int chol_trail_update(nk_ctx* ctx, const GemmCall* calls, int nsys) {
-  int rc_trail = NK_OK;
-  if (!launch_chol_trail_pair(ctx, calls, nsys, &rc_trail)) NK_TRY(launch_gemm_pair(ctx, false, true, calls, nsys));
-  return rc_trail;
+  return NK_OK;
 }
 
 // Launches of block step jb: the diagonal block unless the previous step's fused launch factored it (*diag_done), the panel,
-// and -- with `trailing` -- the trailing update, in one launch with the factorisation of the next diagonal block where
-// `fuse_next` asks for it and the shapes allow (*diag_done is then set for the next step).
-static int chol_step_launches(nk_ctx* ctx, const CholSys* sys, int nsys, int jb, const CholStep& st, bool trailing,
-                              bool fuse_next, bool* diag_done) {
-  if (!*diag_done) NK_TRY(launch_potrf_diag_pair(ctx, st.Ajj, st.lda, st.nbj, st.Li, nsys, jb, st.Pl));
+// and -- with `trailing` -- the trailing update, in one launch with the factorisation of the next diagonal block where `fuse`
+// asks for it and there is one (*diag_done is then set for the next step).
+static int chol_step_launches(nk_ctx* ctx, int jb, const CholStep& st, bool trailing, bool fuse, bool* diag_done) {
+  if (!*diag_done) NK_TRY(launch_potrf_diag_pair(ctx, st.diag, jb));
   *diag_done = false;
-  {
-    int rc_panel = NK_OK;  // 64 x 64 panel product: specialised kernel (nk_trail.hip), generic engine otherwise
-    if (!launch_chol_panel_pair(ctx, st.panel, nsys, &rc_panel)) NK_TRY(launch_gemm_pair(ctx, false, true, st.panel, nsys));
-    NK_TRY(rc_panel);
-  }
+  NK_TRY(launch_chol_panel_pair(ctx, st.panel));
   if (!trailing) return NK_OK;
-  if (fuse_next) {
-    int rc_f = NK_OK;
-    int nbn[2] = {0, 0};
-    double* Lin[2] = {nullptr, nullptr};
-    double* Pln[2] = {nullptr, nullptr};
-    next_block(sys, nsys, jb, nbn, Lin, Pln);
-    if (launch_chol_trail_potrf_pair(ctx, st.trail, nsys, nbn, Lin, jb + 1, Pln, &rc_f)) {
-      NK_TRY(rc_f);
-      *diag_done = true;
-      return NK_OK;
-    }
+  if (fuse && st.has_next) {
+    NK_TRY(launch_chol_trail_potrf_pair(ctx, st.trail, st.next, jb + 1));
+    *diag_done = true;
+    return NK_OK;
   }
-  return chol_trail_update(ctx, st.trail, nsys);
+  return launch_chol_trail_pair(ctx, st.trail);
 }
 
 int cholesky_lower_pair_async(nk_ctx* ctx, const CholSys* sys, int nsys) {
-  constexpr int NB = CHOL_NB;
   NK_REQUIRE(nsys >= 1 && nsys <= 2, "cholesky_lower_pair: 1..2 systems");
   NK_TRY(reset_pivots(ctx));
-  int nblk = 0;
-  for (int q = 0; q < nsys; ++q) nblk = std::max(nblk, (sys[q].m + NB - 1) / NB);
+  const int nblk = pair_blocks(sys, nsys);
   const bool fuse = chol_fuse_enabled();
   const int no_extra[2] = {0, 0};  // (CholSys::extra is not read here)
   bool diag_done = false;
   for (int jb = 0; jb < nblk; ++jb) {
     CholStep st;
-    chol_step_operands(sys, nsys, jb, no_extra, &st);
-    NK_TRY(chol_step_launches(ctx, sys, nsys, jb, st, true, fuse && jb + 1 < nblk, &diag_done));
+    NK_TRY(chol_step_operands(ctx, sys, nsys, jb, no_extra, &st));
+    NK_TRY(chol_step_launches(ctx, jb, st, true, fuse, &diag_done));
   }
   return NK_OK;
 }
@@ -219,16 +216,16 @@ int cholesky_lower_pair(nk_ctx* ctx, const CholSys* sys, int nsys) {
 // of step j needs rest(j-1) [event R] -- the column it touches received its older updates there.  Members of a lock-step
 // group record everything into one sequence (events are no-ops there), which is a valid order of the same graph.
 int cholesky_aug_pair_async(nk_ctx* ctx, const CholSys* sys, int nsys, hipEvent_t pause, int pause_step) {
-  constexpr int NB = CHOL_NB;
   NK_REQUIRE(nsys >= 1 && nsys <= 2, "cholesky_aug_pair: 1..2 systems");
   NK_TRY(reset_pivots(ctx));
-  int nblk = 0, mmin = sys[0].m;
+  const int nblk = pair_blocks(sys, nsys);
+  int ms[2] = {0, 0}, extra[2] = {0, 0};
   for (int q = 0; q < nsys; ++q) {
-    nblk = std::max(nblk, (sys[q].m + NB - 1) / NB);
-    mmin = std::min(mmin, sys[q].m);
+    ms[q] = sys[q].m;
+    extra[q] = sys[q].extra;
   }
   // the whole factorisation as one tile-dataflow launch (nk_chol_flow.hip, same bits); lock-step groups record the chain below
-  if (!ctx->chol_flow_off && mmin >= 256 && !ctx_recording(ctx) && chol_flow_enabled()) {
+  if (chol_route_is_flow(ms, nsys, !ctx->chol_flow_off && !ctx_recording(ctx) && chol_flow_enabled())) {
     if (pause != nullptr && pause_step >= 0 && pause_step < nblk) NK_HIP(hipStreamWaitEvent(ctx->stream, pause, 0));
     NK_TRY(cholesky_flow_pair(ctx, sys, nsys));
     NK_TRY(launch_trsm_right_lower_pair(ctx, sys, nsys));
@@ -254,42 +251,34 @@ int cholesky_aug_pair_async(nk_ctx* ctx, const CholSys* sys, int nsys, hipEvent_
     NK_HIP(hipStreamWaitEvent(s_rest, la_evt[1], 0));
   }
   const bool fuse = chol_fuse_enabled();
-  int extra[2] = {0, 0};
-  for (int q = 0; q < nsys; ++q) extra[q] = sys[q].extra;
   bool diag_done = false;
   for (int jb = 0; jb < nblk; ++jb) {
     if (pause != nullptr && jb == pause_step) NK_HIP(hipStreamWaitEvent(ctx->stream, pause, 0));
     CholStep st;
-    chol_step_operands(sys, nsys, jb, extra, &st);
-    NK_TRY(chol_step_launches(ctx, sys, nsys, jb, st, !lookahead, fuse && jb + 1 < nblk, &diag_done));
+    NK_TRY(chol_step_operands(ctx, sys, nsys, jb, extra, &st));
+    NK_TRY(chol_step_launches(ctx, jb, st, !lookahead, fuse, &diag_done));
     if (lookahead) {
-      // the trailing update split: the next block column (all rows) | everything to the right of it
-      GemmCall next[2], rest[2];
+      // the trailing update split (chol_lookahead_split): the next block column (all rows) | everything to the right of it
+      TrailBatch next = {}, rest = {};
       bool any_rest = false;
       for (int q = 0; q < nsys; ++q) {
-        const GemmCall& trail = st.trail[q];
-        const int rem = (int)trail.N, rows = (int)trail.M;
-        if (rem <= 0) continue;
-        const int nbn = rem < NB ? rem : NB;
-        next[q] = trail;
-        next[q].N = nbn;
-        if (rem > nbn) {
-          rest[q] = trail;
-          rest[q].M = rows - nbn; rest[q].N = rem - nbn;
-          rest[q].A = rest[q].B = trail.A + (int64_t)nbn * trail.lda;
-          rest[q].C = trail.C + (int64_t)nbn * trail.ldc + nbn;
+        const TrailSys& trail = st.trail.s[q];
+        const CholLookahead split = chol_lookahead_split(trail.rows, trail.rem);
+        if (split.next.cols > 0) next.s[q] = trail_part(trail, split.next);
+        if (split.rest.cols > 0) {
+          rest.s[q] = trail_part(trail, split.rest);
           any_rest = true;
         }
       }
       hipEvent_t evP = la_evt[jb & 1], evR = la_evt[2 + (jb & 1)], evR_prev = la_evt[2 + ((jb + 1) & 1)];
       NK_HIP(hipEventRecord(evP, s_chain));                               // panel(jb) is complete
       if (rest_pending) NK_HIP(hipStreamWaitEvent(s_chain, evR_prev, 0));  // the next column has its older updates
-      NK_TRY(chol_trail_update(ctx, next, nsys));
+      NK_TRY(launch_chol_trail_pair(ctx, next));
       rest_pending = false;
       if (any_rest) {
         ctx->stream = s_rest;
         NK_HIP(hipStreamWaitEvent(s_rest, evP, 0));
-        const int rc = chol_trail_update(ctx, rest, nsys);
+        const int rc = launch_chol_trail_pair(ctx, rest);
         if (rc == NK_OK) NK_HIP(hipEventRecord(evR, s_rest));
         last_rest = evR;
         ctx->stream = s_chain;
@@ -307,24 +296,23 @@ int cholesky_aug_pair_async(nk_ctx* ctx, const CholSys* sys, int nsys, hipEvent_
 int cholesky_solve_pair(nk_ctx* ctx, const CholSys* sys, int nsys) {
   constexpr int NB = CHOL_NB;
   NK_REQUIRE(nsys >= 1 && nsys <= 2, "cholesky_solve_pair: 1..2 systems");
-  int nblk = 0;
-  for (int q = 0; q < nsys; ++q) nblk = std::max(nblk, (sys[q].m + NB - 1) / NB);
+  const int nblk = pair_blocks(sys, nsys);
   const ArenaMark mk = arena_mark(ctx);
   double* tmp[2] = {nullptr, nullptr};
   for (int q = 0; q < nsys; ++q) NK_TRY(arena_alloc_t(ctx, (size_t)NB * sys[q].ldr, &tmp[q]));
+  auto rhs_block = [&](int q, int jb) { return sys[q].R + (int64_t)jb * NB * sys[q].ldr; };
   // One diagonal-block solve  R_j <- op(L_jj)^-1 R_j : the product with the explicitly inverted block, then one correction
   // step from the data (the product alone is not backward stable, see chol_panel_kernel):
   //   X = Linv R_j ;  X += Linv (R_j - L_jj X)
   auto diag_solve = [&](int jb, bool trans) -> int {
-    const int j0 = jb * NB;
     GemmCall g1[2], g2[2], g3[2];
     for (int q = 0; q < nsys; ++q) {
       const CholSys& y = sys[q];
-      if (j0 >= y.m) continue;
-      const int nbj = y.m - j0 < NB ? y.m - j0 : NB;
+      const int nbj = chol_block_order(y.m, jb);
+      if (nbj == 0) continue;
       const double* Li = y.Linv + (size_t)jb * CHOL_WS;
       const double* Ld = Li + NB * NB;
-      double* Rj = y.R + (int64_t)j0 * y.ldr;
+      double* Rj = rhs_block(q, jb);
       NK_TRY(launch_copy2d(ctx, Rj, y.ldr, tmp[q], y.ldr, nbj, y.nrhs));
       g1[q].M = nbj; g1[q].N = y.nrhs; g1[q].K = nbj; g1[q].A = Li; g1[q].lda = NB; g1[q].B = tmp[q]; g1[q].ldb = y.ldr;
       g1[q].C = Rj; g1[q].ldc = y.ldr;
@@ -336,40 +324,30 @@ int cholesky_solve_pair(nk_ctx* ctx, const CholSys* sys, int nsys) {
     NK_TRY(launch_gemm_pair(ctx, trans, false, g3, nsys));
     return NK_OK;
   };
+  // R[u.row0 ..] -= op(L[block]) R_jb for the update u of block jb; A: the block of the factor, rows x k (forward) or
+  // k x rows read transposed (backward)
+  auto update = [&](int q, int jb, const CholSolveUpdate& u, const double* A, GemmCall& g) {
+    if (u.rows == 0) return;
+    const CholSys& y = sys[q];
+    g.M = u.rows; g.N = y.nrhs; g.K = u.k; g.alpha = -1.0; g.beta = 1.0;
+    g.A = A; g.lda = y.ldp; g.B = rhs_block(q, jb); g.ldb = y.ldr;
+    g.C = y.R + (int64_t)u.row0 * y.ldr; g.ldc = y.ldr;
+  };
   // forward: L T = R
   for (int jb = 0; jb < nblk; ++jb) {
-    const int j0 = jb * NB;
     GemmCall upd[2];
     for (int q = 0; q < nsys; ++q) {
-      const CholSys& y = sys[q];
-      if (j0 >= y.m) continue;
-      const int nbj = y.m - j0 < NB ? y.m - j0 : NB;
-      double* Rj = y.R + (int64_t)j0 * y.ldr;
-      const int rem = y.m - j0 - nbj;
-      if (rem > 0) {
-        upd[q].M = rem; upd[q].N = y.nrhs; upd[q].K = nbj; upd[q].alpha = -1.0; upd[q].beta = 1.0;
-        upd[q].A = y.P + (int64_t)(j0 + nbj) * y.ldp + j0; upd[q].lda = y.ldp; upd[q].B = Rj; upd[q].ldb = y.ldr;
-        upd[q].C = y.R + (int64_t)(j0 + nbj) * y.ldr; upd[q].ldc = y.ldr;
-      }
+      const CholSolveUpdate u = chol_solve_forward(sys[q].m, jb);
+      update(q, jb, u, sys[q].P + (int64_t)u.row0 * sys[q].ldp + jb * NB, upd[q]);
     }
     NK_TRY(diag_solve(jb, false));
     NK_TRY(launch_gemm_pair(ctx, false, false, upd, nsys));
   }
   // backward: L^T X = T
   for (int jb = nblk - 1; jb >= 0; --jb) {
-    const int j0 = jb * NB;
     GemmCall upd[2];
-    for (int q = 0; q < nsys; ++q) {
-      const CholSys& y = sys[q];
-      if (j0 >= y.m) continue;
-      const int nbj = y.m - j0 < NB ? y.m - j0 : NB;
-      double* Rj = y.R + (int64_t)j0 * y.ldr;
-      if (j0 > 0) {
-        upd[q].M = j0; upd[q].N = y.nrhs; upd[q].K = nbj; upd[q].alpha = -1.0; upd[q].beta = 1.0;
-        upd[q].A = y.P + (int64_t)j0 * y.ldp; upd[q].lda = y.ldp; upd[q].B = Rj; upd[q].ldb = y.ldr;
-        upd[q].C = y.R; upd[q].ldc = y.ldr;
-      }
-    }
+    for (int q = 0; q < nsys; ++q)
+      update(q, jb, chol_solve_backward(sys[q].m, jb), sys[q].P + (int64_t)jb * NB * sys[q].ldp, upd[q]);
     NK_TRY(diag_solve(jb, true));
     NK_TRY(launch_gemm_pair(ctx, true, false, upd, nsys));
   }

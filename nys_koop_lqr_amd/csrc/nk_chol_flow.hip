@@ -26,6 +26,7 @@
 #include <cstdlib>
 
 #include "nk_common.h"
+#include "nk_chol.h"
 #include "nk_panel_body.h"
 #include "nk_potrf_body.h"
 
@@ -34,7 +35,6 @@ namespace nk {
 namespace {
 
 constexpr int FLOW_THREADS = 256;
-constexpr int FLOW_HDR = 16;                 // words ahead of the flags: [0] ticket, [1] status
 constexpr int FLOW_POLL_LIMIT = 1 << 22;     // polls of one wait (~0.5 us each: seconds -- a genuine hang, nothing else)
 
 struct FlowSys {
@@ -353,25 +353,26 @@ static int flow_test_giveup(const CholSys* sys, int nsys, int total) {
 
 // The factorisation part of cholesky_aug_pair_async as one launch (after reset_pivots; the caller queues the backward pass).
 int cholesky_flow_pair(nk_ctx* ctx, const CholSys* sys, int nsys) {
-  constexpr int NB = CHOL_NB;
   NK_REQUIRE(nsys >= 1 && nsys <= 2, "cholesky_flow_pair: 1..2 systems");
   FlowArgs a;
   memset(&a, 0, sizeof(a));
   a.nsys = nsys;
   a.fix = chol_fix_enabled();
-  size_t words = FLOW_HDR;
+  int ms[2] = {0, 0}, extras[2] = {0, 0};
+  CholFlowCounts fc[2];
   for (int q = 0; q < nsys; ++q) {
     const CholSys& y = sys[q];
+    fc[q] = chol_flow_counts(y.m, y.extra);
     FlowSys& s = a.s[q];
     s.P = y.P; s.ldp = y.ldp; s.m = y.m; s.extra = y.extra; s.Linv = y.Linv; s.pivlog = y.pivlog;
     s.info = ctx->d_info + info_base(ctx) + q;
     s.piv = ctx->d_piv + 2 * (info_base(ctx) + q);
-    s.nblk = (y.m + NB - 1) / NB;
-    s.nex = (y.extra + NB - 1) / NB;
-    words += (size_t)(s.nblk + s.nex) * s.nblk;
-    // items: one diagonal item per block column, the tiles of each column below the first sub-diagonal one
-    for (int c = 0; c < s.nblk; ++c) a.total += 1 + std::max(0, s.nblk - c - 2) + s.nex;
+    s.nblk = fc[q].nblk;
+    s.nex = fc[q].nex;
+    ms[q] = y.m; extras[q] = y.extra;
   }
+  const size_t words = chol_flow_words(ms, extras, nsys);
+  a.total = chol_flow_items(ms, extras, nsys);
   // flag words of this stream's slot (persistent: no allocation in steady state)
   const int slot = info_base(ctx) / 2;
   if (ctx->flow_words[slot] < words) {
@@ -383,10 +384,10 @@ int cholesky_flow_pair(nk_ctx* ctx, const CholSys* sys, int nsys) {
   }
   a.test_giveup = flow_test_giveup(sys, nsys, a.total);
   a.hdr = ctx->d_flow[slot];
-  int* f = a.hdr + FLOW_HDR;
+  int* f = a.hdr + CHOL_FLOW_HDR;
   for (int q = 0; q < nsys; ++q) {
     a.s[q].flags = f;
-    f += (size_t)(a.s[q].nblk + a.s[q].nex) * a.s[q].nblk;
+    f += fc[q].flags;
   }
   NK_HIP(hipMemsetAsync(a.hdr, 0, words * sizeof(int), ctx->stream));
   // Half the CUs, one workgroup on each: the launch is latency bound (the diagonal chain), a workgroup of it (320 VGPRs)

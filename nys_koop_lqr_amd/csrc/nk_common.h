@@ -457,72 +457,6 @@ int sqrtm_prepare(nk_ctx* ctx, const double* P, int64_t ldp, int m, SqrtPlan* pl
 int sqrtm_finish(nk_ctx* ctx, SqrtPlan* plan, double* S, double* Sinv);
 // after the stream that ran sqrtm_finish has been synchronised: NK_OK / NK_ERR_NO_CONVERGENCE, iteration count, residual
 int sqrtm_verdict(nk_ctx* ctx, SqrtPlan* plan, int* iters, double* resid);
-// in-place lower Cholesky of P (m x m, ld), Linv workspace holds inverted diagonal blocks
-int cholesky_lower(nk_ctx* ctx, double* P, int64_t ldp, int m, double* Linv /* nblk*NB*NB */);
-int cholesky_solve(nk_ctx* ctx, const double* L, int64_t ldl, int m, const double* Linv, double* R, int64_t ldr,
-                   int nrhs);  // R <- (L L^T)^{-1} R in place
-// the same for TWO independent systems advanced in lock step, every per-block kernel launched once for both
-// (the chains are latency bound: pairing halves their length)
-struct CholSys {
-  double* P = nullptr;   // matrix, overwritten by its lower factor
-  int64_t ldp = 0;
-  int m = 0;
-  // Augmented form (cholesky_aug_pair): `extra` further rows below the m x m matrix hold the right-hand sides
-  // TRANSPOSED (extra x m); the factorisation's panel / trailing updates carry them along (= forward substitution for
-  // free) and a backward pass leaves X^T = (P^-1 R)^T = R^T P^-1 in their place.
-  int extra = 0;
-  bool backward = true;  // false: stop after the factorisation (the extra rows then hold R^T L^-T)
-  double* Linv = nullptr;
-  double* pivlog = nullptr;  // optional device array of m doubles: the factorisation logs every pivot here
-  double* R = nullptr;   // right-hand sides (solve only), overwritten by the solution
-  int64_t ldr = 0;
-  int nrhs = 0;
-};
-int cholesky_lower_pair(nk_ctx* ctx, const CholSys* sys, int nsys);
-int cholesky_lower_pair_async(nk_ctx* ctx, const CholSys* sys, int nsys);  // no host synchronisation
-int cholesky_check_pair(nk_ctx* ctx, const CholSys* sys, int nsys);       // verdict of the async factorisation
-int cholesky_solve_pair(nk_ctx* ctx, const CholSys* sys, int nsys);
-// factor + both substitutions, no host sync; mark / mark_step: optional event recorded after block step `mark_step`
-// pause / pause_step: before block step pause_step the chain's stream waits for the (already recorded) event `pause`
-int cholesky_aug_pair_async(nk_ctx* ctx, const CholSys* sys, int nsys, hipEvent_t pause = nullptr, int pause_step = -1);
-constexpr int CHOL_NB = 64;
-// workspace per diagonal block of a blocked factorisation (CholSys::Linv): the inverted 64 x 64 diagonal block of the factor
-// followed by the diagonal block itself, both dense row-major with exact zeros above the diagonal and identity padding
-// beyond a short last block.  The factor rides along because every product with the explicit inverse is followed by one
-// correction step  x += (b - x L_jj) L_jj^-1  (see chol_panel_kernel): multiplying by an explicit inverse alone is not
-// backward stable -- its error grows with cond(L_jj), 1e6 on the kernel matrices here.
-constexpr int CHOL_WS = 2 * CHOL_NB * CHOL_NB + 8;  // (+ one verdict word, padded to 64 bytes)
-// the verdict word behind the two blocks: 1.0 when ||L_jj||_F ||L_jj^-1||_F exceeds this and the products with the inverse
-// take the correction step (potrf_diag_kernel)
-constexpr double CHOL_FIX_KAPPA = 8.0 * CHOL_NB;
-// NYSKOOP_CHOL_FIX (read per launch: same-process A/B; for measurements only): 0 = never correct, 2 = always, default 1 = where
-// the verdict word says so
-inline int chol_fix_enabled() {
-  const char* e = getenv("NYSKOOP_CHOL_FIX");
-  return (e && e[0] == '0') ? 0 : ((e && e[0] == '2') ? 2 : 1);
-}
-// trailing update C -= P P^T (K = 64) of up to two systems (nk_trail.hip); false: not that shape, use launch_gemm_pair
-bool launch_chol_trail_pair(nk_ctx* ctx, const GemmCall* calls, int ncalls, int* rc);
-// ... fused with the diagonal-block factorisation of the NEXT block step `blk` (nb[q]: its order, 0 = system q has none; the
-// block is calls[q].C): one launch instead of two, the diagonal kernel off the critical path.  false: not that shape, nothing
-// launched (the caller issues the two launches separately)
-bool launch_chol_trail_potrf_pair(nk_ctx* ctx, const GemmCall* calls, int ncalls, const int* nb, double* const* Linv, int blk,
-                                  double* const* plog, int* rc);
-inline bool chol_fuse_enabled() {  // NYSKOOP_CHOL_FUSE=0 (read per call): separate launches, for A/B runs and the bit-identity test
-  const char* e = getenv("NYSKOOP_CHOL_FUSE");
-  return !(e && e[0] == '0');
-}
-// the factorisation of cholesky_aug_pair_async as one tile-dataflow launch (nk_chol_flow.hip): same bits as the chain;
-// NYSKOOP_CHOL_FLOW=0 (read per call) keeps the launch-per-step chain
-bool chol_flow_enabled();
-int cholesky_flow_pair(nk_ctx* ctx, const CholSys* sys, int nsys);
-// failure flag of the systems of a dataflow factorisation that stopped waiting (a bounded wait ran out): cholesky_fail_flags
-// reports it as is (failed[q] == CHOL_FLOW_GIVEUP) and counts CNT_CHOL_FLOW_GIVEUP; the caller re-runs the chain
-constexpr int CHOL_FLOW_GIVEUP = -0x40000000;
-// panel product P <- P Linv_jj^T (64 x 64) of up to two systems (nk_trail.hip); false: not that shape
-bool launch_chol_panel_pair(nk_ctx* ctx, const GemmCall* calls, int ncalls, int* rc);
-// E_q <- E_q L_q^-1 on the extra rows of up to two factored systems, one launch (nk_trsm.hip)
-int launch_trsm_right_lower_pair(nk_ctx* ctx, const CholSys* sys, int nsys);
 
 // E_out (rows x m) = E * pinv(P) for symmetric P with LAPACK gelsd's cut-off (singular values <= rcond * sigma_max are
 // dropped): one-sided Jacobi SVD on the device (nk_pinv.hip), the fallback of the regularised solves
@@ -533,9 +467,6 @@ struct PinvInfo {
 };
 int pinv_right_divide(nk_ctx* ctx, const double* P, int64_t ldp, int m, const double* E, int64_t lde, int rows,
                       double* E_out, int64_t ldeo, double rcond, PinvInfo* info);
-// which systems of the last (paired) factorisation on the current stream met a non-positive pivot (synchronises)
-// piv_ratio (optional, nsys entries): smallest / largest pivot of each factorisation (0 when it failed)
-int cholesky_fail_flags(nk_ctx* ctx, const CholSys* sys, int nsys, int* failed /* nsys entries */, double* piv_ratio = nullptr);
 
 // matrix-vector step of the lifted recursion for up to 8 trajectories (nk_rollout.hip)
 int launch_lifted_step(nk_ctx* ctx, const double* G, int64_t ldg, int m, int mz, int pu, const double* z, int64_t zstride,

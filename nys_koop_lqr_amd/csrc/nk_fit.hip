@@ -2,6 +2,7 @@
 // a sequence of named stages called by NystromFit::run) and the thin-plate-spline fit (nk_spline_fit), with the row selection,
 // pass planning and fp64 kernel blocks they share.
 #include "nk_common.h"
+#include "nk_chol.h"
 #include "nk_tn.h"
 #include "nk_api_internal.h"
 

@@ -44,6 +44,13 @@ template <typename F, typename T, typename... Ts, typename... Us>
 __device__ __forceinline__ void pack_apply(F&& f, const ArgPack<T, Ts...>& p, Us... us) {
   pack_apply(static_cast<F&&>(f), p.rest, us..., p.v);
 }
+// the same with the members passed by reference (NK_BATCHED_TWIN_REF)
+template <typename F, typename... Us>
+__device__ __forceinline__ void pack_apply_ref(F&& f, const ArgPack<>&, const Us&... us) { f(us...); }
+template <typename F, typename T, typename... Ts, typename... Us>
+__device__ __forceinline__ void pack_apply_ref(F&& f, const ArgPack<T, Ts...>& p, const Us&... us) {
+  pack_apply_ref(static_cast<F&&>(f), p.rest, us..., p.v);
+}
 // byte offsets of the members (for launching the direct kernel from a recorded pack)
 inline void pack_offsets(const ArgPack<>&, const char*, std::vector<uint32_t>&) {}
 template <typename T, typename... Ts>
@@ -107,6 +114,15 @@ hipError_t x_event_elapsed(float* ms, hipEvent_t a, hipEvent_t b);
   __global__ void __launch_bounds__ bounds name##_batched(const nk::ArgPack<__VA_ARGS__>* table) {           \
     const nk::ArgPack<__VA_ARGS__> p = table[blockIdx.z];                                                    \
     nk::pack_apply([](auto... a) { name##_body(a...); }, p);                                                 \
+  }                                                                                                          \
+  static nk::TwinReg name##_twin_reg(reinterpret_cast<const void*>(static_cast<void (*)(__VA_ARGS__)>(name)), \
+                                     reinterpret_cast<const void*>(name##_batched), sizeof(nk::ArgPack<__VA_ARGS__>), #name);
+
+// By-reference form, for bodies that take large argument records as `const T&`: the members of table[blockIdx.z] go to the
+// body where they lie, the pack is not copied.
+#define NK_BATCHED_TWIN_REF(name, bounds, ...)                                                               \
+  __global__ void __launch_bounds__ bounds name##_batched(const nk::ArgPack<__VA_ARGS__>* table) {           \
+    nk::pack_apply_ref([](const auto&... a) { name##_body(a...); }, table[blockIdx.z]);                      \
   }                                                                                                          \
   static nk::TwinReg name##_twin_reg(reinterpret_cast<const void*>(static_cast<void (*)(__VA_ARGS__)>(name)), \
                                      reinterpret_cast<const void*>(name##_batched), sizeof(nk::ArgPack<__VA_ARGS__>), #name);

@@ -1,7 +1,7 @@
 // Panel solve of the blocked Cholesky, per 16 rows: shared by the launch-per-step chain (nk_trail.hip) and the dataflow
 // factorisation (nk_chol_flow.hip), so that both compute the same bits.
 #pragma once
-#include "nk_common.h"
+#include "nk_chol.h"
 #include "nk_potrf_body.h"  // (d4)
 
 namespace nk {
@@ -22,16 +22,7 @@ namespace nk {
 // the same dealing and serve both as b-operand of the first product and as the minuend of the residual.
 // Columns beyond `nb` (a short last block; only the right-hand-side rows of an augmented system get there) are masked.
 // ---------------------------------------------------------------------------------------------------------------
-constexpr int PANEL_ROWS = 64;  // rows per workgroup of the panel solve
-struct PanelSys {
-  double* P;
-  int64_t ldp;
-  const double* Linv;  // CHOL_WS doubles: 64 x 64 inverse, then the 64 x 64 factor block (dense, identity padded)
-  int rows;
-  int nb;              // valid columns of the block
-  int fix;             // correction step: 0 never, 1 where the block's verdict word says so, 2 always
-  int nblocks;
-};
+constexpr int PANEL_ROWS = CHOL_PANEL_ROWS;  // rows per workgroup of the panel solve: four waves of 16
 // Rows m0 .. m0 + 15 of the panel, one wave (lane 0..63); every wave of the workgroup calls it (one barrier inside).
 __device__ __forceinline__ void chol_panel_rows(const PanelSys& s, int m0, int lane) {
   __builtin_amdgcn_s_setprio(2);

@@ -1,7 +1,7 @@
 // Diagonal-block Cholesky of the blocked factorisation (nk_chol.hip), in its own translation unit (fully unrolled).  Replaces the LAPACK potrf inside lstsq's role
 // (regressors.py:155,165).
 #pragma once
-#include "nk_common.h"
+#include "nk_chol.h"
 
 namespace nk {
 
@@ -24,18 +24,6 @@ __device__ __forceinline__ double readlane_f64(double v, int lane) {
   const int hi = __builtin_amdgcn_readlane(__double2hiint(v), lane);
   return __hiloint2double(hi, lo);
 }
-
-struct PotrfBatch {
-  double* A[2];
-  int64_t lda[2];
-  int nb[2];
-  double* Linv[2];
-  int* info[2];
-  unsigned long long* piv[2];  // [min, max] pivot of the whole factorisation as bit patterns (positive doubles order like
-                               // their bit patterns)
-  double* plog[2];             // optional: every pivot of this block, in order (the numerical-rank verdict of
-                               // cholesky_fail_flags looks for an isolated cluster of rounding-level pivots)
-};
 
 constexpr int PLD = CHOL_NB + 1;  // LDS row stride of the 64 x 64 images
 constexpr int SLD = 17;           // LDS row stride of a 16 x 16 scratch tile
@@ -60,8 +48,9 @@ __device__ __forceinline__ void store_tile(double* T, int ldt, d4 acc, int l15, 
 }
 
 // Barrier between the LDS phases of the diagonal body.  WAVE_SYNC: the body runs in ONE wave of a larger workgroup whose other
-// waves wait elsewhere (nk_chol_flow.hip), so the barrier is the wave's own: LDS operations of one wave complete in order, and
-// the workgroup-scope fences keep the compiler from moving LDS accesses across it.
+// waves are elsewhere -- waiting (nk_chol_flow.hip), still on their tiles or already gone (nk_trail.hip) -- so the barrier is
+// the wave's own: LDS operations of one wave complete in order, and the workgroup-scope fences keep the compiler from moving
+// LDS accesses across it.  No workgroup barrier may stand in such a body: the other waves never reach it.
 template <bool WAVE_SYNC>
 __device__ __forceinline__ void potrf_sync() {
   if (WAVE_SYNC) {
@@ -73,9 +62,9 @@ __device__ __forceinline__ void potrf_sync() {
   }
 }
 
-// `which`: the system of a paired factorisation this wave works on; `lane`: 0..63 within the wave (the wave may be one of
-// several in its workgroup: chol_trail_potrf_kernel -- every __syncthreads below (WAVE_SYNC = false) then only waits for the
-// waves that are still alive, which is this one once the others have finished their tiles; chol_flow_kernel: WAVE_SYNC)
+// `which`: the system of a paired factorisation this wave works on; `lane`: 0..63 within the wave.  WAVE_SYNC = false only
+// where the wave is the whole workgroup (potrf_diag_kernel); one wave of several (chol_trail_potrf_kernel, chol_flow_kernel)
+// takes WAVE_SYNC = true.  The LDS arrays below are touched by that one wave only.
 template <bool WAVE_SYNC = false>
 __device__ __forceinline__ void potrf_diag_kernel_body(const PotrfBatch& pb, int blk, int which, int lane) {
   constexpr int NB = CHOL_NB;

@@ -3,6 +3,7 @@
 // kept as the fallback for numerically singular input), replacing scipy.linalg.sqrtm + solve(assume_a='her')
 // (regressors.py:140,152,153,163,175,177).  The step arithmetic of both iterations is nk_sqrt_schedule.h.
 #include "nk_common.h"
+#include "nk_chol.h"
 #include "nk_tn.h"
 #include "nk_sqrt_schedule.h"
 

@@ -8,24 +8,11 @@
 // lane groups, any assignment works as long as both operands use the same one), multiplies on the matrix pipe
 // (4 waves x 4 x 4 tiles of v_mfma_f64_16x16x4) and read-modify-writes the 128 x 128 tile of C.  No LDS, no barriers.
 #include "nk_common.h"
+#include "nk_chol.h"
 #include "nk_potrf_body.h"
 #include "nk_panel_body.h"
 
 namespace nk {
-
-
-struct TrailSys {
-  const double* P;  // panel: rows x 64
-  int64_t ldp;
-  double* C;        // trailing matrix: rows x rem (lower tiles of the leading rem x rem part + all tiles below it)
-  int64_t ldc;
-  int rows, rem;
-  int tiles_n;      // ceil(rem / 128)
-  int nblocks;
-};
-struct TrailBatch {
-  TrailSys s[2];
-};
 
 __device__ __forceinline__ void chol_trail_kernel_body(const TrailBatch& tb) {
   const TrailSys s = tb.s[blockIdx.y];
@@ -99,13 +86,21 @@ __device__ __forceinline__ void chol_trail_kernel_body(const TrailBatch& tb) {
       }
 }
 __global__ void __launch_bounds__(256) chol_trail_kernel(TrailBatch tb) { chol_trail_kernel_body(tb); }
-__global__ void __launch_bounds__(256) chol_trail_kernel_batched(const nk::ArgPack<TrailBatch>* table) { chol_trail_kernel_body(table[blockIdx.z].v); }
-static nk::TwinReg chol_trail_kernel_twin_reg(reinterpret_cast<const void*>(static_cast<void (*)(TrailBatch)>(chol_trail_kernel)),
-                                 reinterpret_cast<const void*>(chol_trail_kernel_batched), sizeof(nk::ArgPack<TrailBatch>), "chol_trail_kernel");
+NK_BATCHED_TWIN_REF(chol_trail_kernel, (256), TrailBatch)
 
-// trailing updates of up to two systems; calls[q] as prepared for the generic engine (A = B = panel, K = 64, alpha = -1,
-// beta = 1, TRI_LOWER).  Returns false when a call does not have that shape (the caller then uses the generic engine).
-bool launch_chol_trail_pair(nk_ctx* ctx, const GemmCall* calls, int ncalls, int* rc);
+// workgroups of a launch: the larger of the two slots (blockIdx.y selects the slot; workgroups past a slot's count leave)
+template <typename Batch>
+static unsigned pair_workgroups(const Batch& b) {
+  return (unsigned)(b.s[0].nblocks > b.s[1].nblocks ? b.s[0].nblocks : b.s[1].nblocks);
+}
+
+int launch_chol_trail_pair(nk_ctx* ctx, const TrailBatch& tb) {
+  const unsigned wgs = pair_workgroups(tb);
+  if (wgs == 0) return NK_OK;
+  hipLaunchKernelGGL(chol_trail_kernel, dim3(wgs, 2), dim3(256), 0, ctx->stream, tb);
+  NK_HIP(hipGetLastError());
+  return NK_OK;
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // Trailing update of step j AND the diagonal-block factorisation of step j + 1 in one launch.  The next diagonal block is the
@@ -115,88 +110,28 @@ bool launch_chol_trail_pair(nk_ctx* ctx, const GemmCall* calls, int ncalls, int*
 // kernel boundaries.  Same arithmetic in the same order as the two separate launches: bit-identical results
 // (NYSKOOP_CHOL_FUSE=0 issues them separately).
 // ---------------------------------------------------------------------------------------------------------------
+// The diagonal body takes the wave-level sync (potrf_sync<true>): its LDS arrays are touched by this one wave only, the
+// __threadfence() in front of it orders the wave's own global stores of the block before its loads, and the workgroup's other
+// waves need nothing from it -- they run to the end of their tiles and leave, at whatever time.
 __device__ __forceinline__ void chol_trail_potrf_kernel_body(const TrailBatch& tb, const PotrfBatch& pb, int blk) {
   chol_trail_kernel_body(tb);
   if (blockIdx.x == 0 && __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) == 0 && pb.nb[blockIdx.y] > 0) {
     __threadfence();  // this wave's own stores of the block are visible to its loads (another lane layout) below
-    potrf_diag_kernel_body(pb, blk, blockIdx.y, threadIdx.x & 63);
+    potrf_diag_kernel_body<true>(pb, blk, blockIdx.y, threadIdx.x & 63);
   }
 }
 __global__ void __launch_bounds__(256) chol_trail_potrf_kernel(TrailBatch tb, PotrfBatch pb, int blk) { chol_trail_potrf_kernel_body(tb, pb, blk); }
-__global__ void __launch_bounds__(256) chol_trail_potrf_kernel_batched(const nk::ArgPack<TrailBatch, PotrfBatch, int>* table) {
-  chol_trail_potrf_kernel_body(table[blockIdx.z].v, table[blockIdx.z].rest.v, table[blockIdx.z].rest.rest.v);
-}
-static nk::TwinReg chol_trail_potrf_twin_reg(reinterpret_cast<const void*>(static_cast<void (*)(TrailBatch, PotrfBatch, int)>(chol_trail_potrf_kernel)),
-                                             reinterpret_cast<const void*>(chol_trail_potrf_kernel_batched),
-                                             sizeof(nk::ArgPack<TrailBatch, PotrfBatch, int>), "chol_trail_potrf_kernel");
+NK_BATCHED_TWIN_REF(chol_trail_potrf_kernel, (256), TrailBatch, PotrfBatch, int)
 
-static bool fill_trail_batch(const GemmCall* calls, int ncalls, TrailBatch& tb, int& maxblocks) {
-  maxblocks = 0;
-  for (int q = 0; q < 2; ++q) {
-    TrailSys& t = tb.s[q];
-    t = TrailSys{};
-    if (q >= ncalls || calls[q].M <= 0 || calls[q].N <= 0) continue;
-    const GemmCall& c = calls[q];
-    if (c.K != 64 || c.A != c.B || c.lda != c.ldb || c.alpha != -1.0 || c.beta != 1.0 || c.opts.tri != TRI_LOWER ||
-        c.M < c.N)
-      return false;
-    t.P = c.A; t.ldp = c.lda; t.C = c.C; t.ldc = c.ldc; t.rows = (int)c.M; t.rem = (int)c.N;
-    t.tiles_n = (t.rem + 127) / 128;
-    const int tiles_m = (t.rows + 127) / 128;
-    t.nblocks = t.tiles_n * (t.tiles_n + 1) / 2 + (tiles_m - t.tiles_n) * t.tiles_n;
-    if (t.nblocks > maxblocks) maxblocks = t.nblocks;
-  }
-  return true;
-}
-
-bool launch_chol_trail_pair(nk_ctx* ctx, const GemmCall* calls, int ncalls, int* rc) {
-  *rc = NK_OK;
-  TrailBatch tb;
-  int maxblocks = 0;
-  if (!fill_trail_batch(calls, ncalls, tb, maxblocks)) return false;
-  if (maxblocks == 0) return true;
-  hipLaunchKernelGGL(chol_trail_kernel, dim3((unsigned)maxblocks, 2), dim3(256), 0, ctx->stream, tb);
-  if (hipGetLastError() != hipSuccess) {
-    set_error("chol_trail launch failed");
-    *rc = NK_ERR_HIP;
-  }
-  return true;
-}
-
-// trailing updates of step `blk - 1` (calls[q] as for launch_chol_trail_pair) fused with the diagonal-block factorisation of
-// step `blk` of the same systems (nb[q] = order of that block, 0: the system has none; its block is calls[q].C).  false: not
-// that shape, nothing launched.
-bool launch_chol_trail_potrf_pair(nk_ctx* ctx, const GemmCall* calls, int ncalls, const int* nb, double* const* Linv, int blk,
-                                  double* const* plog, int* rc) {
-  *rc = NK_OK;
-  TrailBatch tb;
-  int maxblocks = 0;
-  if (!fill_trail_batch(calls, ncalls, tb, maxblocks) || maxblocks == 0) return false;
-  PotrfBatch pb;
-  for (int q = 0; q < 2; ++q) {
-    const bool on = q < ncalls && nb[q] > 0 && tb.s[q].nblocks > 0;
-    if (q < ncalls && nb[q] > 0 && tb.s[q].nblocks == 0) return false;  // a diagonal block without a trailing update before it
-    pb.A[q] = on ? tb.s[q].C : nullptr;
-    pb.lda[q] = on ? tb.s[q].ldc : 0;
-    pb.nb[q] = on ? nb[q] : 0;
-    pb.Linv[q] = on ? Linv[q] : nullptr;
-    pb.info[q] = ctx->d_info + info_base(ctx) + q;
-    pb.piv[q] = ctx->d_piv + 2 * (info_base(ctx) + q);
-    pb.plog[q] = (on && plog) ? plog[q] : nullptr;
-  }
-  hipLaunchKernelGGL(chol_trail_potrf_kernel, dim3((unsigned)maxblocks, 2), dim3(256), 0, ctx->stream, tb, pb, blk);
-  if (hipGetLastError() != hipSuccess) {
-    set_error("chol_trail_potrf launch failed");
-    *rc = NK_ERR_HIP;
-  }
-  return true;
+int launch_chol_trail_potrf_pair(nk_ctx* ctx, const TrailBatch& tb, const PotrfBatch& pb, int blk) {
+  const unsigned wgs = pair_workgroups(tb);
+  if (wgs == 0) return NK_OK;
+  hipLaunchKernelGGL(chol_trail_potrf_kernel, dim3(wgs, 2), dim3(256), 0, ctx->stream, tb, pb, blk);
+  NK_HIP(hipGetLastError());
+  return NK_OK;
 }
 
 // Panel solve of the same step: chol_panel_rows (nk_panel_body.h).
-struct PanelBatch {
-  PanelSys s[2];
-};
-
 __device__ __forceinline__ void chol_panel_kernel_body(const PanelBatch& pb) {
   const PanelSys s = pb.s[blockIdx.y];
   if ((int)blockIdx.x >= s.nblocks) return;
@@ -206,33 +141,14 @@ __device__ __forceinline__ void chol_panel_kernel_body(const PanelBatch& pb) {
   chol_panel_rows(s, blockIdx.x * PANEL_ROWS + wave * 16, threadIdx.x & 63);
 }
 __global__ void __launch_bounds__(256) chol_panel_kernel(PanelBatch pb) { chol_panel_kernel_body(pb); }
-__global__ void __launch_bounds__(256) chol_panel_kernel_batched(const nk::ArgPack<PanelBatch>* table) { chol_panel_kernel_body(table[blockIdx.z].v); }
-static nk::TwinReg chol_panel_kernel_twin_reg(reinterpret_cast<const void*>(static_cast<void (*)(PanelBatch)>(chol_panel_kernel)),
-                                 reinterpret_cast<const void*>(chol_panel_kernel_batched), sizeof(nk::ArgPack<PanelBatch>), "chol_panel_kernel");
+NK_BATCHED_TWIN_REF(chol_panel_kernel, (256), PanelBatch)
 
-// panel solves of up to two systems; calls[q] as prepared for the generic engine (C = A in place, B = the block's CHOL_WS
-// workspace with leading dimension 64, N = K = valid columns <= 64, alpha = 1, beta = 0).  false: not that shape.
-bool launch_chol_panel_pair(nk_ctx* ctx, const GemmCall* calls, int ncalls, int* rc) {
-  *rc = NK_OK;
-  PanelBatch pb;
-  int maxblocks = 0;
-  for (int q = 0; q < 2; ++q) {
-    PanelSys& t = pb.s[q];
-    t = PanelSys{};
-    if (q >= ncalls || calls[q].M <= 0 || calls[q].N <= 0) continue;
-    const GemmCall& c = calls[q];
-    if (c.K != c.N || c.N > 64 || c.A != c.C || c.lda != c.ldc || c.ldb != 64 || c.alpha != 1.0 || c.beta != 0.0) return false;
-    t.P = c.C; t.ldp = c.ldc; t.Linv = c.B; t.rows = (int)c.M; t.nb = (int)c.N; t.fix = chol_fix_enabled();
-    t.nblocks = (t.rows + PANEL_ROWS - 1) / PANEL_ROWS;
-    if (t.nblocks > maxblocks) maxblocks = t.nblocks;
-  }
-  if (maxblocks == 0) return true;
-  hipLaunchKernelGGL(chol_panel_kernel, dim3((unsigned)maxblocks, 2), dim3(256), 0, ctx->stream, pb);
-  if (hipGetLastError() != hipSuccess) {
-    set_error("chol_panel launch failed");
-    *rc = NK_ERR_HIP;
-  }
-  return true;
+int launch_chol_panel_pair(nk_ctx* ctx, const PanelBatch& pb) {
+  const unsigned wgs = pair_workgroups(pb);
+  if (wgs == 0) return NK_OK;
+  hipLaunchKernelGGL(chol_panel_kernel, dim3(wgs, 2), dim3(256), 0, ctx->stream, pb);
+  NK_HIP(hipGetLastError());
+  return NK_OK;
 }
 
 }  // namespace nk

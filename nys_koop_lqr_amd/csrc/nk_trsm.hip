@@ -12,6 +12,7 @@
 // every band from L2; 16 MB at m = 2000), the next block pair is fetched while the current one is multiplied, and
 // nothing but the finished X_j is written.  125 + 24 workgroups at the C4 shape.
 #include "nk_common.h"
+#include "nk_chol.h"
 
 namespace nk {
 
@@ -35,6 +36,7 @@ struct TrsmBatch {
 
 constexpr int TR_RT = 1;              // 16-row MFMA tiles per wave
 constexpr int TR_ROWS = 16 * TR_RT;  // rows per workgroup; wave w owns columns 16w..16w+15 of the current block
+static_assert(TR_ROWS == CHOL_TRSM_ROWS, "chol_trsm_workgroups (nk_chol_plan.h) counts bands of TR_ROWS rows");
 constexpr int TR_PA = TR_ROWS / 4;    // doubles per thread of a cooperative band-block load (256 threads, 64 columns)
 constexpr int TLD = 65;      // odd row stride: the 16 rows an operand fetch touches fall into distinct LDS banks
 
@@ -236,12 +238,7 @@ __device__ __forceinline__ void trsm_right_lower_kernel_body(const TrsmBatch& tb
   }
 }
 __global__ void __launch_bounds__(256) trsm_right_lower_kernel(TrsmBatch tb) { trsm_right_lower_kernel_body(tb); }
-__global__ void __launch_bounds__(256) trsm_right_lower_kernel_batched(const nk::ArgPack<TrsmBatch>* table) {
-  trsm_right_lower_kernel_body(table[blockIdx.z].v);
-}
-static nk::TwinReg trsm_twin_reg(reinterpret_cast<const void*>(static_cast<void (*)(TrsmBatch)>(trsm_right_lower_kernel)),
-                                 reinterpret_cast<const void*>(trsm_right_lower_kernel_batched), sizeof(nk::ArgPack<TrsmBatch>),
-                                 "trsm_right_lower_kernel");
+NK_BATCHED_TWIN_REF(trsm_right_lower_kernel, (256), TrsmBatch)
 
 // E_q <- E_q L_q^-1 for up to two systems (E: extra x m rows below the factor in the same array, see CholSys)
 int launch_trsm_right_lower_pair(nk_ctx* ctx, const CholSys* sys, int nsys) {
@@ -254,7 +251,7 @@ int launch_trsm_right_lower_pair(nk_ctx* ctx, const CholSys* sys, int nsys) {
     TrsmSys& t = tb.s[tb.nsys++];
     t.E = y.P + (int64_t)y.m * y.ldp; t.lde = y.ldp; t.rows = y.extra;
     t.L = y.P; t.ldl = y.ldp; t.m = y.m; t.Dinv = y.Linv; t.wg_begin = wgs; t.fix = chol_fix_enabled();
-    wgs += (y.extra + TR_ROWS - 1) / TR_ROWS;
+    wgs += chol_trsm_workgroups(y.extra);
   }
   if (tb.nsys == 0) return NK_OK;
   if (tb.nsys == 1) tb.s[1] = tb.s[0];

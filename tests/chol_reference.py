@@ -246,7 +246,8 @@ def counters():
 
 
 def flow_items(systems):
-    """Work items (tickets) of the dataflow launch for systems [(m, extra), ...]: nk_chol_flow.hip's count."""
+    """Work items (tickets) of the dataflow launch for systems [(m, extra), ...].  Mirrors chol_flow_counts / chol_flow_items
+    of csrc/nk_chol_plan.h, which the library takes its count from (tests/test_chol_plan_host.py holds the two together)."""
     total = 0
     for m, extra in systems:
         nblk, nex = -(-m // NB), -(-extra // NB)
